@@ -22,6 +22,13 @@ N > 1 lines carry `rccl_ranks` (ncclCommCount of the library's communicator), th
 measured in the same run (`single_gpu`), `parallel_efficiency` = value / (N x that rate) and
 `tiled_equals_untiled_bitwise` (every rank advances the whole grid alone from the same state and compares its tile).
 Prints ONE JSON line on rank 0.
+
+A plain run sets up, warms up, times `--steps` steps and prints the line: `metric`, `value`, `unit`, `higher_is_better`, `dtype`,
+`ms_per_step` (wall time of one timed step), `config` and `path` (what the timed steps ran).  Everything else -- the roofline of the
+dominant kernel and its profiling pass, the clock / power sampler, the result check, whole RK3 steps, the advection / config 3 /
+structure configurations, the unfused path, the CPU baseline and, at N > 1, the tiled == untiled check, the other transports and
+decomposition, tier 0 and the one-GPU rate -- runs only with `--full` (the `--no-*` options then leave parts of it out).
+`--dump-outputs DIR` writes what the last timed step left in the model (u, v, s11, s22, s12 of rank 0's tile) as DIR/<name>.npy.
 """
 import argparse
 import ctypes
@@ -486,7 +493,44 @@ def parse_args(argv=None):
     ap.add_argument("--no-unfused", action="store_true", help="one GPU: do not time the unfused three-kernel path (roofline.unfused) after the headline")
     ap.add_argument("--no-structure", action="store_true", help="one GPU: do not time the masked / tripolar configurations (`structure`) and config 3's 1024^2 after the headline")
     ap.add_argument("--no-verify", action="store_true", help="N > 1: skip the tiled == untiled bitwise check and the one-GPU rate of the same grid")
-    return ap.parse_args(argv)
+    ap.add_argument("--full", action="store_true",
+                    help="after the headline, also measure and check everything else (roofline, clock, result check, whole steps, other "
+                         "configurations, CPU baseline; N > 1: bitwise check, other transports / decomposition, one-GPU rate)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default="",
+                    help="write the fields the last timed step produced (rank 0's tile) to DIR/<name>.npy, float64, at most 64 MB in all")
+    args = ap.parse_args(argv)
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
+    if args.warmup < 0:
+        ap.error("--warmup must not be negative")
+    return args
+
+
+DUMP_FIELDS = ("u", "v", "s11", "s22", "s12")
+DUMP_MAX_VALUES = 1 << 20          # per field: 5 fields + the index of a sample stay below 64 MB in float64
+
+
+def dump_outputs(R, out_dir):
+    """--dump-outputs: the velocities and stresses the last timed step left in the model, rank 0's owned cells, as float64 .npy files.
+    A field with more than DUMP_MAX_VALUES cells is written as a sample at fixed, seeded positions (the same on every run with the same
+    arguments): `<name>.npy` holds the sampled values, `sample_index.npy` their flat row-major positions in the (Ny, Nx) field."""
+    if R.rank != 0:
+        return
+    np, m = R.np, R.model
+    m.synchronize()
+    g = R.tg
+    fields = {"u": m.velocities.u, "v": m.velocities.v}
+    fields.update({n: getattr(m.dynamics.auxiliaries.fields, n) for n in R.SIG})
+    os.makedirs(out_dir, exist_ok=True)
+    idx = None
+    for name in DUMP_FIELDS:
+        a = np.ascontiguousarray(fields[name].interior_numpy()[:g.Ny, :g.Nx], dtype=np.float64)
+        if a.size > DUMP_MAX_VALUES:
+            if idx is None:
+                idx = np.sort(np.random.default_rng(20240901).choice(a.size, DUMP_MAX_VALUES, replace=False))
+                np.save(os.path.join(out_dir, "sample_index.npy"), idx.astype(np.float64))
+            a = a.reshape(-1)[idx]
+        np.save(os.path.join(out_dir, f"{name}.npy"), a)
 
 
 def self_test_launch():
@@ -663,7 +707,7 @@ def warm_up_and_verify(R):
     tier; a library error (a wait that timed out: sticky, the flags cannot recover) goes straight to the RCCL exchange on freshly
     built models.  Returns (verify, bitwise, ladder, transport_note)."""
     args, csi = R.args, R.csi
-    verify = R.world > 1 and not args.no_verify
+    verify = R.world > 1 and args.full and not args.no_verify
     if verify:
         gg = csi.RectilinearGrid(R.gN, x=(0.0, R.gN[0] * 2000.0), y=(0.0, R.gN[1] * 2000.0), topology=(csi.Periodic, csi.Periodic), halo=(4, 4))
         R.whole = R.make_model(gg)
@@ -1005,49 +1049,14 @@ def single_gpu_record(R, verify):
                                         "(every rank runs its own copy at the same time, each on its own GPU)"}
 
 
-def main():
-    args = parse_args()
-    if args.gpus not in PARTITION:
-        raise SystemExit(f"--gpus must be one of {sorted(PARTITION)}")
-    if "WORLD_SIZE" not in os.environ:
-        if args.gpus > 1 or args.print_launch:
-            # the parent: nothing below this line has touched HIP (no torch.cuda call, no library load)
-            sys.exit(run_parent(args, sys.argv[1:]))
-    elif int(os.environ["WORLD_SIZE"]) != args.gpus:
-        raise SystemExit(f"bench.py: --gpus {args.gpus} but WORLD_SIZE = {os.environ['WORLD_SIZE']}: start N ranks with --gpus N "
-                         f"(python -m torch.distributed.run --nproc-per-node N bench.py --gpus N), or run `python bench.py --gpus N` alone")
-    if args.self_test_launch:
-        return self_test_launch()
-
-    R = Rank(args)
-    csi, np, torch = R.csi, R.np, R.torch
-    world, rank, tiled, dt = R.world, R.rank, R.tiled, R.dt
-    Rx, Ry, nx_l, ny_l = R.Rx, R.Ry, R.nx_l, R.ny_l
-    R.tg, R.f, R.model, args.halo = R.build(args.transport)
-
-    # ---- warm-up, the N > 1 bitwise check and the peer tier ladder; then the headline region --------------------------------------------
-    verify, bitwise, ladder, transport_note = warm_up_and_verify(R)
-    R.barrier()
-    # RCCL prints its version banner through C stdio at communicator creation; flush it now so that the JSON line
-    # below is the last thing this process writes
-    ctypes.CDLL(None).fflush(None)
-    elapsed = R.timed(args.steps, stats=True)
-    # the clock / power sampler reads sysfs from a Python thread: it runs over a REPETITION of the timed loop right behind it, so that
-    # the headline region holds the launch loop alone, as in rounds 1-4
-    with ClockSampler(R.local_rank) as clock:
-        R.timed(args.steps)
-
-    model = R.model
-    value = R.rate(elapsed)
-    subcycle_ms = model.ctx.last_subcycle_ms()            # HIP events on the launch stream, last step
-    path = model.ctx.last_path()
-    path["halo_transport"] = model.ctx.halo_transport() if tiled else "none"
-    if transport_note:
-        path["halo_transport_note"] = transport_note
-    if tiled and path["halo_transport"] == "peer":
-        path["peer_tier"] = model.ctx.peer_tier()
-    if ladder:
-        path["peer_tier_ladder"] = ladder          # which tiers were tried before the timed region, and what each check said
+def full_records(R, out, path, clock, verify, bitwise, transport_note):
+    """--full: everything the headline figure does not need, measured after it on the same process -- the result check, the roofline of
+    the dominant kernel, whole RK3 steps, the other one-GPU configurations, at N > 1 the other transports and decomposition, tier 0 and
+    the one-GPU rate of the same grid, and the CPU baseline -- added to the result line `out`."""
+    args, csi, np, torch = R.args, R.csi, R.np, R.torch
+    world, rank, tiled, dt, model = R.world, R.rank, R.tiled, R.dt, R.model
+    nx_l, ny_l, Rx = R.nx_l, R.ny_l, R.Rx
+    value = out["value"]
     chk = result_check(R)
 
     # ---- outside the timed region: the roofline of the dominant kernel, whole model steps, the other configurations ----------------------
@@ -1074,32 +1083,11 @@ def main():
     rccl16, k1 = other_transports(R, path)
     second = second_partition(R, verify, transport_note)
     tier0 = tier0_record(R, path, verify)
-    rccl_ranks = R.model.ctx.comm_count()
-    if world > 1 and rccl_ranks != world:
-        raise SystemExit(f"bench.py: {world} ranks but the library's RCCL communicator has {rccl_ranks}")
     single = single_gpu_record(R, verify)
-
-    out = {
-        "metric": "EVP sub-cycle cell-updates/s", "value": value, "unit": "cell-updates/s",
-        "n_gpus": world, "steps": args.steps, "warmup": args.warmup, "ms_per_step": 1e3 * elapsed / args.steps,
-        "higher_is_better": True, "scaling": args.scaling, "vs_baseline": None, "dtype": "f64", "data": "synthetic",
-        "config": {"workload": f"evp_subcycle_fplane_periodic_{nx_l * Rx}x{ny_l * Ry}_as_{Rx}x{Ry}_tiles_of_{nx_l}x{ny_l}"
-                               f"_{args.substeps}substeps",
-                   "global_grid": [nx_l * Rx, ny_l * Ry], "tile": [nx_l, ny_l], "partition": [Rx, Ry],
-                   "substeps": args.substeps, "mode": args.mode,
-                   "halo": args.halo,
-                   "halo_exchange": "none (one tile)" if not tiled
-                   else ("peer-direct halo writes over xGMI (IPC-mapped neighbour arrays, per-tile flags) inside every launch; "
-                         "one RCCL exchange of u, v, sigma per sub-cycle" if path["halo_transport"] == "peer"
-                         else f"RCCL send/recv of u, v, sigma: width {2 * path['exchange_interval']} every {path['exchange_interval']} sub-steps "
-                              f"({path['exchanges']} exchanges per step)")},
-        "model_days_per_hr": model_days_per_hr,
-        "model_days_per_hr_config": "full RK3 time_step! (3 stages x [WENO7 advection of h, aice + sub-cycle + tracer update]), dt = 120 s",
-        "subcycle_ms_hip_events": subcycle_ms,
-        "path": path,
-        "result_check": chk,
-        "roofline": roof,
-    }
+    out["model_days_per_hr"] = model_days_per_hr
+    out["model_days_per_hr_config"] = "full RK3 time_step! (3 stages x [WENO7 advection of h, aice + sub-cycle + tracer update]), dt = 120 s"
+    out["result_check"] = chk
+    out["roofline"] = roof
     if advection is not None:
         out["advection"] = advection
     if config3 is not None:
@@ -1110,12 +1098,7 @@ def main():
         out["exchange_every_substep"] = k1
     if rccl16 is not None:
         out["rccl_exchange"] = rccl16
-    if R.rehearsal:
-        out["rehearsal_on_one_gpu"] = True
-        out["rehearsal_note"] = (f"{world} ranks are PROCESSES sharing GPU 0 (host-channel group: shared memory + HIP IPC, gloo): a rehearsal of the "
-                                 "N > 1 path, NOT a scaling measurement -- value, ms_per_step and parallel_efficiency are those of a shared device")
     if world > 1:
-        out["rccl_ranks"] = rccl_ranks
         out["single_gpu"] = single
         out["tiled_equals_untiled_bitwise"] = bitwise
         if single is not None:
@@ -1141,6 +1124,84 @@ def main():
                                  "(partition_2x4), `--partition 2x4` makes it the headline") if Rx == 1 and world > 1 else None
     if rank == 0 and not args.no_cpu_baseline and world == 1:
         out["cpu_baseline"] = cpu_baseline()
+
+
+def main():
+    args = parse_args()
+    if args.gpus not in PARTITION:
+        raise SystemExit(f"--gpus must be one of {sorted(PARTITION)}")
+    if "WORLD_SIZE" not in os.environ:
+        if args.gpus > 1 or args.print_launch:
+            # the parent: nothing below this line has touched HIP (no torch.cuda call, no library load)
+            sys.exit(run_parent(args, sys.argv[1:]))
+    elif int(os.environ["WORLD_SIZE"]) != args.gpus:
+        raise SystemExit(f"bench.py: --gpus {args.gpus} but WORLD_SIZE = {os.environ['WORLD_SIZE']}: start N ranks with --gpus N "
+                         f"(python -m torch.distributed.run --nproc-per-node N bench.py --gpus N), or run `python bench.py --gpus N` alone")
+    if args.self_test_launch:
+        return self_test_launch()
+
+    R = Rank(args)
+    world, rank, tiled = R.world, R.rank, R.tiled
+    Rx, Ry, nx_l, ny_l = R.Rx, R.Ry, R.nx_l, R.ny_l
+    R.tg, R.f, R.model, args.halo = R.build(args.transport)
+
+    # ---- warm-up, the N > 1 bitwise check and the peer tier ladder; then the headline region --------------------------------------------
+    verify, bitwise, ladder, transport_note = warm_up_and_verify(R)
+    R.barrier()
+    # RCCL prints its version banner through C stdio at communicator creation; flush it now so that the JSON line
+    # below is the last thing this process writes
+    ctypes.CDLL(None).fflush(None)
+    elapsed = R.timed(args.steps, stats=True)
+    if args.dump_outputs:
+        dump_outputs(R, args.dump_outputs)                 # the state of the last timed step, before anything else runs on the model
+    clock = None
+    if args.full:
+        # the clock / power sampler reads sysfs from a Python thread: it runs over a REPETITION of the timed loop right behind it, so that
+        # the headline region holds the launch loop alone, as in rounds 1-4
+        with ClockSampler(R.local_rank) as clock:
+            R.timed(args.steps)
+
+    model = R.model
+    value = R.rate(elapsed)
+    subcycle_ms = model.ctx.last_subcycle_ms()            # HIP events on the launch stream, last step
+    path = model.ctx.last_path()
+    path["halo_transport"] = model.ctx.halo_transport() if tiled else "none"
+    if transport_note:
+        path["halo_transport_note"] = transport_note
+    if tiled and path["halo_transport"] == "peer":
+        path["peer_tier"] = model.ctx.peer_tier()
+    if ladder:
+        path["peer_tier_ladder"] = ladder          # which tiers were tried before the timed region, and what each check said
+    rccl_ranks = R.model.ctx.comm_count()
+    if world > 1 and rccl_ranks != world:
+        raise SystemExit(f"bench.py: {world} ranks but the library's RCCL communicator has {rccl_ranks}")
+
+    out = {
+        "metric": "EVP sub-cycle cell-updates/s", "value": value, "unit": "cell-updates/s",
+        "n_gpus": world, "steps": args.steps, "warmup": args.warmup, "ms_per_step": 1e3 * elapsed / args.steps,
+        "higher_is_better": True, "scaling": args.scaling, "vs_baseline": None, "dtype": "f64", "data": "synthetic",
+        "config": {"workload": f"evp_subcycle_fplane_periodic_{nx_l * Rx}x{ny_l * Ry}_as_{Rx}x{Ry}_tiles_of_{nx_l}x{ny_l}"
+                               f"_{args.substeps}substeps",
+                   "global_grid": [nx_l * Rx, ny_l * Ry], "tile": [nx_l, ny_l], "partition": [Rx, Ry],
+                   "substeps": args.substeps, "mode": args.mode,
+                   "halo": args.halo,
+                   "halo_exchange": "none (one tile)" if not tiled
+                   else ("peer-direct halo writes over xGMI (IPC-mapped neighbour arrays, per-tile flags) inside every launch; "
+                         "one RCCL exchange of u, v, sigma per sub-cycle" if path["halo_transport"] == "peer"
+                         else f"RCCL send/recv of u, v, sigma: width {2 * path['exchange_interval']} every {path['exchange_interval']} sub-steps "
+                              f"({path['exchanges']} exchanges per step)")},
+        "subcycle_ms_hip_events": subcycle_ms,
+        "path": path,
+        "full": bool(args.full),
+    }
+    if R.rehearsal:
+        out["rehearsal_on_one_gpu"] = True
+        out["rehearsal_note"] = (f"{world} ranks are PROCESSES sharing GPU 0 (host-channel group: shared memory + HIP IPC, gloo): a rehearsal of the "
+                                 "N > 1 path, NOT a scaling measurement -- value, ms_per_step and parallel_efficiency are those of a shared device")
+    if world > 1:
+        out["rccl_ranks"] = rccl_ranks
+    if args.full:
+        full_records(R, out, path, clock, verify, bitwise, transport_note)
     model = None                                   # contexts (and their RCCL communicators) go before the line is printed
     R.model = R.whole = None
     import gc

@@ -5,7 +5,7 @@ for round in 1 2; do
   for spec in "$@"; do
     label=${spec%%:*}; envs=${spec#*:}
     ( for e in $envs; do export $e; done
-      timeout 120 python bench.py --steps 10 --warmup 3 --no-cpu-baseline --no-full-step --tile $TILE 2>/dev/null | python -c "
+      timeout 120 python bench.py --full --steps 10 --warmup 3 --no-cpu-baseline --no-full-step --tile $TILE 2>/dev/null | python -c "
 import json,sys
 d=json.loads(sys.stdin.readlines()[-1]); print('$label', round(d['value']/1e9,2), round(d['roofline']['avg_launch_ms']*1e3,1))" >> gpurun_out/${TAG}.log )
   done

@@ -12,7 +12,7 @@ sample() {
 }
 echo "idle: $(sample)"
 if [ "$1" = "--cmd" ]; then shift; "$@" > /tmp/cw_cmd.txt 2>&1 &
-else python bench.py --steps ${STEPS:-1500} --warmup 3 --no-cpu-baseline --no-full-step --no-unfused "$@" > /tmp/cw_bench.json 2>/dev/null &
+else python bench.py --full --steps ${STEPS:-1500} --warmup 3 --no-cpu-baseline --no-full-step --no-unfused "$@" > /tmp/cw_bench.json 2>/dev/null &
 fi
 pid=$!
 for i in $(seq 1 200); do

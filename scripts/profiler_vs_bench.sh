@@ -18,7 +18,7 @@ sample() {
 watch() {   # $1: pid, $2: file
   while kill -0 $1 2>/dev/null; do sample >> $2; sleep 0.1; done
 }
-ARGS="$R/bench.py --steps 150 --warmup 5 --no-cpu-baseline --no-full-step --no-unfused --no-structure"
+ARGS="$R/bench.py --full --steps 150 --warmup 5 --no-cpu-baseline --no-full-step --no-unfused --no-structure"
 cd /tmp && export TMPDIR=/tmp
 sample > $OUT/idle.txt
 for rep in 1 2; do
@@ -28,7 +28,7 @@ for rep in 1 2; do
   pid=$!; watch $pid $OUT/traced$rep.clock; wait $pid
 done
 # ... and the SHORT command round 5's profile passes used (3 steps in all: 20 ms of GPU work from an idle chip), plain and traced
-SHORT="$R/bench.py --steps 2 --warmup 1 --no-cpu-baseline --no-full-step --no-unfused --no-structure"
+SHORT="$R/bench.py --full --steps 2 --warmup 1 --no-cpu-baseline --no-full-step --no-unfused --no-structure"
 for rep in 1 2 3; do
   python3 $SHORT > $OUT/short_plain$rep.json 2> /dev/null
   rocprofv3 --kernel-trace --output-format csv -d $OUT/short_trace$rep -- python3 $SHORT > $OUT/short_traced$rep.json 2> /dev/null

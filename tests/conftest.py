@@ -7,7 +7,13 @@ import pytest
 # each other's flags (the peer halo transport).  HIP maps streams onto GPU_MAX_HW_QUEUES (default 4) hardware queues and two
 # streams that share one run their kernels in submission order -- a waiting kernel in front of the one it waits for would sit
 # there until its 3 s timeout.  Ask for enough queues before the runtime initialises (one process per GPU never needs this).
-os.environ.setdefault("GPU_MAX_HW_QUEUES", "16")
+# An environment that already sets a smaller value (4, HIP's default, is common) is raised too: the 8-tile groups need more than 8.
+try:
+    _queues = int(os.environ.get("GPU_MAX_HW_QUEUES", "0"))
+except ValueError:
+    _queues = 0
+if _queues < 16:
+    os.environ["GPU_MAX_HW_QUEUES"] = "16"
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 for p in (ROOT, os.path.join(ROOT, "oracle"), os.path.dirname(os.path.abspath(__file__))):

@@ -54,3 +54,51 @@ def test_parent_starts_ranks_and_relays_rank0_line():
     assert len(lines) == 1                                         # exactly ONE line on stdout
     out = json.loads(lines[0])
     assert out["n_gpus"] == 2 and out["self_test"] and out["launched_by_parent"]
+
+
+def test_plain_run_options():
+    """--full is off by default, --steps sets the timed steps, --dump-outputs takes a directory; no timed steps is refused."""
+    sys.path.insert(0, ROOT)
+    import bench
+    a = bench.parse_args(["--steps", "7", "--warmup", "2"])
+    assert a.steps == 7 and a.warmup == 2 and a.full is False and a.dump_outputs == ""
+    a = bench.parse_args(["--full", "--dump-outputs", "some/dir"])
+    assert a.full is True and a.dump_outputs == "some/dir"
+    with pytest.raises(SystemExit):
+        bench.parse_args(["--steps", "0"])
+
+
+def test_dump_outputs_writes_fixed_samples_of_large_fields(tmp_path):
+    """A 2048^2 tile (the headline grid) is larger than a dump may hold in full: every field is written at the same seeded positions,
+    the same on every call, with those positions beside them; 64 MB at most in all.  A small field is written whole."""
+    sys.path.insert(0, ROOT)
+    import types
+    import numpy as np
+    import bench
+
+    def fake(n, rank=0):
+        rng = np.random.default_rng(5)
+        mk = lambda: types.SimpleNamespace(interior_numpy=(lambda a=rng.standard_normal((n, n)): a))
+        aux = types.SimpleNamespace(s11=mk(), s22=mk(), s12=mk())
+        model = types.SimpleNamespace(synchronize=lambda: None, velocities=types.SimpleNamespace(u=mk(), v=mk()),
+                                      dynamics=types.SimpleNamespace(auxiliaries=types.SimpleNamespace(fields=aux)))
+        return types.SimpleNamespace(rank=rank, np=np, model=model, tg=types.SimpleNamespace(Nx=n, Ny=n), SIG=bench.Rank.SIG)
+
+    R = fake(2048)
+    for d in ("a", "b"):
+        bench.dump_outputs(R, str(tmp_path / d))
+    files = sorted(p.name for p in (tmp_path / "a").iterdir())
+    assert files == ["s11.npy", "s12.npy", "s22.npy", "sample_index.npy", "u.npy", "v.npy"]
+    assert sum(p.stat().st_size for p in (tmp_path / "a").iterdir()) <= 64 << 20
+    idx = np.load(tmp_path / "a" / "sample_index.npy")
+    assert idx.dtype == np.float64 and idx.size == bench.DUMP_MAX_VALUES and np.all(np.diff(idx) > 0)
+    u = R.model.velocities.u.interior_numpy()
+    assert np.array_equal(np.load(tmp_path / "a" / "u.npy"), u.reshape(-1)[idx.astype(np.int64)])
+    for f in files:
+        assert np.array_equal(np.load(tmp_path / "a" / f), np.load(tmp_path / "b" / f)), f
+    small = fake(64)
+    bench.dump_outputs(small, str(tmp_path / "c"))
+    assert not (tmp_path / "c" / "sample_index.npy").exists()
+    assert np.array_equal(np.load(tmp_path / "c" / "v.npy"), small.model.velocities.v.interior_numpy())
+    bench.dump_outputs(fake(64, rank=1), str(tmp_path / "d"))
+    assert not (tmp_path / "d").exists()                           # rank 0 alone writes

@@ -20,7 +20,7 @@ def _line(*extra):
 
 
 def test_single_gpu_line_keeps_the_contract():
-    d, lines = _line()
+    d, lines = _line("--full")
     assert lines[-1].lstrip().startswith("{") and sum(1 for ln in lines if ln.lstrip().startswith("{")) == 1      # ONE JSON line, the last thing printed
     assert d["metric"] == "EVP sub-cycle cell-updates/s" and d["unit"] == "cell-updates/s" and d["higher_is_better"] is True
     assert d["n_gpus"] == 1 and d["steps"] == 3 and d["warmup"] == 1 and d["dtype"] == "f64" and d["data"] == "synthetic"
@@ -47,6 +47,33 @@ def test_single_gpu_line_keeps_the_contract():
 
 
 def test_line_without_the_optional_legs():
-    d, _ = _line("--no-cpu-baseline", "--no-full-step", "--no-unfused")
+    d, _ = _line("--full", "--no-cpu-baseline", "--no-full-step", "--no-unfused")
     assert "roofline" in d and d["value"] > 0
     assert not d.get("cpu_baseline") and "unfused" not in d["roofline"]
+
+
+def test_plain_line_is_the_headline_alone_and_dumps_what_the_timed_steps_computed(tmp_path):
+    """Without --full the run sets up, warms up, times --steps steps and prints the line; --dump-outputs writes the fields the last timed
+    step left (512^2: whole fields, float64), and a second run with the same arguments writes the same arrays bit for bit."""
+    import numpy as np
+    runs = []
+    for k in range(2):
+        out = tmp_path / f"run{k}"
+        d, lines = _line("--steps", "4", "--dump-outputs", str(out))
+        assert sum(1 for ln in lines if ln.lstrip().startswith("{")) == 1
+        assert d["metric"] == "EVP sub-cycle cell-updates/s" and d["unit"] == "cell-updates/s" and d["higher_is_better"] is True
+        assert d["steps"] == 4 and d["warmup"] == 1 and d["dtype"] == "f64" and d["full"] is False
+        assert abs(d["value"] - 512 * 512 * 24 * 4 / (4 * d["ms_per_step"] * 1e-3)) <= 1e-6 * d["value"]
+        for key in ("roofline", "result_check", "cpu_baseline", "model_days_per_hr", "advection", "structure", "config3_1024"):
+            assert key not in d, key
+        assert d["path"]["level"] == 2 and d["path"]["halo_transport"] == "none", d["path"]
+        got = {p.stem: np.load(p) for p in out.glob("*.npy")}
+        assert sorted(got) == ["s11", "s12", "s22", "u", "v"]
+        assert sum(p.stat().st_size for p in out.glob("*.npy")) <= 64 << 20
+        for name, a in got.items():
+            assert a.dtype == np.float64 and a.shape == (512, 512) and np.isfinite(a).all(), name
+        # what the result check of --full asks of the state the timed steps leave
+        assert 0 < np.abs(got["u"]).max() < 10.0 and (got["u"] != 0).mean() > 0.5 and np.abs(got["s11"]).max() > 0
+        runs.append(got)
+    for name in runs[0]:
+        assert np.array_equal(runs[0][name], runs[1][name]), name

@@ -116,7 +116,7 @@ def test_bench_rehearsal_of_the_multi_rank_path_on_one_gpu(n, partition):
     import sys
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
     cmd = [sys.executable, os.path.join(root, "bench.py"), "--gpus", str(n), "--rehearse-on-one-gpu", "--size", "512", "--substeps", "24",
-           "--steps", "2", "--warmup", "1", "--no-full-step"] + (["--partition", partition] if partition else [])
+           "--steps", "2", "--warmup", "1", "--no-full-step", "--full"] + (["--partition", partition] if partition else [])
     p = subprocess.run(cmd, stdout=subprocess.PIPE, stderr=subprocess.PIPE, text=True, timeout=900, cwd=root)
     assert p.returncode == 0, (p.returncode, p.stderr[-3000:])
     line = [ln for ln in p.stdout.splitlines() if ln.startswith("{") and '"metric"' in ln][-1]
@@ -134,3 +134,24 @@ def test_bench_rehearsal_of_the_multi_rank_path_on_one_gpu(n, partition):
     assert d["roofline"]["launches_x_avg_ms"] <= d["ms_per_step"] * 1.0001, (d["roofline"]["launches_x_avg_ms"], d["ms_per_step"])
     assert d["config"]["partition"] == ([int(t) for t in partition.split("x")] if partition else [1, n])
     assert d["single_gpu"]["value"] > 0 and d["parallel_efficiency"] > 0 and d["value"] > 0
+
+
+def test_bench_rehearsal_plain_line_is_the_headline_alone(tmp_path):
+    """bench.py --gpus 2 --rehearse-on-one-gpu without --full: the ranks set up the peer transport, warm up, time the steps and rank 0
+    prints the line (and writes its tile's fields with --dump-outputs) -- no bitwise check, no other transports, no one-GPU rate."""
+    import json
+    import subprocess
+    import sys
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    cmd = [sys.executable, os.path.join(root, "bench.py"), "--gpus", "2", "--rehearse-on-one-gpu", "--size", "512", "--substeps", "24",
+           "--steps", "2", "--warmup", "1", "--dump-outputs", str(tmp_path)]
+    p = subprocess.run(cmd, stdout=subprocess.PIPE, stderr=subprocess.PIPE, text=True, timeout=900, cwd=root)
+    assert p.returncode == 0, (p.returncode, p.stderr[-3000:])
+    d = json.loads([ln for ln in p.stdout.splitlines() if ln.startswith("{") and '"metric"' in ln][-1])
+    assert d["n_gpus"] == 2 and d["rehearsal_on_one_gpu"] is True and d["rccl_ranks"] == 2 and d["full"] is False
+    assert d["value"] > 0 and abs(d["value"] - 512 * 512 * 24 / (d["ms_per_step"] * 1e-3)) <= 1e-6 * d["value"]
+    assert d["path"]["halo_transport"] == "peer" and d["path"]["peer_tier"] == 1, d["path"]
+    for key in ("roofline", "tiled_equals_untiled_bitwise", "single_gpu", "peer_tier0", "partition_2x1"):
+        assert key not in d, key
+    u = np.load(tmp_path / "u.npy")
+    assert u.dtype == np.float64 and u.shape == (256, 512) and np.isfinite(u).all() and np.abs(u).max() > 0
