@@ -7,14 +7,15 @@ contains a dot, so import it through the repo-root shim: `import climaseaice_jl_
 """
 from . import _lib
 from ._lib import Context, CsiError, LocalGroup, plan_exchange, plan_ranges
-from .dynamics import (Auxiliaries, BetaPlane, PointwiseCoriolis, ElastoViscoPlasticRheology, FPlane, IceStrength, ReplacementPressure,
-                       SeaIceMomentumEquation, SemiImplicitStress, SplitExplicitSolver, StressBalanceFreeDrift)
+from .dynamics import (Auxiliaries, BetaPlane, PointwiseCoriolis, ElastoViscoPlasticRheology, ExplicitSolver, FPlane, IceStrength,
+                       ReplacementPressure, SeaIceMomentumEquation, SemiImplicitStress, SplitExplicitSolver, StressBalanceFreeDrift,
+                       ViscousRheology)
 from .fields import CenterField, CornerField, Field, XFaceField, YFaceField
 from .grids import (Bounded, Center, Face, Flat, FullyConnected, LatitudeLongitudeGrid, LeftConnected,
                     OrthogonalCurvilinearGrid, Periodic, LeftConnectedRightFolded, RightFolded, fold_north,
                     RectilinearGrid, RightConnected, TileGrid, TripolarGrid)
 from .model import (FieldBoundaryConditions, FluxBoundaryCondition, ImmersedBoundaryCondition, MeltingConstrainedFluxBalance, ValueBoundaryCondition, PrescribedTemperature, SeaIceModel, SlabThermodynamics, SnowSlabThermodynamics,
-                    snow_slab_thermodynamics, UpwindBiased, WENO, set_, time_step, time_step_momentum, update_state,
+                    snow_slab_thermodynamics, UpwindBiased, WENO, set_, time_step, time_step_momentum, compute_momentum_tendencies, update_state,
                     prognostic_state, restore_prognostic_state)
 
 __all__ = [n for n in dir() if not n.startswith("_")]

@@ -135,6 +135,7 @@ int32_t csi_context_destroy(csi_context* c) {
     for (int k = 0; k < 2; ++k) if (c->fbar[k]) hipFree(c->fbar[k]);
     for (int k = 0; k < 2; ++k) if (c->fbar_top[k]) hipFree(c->fbar_top[k]);
     for (int k = 0; k < 2; ++k) if (c->fd[k]) hipFree(c->fd[k]);
+    for (int k = 0; k < 2; ++k) if (c->vis_alt[k]) hipFree(c->vis_alt[k]);
     for (int k = 0; k < 2; ++k) if (c->xd[k]) hipFree(c->xd[k]);
     if (c->dev_tables) hipFree(c->dev_tables);
     if (c->sendbuf) hipFree(c->sendbuf);
@@ -475,10 +476,10 @@ int32_t csi_evp_finalize(csi_context* c) {
 
 int32_t csi_time_step_momentum(csi_context* c, double dt, int32_t substeps, int32_t rk_reset) {
     if (!c) return CSI_ERR_INVALID_ARGUMENT;
-    int32_t rc = need_evp(c);
+    int32_t rc = need_momentum(c);          // (EVP + split-explicit: need_evp)
     if (rc) return rc;
     if (substeps < 0) return fail(c, CSI_ERR_INVALID_ARGUMENT, "substeps >= 0 required");
-    rc = do_time_step_momentum(c, dt, substeps, rk_reset);
+    rc = do_momentum(c, dt, substeps, rk_reset);       // (EVP + split-explicit: do_time_step_momentum)
     return rc ? rc : peer_check(c);
 }
 
@@ -537,11 +538,12 @@ int32_t csi_time_step_fe(csi_context* c, double dt, int32_t substeps, int32_t sc
     // dynamics = nothing (csi_evp_params_set never called): prescribed velocities, time_step_momentum! is a no-op
     // (SeaIceDynamics.jl:40) -- the advection-only models of examples/ice_advected_by_anticyclone.jl's family
     const bool dynamics = c->evp_set;
-    int32_t rc = dynamics ? need_evp(c) : need(c, {CSI_F_H, CSI_F_A});
+    int32_t rc = dynamics ? need_momentum(c) : need(c, {CSI_F_H, CSI_F_A});
     if (rc) return rc;
     if (first_iteration && (rc = do_update_state(c))) return rc;          // sea_ice_fe_step.jl:16
-    if ((rc = do_tendencies_or_zero(c, scheme))) return rc;               // :19
-    if (dynamics && (rc = do_time_step_momentum(c, dt, substeps, 0))) return rc;      // :22
+    if ((rc = do_tendencies_or_zero(c, scheme))) return rc;               // :19 (compute_tracer_tendencies!)
+    if (dynamics && (rc = do_momentum_tendencies(c, dt))) return rc;      // :19 (compute_momentum_tendencies!: ExplicitSolver only)
+    if (dynamics && (rc = do_momentum(c, dt, substeps, 0))) return rc;    // :22
     // without a mask and without a thermodynamic step the tracer update's stores write the halo images themselves
     const bool fused_fill = !c->g.has_mask && !c->slab_set;
     if ((rc = do_tracer_step(c, dt, 0, fused_fill))) return rc;           // :25
@@ -603,7 +605,7 @@ int32_t rk3_advection_only(csi_context* c, double dt, int scheme) {
 int32_t csi_time_step_rk3(csi_context* c, double dt, int32_t substeps, int32_t scheme) {
     if (!c) return CSI_ERR_INVALID_ARGUMENT;
     const bool dynamics = c->evp_set;                                     // see csi_time_step_fe
-    int32_t rc = dynamics ? need_evp(c) : need(c, {CSI_F_H, CSI_F_A});
+    int32_t rc = dynamics ? need_momentum(c) : need(c, {CSI_F_H, CSI_F_A});
     if (rc) return rc;
     if ((rc = dynamics ? need(c, {CSI_F_HM, CSI_F_AM, CSI_F_UM, CSI_F_VM}) : need(c, {CSI_F_HM, CSI_F_AM}))) return rc;
     if (advect_stage_supported(c, scheme)) {
@@ -617,7 +619,8 @@ int32_t csi_time_step_rk3(csi_context* c, double dt, int32_t substeps, int32_t s
     for (int beta = 3; beta >= 1; --beta) {                               // upstream stage loop
         const double dtau = dt / beta;
         if ((rc = do_tendencies_or_zero(c, scheme))) return rc;           // :84
-        if (dynamics && (rc = do_time_step_momentum(c, dtau, substeps, 1))) return rc;   // :87
+        if (dynamics && (rc = do_momentum_tendencies(c, dtau))) return rc;               // :84 (ExplicitSolver only)
+        if (dynamics && (rc = do_momentum(c, dtau, substeps, 1))) return rc;             // :87
         const bool fused_fill = !c->g.has_mask && !c->slab_set;
         if ((rc = do_tracer_step(c, dtau, 1, fused_fill))) return rc;     // :89
         if ((rc = do_thermo(c, dtau))) return rc;                         // :91 thermodynamic_time_step!

@@ -9,6 +9,7 @@
 #include "../../include/csi.h"
 #include "csi_dev.h"
 #include "csi_kernels.h"
+#include "momentum_dev.h"
 #include "csi_hostgroup.h"
 #include "csi_comm.h"
 #include <rccl/rccl.h>
@@ -48,11 +49,12 @@ static const int kLoc[CSI_F_COUNT][2] = {
     {LOC_C, LOC_C},                                                   // MASS_FLUX
     {LOC_C, LOC_C}, {LOC_C, LOC_C}, {LOC_C, LOC_C},                   // HS GHS HSM
     {LOC_C, LOC_C}, {LOC_C, LOC_C}, {LOC_C, LOC_C}, {LOC_C, LOC_C},   // MASS_FLUX_SNOW SNOWFALL_INTERCEPTED TU TUS
-    {LOC_F, LOC_C}, {LOC_C, LOC_F}};                                  // FORCING_U FORCING_V
+    {LOC_F, LOC_C}, {LOC_C, LOC_F},                                   // FORCING_U FORCING_V
+    {LOC_F, LOC_C}, {LOC_C, LOC_F}};                                  // GU GV
 static const char* const kName[CSI_F_COUNT] = {"u", "v", "h", "aice", "sigma11", "sigma22", "sigma12", "un", "vn", "P", "alpha",
                                   "Delta", "zeta_f", "zeta_c", "Gh", "Gaice", "h-", "aice-", "u-", "v-",
                                   "top_u", "top_v", "bottom_u", "bottom_v", "mass_flux",
-                                  "hs", "Ghs", "hs-", "mass_flux_snow", "intercepted_snowfall", "Tu", "Tu_snow", "forcing_u", "forcing_v"};
+                                  "hs", "Ghs", "hs-", "mass_flux_snow", "intercepted_snowfall", "Tu", "Tu_snow", "forcing_u", "forcing_v", "Gu", "Gv"};
 
 extern std::string g_create_error;      // csi_context_create failures (no context to hold the message)
 
@@ -187,6 +189,12 @@ struct csi_context {
     bool snow_set = false;   // layered (snow + ice) step instead of the bare-ice one
     SnowDev snow{};
     int weno_w32 = 0;     // csi_set_weno_weight_dtype: 1 = WENO weights in single precision (upstream's FT2 = Float32, recalled)
+    // csi_rheology_set / csi_momentum_solver_set (csi_momentum.hip): ViscousRheology, ExplicitSolver
+    int rheology = CSI_RHEOLOGY_EVP;
+    double nu = 1000.0;
+    int solver = CSI_SOLVER_SPLIT_EXPLICIT;
+    double* vis_alt[2] = {nullptr, nullptr};     // the viscous sub-cycle's second u / v arrays (ping-pong with the bound ones)
+    size_t vis_alt_elems[2] = {0, 0};
     int fusion = 1;       // 1: use the fused sub-step kernel when the configuration allows it
     int pairing = 1;      // 1: two sub-steps per launch where supported (csi_set_fusion level 2)
     int last_launches = 0, last_substeps = 0, last_used_pairs = 0;   // kernel launches / sub-steps of the last fused sub-cycle
@@ -373,7 +381,13 @@ int32_t run_fused_fold(csi_context* c, const EvpDev& Pfull, const FastCoef& fc, 
 int32_t do_subcycle(csi_context* c, double dt, int substeps, int first);
 int32_t do_finalize(csi_context* c);
 int32_t need_evp(csi_context* c);
+int32_t need_dynamics_common(csi_context* c);
 int32_t do_time_step_momentum(csi_context* c, double dt, int substeps, int rk_reset);
+// csi_momentum.hip: the rheology / solver dispatch (EVP + split-explicit: need_evp / do_time_step_momentum, unchanged)
+int32_t momentum_config_check(csi_context* c);
+int32_t need_momentum(csi_context* c);
+int32_t do_momentum(csi_context* c, double dt, int substeps, int rk_reset);
+int32_t do_momentum_tendencies(csi_context* c, double dt);
 AdvDev adv_dev(const csi_context* c, int scheme, double dt, int from_cache);
 int32_t do_update_state(csi_context* c, bool in_step = false, bool tracers_filled = false);
 int32_t do_tendencies(csi_context* c, int scheme);

@@ -583,10 +583,16 @@ int32_t need_evp(csi_context* c) {
     int32_t rc = need(c, {CSI_F_U, CSI_F_V, CSI_F_H, CSI_F_A, CSI_F_S11, CSI_F_S22, CSI_F_S12, CSI_F_UN, CSI_F_VN,
                           CSI_F_P, CSI_F_ALPHA, CSI_F_DELTA, CSI_F_ZETA_F, CSI_F_ZETA_C});
     if (rc) return rc;
+    return need_dynamics_common(c);
+}
+
+// the checks of a momentum step after its field slots, every rheology and solver (csi_momentum.hip need_dynamics, need_evp)
+int32_t need_dynamics_common(csi_context* c) {
+    int32_t rc;
     if (!c->evp_set) return fail(c, CSI_ERR_NOT_BOUND, "csi_evp_params_set has not been called");
     if ((rc = check_stress_fields(c, CSI_STRESS_TOP))) return rc;
     if ((rc = check_stress_fields(c, CSI_STRESS_BOTTOM))) return rc;
-    if (c->Hx < 2 || c->Hy < 2) return fail(c, CSI_ERR_INVALID_ARGUMENT, "EVP needs halo >= 2");
+    if (c->Hx < 2 || c->Hy < 2) return fail(c, CSI_ERR_INVALID_ARGUMENT, "the momentum step needs halo >= 2");
     if (c->free_drift) {   // stress_balance_free_drift.jl:21-35: exactly one of the two stresses is a SemiImplicitStress
         const bool ts = c->stress[CSI_STRESS_TOP].kind == CSI_STRESS_SEMI_IMPLICIT, bs = c->stress[CSI_STRESS_BOTTOM].kind == CSI_STRESS_SEMI_IMPLICIT;
         if (ts == bs) return fail(c, CSI_ERR_INVALID_ARGUMENT, "StressBalanceFreeDrift needs exactly one SemiImplicitStress (top or bottom)");

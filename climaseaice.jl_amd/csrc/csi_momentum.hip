@@ -1,0 +1,244 @@
+// csi_momentum.hip -- the rheology / momentum-solver dispatch: ViscousRheology's split-explicit sub-cycle and the ExplicitSolver
+// (include/csi.h csi_rheology_set, csi_momentum_solver_set; kernels in momentum_viscous.hip / momentum_explicit.hip).  EVP with the
+// split-explicit solver goes on through need_evp / do_time_step_momentum (csi_launch.hip), untouched.  See csi_ctx.h.
+#include "csi_ctx.h"
+
+namespace csi_host {
+
+static const char* rheology_name(int k) { return k == CSI_RHEOLOGY_VISCOUS ? "ViscousRheology" : "ElastoViscoPlasticRheology"; }
+static const char* solver_name(int k) { return k == CSI_SOLVER_EXPLICIT ? "ExplicitSolver" : "SplitExplicitSolver"; }
+
+// Tiles and north folds run EVP with the split-explicit solver only (the reference's distributed and tripolar tests use nothing else)
+int32_t momentum_config_check(csi_context* c) {
+    if (c->rheology == CSI_RHEOLOGY_EVP && c->solver == CSI_SOLVER_SPLIT_EXPLICIT) return CSI_OK;
+    if (!c->grid_set) return CSI_OK;
+    const bool fold = c->g.yhi == SIDE_FOLD;
+    if (is_tiled(c) || c->tile.set || fold) {
+        const char* what = c->rheology != CSI_RHEOLOGY_EVP ? rheology_name(c->rheology) : solver_name(c->solver);
+        return fail(c, CSI_ERR_UNSUPPORTED, std::string(what) + " is not supported on " + (fold ? "north-fold (tripolar)" : "tiled") +
+                                                " grids: only ElastoViscoPlasticRheology with the SplitExplicitSolver runs there");
+    }
+    return CSI_OK;
+}
+
+// need_evp without the ten auxiliary slots: what every rheology needs (the checks after the slots are need_dynamics_common's, shared
+// with need_evp)
+static int32_t need_dynamics(csi_context* c) {
+    int32_t rc = need(c, {CSI_F_U, CSI_F_V, CSI_F_H, CSI_F_A});
+    if (rc) return rc;
+    if (c->evp_set && (rc = momentum_config_check(c))) return rc;
+    return need_dynamics_common(c);
+}
+
+int32_t need_momentum(csi_context* c) {
+    if (c->rheology == CSI_RHEOLOGY_EVP && c->solver == CSI_SOLVER_SPLIT_EXPLICIT) return need_evp(c);
+    int32_t rc = need_dynamics(c);
+    if (rc) return rc;
+    // the explicit step with EVP reads the stored sigma, u^n and alpha: the EVP slots
+    if (c->rheology == CSI_RHEOLOGY_EVP && (rc = need_evp(c))) return rc;
+    if (c->solver == CSI_SOLVER_EXPLICIT && (rc = need(c, {CSI_F_GU, CSI_F_GV}))) return rc;
+    if ((c->f[CSI_F_FORCING_U].p != nullptr) != (c->f[CSI_F_FORCING_V].p != nullptr))
+        return fail(c, CSI_ERR_NOT_BOUND, "model.forcing arrays: bind both CSI_F_FORCING_U and CSI_F_FORCING_V or neither");
+    return CSI_OK;
+}
+
+// StressBalanceFreeDrift: the velocities of marginal ice depend on the forcing only -- once per call into library arrays (as do_subcycle)
+static int32_t free_drift_fields(csi_context* c, double dt) {
+    if (!c->free_drift) return CSI_OK;
+    const int src[2] = {CSI_F_U, CSI_F_V};
+    for (int q = 0; q < 2; ++q) {
+        const size_t n = (size_t)c->f[src[q]].ld * (size_t)c->f[src[q]].nj;
+        if (c->fd_elems[q] != n) {
+            if (c->fd[q]) { HIP_TRY(c, hipStreamSynchronize(c->stream)); hipFree(c->fd[q]); c->fd[q] = nullptr; }
+            HIP_TRY(c, hipMalloc((void**)&c->fd[q], n * sizeof(double)));
+            HIP_TRY(c, hipMemsetAsync(c->fd[q], 0, n * sizeof(double), c->stream));
+            c->fd_elems[q] = n;
+        }
+    }
+    launch_free_drift(evp_dev(c, dt), Range{2 - c->Hx, c->Nx + c->Hx - 1, 2 - c->Hy, c->Ny + c->Hy - 1}, c->stream);
+    HIP_TRY(c, hipGetLastError());
+    return CSI_OK;
+}
+
+// update_external_stress! (split_explicit_momentum_equations.jl:133-134): local halos of the stress / forcing arrays
+static int32_t fill_forcing_halos(csi_context* c) {
+    int32_t rc;
+    for (int id : {CSI_F_TOP_U, CSI_F_TOP_V, CSI_F_BOT_U, CSI_F_BOT_V, CSI_F_FORCING_U, CSI_F_FORCING_V})
+        if (c->f[id].p && (rc = fill_halo(c, id))) return rc;
+    return CSI_OK;
+}
+
+static MomDev mom_dev(const csi_context* c, double dt) {
+    MomDev M{};
+    M.P = evp_dev(c, dt);
+    M.nu = c->nu;
+    M.Gu = ref_of(c, CSI_F_GU);
+    M.Gv = ref_of(c, CSI_F_GV);
+    return M;
+}
+
+// ---- ViscousRheology, split-explicit (split_explicit_momentum_equations.jl:103-195 with Rheologies.jl:42-55) ----------------
+static int32_t viscous_subcycle(csi_context* c, double dt, int substeps, int rk_reset) {
+    int32_t rc;
+    if (rk_reset) {                                         // reset_velocities! :89-93
+        if ((rc = need(c, {CSI_F_UM, CSI_F_VM}))) return rc;
+        if ((rc = copy_parent(c, CSI_F_U, CSI_F_UM))) return rc;
+        if ((rc = copy_parent(c, CSI_F_V, CSI_F_VM))) return rc;
+    }
+    if ((rc = fill_forcing_halos(c))) return rc;           // :133-134 (initialize_rheology!: nothing)
+    {                                                       // :170-171
+        HaloBatch B{};
+        B.f[0] = ref_of(c, CSI_F_U); B.im[0] = image_spec(c, CSI_F_U);
+        B.f[1] = ref_of(c, CSI_F_V); B.im[1] = image_spec(c, CSI_F_V);
+        B.n = 2;
+        launch_fill_halo_batch(B, c->g, c->stream);
+    }
+    if ((rc = free_drift_fields(c, dt))) return rc;
+    // the second array of each component.  A launch rewrites every interior point and the halo images of its stores; what no store
+    // reaches (halos beyond walls, deeper layers of a ValueBoundaryCondition side) must agree in both arrays: copied once, unless every
+    // cell is an image (doubly periodic)
+    const int comp[2] = {CSI_F_U, CSI_F_V};
+    for (int q = 0; q < 2; ++q) {
+        const Bound& b = c->f[comp[q]];
+        const size_t n = (size_t)b.ld * (size_t)b.nj;
+        if (c->vis_alt_elems[q] != n) {
+            if (c->vis_alt[q]) { HIP_TRY(c, hipStreamSynchronize(c->stream)); hipFree(c->vis_alt[q]); c->vis_alt[q] = nullptr; }
+            HIP_TRY(c, hipMalloc((void**)&c->vis_alt[q], n * sizeof(double)));
+            c->vis_alt_elems[q] = n;
+        }
+    }
+    const bool every_cell_imaged = c->g.xlo == SIDE_PERIODIC && c->g.xhi == SIDE_PERIODIC && c->g.ylo == SIDE_PERIODIC && c->g.yhi == SIDE_PERIODIC;
+    if (!every_cell_imaged && substeps > 0) {
+        CopyBatch B{};
+        B.aligned16 = 1;
+        for (int q = 0; q < 2; ++q) {
+            const Bound& b = c->f[comp[q]];
+            B.src[B.count] = b.p; B.dst[B.count] = c->vis_alt[q]; B.n[B.count] = (long)b.ld * b.nj; ++B.count;
+            if ((((uintptr_t)b.p) | ((uintptr_t)c->vis_alt[q])) & 15) B.aligned16 = 0;
+        }
+        launch_copy_batch(B, c->stream);
+    }
+    FRef bound[2], alt[2];
+    for (int q = 0; q < 2; ++q) {
+        bound[q] = ref_of(c, comp[q]);
+        alt[q] = bound[q];
+        alt[q].p = c->vis_alt[q] + (c->Hx - 1) + (int64_t)(c->Hy - 1) * c->f[comp[q]].ld;
+    }
+    MomDev M = mom_dev(c, dt / substeps);                   // Delta tau = Delta t / substeps (Rheologies.jl:48-49)
+    const ImageSpec imu = image_spec(c, CSI_F_U), imv = image_spec(c, CSI_F_V);
+    const Range r = interior_range(c);
+    const int fast = c->mode == CSI_MODE_FAST;
+    int cur[2] = {0, 0};                                    // 0: the bound array holds the component's current values
+    auto step = [&](int q) {
+        M.P.u = cur[0] ? alt[0] : bound[0];
+        M.P.v = cur[1] ? alt[1] : bound[1];
+        M.out = cur[q] ? bound[q] : alt[q];
+        if (q == 0) launch_viscous_ustep(M, r, imu, fast, c->stream);
+        else launch_viscous_vstep(M, r, imv, fast, c->stream);
+        cur[q] ^= 1;
+    };
+    HIP_TRY(c, hipEventRecord(c->ev0, c->stream));
+    for (int s = 1; s <= substeps; ++s) {
+        if (s % 2 == 0) { step(0); step(1); }               // :178-182
+        else { step(1); step(0); }                          // :184-187
+    }
+    HIP_TRY(c, hipEventRecord(c->ev1, c->stream));
+    if (cur[0] | cur[1]) {                                  // one copy back: the components whose result sits in the scratch
+        CopyBatch B{};
+        B.aligned16 = 1;
+        for (int q = 0; q < 2; ++q)
+            if (cur[q]) {
+                const Bound& b = c->f[comp[q]];
+                B.src[B.count] = c->vis_alt[q]; B.dst[B.count] = b.p; B.n[B.count] = (long)b.ld * b.nj; ++B.count;
+                if ((((uintptr_t)b.p) | ((uintptr_t)c->vis_alt[q])) & 15) B.aligned16 = 0;
+            }
+        launch_copy_batch(B, c->stream);
+    }
+    HIP_TRY(c, hipGetLastError());
+    c->timed = true;
+    c->last_fused = 0;
+    c->last_launches = 2 * substeps;
+    c->last_substeps = substeps;
+    c->launches_per_substep = 2;
+    c->last_exchanges = 0;
+    c->last_k = 1;
+    return CSI_OK;                                          // finalize_rheology!: nothing
+}
+
+// ---- ExplicitSolver (explicit_momentum_equations.jl) ---------------------------------------------------------------------------
+int32_t do_momentum_tendencies(csi_context* c, double dt) {
+    if (c->solver != CSI_SOLVER_EXPLICIT) return CSI_OK;     // SplitExplicitSolver: compute_momentum_tendencies! is nothing
+    MomDev M = mom_dev(c, dt);
+    launch_explicit_tendencies(M, interior_range(c), c->rheology == CSI_RHEOLOGY_VISCOUS, c->mode == CSI_MODE_FAST, c->stream);
+    HIP_TRY(c, hipGetLastError());
+    return CSI_OK;
+}
+
+static int32_t explicit_step(csi_context* c, double dt, int rk_reset) {
+    int32_t rc;
+    if (rk_reset && (rc = need(c, {CSI_F_UM, CSI_F_VM}))) return rc;
+    if ((rc = fill_forcing_halos(c))) return rc;
+    if ((rc = free_drift_fields(c, dt))) return rc;
+    MomDev M = mom_dev(c, dt);
+    M.um = rk_reset ? ref_of(c, CSI_F_UM) : M.P.u;          // previous_velocities, :3-5
+    M.vm = rk_reset ? ref_of(c, CSI_F_VM) : M.P.v;
+    const Range r = interior_range(c);
+    const int fast = c->mode == CSI_MODE_FAST;
+    HIP_TRY(c, hipEventRecord(c->ev0, c->stream));
+    M.out = M.P.u;
+    launch_explicit_ustep(M, r, image_spec(c, CSI_F_U), fast, c->stream);     // :31-32
+    M.out = M.P.v;
+    launch_explicit_vstep(M, r, image_spec(c, CSI_F_V), fast, c->stream);     // :34-35
+    HIP_TRY(c, hipEventRecord(c->ev1, c->stream));
+    HIP_TRY(c, hipGetLastError());
+    c->timed = true;
+    c->last_fused = 0;
+    c->last_launches = 2;                                   // (the tendency launch belongs to csi_compute_momentum_tendencies)
+    c->last_substeps = 1;
+    c->launches_per_substep = 2;
+    c->last_exchanges = 0;
+    c->last_k = 1;
+    return CSI_OK;
+}
+
+int32_t do_momentum(csi_context* c, double dt, int substeps, int rk_reset) {
+    if (c->solver == CSI_SOLVER_EXPLICIT) return explicit_step(c, dt, rk_reset);
+    if (c->rheology == CSI_RHEOLOGY_VISCOUS) return viscous_subcycle(c, dt, substeps, rk_reset);
+    return do_time_step_momentum(c, dt, substeps, rk_reset);
+}
+
+}  // namespace csi_host
+
+extern "C" {
+
+int32_t csi_rheology_set(csi_context* c, int32_t kind, double nu) {
+    if (!c) return CSI_ERR_INVALID_ARGUMENT;
+    if (kind != CSI_RHEOLOGY_EVP && kind != CSI_RHEOLOGY_VISCOUS) return fail(c, CSI_ERR_INVALID_ARGUMENT, "unknown rheology kind");
+    if (kind == CSI_RHEOLOGY_VISCOUS && !std::isfinite(nu)) return fail(c, CSI_ERR_INVALID_ARGUMENT, "ViscousRheology: nu must be a finite number");
+    const int old = c->rheology;
+    c->rheology = kind;
+    int32_t rc = momentum_config_check(c);
+    if (rc) { c->rheology = old; return rc; }
+    if (kind == CSI_RHEOLOGY_VISCOUS) c->nu = nu;
+    return CSI_OK;
+}
+
+int32_t csi_momentum_solver_set(csi_context* c, int32_t kind) {
+    if (!c) return CSI_ERR_INVALID_ARGUMENT;
+    if (kind != CSI_SOLVER_SPLIT_EXPLICIT && kind != CSI_SOLVER_EXPLICIT) return fail(c, CSI_ERR_INVALID_ARGUMENT, "unknown momentum solver kind");
+    const int old = c->solver;
+    c->solver = kind;
+    int32_t rc = momentum_config_check(c);
+    if (rc) { c->solver = old; return rc; }
+    return CSI_OK;
+}
+
+int32_t csi_compute_momentum_tendencies(csi_context* c, double dt) {
+    if (!c) return CSI_ERR_INVALID_ARGUMENT;
+    if (c->solver != CSI_SOLVER_EXPLICIT) return CSI_OK;
+    int32_t rc = need_momentum(c);
+    if (rc) return rc;
+    return do_momentum_tendencies(c, dt);
+}
+
+}  // extern "C"

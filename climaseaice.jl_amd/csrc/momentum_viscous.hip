@@ -1,0 +1,83 @@
+// momentum_viscous.hip -- the split-explicit sub-step of ViscousRheology (csi_rheology_set(ctx, CSI_RHEOLOGY_VISCOUS, nu)).
+//
+//   k_visc_ustep   _u_velocity_step!   SeaIceDynamics/split_explicit_momentum_equations.jl:197-229
+//   k_visc_vstep   _v_velocity_step!   :231-264
+// with ViscousRheology's stresses computed inline from the velocities (Rheologies/viscous_rheology.jl:15-22), the sub-step
+// Delta t / substeps and the user forcing alone (Rheologies.jl:42-55).  One launch per component and sub-step; the local halo
+// fill that follows each kernel in the reference (:180-187) is fused into the store (store_with_images).
+//
+// Deliberate departure (include/csi.h): the reference's kernel writes u[i, j] in place while its viscous stencil reads u
+// at the neighbouring points, so its result depends on scheduling.  Here a launch reads the OLD values of its own component (M.P.u /
+// M.P.v) and writes the new ones into another array (M.out): Jacobi within a component, Gauss-Seidel between the two (the second
+// component of a sub-step reads the first one's new values, the order alternating with the parity of the sub-step, :178).
+//
+// STRICT (FAST = false): the reference's operation order, compiled without contraction: bit-for-bit the test-side restatement
+// (tests/momentum_ref.py).  FAST: explicit FMAs, reciprocals of the mass and the metrics; both gather every load of a point first.
+#include "momentum_dev.h"
+
+namespace csi {
+namespace mom {
+
+#define MOM_CELL(r)                                                            \
+    const int i = (r).i0 + (int)(blockIdx.x * blockDim.x + threadIdx.x);       \
+    const int j = (r).j0 + (int)(blockIdx.y * blockDim.y + threadIdx.y);       \
+    if (i > (r).i1 || j > (r).j1) return;
+
+template <bool FAST>
+__global__ void __launch_bounds__(256) k_visc_ustep(MomDev M, Range r, ImageSpec im) {
+    MOM_CELL(r)
+    const EvpDev& P = M.P;
+    UPoint q;
+    gather_u<true>(P, P.u, P.v, i, j, q);
+    const double dtau = P.dt;                                          // Delta t / substeps (host), Rheologies.jl:49
+    double mi, ai;
+    const double G = u_tendency<FAST, true>(P, M.nu, q, i, j, 0.0, mi, ai);
+    double tau_i = implicit_coef<FAST>(P, q.top, q.bot, q.uc, q.v4, mi, ai);
+    tau_i = (mi <= 0) ? 0.0 : tau_i;
+    const double uD = FAST ? fma(dtau, G, q.uc) / fma(dtau, tau_i, 1.0) : (q.uc + dtau * G) / (1 + dtau * tau_i);
+    const double uF = P.free_drift ? q.fd : 0.0;
+    const bool marginal = (mi > MOM_EPS64) & (ai > MOM_EPS64);
+    const bool active_ice = (mi >= P.min_mass) & (ai >= P.min_conc);
+    const double sel = active_ice ? uD : (marginal ? uF : 0.0);
+    const bool peripheral = q.c.inact[3] | q.c.inact[2];               // peripheral_node (f, c, c): cells (i, j), (i - 1, j)
+    store_with_images(M.out, P.g, im, i, j, peripheral ? copysign(0.0, sel) : sel);   // `* active` with a Bool, :228
+}
+
+template <bool FAST>
+__global__ void __launch_bounds__(256) k_visc_vstep(MomDev M, Range r, ImageSpec im) {
+    MOM_CELL(r)
+    const EvpDev& P = M.P;
+    VPoint q;
+    gather_v<true>(P, P.u, P.v, i, j, q);
+    const double dtau = P.dt;
+    double mi, ai;
+    const double G = v_tendency<FAST, true>(P, M.nu, q, i, j, 0.0, mi, ai);
+    double tau_i = implicit_coef<FAST>(P, q.top, q.bot, q.vc, q.u4, mi, ai);
+    tau_i = (mi <= 0) ? 0.0 : tau_i;
+    const double vD = FAST ? fma(dtau, G, q.vc) / fma(dtau, tau_i, 1.0) : (q.vc + dtau * G) / (1 + dtau * tau_i);
+    const double vF = P.free_drift ? q.fd : 0.0;
+    const bool marginal = (mi > MOM_EPS64) & (ai > MOM_EPS64);
+    const bool active_ice = (mi >= P.min_mass) & (ai >= P.min_conc);
+    const double sel = active_ice ? vD : (marginal ? vF : 0.0);
+    const bool peripheral = q.c.inact[4] | q.c.inact[1];               // peripheral_node (c, f, c): cells (i, j), (i, j - 1)
+    store_with_images(M.out, P.g, im, i, j, peripheral ? copysign(0.0, sel) : sel);
+}
+
+}  // namespace mom
+
+static inline dim3 mom_grid(const Range& r, dim3 b) {
+    return dim3((unsigned)((r.i1 - r.i0 + 1 + b.x - 1) / b.x), (unsigned)((r.j1 - r.j0 + 1 + b.y - 1) / b.y), 1);
+}
+
+void launch_viscous_ustep(const MomDev& M, const Range& r, const ImageSpec& im, int fast, hipStream_t s) {
+    const dim3 b(64, 4);
+    if (fast) hipLaunchKernelGGL(mom::k_visc_ustep<true>, mom_grid(r, b), b, 0, s, M, r, im);
+    else hipLaunchKernelGGL(mom::k_visc_ustep<false>, mom_grid(r, b), b, 0, s, M, r, im);
+}
+void launch_viscous_vstep(const MomDev& M, const Range& r, const ImageSpec& im, int fast, hipStream_t s) {
+    const dim3 b(64, 4);
+    if (fast) hipLaunchKernelGGL(mom::k_visc_vstep<true>, mom_grid(r, b), b, 0, s, M, r, im);
+    else hipLaunchKernelGGL(mom::k_visc_vstep<false>, mom_grid(r, b), b, 0, s, M, r, im);
+}
+
+}  // namespace csi

@@ -1,8 +1,10 @@
 """Host-side mirror of the reference's dynamics containers (plain data; no arithmetic here).
 
 ElastoViscoPlasticRheology   Rheologies/elasto_visco_plastic_rheology.jl:14-25,119-137
-Auxiliaries                  :140-173
+ViscousRheology              Rheologies/viscous_rheology.jl:1-10 (a Number nu only)
+Auxiliaries                  :140-173 (EVP); Rheologies.jl:33 (every other rheology: no fields)
 SplitExplicitSolver          SeaIceDynamics/split_explicit_momentum_equations.jl:18-46
+ExplicitSolver               SeaIceDynamics/sea_ice_momentum_equations.jl:14-15
 SemiImplicitStress           SeaIceDynamics/sea_ice_external_stress.jl:84-130
 SeaIceMomentumEquation       SeaIceDynamics/sea_ice_momentum_equations.jl:3-12,67-94
 FPlane, BetaPlane            upstream Oceananigans.Coriolis
@@ -35,6 +37,31 @@ class ElastoViscoPlasticRheology:
     max_relaxation_parameter: float = 300.0
     relaxation_strength: float = math.pi ** 2
     pressure_formulation: object = dc_field(default_factory=ReplacementPressure)
+
+
+class ViscousRheology:
+    """ViscousRheology(nu = 1000.0): stresses nu * delta u computed from the velocities (viscous_rheology.jl:15-22), no
+    auxiliary fields.  nu must be a Number: a Field- or function-valued nu (whose face interpolation lives in Oceananigans) is
+    not on the accelerated path."""
+
+    def __init__(self, nu=1000.0):
+        if isinstance(nu, bool) or not isinstance(nu, (int, float, np.integer, np.floating)):
+            raise NotImplementedError(f"ViscousRheology: nu must be a Number; a {type(nu).__name__}-valued nu (Field or function) "
+                                      "is not supported on the accelerated path")
+        self.nu = float(nu)
+        if not math.isfinite(self.nu):
+            raise ValueError("ViscousRheology: nu must be finite")
+
+    def __repr__(self):
+        return f"ViscousRheology(nu={self.nu!r})"
+
+
+class ExplicitSolver:
+    """ExplicitSolver(): G^n from compute_momentum_tendencies!, then one explicit step u = (u^- + dt G) / (1 + dt tau_i)
+    (explicit_momentum_equations.jl)."""
+
+    def __repr__(self):
+        return "ExplicitSolver()"
 
 
 @dataclass
@@ -105,7 +132,10 @@ class SemiImplicitStress:
 
 
 def Auxiliaries(rheology, grid, device=None):
-    """The ten auxiliary fields of the EVP rheology; alpha pre-filled with alpha+ (evp:147-161)."""
+    """The ten auxiliary fields of the EVP rheology; alpha pre-filled with alpha+ (evp:147-161).  Any other rheology: no fields
+    (Rheologies.jl:33)."""
+    if not isinstance(rheology, ElastoViscoPlasticRheology):
+        return SimpleNamespace(fields=SimpleNamespace())
     f = SimpleNamespace(
         s11=CenterField(grid, device, "sigma11"), s22=CenterField(grid, device, "sigma22"),
         s12=CornerField(grid, device, "sigma12"),
@@ -133,9 +163,11 @@ class SeaIceMomentumEquation:
         self.grid = grid
         self.coriolis = coriolis
         self.rheology = rheology if rheology is not None else ElastoViscoPlasticRheology()
-        if not isinstance(self.rheology, ElastoViscoPlasticRheology):
-            raise NotImplementedError("only ElastoViscoPlasticRheology is on the accelerated path (SURVEY.md 2, row 3)")
+        if not isinstance(self.rheology, (ElastoViscoPlasticRheology, ViscousRheology)):
+            raise NotImplementedError("rheology: ElastoViscoPlasticRheology or ViscousRheology")
         self.solver = solver if solver is not None else SplitExplicitSolver(substeps=150)
+        if not isinstance(self.solver, (SplitExplicitSolver, ExplicitSolver)):
+            raise NotImplementedError("solver: SplitExplicitSolver or ExplicitSolver")
         # free_drift: None (`nothing`: marginal ice is at rest) or StressBalanceFreeDrift(); like the reference's
         # materialize_free_drift (stress_balance_free_drift.jl:44-46) the balance uses the model's own stresses
         if free_drift is not None and not isinstance(free_drift, StressBalanceFreeDrift):

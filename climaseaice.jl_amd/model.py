@@ -14,7 +14,8 @@ import numpy as np
 import torch
 
 from . import _lib
-from .dynamics import (ElastoViscoPlasticRheology, FPlane, IceStrength, SeaIceMomentumEquation, SemiImplicitStress)
+from .dynamics import (ElastoViscoPlasticRheology, ExplicitSolver, FPlane, IceStrength, SeaIceMomentumEquation, SemiImplicitStress,
+                       ViscousRheology)
 from .fields import CenterField, Field, XFaceField, YFaceField
 from .grids import (METRIC_NAMES, Bounded, FullyConnected, LeftConnected, LeftConnectedRightFolded, Periodic, RightConnected,
                     RightFolded, TileGrid)
@@ -187,6 +188,9 @@ class SeaIceModel:
         # TimeStepper(timestepper, grid, prognostic_fields): G^n for both, Psi^- for RK (:235)
         Gn = SimpleNamespace(h=CenterField(grid, dev, "Gh"), aice=CenterField(grid, dev, "Gaice"))
         self.timestepper = SimpleNamespace(Gn=Gn, Psi_minus=None)
+        if dynamics is not None and isinstance(dynamics.solver, ExplicitSolver):
+            # the ExplicitSolver's velocity tendencies (explicit_momentum_equations.jl:103-104)
+            Gn.u, Gn.v = XFaceField(grid, dev, "Gu"), YFaceField(grid, dev, "Gv")
         if timestepper == "SplitRungeKutta3":
             self.timestepper.Psi_minus = SimpleNamespace(h=CenterField(grid, dev, "h-"), aice=CenterField(grid, dev, "aice-"),
                                                          u=XFaceField(grid, dev, "u-"), v=YFaceField(grid, dev, "v-"))
@@ -247,6 +251,9 @@ class SeaIceModel:
         self._bind("V", self.velocities.v)
         self._bind("GH", self.timestepper.Gn.h)
         self._bind("GA", self.timestepper.Gn.aice)
+        if hasattr(self.timestepper.Gn, "u"):
+            self._bind("GU", self.timestepper.Gn.u)
+            self._bind("GV", self.timestepper.Gn.v)
         if self.timestepper.Psi_minus is not None:
             pm = self.timestepper.Psi_minus
             self._bind("HM", pm.h); self._bind("AM", pm.aice); self._bind("UM", pm.u); self._bind("VM", pm.v)
@@ -294,10 +301,13 @@ class SeaIceModel:
         for fld in vars(f).values():
             if fld.data.device != self.device:
                 fld.data = fld.data.to(self.device)
-        for name, fld in (("S11", f.s11), ("S22", f.s22), ("S12", f.s12), ("UN", f.un), ("VN", f.vn), ("P", f.P),
-                          ("ALPHA", f.alpha), ("DELTA", f.Delta), ("ZETA_F", f.zeta_f), ("ZETA_C", f.zeta_c)):
-            self._bind(name, fld)
-        r = d.rheology
+        viscous = isinstance(d.rheology, ViscousRheology)
+        if not viscous:                            # ViscousRheology: no auxiliary fields (Rheologies.jl:33)
+            for name, fld in (("S11", f.s11), ("S22", f.s22), ("S12", f.s12), ("UN", f.un), ("VN", f.vn), ("P", f.P),
+                              ("ALPHA", f.alpha), ("DELTA", f.Delta), ("ZETA_F", f.zeta_f), ("ZETA_C", f.zeta_c)):
+                self._bind(name, fld)
+        # (the scalars every rheology shares travel in csi_evp_params; a viscous model leaves the EVP ones at their defaults)
+        r = ElastoViscoPlasticRheology() if viscous else d.rheology
         p = _lib.EvpParams(r.ice_compressive_strength, r.ice_compaction_hardening, r.yield_curve_eccentricity,
                            r.minimum_plastic_stress, r.min_relaxation_parameter, r.max_relaxation_parameter,
                            r.relaxation_strength,
@@ -305,6 +315,8 @@ class SeaIceModel:
                            0 if d.coriolis is None else 1, float(getattr(d.coriolis, "f", 0.0)),
                            d.minimum_concentration, d.minimum_mass, self.sea_ice_density)
         self.ctx.call("csi_evp_params_set", C.byref(p))
+        self.ctx.call("csi_rheology_set", _lib.RHEOLOGY_VISCOUS if viscous else _lib.RHEOLOGY_EVP, d.rheology.nu if viscous else 0.0)
+        self.ctx.call("csi_momentum_solver_set", _lib.SOLVER_EXPLICIT if isinstance(d.solver, ExplicitSolver) else _lib.SOLVER_SPLIT_EXPLICIT)
         if hasattr(d.coriolis, "points"):          # per-point f (curvilinear grids)
             fu, fv = d.coriolis.points(g)
             self._keep += [fu, fv]
@@ -476,7 +488,7 @@ class SeaIceModel:
     # ---- convenience ----------------------------------------------------------------------------
     @property
     def substeps(self):
-        return 0 if self.dynamics is None else self.dynamics.solver.substeps
+        return 0 if self.dynamics is None else getattr(self.dynamics.solver, "substeps", 0)      # (ExplicitSolver: none)
 
     @property
     def scheme(self):
@@ -569,8 +581,16 @@ def restore_prognostic_state(model, state):
 
 
 def time_step_momentum(model, dt, rk_reset=False):
-    """time_step_momentum!(model, model.dynamics, dt), split_explicit_momentum_equations.jl:103-195."""
+    """time_step_momentum!(model, model.dynamics, dt): split_explicit_momentum_equations.jl:103-195 (EVP or viscous sub-cycle;
+    rk_reset: reset_velocities! from Psi^-) or explicit_momentum_equations.jl:8-38 (ExplicitSolver: u^- = Psi^-.u when rk_reset,
+    the current velocities otherwise; G^n from compute_momentum_tendencies)."""
     model.ctx.call("csi_time_step_momentum", float(dt), model.substeps, int(rk_reset))
+
+
+def compute_momentum_tendencies(model, dt):
+    """compute_momentum_tendencies!(model, model.dynamics, dt): G^n.u / G^n.v of the ExplicitSolver (explicit_momentum_equations.jl:
+    85-113); nothing for the split-explicit solver."""
+    model.ctx.call("csi_compute_momentum_tendencies", float(dt))
 
 
 def time_step(model, dt):

@@ -137,6 +137,8 @@ typedef enum {
     CSI_F_FORCING_U,  /* (f,c) model.forcing.u given as an array: the `user_forcing` of sum_of_forcing_u
                        * (elasto_visco_plastic_rheology.jl:391-395), an acceleration in m s^-2; optional, both or neither */
     CSI_F_FORCING_V,  /* (c,f) model.forcing.v (:397-401) */
+    CSI_F_GU,         /* (f,c) timestepper.G^n.u: the ExplicitSolver's velocity tendency (explicit_momentum_equations.jl:103-104) */
+    CSI_F_GV,         /* (c,f) timestepper.G^n.v */
     CSI_F_COUNT
 } csi_field_id;
 
@@ -392,6 +394,39 @@ int32_t csi_halo_exchange(csi_context* ctx, const int32_t* field_ids, int32_t nf
  * Evaluated once per sub-cycle into library-owned arrays (it depends on the forcing only); the three-kernel paths and
  * the two-sub-steps-per-launch kernel read them. */
 int32_t csi_free_drift_set(csi_context* ctx, int32_t kind);
+
+/* ---- rheology and momentum solver (SeaIceMomentumEquation(grid; rheology, solver), sea_ice_momentum_equations.jl:67-94) ------------
+ * Defaults: CSI_RHEOLOGY_EVP with CSI_SOLVER_SPLIT_EXPLICIT -- the library's EVP path, unchanged by these calls.  The scalars both
+ * rheologies share (minimum mass / concentration, sea_ice_density, FPlane f) still come from csi_evp_params_set, which marks the model
+ * as having dynamics; the EVP fields of that struct are ignored by a viscous model.
+ *
+ * CSI_RHEOLOGY_VISCOUS: ViscousRheology(nu) with a Number nu (Rheologies/viscous_rheology.jl:1-22): stresses nu * delta u computed
+ *   inline from the velocities, no auxiliary fields (the ten EVP slots need not be bound), sub-step Delta t / substeps, sum_of_forcing_*
+ *   = the user forcing alone, initialize_rheology! / compute_stresses! / finalize_rheology! no-ops (Rheologies.jl:42-55).  A Field- or
+ *   function-valued nu is not supported (its face interpolation lives in un-vendored Oceananigans).
+ *   Split-explicit sub-cycle: per sub-step a u launch and a v launch in the parity order of split_explicit_momentum_equations.jl:178,
+ *   each writing its halo images with its stores (2 x substeps launches, at most one device copy at the end).  DELIBERATE DEPARTURE:
+ *   the reference's velocity kernel writes u[i, j] in place while its viscous stencil reads u at the neighbouring points, a race whose
+ *   result depends on scheduling; here each launch reads only the OLD values of its own component (separate input and output arrays,
+ *   ping-ponged between the bound array and a context-owned scratch) -- Jacobi within a component, Gauss-Seidel between the two.
+ * CSI_SOLVER_EXPLICIT: ExplicitSolver (explicit_momentum_equations.jl): csi_compute_momentum_tendencies writes G^n.u / G^n.v
+ *   (CSI_F_GU / CSI_F_GV) from the current state -- with EVP from the STORED sigma (compute_stresses! is never called) and the
+ *   (u^n - u) / Delta t / Ixᶠᵃᵃ(alpha) forcing term with u^n as it stands --; csi_time_step_momentum then sets
+ *   u = select((u^- + dt G) / (1 + dt tau_i), free drift, 0) and the same for v (u^- = Psi^-.u when rk_reset != 0, the current u otherwise),
+ *   no `* active` factor, no m <= 0 guard on tau_i; three launches, each velocity launch writing its halo images.  csi_time_step_fe /
+ *   _rk3 call both where the reference does (sea_ice_fe_step.jl:19-22, sea_ice_rk_substep.jl:84-87).  The values the local fill and
+ *   update_state! leave on wall faces and immersed faces are recalled fill semantics, not pinned (as for the fold).
+ * Both: csi_set_fusion levels are ignored (no fused kernels on these paths); STRICT is the reference's operation order, FAST uses
+ * explicit FMAs and reciprocals.  Tiled contexts (connected topologies / csi_tile_set) and north-fold topologies return
+ * CSI_ERR_UNSUPPORTED for a rheology other than EVP or a solver other than the split-explicit one. */
+typedef enum { CSI_RHEOLOGY_EVP = 0, CSI_RHEOLOGY_VISCOUS = 1 } csi_rheology_kind;
+typedef enum { CSI_SOLVER_SPLIT_EXPLICIT = 0, CSI_SOLVER_EXPLICIT = 1 } csi_momentum_solver_kind;
+/* nu: ViscousRheology's nu (m^2 s^-1 as the reference scales it; ignored for EVP) */
+int32_t csi_rheology_set(csi_context* ctx, int32_t kind, double nu);
+int32_t csi_momentum_solver_set(csi_context* ctx, int32_t kind);
+/* compute_momentum_tendencies!(model, dynamics, dt): explicit_momentum_equations.jl:85-113 for CSI_SOLVER_EXPLICIT (needs CSI_F_GU,
+ * CSI_F_GV); a no-op for the split-explicit solver (SeaIceDynamics.jl:41). */
+int32_t csi_compute_momentum_tendencies(csi_context* ctx, double dt);
 
 /* FAST mode only.  level 0: always the three-kernel path.  level 1: a sub-step is ONE launch of the fused
  * kernel (stress + both velocity updates, ring recomputation per wavefront, double-buffered u, v, sigma in

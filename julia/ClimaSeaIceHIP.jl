@@ -9,7 +9,7 @@ module ClimaSeaIceHIP
 using ClimaSeaIce
 using ClimaSeaIce: SeaIceModel
 using ClimaSeaIce.SeaIceDynamics: SeaIceMomentumEquation, SplitExplicitSolver, SemiImplicitStress, StressBalanceFreeDrift
-using ClimaSeaIce.Rheologies: ElastoViscoPlasticRheology, ReplacementPressure
+using ClimaSeaIce.Rheologies: ElastoViscoPlasticRheology, ViscousRheology, ReplacementPressure
 using Oceananigans
 using Oceananigans: CPU
 using Oceananigans.Architectures: architecture
@@ -48,7 +48,8 @@ end
 # field slots, in the order of csi_field_id
 const F = (U=0, V=1, H=2, A=3, S11=4, S22=5, S12=6, UN=7, VN=8, P=9, ALPHA=10, DELTA=11, ZETA_F=12, ZETA_C=13,
            GH=14, GA=15, HM=16, AM=17, UM=18, VM=19, TOP_U=20, TOP_V=21, BOT_U=22, BOT_V=23, MASS_FLUX=24,
-           HS=25, GHS=26, HSM=27, MASS_FLUX_SNOW=28, SNOWFALL_INTERCEPTED=29, TU=30, TUS=31, FORCING_U=32, FORCING_V=33)
+           HS=25, GHS=26, HSM=27, MASS_FLUX_SNOW=28, SNOWFALL_INTERCEPTED=29, TU=30, TUS=31, FORCING_U=32, FORCING_V=33,
+           GU=34, GV=35)
 
 mutable struct Context
     handle::Ptr{Cvoid}
@@ -184,10 +185,17 @@ function attach!(model::SeaIceModel)
     set_grid!(ctx, grid)
     a = dyn.auxiliaries.fields
     for (slot, f) in ((F.U, model.velocities.u), (F.V, model.velocities.v), (F.H, model.ice_thickness),
-                      (F.A, model.ice_concentration), (F.S11, a.σ₁₁), (F.S22, a.σ₂₂), (F.S12, a.σ₁₂), (F.UN, a.uⁿ),
-                      (F.VN, a.vⁿ), (F.P, a.P), (F.ALPHA, a.α), (F.DELTA, a.Δ), (F.ZETA_F, a.ζᶠᶠᶜ), (F.ZETA_C, a.ζᶜᶜᶜ),
-                      (F.GH, model.timestepper.Gⁿ.h), (F.GA, model.timestepper.Gⁿ.ℵ))
+                      (F.A, model.ice_concentration), (F.GH, model.timestepper.Gⁿ.h), (F.GA, model.timestepper.Gⁿ.ℵ))
         bind!(ctx, slot, f)
+    end
+    if dyn.rheology isa ElastoViscoPlasticRheology        # ViscousRheology has no auxiliary fields (Rheologies.jl:33)
+        for (slot, f) in ((F.S11, a.σ₁₁), (F.S22, a.σ₂₂), (F.S12, a.σ₁₂), (F.UN, a.uⁿ), (F.VN, a.vⁿ), (F.P, a.P), (F.ALPHA, a.α),
+                          (F.DELTA, a.Δ), (F.ZETA_F, a.ζᶠᶠᶜ), (F.ZETA_C, a.ζᶜᶜᶜ))
+            bind!(ctx, slot, f)
+        end
+    end
+    if dyn.solver isa HIPExplicitSolver                    # the ExplicitSolver's G^n.u / G^n.v (explicit_momentum_equations.jl:103-104)
+        bind!(ctx, F.GU, model.timestepper.Gⁿ.u); bind!(ctx, F.GV, model.timestepper.Gⁿ.v)
     end
     if model.timestepper isa SplitRungeKuttaTimeStepper
         Ψ = model.timestepper.Ψ⁻
@@ -203,7 +211,8 @@ function attach!(model::SeaIceModel)
     mf = model.mass_fluxes
     bind!(ctx, F.MASS_FLUX, mf.thermodynamics.ice); bind!(ctx, F.MASS_FLUX_SNOW, mf.thermodynamics.snow)
     bind!(ctx, F.SNOWFALL_INTERCEPTED, mf.intercepted_snowfall)
-    r = dyn.rheology
+    # the scalars every rheology shares travel in CsiEvpParams; a viscous model sends the EVP defaults beside them
+    r = dyn.rheology isa ViscousRheology ? ElastoViscoPlasticRheology() : dyn.rheology
     cor = dyn.coriolis
     p = Ref(CsiEvpParams(r.ice_compressive_strength, r.ice_compaction_hardening, r.yield_curve_eccentricity,
                          r.minimum_plastic_stress, r.min_relaxation_parameter, r.max_relaxation_parameter,
@@ -211,6 +220,7 @@ function attach!(model::SeaIceModel)
                          isnothing(cor) ? 0 : 1, cor isa FPlane ? cor.f : 0.0,
                          dyn.minimum_concentration, dyn.minimum_mass, model.sea_ice_density[1, 1, 1]))
     check(ctx, ccall((:csi_evp_params_set, libcsi), Int32, (Ptr{Cvoid}, Ref{CsiEvpParams}), ctx.handle, p))
+    set_rheology_and_solver!(ctx, dyn)
     if cor isa BetaPlane
         # f = f₀ + β y at the (Face, Center) / (Center, Face) nodes of every row, halo rows included (ynode follows the
         # halo of a distributed or periodic grid, so ring rows see their owner's value); host vectors like the metrics
@@ -376,6 +386,45 @@ function ClimaSeaIce.SeaIceDynamics.time_step_momentum!(model, dynamics::HIPMome
         check(ctx, ccall((:csi_time_step_momentum, libcsi), Int32, (Ptr{Cvoid}, Cdouble, Int32, Int32),
                          ctx.handle, Δt, dynamics.solver.substeps, rk ? 1 : 0))
     end
+    return nothing
+end
+
+# ---- ViscousRheology (a Number ν) and the ExplicitSolver ------------------------------------------------------------------------
+"""
+    HIPExplicitSolver()
+
+Drop-in for `ExplicitSolver`: `SeaIceMomentumEquation(grid; solver = HIPExplicitSolver())` (explicit_momentum_equations.jl).
+"""
+struct HIPExplicitSolver end
+const HIPExplicitMomentumEquation = SeaIceMomentumEquation{<:HIPExplicitSolver}
+
+# csi_rheology_set / csi_momentum_solver_set (include/csi.h): ViscousRheology(ν::Number) -> CSI_RHEOLOGY_VISCOUS; a Field- or
+# function-valued ν is refused (its face interpolation lives in Oceananigans); HIPExplicitSolver -> CSI_SOLVER_EXPLICIT
+function set_rheology_and_solver!(ctx, dyn)
+    vr = dyn.rheology
+    if vr isa ViscousRheology
+        vr.ν isa Number || error("ClimaSeaIceHIP: ViscousRheology with a $(typeof(vr.ν)) ν is not supported; give a Number")
+        check(ctx, ccall((:csi_rheology_set, libcsi), Int32, (Ptr{Cvoid}, Int32, Cdouble), ctx.handle, 1, vr.ν))
+    else
+        check(ctx, ccall((:csi_rheology_set, libcsi), Int32, (Ptr{Cvoid}, Int32, Cdouble), ctx.handle, 0, 0.0))
+    end
+    check(ctx, ccall((:csi_momentum_solver_set, libcsi), Int32, (Ptr{Cvoid}, Int32), ctx.handle,
+                     dyn.solver isa HIPExplicitSolver ? 1 : 0))
+    return nothing
+end
+
+# compute_momentum_tendencies!, explicit_momentum_equations.jl:85-113 (called by compute_tendencies! before the momentum step)
+function ClimaSeaIce.SeaIceDynamics.compute_momentum_tendencies!(model, dynamics::HIPExplicitMomentumEquation, Δt)
+    ctx = context(model)
+    check(ctx, ccall((:csi_compute_momentum_tendencies, libcsi), Int32, (Ptr{Cvoid}, Cdouble), ctx.handle, Δt))
+    return nothing
+end
+
+# time_step_momentum!, explicit_momentum_equations.jl:8-38: u⁻ = Ψ⁻.u under the SplitRungeKuttaTimeStepper, the current u otherwise
+function ClimaSeaIce.SeaIceDynamics.time_step_momentum!(model, dynamics::HIPExplicitMomentumEquation, Δt)
+    ctx = context(model)
+    rk = model.timestepper isa SplitRungeKuttaTimeStepper
+    check(ctx, ccall((:csi_time_step_momentum, libcsi), Int32, (Ptr{Cvoid}, Cdouble, Int32, Int32), ctx.handle, Δt, 0, rk ? 1 : 0))
     return nothing
 end
 
