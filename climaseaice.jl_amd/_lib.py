@@ -17,7 +17,8 @@ METRIC_UNIFORM, METRIC_PER_J, METRIC_FULL = 0, 1, 2
 FIELD_IDS = ["U", "V", "H", "A", "S11", "S22", "S12", "UN", "VN", "P", "ALPHA", "DELTA", "ZETA_F", "ZETA_C",
              "GH", "GA", "HM", "AM", "UM", "VM", "TOP_U", "TOP_V", "BOT_U", "BOT_V", "MASS_FLUX",
              "HS", "GHS", "HSM", "MASS_FLUX_SNOW", "SNOWFALL_INTERCEPTED", "TU", "TUS", "FORCING_U", "FORCING_V", "GU", "GV"]
-F = {n: k for k, n in enumerate(FIELD_IDS)}
+THERMO_FIELD_IDS = ["TOP_HEAT_FLUX", "BOTTOM_HEAT_FLUX", "SNOWFALL"]     # csi_thermo_field_id: numbered from CSI_F_COUNT on
+F = {n: k for k, n in enumerate(FIELD_IDS + THERMO_FIELD_IDS)}
 STRESS_NONE, STRESS_CONST, STRESS_FIELD, STRESS_SEMI_IMPLICIT = 0, 1, 2, 3
 VEL_ZERO, VEL_CONST, VEL_FIELD = 0, 1, 2
 STRESS_TOP, STRESS_BOTTOM = 0, 1
@@ -25,6 +26,9 @@ MODE_STRICT, MODE_FAST = 0, 1
 PRESSURE_REPLACEMENT, PRESSURE_ICE_STRENGTH = 0, 1
 RHEOLOGY_EVP, RHEOLOGY_VISCOUS = 0, 1
 SOLVER_SPLIT_EXPLICIT, SOLVER_EXPLICIT = 0, 1
+FLUX_CONSTANT, FLUX_ARRAY, FLUX_RADIATIVE_EMISSION = 0, 1, 2
+HEAT_TOP, HEAT_BOTTOM = 0, 1
+MAX_HEAT_FLUX_TERMS = 8
 
 # every symbol include/csi.h declares (checked by tests/test_abi.py against the header text)
 SYMBOLS = ["csi_version", "csi_context_create", "csi_context_destroy", "csi_last_error", "csi_sync", "csi_set_mode",
@@ -36,7 +40,8 @@ SYMBOLS = ["csi_version", "csi_context_create", "csi_context_destroy", "csi_last
            "csi_plan_exchange", "csi_set_fusion", "csi_set_exchange_interval", "csi_set_halo_transport", "csi_halo_transport", "csi_set_peer_tier", "csi_peer_tier", "csi_plan_ranges", "csi_profile_substeps", "csi_last_path", "csi_last_subcycle_ms", "csi_launches_per_substep", "csi_last_launches", "csi_plan_pair", "csi_plan_peer_chunks", "csi_free_drift_set", "csi_coriolis_rows_set", "csi_velocity_bc_set",
            "csi_immersed_flux_bc_set", "csi_coriolis_points_set", "csi_validate_all", "csi_debug_peer_abort", "csi_set_weno_weight_dtype", "csi_weno_weight_dtype", "csi_subcycle_stats_begin", "csi_subcycle_stats_end",
            "csi_set_tile_skipping", "csi_tile_activity", "csi_set_row_constant", "csi_row_constant_rows",
-           "csi_rheology_set", "csi_momentum_solver_set", "csi_compute_momentum_tendencies"]
+           "csi_rheology_set", "csi_momentum_solver_set", "csi_compute_momentum_tendencies",
+           "csi_heat_fluxes_set", "csi_surface_solve_set"]
 
 
 class Metrics(C.Structure):
@@ -75,6 +80,16 @@ class SlabParams(C.Structure):
 class SnowParams(C.Structure):
     _fields_ = [("conductivity", C.c_double), ("snow_density", C.c_double), ("snowfall", C.c_double),
                 ("top_temperature", C.c_double), ("top_bc_kind", C.c_int32), ("pad_", C.c_int32)]
+
+
+class HeatFluxTerm(C.Structure):
+    _fields_ = [("kind", C.c_int32), ("reserved", C.c_int32), ("value", C.c_double), ("emissivity", C.c_double),
+                ("stefan_boltzmann_constant", C.c_double), ("reference_temperature", C.c_double)]
+
+
+class SurfaceSolve(C.Structure):
+    _fields_ = [("tol", C.c_double), ("maxiters", C.c_int32), ("prescribed_array", C.c_int32), ("snowfall_array", C.c_int32),
+                ("reserved", C.c_int32)]
 
 
 class CsiError(RuntimeError):
@@ -144,6 +159,7 @@ def load():
         "csi_validate_all": [vp], "csi_debug_peer_abort": [vp], "csi_set_weno_weight_dtype": [vp, i32], "csi_weno_weight_dtype": [vp, C.POINTER(i32)], "csi_subcycle_stats_begin": [vp],
         "csi_subcycle_stats_end": [vp, C.POINTER(dbl), C.POINTER(i32), C.POINTER(i32)],
         "csi_rheology_set": [vp, i32, dbl], "csi_momentum_solver_set": [vp, i32], "csi_compute_momentum_tendencies": [vp, dbl],
+        "csi_heat_fluxes_set": [vp, i32, C.POINTER(HeatFluxTerm), i32], "csi_surface_solve_set": [vp, C.POINTER(SurfaceSolve)],
     }
     for name, args in sig.items():
         fn = getattr(L, name, None)

@@ -24,14 +24,55 @@ static SnowDev snow_dev(const csi_snow_params* p) {
     W.k = p->conductivity; W.rho = p->snow_density; W.snowfall = p->snowfall; W.Tu = p->top_temperature; W.top_bc_kind = p->top_bc_kind;
     return W;
 }
+// The flux-term path (thermo_flux.hip) runs once a side has terms, the prescribed temperature is an array or snowfall is; its
+// arrays are checked here.  `tu_id`: the surface whose temperature is solved / prescribed (CSI_F_TU bare ice, CSI_F_TUS snow).
+static bool flux_path(const csi_context* c, bool snow) {
+    const HeatFluxDev& F = c->heat;
+    return F.top.n > 0 || F.bot.n > 0 || F.prescribed_array || (snow && F.snowfall_array);
+}
+static bool has_array_term(const FluxTermsDev& t) {
+    for (int k = 0; k < t.n; ++k)
+        if (t.kind[k] == FLUX_ARRAY) return true;
+    return false;
+}
+static int32_t flux_fields(csi_context* c, const SlabDev& S, int top_bc_kind, int tu_id, bool snow, FluxFields& ff) {
+    const HeatFluxDev& F = c->heat;
+    if (F.top.n > 0 && S.top_flux_kind != 0)
+        return fail(c, CSI_ERR_UNSUPPORTED, "top heat-flux terms replace top_flux_kind 1 (the internal-flux equilibrium): set top_flux_kind 0");
+    if (F.bot.n > 0 && S.bot_flux_kind != 0)
+        return fail(c, CSI_ERR_UNSUPPORTED, "bottom heat-flux terms replace the frazil bottom_flux_kind 1: set bottom_flux_kind 0");
+    if (F.prescribed_array && top_bc_kind != 0)
+        return fail(c, CSI_ERR_INVALID_ARGUMENT, "csi_surface_solve.prescribed_array needs a PrescribedTemperature top (top_bc_kind 0)");
+    ff = FluxFields{};
+    std::vector<int> ids;
+    if (has_array_term(F.top)) { ids.push_back(CSI_F_TOP_HEAT_FLUX); ff.qtop = ref_of(c, CSI_F_TOP_HEAT_FLUX); }
+    if (has_array_term(F.bot)) { ids.push_back(CSI_F_BOTTOM_HEAT_FLUX); ff.qbot = ref_of(c, CSI_F_BOTTOM_HEAT_FLUX); }
+    if (snow && F.snowfall_array) { ids.push_back(CSI_F_SNOWFALL); ff.snowfall = ref_of(c, CSI_F_SNOWFALL); }
+    // the surface temperature: read per cell (prescribed, Tu- of the secant), written by the flux balance
+    if (F.prescribed_array || (top_bc_kind == 1 && flux_has_emission(F.top))) ids.push_back(tu_id);
+    for (int id : ids) {
+        int32_t rc = need(c, {id});
+        if (rc) return rc;
+    }
+    ff.tu = ref_of(c, tu_id);
+    return CSI_OK;
+}
 static int32_t do_layered(csi_context* c, const SlabDev& S, const SnowDev& W, double dt) {
     int32_t rc = need(c, {CSI_F_H, CSI_F_A, CSI_F_HS});
     if (rc) return rc;
-    if (S.top_flux_kind != 0) return fail(c, CSI_ERR_UNSUPPORTED, "the layered (snow) step takes a numeric top heat flux (top_flux_kind 0)");
+    if (S.top_flux_kind != 0)
+        return fail(c, CSI_ERR_UNSUPPORTED, "the layered (snow) step takes numbers, arrays and RadiativeEmission as top heat flux "
+                                            "(top_flux_kind 0, csi_heat_fluxes_set), not the internal-flux equilibrium (top_flux_kind 1)");
     LayeredOut o{};
     o.mf_ice = ref_of(c, CSI_F_MASS_FLUX); o.mf_snow = ref_of(c, CSI_F_MASS_FLUX_SNOW); o.mf_int = ref_of(c, CSI_F_SNOWFALL_INTERCEPTED);
     o.tu_ice = ref_of(c, CSI_F_TU); o.tu_snow = ref_of(c, CSI_F_TUS);
-    launch_layered_step(S, W, c->g, ref_of(c, CSI_F_H), ref_of(c, CSI_F_A), ref_of(c, CSI_F_HS), o, dt, c->stream);
+    if (flux_path(c, true)) {
+        FluxFields ff;
+        if ((rc = flux_fields(c, S, W.top_bc_kind, CSI_F_TUS, true, ff))) return rc;
+        launch_layered_flux_step(S, W, c->heat, ff, c->g, ref_of(c, CSI_F_H), ref_of(c, CSI_F_A), ref_of(c, CSI_F_HS), o, dt, c->stream);
+    } else {
+        launch_layered_step(S, W, c->g, ref_of(c, CSI_F_H), ref_of(c, CSI_F_A), ref_of(c, CSI_F_HS), o, dt, c->stream);
+    }
     HIP_TRY(c, hipGetLastError());
     return CSI_OK;
 }
@@ -40,8 +81,16 @@ static int32_t do_thermo(csi_context* c, double dt);
 static int32_t do_slab(csi_context* c, const SlabDev& S, double dt) {
     const bool has_mf = c->f[CSI_F_MASS_FLUX].p != nullptr;
     if (S.top_bc_kind == 1 && S.top_flux_kind != 0)
-        return fail(c, CSI_ERR_UNSUPPORTED, "MeltingConstrainedFluxBalance takes a numeric top heat flux (top_flux_kind 0)");
-    launch_slab_step(S, c->g, ref_of(c, CSI_F_H), ref_of(c, CSI_F_A), ref_of(c, CSI_F_MASS_FLUX), has_mf, dt, c->stream);
+        return fail(c, CSI_ERR_UNSUPPORTED, "MeltingConstrainedFluxBalance takes numbers, arrays and RadiativeEmission as top heat flux "
+                                            "(top_flux_kind 0, csi_heat_fluxes_set), not the internal-flux equilibrium (top_flux_kind 1)");
+    if (flux_path(c, false)) {
+        FluxFields ff;
+        int32_t rc = flux_fields(c, S, S.top_bc_kind, CSI_F_TU, false, ff);
+        if (rc) return rc;
+        launch_slab_flux_step(S, c->heat, ff, c->g, ref_of(c, CSI_F_H), ref_of(c, CSI_F_A), ref_of(c, CSI_F_MASS_FLUX), has_mf, dt, c->stream);
+    } else {
+        launch_slab_step(S, c->g, ref_of(c, CSI_F_H), ref_of(c, CSI_F_A), ref_of(c, CSI_F_MASS_FLUX), has_mf, dt, c->stream);
+    }
     HIP_TRY(c, hipGetLastError());
     return CSI_OK;
 }
@@ -347,7 +396,7 @@ int32_t csi_mask_set(csi_context* c, const uint8_t* dev_mask, int64_t ld) {
 int32_t csi_field_bind(csi_context* c, int32_t fid, void* dev_ptr, int64_t ld, int32_t ni, int32_t nj) {
     if (!c) return CSI_ERR_INVALID_ARGUMENT;
     if (!c->grid_set) return fail(c, CSI_ERR_NOT_BOUND, "csi_grid_set has not been called");
-    if (fid < 0 || fid >= CSI_F_COUNT) return fail(c, CSI_ERR_INVALID_ARGUMENT, "unknown field id");
+    if (fid < 0 || fid >= CSI_F_COUNT_ALL) return fail(c, CSI_ERR_INVALID_ARGUMENT, "unknown field id");
     if (!dev_ptr) { c->f[fid] = Bound{}; return CSI_OK; }
     const int eni = c->Nx + 2 * c->Hx + extra_x(c, fid), enj = c->Ny + 2 * c->Hy + extra_y(c, fid);
     if (ni != eni || nj != enj || ld < ni) {
@@ -652,6 +701,46 @@ int32_t csi_slab_params_set(csi_context* c, const csi_slab_params* p) {
     if (!c) return CSI_ERR_INVALID_ARGUMENT;
     c->slab_set = p != nullptr;
     if (p) c->slab = slab_dev(p);
+    return CSI_OK;
+}
+
+int32_t csi_heat_fluxes_set(csi_context* c, int32_t side, const csi_heat_flux_term* terms, int32_t n) {
+    if (!c) return CSI_ERR_INVALID_ARGUMENT;
+    if (side != CSI_HEAT_TOP && side != CSI_HEAT_BOTTOM) return fail(c, CSI_ERR_INVALID_ARGUMENT, "side must be CSI_HEAT_TOP or CSI_HEAT_BOTTOM");
+    if (!terms) n = 0;
+    if (n < 0) return fail(c, CSI_ERR_INVALID_ARGUMENT, "n < 0");
+    if (n > CSI_MAX_HEAT_FLUX_TERMS)
+        return fail(c, CSI_ERR_UNSUPPORTED, "more than CSI_MAX_HEAT_FLUX_TERMS heat-flux terms on one side");
+    FluxTermsDev t{};
+    int arrays = 0;
+    for (int k = 0; k < n; ++k) {
+        const csi_heat_flux_term& q = terms[k];
+        if (q.kind != CSI_FLUX_CONSTANT && q.kind != CSI_FLUX_ARRAY && q.kind != CSI_FLUX_RADIATIVE_EMISSION)
+            return fail(c, CSI_ERR_INVALID_ARGUMENT, "unknown heat-flux term kind");
+        if (q.kind == CSI_FLUX_ARRAY && ++arrays > 1)
+            return fail(c, CSI_ERR_UNSUPPORTED, "at most one ARRAY heat-flux term per side (sum the arrays into one)");
+        if (q.kind == CSI_FLUX_RADIATIVE_EMISSION && side != CSI_HEAT_TOP)
+            return fail(c, CSI_ERR_UNSUPPORTED, "RadiativeEmission is a top heat flux only");
+        t.kind[k] = q.kind == CSI_FLUX_ARRAY ? FLUX_ARRAY : (q.kind == CSI_FLUX_RADIATIVE_EMISSION ? FLUX_EMISSION : FLUX_CONST);
+        t.value[k] = q.value;
+        t.eps[k] = q.emissivity; t.sigma[k] = q.stefan_boltzmann_constant; t.Tr[k] = q.reference_temperature;
+    }
+    t.n = n;
+    (side == CSI_HEAT_TOP ? c->heat.top : c->heat.bot) = t;
+    return CSI_OK;
+}
+
+int32_t csi_surface_solve_set(csi_context* c, const csi_surface_solve* p) {
+    if (!c) return CSI_ERR_INVALID_ARGUMENT;
+    const HeatFluxDev defaults{};
+    if (!p) {
+        c->heat.tol = defaults.tol; c->heat.maxiters = defaults.maxiters;
+        c->heat.prescribed_array = 0; c->heat.snowfall_array = 0;
+        return CSI_OK;
+    }
+    if (!(p->tol > 0) || p->maxiters < 1) return fail(c, CSI_ERR_INVALID_ARGUMENT, "the surface solve needs tol > 0 and maxiters >= 1");
+    c->heat.tol = p->tol; c->heat.maxiters = p->maxiters;
+    c->heat.prescribed_array = p->prescribed_array != 0; c->heat.snowfall_array = p->snowfall_array != 0;
     return CSI_OK;
 }
 

@@ -38,7 +38,7 @@ struct Bound {
 };
 
 // (x, y) location of every field slot
-static const int kLoc[CSI_F_COUNT][2] = {
+static const int kLoc[CSI_F_COUNT_ALL][2] = {
     {LOC_F, LOC_C}, {LOC_C, LOC_F}, {LOC_C, LOC_C}, {LOC_C, LOC_C},   // U V H A
     {LOC_C, LOC_C}, {LOC_C, LOC_C}, {LOC_F, LOC_F},                   // S11 S22 S12
     {LOC_F, LOC_C}, {LOC_C, LOC_F}, {LOC_C, LOC_C}, {LOC_C, LOC_C}, {LOC_C, LOC_C},  // UN VN P ALPHA DELTA
@@ -50,11 +50,13 @@ static const int kLoc[CSI_F_COUNT][2] = {
     {LOC_C, LOC_C}, {LOC_C, LOC_C}, {LOC_C, LOC_C},                   // HS GHS HSM
     {LOC_C, LOC_C}, {LOC_C, LOC_C}, {LOC_C, LOC_C}, {LOC_C, LOC_C},   // MASS_FLUX_SNOW SNOWFALL_INTERCEPTED TU TUS
     {LOC_F, LOC_C}, {LOC_C, LOC_F},                                   // FORCING_U FORCING_V
-    {LOC_F, LOC_C}, {LOC_C, LOC_F}};                                  // GU GV
-static const char* const kName[CSI_F_COUNT] = {"u", "v", "h", "aice", "sigma11", "sigma22", "sigma12", "un", "vn", "P", "alpha",
+    {LOC_F, LOC_C}, {LOC_C, LOC_F},                                   // GU GV
+    {LOC_C, LOC_C}, {LOC_C, LOC_C}, {LOC_C, LOC_C}};                  // TOP_HEAT_FLUX BOTTOM_HEAT_FLUX SNOWFALL
+static const char* const kName[CSI_F_COUNT_ALL] = {"u", "v", "h", "aice", "sigma11", "sigma22", "sigma12", "un", "vn", "P", "alpha",
                                   "Delta", "zeta_f", "zeta_c", "Gh", "Gaice", "h-", "aice-", "u-", "v-",
                                   "top_u", "top_v", "bottom_u", "bottom_v", "mass_flux",
-                                  "hs", "Ghs", "hs-", "mass_flux_snow", "intercepted_snowfall", "Tu", "Tu_snow", "forcing_u", "forcing_v", "Gu", "Gv"};
+                                  "hs", "Ghs", "hs-", "mass_flux_snow", "intercepted_snowfall", "Tu", "Tu_snow", "forcing_u", "forcing_v", "Gu", "Gv",
+                                  "top_heat_flux", "bottom_heat_flux", "snowfall"};
 
 extern std::string g_create_error;      // csi_context_create failures (no context to hold the message)
 
@@ -101,7 +103,7 @@ struct csi_context {
     long fcor2_ld = 0, fcor2_plane = 0;
     bool cor_dirty = true;               // Coriolis columns of the FAST table need (re)building
     double cor_synced = 0.0;             // FPlane value they were built with
-    Bound f[CSI_F_COUNT];
+    Bound f[CSI_F_COUNT_ALL];
     csi_evp_params evp{};
     csi_stress stress[2]{};
     int mode = CSI_MODE_STRICT;
@@ -188,6 +190,7 @@ struct csi_context {
     double vel_bc_value[2][2] = {{0, 0}, {0, 0}};
     bool snow_set = false;   // layered (snow + ice) step instead of the bare-ice one
     SnowDev snow{};
+    HeatFluxDev heat{};      // csi_heat_fluxes_set / csi_surface_solve_set (thermo_flux.hip); heat.top.n = heat.bot.n = 0: numbers only
     int weno_w32 = 0;     // csi_set_weno_weight_dtype: 1 = WENO weights in single precision (upstream's FT2 = Float32, recalled)
     // csi_rheology_set / csi_momentum_solver_set (csi_momentum.hip): ViscousRheology, ExplicitSolver
     int rheology = CSI_RHEOLOGY_EVP;

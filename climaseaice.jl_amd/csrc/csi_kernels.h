@@ -194,4 +194,28 @@ void launch_layered_step(const SlabDev& S, const SnowDev& W, const GridDev& g, c
 void launch_slab_step(const SlabDev& S, const GridDev& g, const FRef& h, const FRef& a, const FRef& mf, int has_mf,
                       double dt, hipStream_t s);
 
+// per-cell heat fluxes, RadiativeEmission, the surface-temperature solve (thermo_flux.hip; include/csi.h csi_heat_fluxes_set)
+constexpr int kMaxFluxTerms = 8;
+enum : int { FLUX_CONST = 0, FLUX_ARRAY = 1, FLUX_EMISSION = 2 };
+struct FluxTermsDev {
+    int n;                     // 0: the side takes SlabDev's number (Qu / Qb with top_flux_kind / bot_flux_kind)
+    int kind[kMaxFluxTerms];
+    double value[kMaxFluxTerms], eps[kMaxFluxTerms], sigma[kMaxFluxTerms], Tr[kMaxFluxTerms];
+};
+struct HeatFluxDev {
+    FluxTermsDev top, bot;
+    double tol = 1e-3;
+    int maxiters = 1000;
+    int prescribed_array = 0;  // PrescribedTemperature read per cell from the surface's temperature field
+    int snowfall_array = 0;
+};
+// qtop / qbot: the ARRAY terms' fields; snowfall: per-cell snowfall; tu: the solved surface's temperature field (CSI_F_TU for the
+// bare-ice step, CSI_F_TUS for the layered one) -- Tu- of the secant, the prescribed per-cell value, and the output
+struct FluxFields { FRef qtop, qbot, snowfall, tu; };
+bool flux_has_emission(const FluxTermsDev& t);
+void launch_slab_flux_step(const SlabDev& S, const HeatFluxDev& F, const FluxFields& ff, const GridDev& g, const FRef& h, const FRef& a,
+                           const FRef& mf, int has_mf, double dt, hipStream_t s);
+void launch_layered_flux_step(const SlabDev& S, const SnowDev& W, const HeatFluxDev& F, const FluxFields& ff, const GridDev& g,
+                              const FRef& h, const FRef& a, const FRef& hs, const LayeredOut& o, double dt, hipStream_t s);
+
 }  // namespace csi

@@ -17,8 +17,68 @@ from . import _lib
 from .dynamics import (ElastoViscoPlasticRheology, ExplicitSolver, FPlane, IceStrength, SeaIceMomentumEquation, SemiImplicitStress,
                        ViscousRheology)
 from .fields import CenterField, Field, XFaceField, YFaceField
-from .grids import (METRIC_NAMES, Bounded, FullyConnected, LeftConnected, LeftConnectedRightFolded, Periodic, RightConnected,
+from .grids import (METRIC_NAMES, Bounded, Center, FullyConnected, LeftConnected, LeftConnectedRightFolded, Periodic, RightConnected,
                     RightFolded, TileGrid)
+
+
+_OWN = object()      # SlabThermodynamics.params: use the object's own fluxes
+
+
+def _cell_shape_ok(value, grid):
+    """An (Ny, Nx) array of the grid (on a TileGrid also of the global grid) or a CenterField of the grid."""
+    if isinstance(value, Field):
+        return value.location == (Center, Center) and (value.ni, value.nj) == tuple(grid.field_size(Center, Center))
+    shape = np.shape(value)
+    if isinstance(grid, TileGrid) and shape == (grid.global_grid.Ny, grid.global_grid.Nx):
+        return True
+    return shape == (grid.Ny, grid.Nx)
+
+
+def check_heat_flux(spec, side, grid):
+    """Refuse, by name, what the C ABI cannot take: closures (FluxFunction, callables), RadiativeEmission at the bottom, more than
+    one array per side, arrays of the wrong shape (ValueError)."""
+    if spec is None or _is_number(spec) or (side == "bottom" and isinstance(spec, str) and spec == "frazil"):
+        return
+    items = spec if isinstance(spec, tuple) else (spec,)
+    if len(items) > _lib.MAX_HEAT_FLUX_TERMS:
+        raise NotImplementedError(f"{side}_heat_flux: at most {_lib.MAX_HEAT_FLUX_TERMS} terms")
+    arrays = 0
+    for x in items:
+        if _is_number(x):
+            continue
+        if isinstance(x, RadiativeEmission):
+            if side != "top":
+                raise NotImplementedError("RadiativeEmission is a top heat flux only")
+        elif isinstance(x, (Field, np.ndarray, list)):
+            arrays += 1
+            if arrays > 1:
+                raise NotImplementedError(f"{side}_heat_flux: at most one array / CenterField term (sum the arrays into one)")
+            if not _cell_shape_ok(x, grid):
+                raise ValueError(f"{side}_heat_flux: an array of shape (Ny, Nx) = {(grid.Ny, grid.Nx)} or a CenterField of the grid "
+                                 f"is needed, got {np.shape(x) if not isinstance(x, Field) else 'a field of another shape'}")
+        elif callable(x) or type(x).__name__ == "FluxFunction":
+            raise NotImplementedError(f"{side}_heat_flux: {type(x).__name__} is not supported -- FluxFunction and other callables "
+                                      "cannot cross the C ABI; give numbers, (Ny, Nx) arrays, CenterFields, RadiativeEmission "
+                                      "or a tuple of them")
+        else:
+            raise TypeError(f"{side}_heat_flux: unsupported term {type(x).__name__}")
+
+
+def check_heat_fluxes(grid, ice, top_heat_flux, bottom_heat_flux, snowfall=None):
+    """The checks SeaIceModel makes before it touches a device: fluxes given in one place only, and each one acceptable."""
+    if top_heat_flux is not None and ice.top_heat_flux is not None:
+        raise ValueError("top_heat_flux is given both to SeaIceModel and to SlabThermodynamics")
+    if bottom_heat_flux is not None and ice.bottom_heat_flux is not None:
+        raise ValueError("bottom_heat_flux is given both to SeaIceModel and to SlabThermodynamics")
+    check_heat_flux(top_heat_flux if top_heat_flux is not None else ice.top_heat_flux, "top", grid)
+    check_heat_flux(bottom_heat_flux if bottom_heat_flux is not None else ice.bottom_heat_flux, "bottom", grid)
+    for name, value in (("snowfall", snowfall), ("PrescribedTemperature", ice.prescribed)):
+        if value is not None and not _is_number(value) and not _cell_shape_ok(value, grid):
+            raise ValueError(f"{name}: an array of shape (Ny, Nx) = {(grid.Ny, grid.Nx)} or a CenterField of the grid is needed")
+
+
+def _is_number(x):
+    return isinstance(x, (int, float, np.integer, np.floating)) and not isinstance(x, bool)
 
 
 class ValueBoundaryCondition:
@@ -64,47 +124,73 @@ class ImmersedBoundaryCondition:
 
 
 class PrescribedTemperature:
-    """HeatBoundaryConditions.PrescribedTemperature(T)."""
+    """HeatBoundaryConditions.PrescribedTemperature(T): a number, or per cell an (Ny, Nx) array / CenterField
+    (slab_sea_ice_thermodynamics.jl:83-100)."""
 
     def __init__(self, temperature):
-        self.temperature = float(temperature)
+        self.per_cell = not _is_number(temperature)
+        self.temperature = temperature if self.per_cell else float(temperature)
+
+
+class RadiativeEmission:
+    """HeatBoundaryConditions.RadiativeEmission (boundary_fluxes.jl:98-127): the top heat flux eps sigma (T + T_r)^4 at the
+    surface temperature T.  A term of top_heat_flux, alone or in a tuple; with MeltingConstrainedFluxBalance the surface
+    temperature is solved per cell by the secant method (include/csi.h, csi_heat_fluxes_set)."""
+
+    def __init__(self, emissivity=1.0, stefan_boltzmann_constant=5.67e-8, reference_temperature=273.15):
+        self.emissivity = float(emissivity)
+        self.stefan_boltzmann_constant = float(stefan_boltzmann_constant)
+        self.reference_temperature = float(reference_temperature)
 
 
 class MeltingConstrainedFluxBalance:
     """HeatBoundaryConditions.MeltingConstrainedFluxBalance (top_heat_boundary_conditions.jl:5-52): the top temperature
     balances the external and conductive fluxes, capped at the melting temperature.  On the accelerated path the
-    external flux is a number, for which the reference's secant solve has a closed-form root (include/csi.h)."""
+    external flux does not depend on the temperature unless it has a RadiativeEmission term: then the reference's secant solve
+    runs per cell, otherwise its closed-form root is used (include/csi.h)."""
 
 
 class SlabThermodynamics:
     """SlabThermodynamics of the ice layer with a PrescribedTemperature (top_temperature = number) or
     MeltingConstrainedFluxBalance (top_heat_boundary_condition) top boundary condition and IceWaterThermalEquilibrium
     at the bottom (SeaIceThermodynamics/slab_sea_ice_thermodynamics.jl:82-109); PhaseTransitions defaults
-    (SeaIceThermodynamics.jl:106-124).  Heat fluxes: numbers; top_heat_flux=None is the reference's default: for a
-    prescribed temperature the external flux in equilibrium with the internal conductive flux, otherwise 0
-    (sea_ice_model.jl:243-256); bottom_heat_flux="frazil" is the -(1 - aice) W m^-2 flux of
-    examples/freezing_bucket.jl:79-81."""
+    (SeaIceThermodynamics.jl:106-124).  Heat fluxes: a number, an (Ny, Nx) array, a CenterField, RadiativeEmission (top only) or
+    a tuple of them (summed as the reference's getflux does), here or in SeaIceModel (not both); top_heat_flux=None is the
+    reference's default: for a prescribed temperature the external flux in equilibrium with the internal conductive flux,
+    otherwise 0 (sea_ice_model.jl:243-256); bottom_heat_flux=None is 0 and "frazil" the -(1 - aice) W m^-2 flux of
+    examples/freezing_bucket.jl:79-81.  top_surface_temperature: the CenterField the model binds when the step reads or writes
+    the surface temperature per cell (None before)."""
 
-    def __init__(self, top_temperature=-10.0, conductivity=2.0, top_heat_flux=None, bottom_heat_flux=0.0,
+    def __init__(self, top_temperature=-10.0, conductivity=2.0, top_heat_flux=None, bottom_heat_flux=None,
                  heat_capacity=2000.0, density=917.0, liquid_density=999.8, liquid_heat_capacity=4186.0,
                  reference_latent_heat=334e3, reference_temperature=0.0, liquidus_slope=0.054,
                  freshwater_melting_temperature=0.0, bottom_salinity=0.0, ice_consolidation_thickness=0.05,
                  top_heat_boundary_condition=None, ice_salinity=0.0):
         self.__dict__.update(locals())
         del self.__dict__["self"]
+        self.prescribed = None            # PrescribedTemperature given per cell
         if isinstance(top_heat_boundary_condition, PrescribedTemperature):
-            self.top_temperature = top_heat_boundary_condition.temperature
+            if top_heat_boundary_condition.per_cell:
+                self.prescribed = top_heat_boundary_condition.temperature
+                self.top_temperature = 0.0
+            else:
+                self.top_temperature = top_heat_boundary_condition.temperature
         self.flux_balance = isinstance(top_heat_boundary_condition, MeltingConstrainedFluxBalance)
+        self.top_surface_temperature = None
 
-    def params(self, sea_ice_density, snow=False):
-        frazil = self.bottom_heat_flux == "frazil"
-        equilibrium = self.top_heat_flux is None and not self.flux_balance and not snow     # sea_ice_model.jl:245-256
+    def params(self, sea_ice_density, snow=False, top_heat_flux=_OWN, bottom_heat_flux=_OWN):
+        """csi_slab_params.  top_heat_flux / bottom_heat_flux: the model's resolved fluxes (default: this object's); those that
+        are not numbers travel as heat-flux terms (SeaIceModel) and leave 0 here."""
+        top = self.top_heat_flux if top_heat_flux is _OWN else top_heat_flux
+        bottom = self.bottom_heat_flux if bottom_heat_flux is _OWN else bottom_heat_flux
+        frazil = isinstance(bottom, str) and bottom == "frazil"
+        equilibrium = top is None and not self.flux_balance and not snow     # sea_ice_model.jl:245-256
         return _lib.SlabParams(self.conductivity, sea_ice_density, self.density, self.liquid_density, self.liquid_heat_capacity,
                                self.heat_capacity, self.reference_latent_heat, self.reference_temperature, self.liquidus_slope,
                                self.freshwater_melting_temperature, self.bottom_salinity, self.ice_consolidation_thickness,
                                self.top_temperature, 1 if equilibrium else 0, 1 if frazil else 0,
-                               0.0 if self.top_heat_flux is None else float(self.top_heat_flux),
-                               1.0 if frazil else float(self.bottom_heat_flux),
+                               float(top) if _is_number(top) else 0.0,
+                               1.0 if frazil else (float(bottom) if _is_number(bottom) else 0.0),
                                1 if self.flux_balance else 0, 0, float(self.ice_salinity))
 
 
@@ -116,11 +202,19 @@ class SnowSlabThermodynamics:
         self.conductivity = float(conductivity)
         self.top_heat_boundary_condition = top_heat_boundary_condition or MeltingConstrainedFluxBalance()
 
+        self.top_surface_temperature = None
+
+    @property
+    def prescribed(self):
+        """The per-cell PrescribedTemperature of the snow surface (None: a number or the flux balance)."""
+        bc = self.top_heat_boundary_condition
+        return bc.temperature if isinstance(bc, PrescribedTemperature) and bc.per_cell else None
+
     def params(self, snow_density, snowfall):
         bc = self.top_heat_boundary_condition
         prescribed = isinstance(bc, PrescribedTemperature)
-        return _lib.SnowParams(self.conductivity, float(snow_density), float(snowfall),
-                               bc.temperature if prescribed else 0.0, 0 if prescribed else 1, 0)
+        return _lib.SnowParams(self.conductivity, float(snow_density), float(snowfall) if _is_number(snowfall) else 0.0,
+                               bc.temperature if prescribed and not bc.per_cell else 0.0, 0 if prescribed else 1, 0)
 
 
 def snow_slab_thermodynamics(grid=None, conductivity=0.31, **kw):
@@ -162,7 +256,8 @@ def _dptr(a):
 class SeaIceModel:
     def __init__(self, grid, dynamics=None, advection=None, timestepper="SplitRungeKutta3", sea_ice_density=900.0,
                  ice_thermodynamics=None, snow_thermodynamics=None, snow_density=330.0, snowfall=0.0,
-                 boundary_conditions=None, forcing=None, device="cuda:0", mode="fast", stream=None):
+                 boundary_conditions=None, forcing=None, device="cuda:0", mode="fast", stream=None, top_heat_flux=None,
+                 bottom_heat_flux=None):
         self.grid = grid
         self.dynamics = dynamics
         self.advection = advection
@@ -170,7 +265,13 @@ class SeaIceModel:
         self.boundary_conditions = boundary_conditions or {}
         self.forcing = forcing          # dict(u = array-like, v = array-like): model.forcing given as arrays (m s^-2)
         self.snow_thermodynamics = snow_thermodynamics
-        self.snow_density, self.snowfall = float(snow_density), float(snowfall)
+        # snowfall: a number or per cell an (Ny, Nx) array / CenterField (thermodynamic_time_step.jl:328-334)
+        self.snow_density, self.snowfall = float(snow_density), float(snowfall) if _is_number(snowfall) else snowfall
+        # external_heat_fluxes (sea_ice_model.jl:262-264): given here or in SlabThermodynamics; _configure_heat resolves them
+        self._heat_flux_args = (top_heat_flux, bottom_heat_flux)
+        if ice_thermodynamics is not None:
+            check_heat_fluxes(grid, ice_thermodynamics, top_heat_flux, bottom_heat_flux, snowfall if snow_thermodynamics else None)
+        self.external_heat_fluxes = SimpleNamespace(top=None, bottom=None)
         if snow_thermodynamics is not None and ice_thermodynamics is None:
             raise ValueError("a snow layer needs ice_thermodynamics")
         if timestepper not in ("SplitRungeKutta3", "ForwardEuler"):
@@ -257,9 +358,6 @@ class SeaIceModel:
         if self.timestepper.Psi_minus is not None:
             pm = self.timestepper.Psi_minus
             self._bind("HM", pm.h); self._bind("AM", pm.aice); self._bind("UM", pm.u); self._bind("VM", pm.v)
-        if self.ice_thermodynamics is not None:
-            sp = self.ice_thermodynamics.params(self.sea_ice_density, snow=self.snow_thermodynamics is not None)
-            self.ctx.call("csi_slab_params_set", C.byref(sp))
         if self.snow_thermodynamics is not None:
             self._bind("HS", self.snow_thickness)
             self._bind("GHS", self.timestepper.Gn.hs)
@@ -272,6 +370,9 @@ class SeaIceModel:
             self._bind("TUS", self.snow_top_temperature)
             wp = self.snow_thermodynamics.params(self.snow_density, self.snowfall)
             self.ctx.call("csi_snow_params_set", C.byref(wp))
+            self._snow_params = wp
+        if self.ice_thermodynamics is not None:
+            self._configure_heat()
         # boundary_conditions = (u = FieldBoundaryConditions(north = ValueBoundaryCondition(0), ...), v = ...)
         for name, sides in (("U", ("south", "north")), ("V", ("west", "east"))):
             bcs = self.boundary_conditions.get(name.lower())
@@ -330,6 +431,91 @@ class SeaIceModel:
         self._set_stress(_lib.STRESS_TOP, d.external_momentum_stresses.top, "TOP")
         self._set_stress(_lib.STRESS_BOTTOM, d.external_momentum_stresses.bottom, "BOT")
         self.ctx.call("csi_free_drift_set", 1 if d.free_drift is not None else 0)
+
+    def _cell_field(self, value, name):
+        """A (Center, Center) field on the model grid from a CenterField (used as it is: writes into it reach the next step) or an
+        (Ny, Nx) array -- on a TileGrid also one of the global grid's shape, of which the tile's part is taken."""
+        g = self.grid
+        if isinstance(value, Field):
+            if value.location != (Center, Center) or (value.ni, value.nj) != tuple(g.field_size(Center, Center)):
+                raise ValueError(f"{name}: a CenterField on the model's grid is needed")
+            if value.data.device != self.device:
+                value.data = value.data.to(self.device)
+            return value
+        arr = np.asarray(value, dtype=np.float64)
+        if isinstance(g, TileGrid) and arr.shape == (g.global_grid.Ny, g.global_grid.Nx):
+            arr = arr[g.j_off:g.j_off + g.Ny, g.i_off:g.i_off + g.Nx]
+        if arr.shape != (g.Ny, g.Nx):
+            raise ValueError(f"{name}: an array of shape (Ny, Nx) = {(g.Ny, g.Nx)} is needed, got {arr.shape}")
+        fld = CenterField(g, self.device, name)
+        fld.set(arr)
+        return fld
+
+    def _heat_terms(self, spec, side):
+        """getflux's forms (boundary_fluxes.jl:8-22, 98-127) as csi_heat_flux_term entries: None for the numeric path (None, a
+        number, "frazil"), else (terms, the ARRAY term's field or None).  check_heat_flux has vetted spec."""
+        if spec is None or _is_number(spec) or isinstance(spec, str):
+            return None
+        items = spec if isinstance(spec, tuple) else (spec,)
+        terms, field = [], None
+        for x in items or (0.0,):            # getflux(()) = zero(grid)
+            t = _lib.HeatFluxTerm()
+            if _is_number(x):
+                t.kind, t.value = _lib.FLUX_CONSTANT, float(x)
+            elif isinstance(x, RadiativeEmission):
+                t.kind = _lib.FLUX_RADIATIVE_EMISSION
+                t.emissivity, t.stefan_boltzmann_constant, t.reference_temperature = (x.emissivity, x.stefan_boltzmann_constant,
+                                                                                       x.reference_temperature)
+            else:
+                field = self._cell_field(x, f"{side}_heat_flux")
+                t.kind = _lib.FLUX_ARRAY
+            terms.append(t)
+        return terms, field
+
+    def _configure_heat(self):
+        """External heat fluxes, per-cell prescribed temperature and snowfall (include/csi.h, csi_heat_fluxes_set)."""
+        ice, snow = self.ice_thermodynamics, self.snow_thermodynamics
+        top_arg, bottom_arg = self._heat_flux_args
+        top = top_arg if top_arg is not None else ice.top_heat_flux
+        bottom = bottom_arg if bottom_arg is not None else ice.bottom_heat_flux
+        sp = ice.params(self.sea_ice_density, snow=snow is not None, top_heat_flux=top, bottom_heat_flux=bottom)
+        self.ctx.call("csi_slab_params_set", C.byref(sp))
+        self._slab_params = sp
+        fields = {}
+        for side, spec, slot, k in (("top", top, "TOP_HEAT_FLUX", _lib.HEAT_TOP), ("bottom", bottom, "BOTTOM_HEAT_FLUX", _lib.HEAT_BOTTOM)):
+            got = self._heat_terms(spec, side)
+            if got is None:
+                self.ctx.call("csi_heat_fluxes_set", k, None, 0)
+                setattr(self.external_heat_fluxes, side, spec)
+                continue
+            terms, fld = got
+            arr = (_lib.HeatFluxTerm * len(terms))(*terms)
+            self._keep.append(arr)
+            if fld is not None:
+                self._bind(slot, fld)
+            self.ctx.call("csi_heat_fluxes_set", k, arr, len(terms))
+            setattr(self.external_heat_fluxes, side, fld if fld is not None else spec)
+            fields[side] = got
+        prescribed = snow.prescribed if snow is not None else ice.prescribed
+        snowfall_array = snow is not None and not _is_number(self.snowfall)
+        if snowfall_array:
+            self.snowfall = self._cell_field(self.snowfall, "snowfall")
+            self._bind("SNOWFALL", self.snowfall)
+        ss = _lib.SurfaceSolve(1e-3, 1000, int(prescribed is not None), int(snowfall_array), 0)
+        self.ctx.call("csi_surface_solve_set", C.byref(ss))
+        # top_surface_temperature (top_heat_boundary_conditions.jl:82-100): state that starts at 0 wherever the step reads or writes it
+        if snow is not None:
+            if prescribed is not None:
+                if isinstance(prescribed, Field):
+                    self.snow_top_temperature = self._cell_field(prescribed, "Tu_snow")
+                    self._bind("TUS", self.snow_top_temperature)
+                else:
+                    self.snow_top_temperature.set(self._cell_field(prescribed, "Tu_snow").interior_numpy())
+            ice.top_surface_temperature, snow.top_surface_temperature = self.ice_top_temperature, self.snow_top_temperature
+        elif prescribed is not None or (ice.flux_balance and fields):
+            tu = self._cell_field(prescribed, "Tu") if prescribed is not None else CenterField(self.grid, self.device, "Tu")
+            self.ice_top_temperature = ice.top_surface_temperature = tu
+            self._bind("TU", tu)
 
     def _init_tiles(self, g):
         """csi_tile_set + RCCL communicator: rank 0 makes the unique id, the host broadcasts it
@@ -600,13 +786,10 @@ def time_step(model, dt):
         # (sea_ice_fe_step.jl:13-34 with time_step_momentum!, compute_tendencies! and dynamic_time_step! no-ops)
         if model.ice_thermodynamics is None:
             raise NotImplementedError("a model without dynamics, advection and thermodynamics has nothing to step")
-        snow = model.snow_thermodynamics
-        sp = model.ice_thermodynamics.params(model.sea_ice_density, snow=snow is not None)
-        if snow is None:
-            model.ctx.call("csi_slab_thermo_step", C.byref(sp), float(dt))
+        if model.snow_thermodynamics is None:
+            model.ctx.call("csi_slab_thermo_step", C.byref(model._slab_params), float(dt))
         else:
-            wp = snow.params(model.snow_density, model.snowfall)
-            model.ctx.call("csi_layered_thermo_step", C.byref(sp), C.byref(wp), float(dt))
+            model.ctx.call("csi_layered_thermo_step", C.byref(model._slab_params), C.byref(model._snow_params), float(dt))
         model.ctx.call("csi_update_state")
     elif model.timestepper_kind == "ForwardEuler":
         model.ctx.call("csi_time_step_fe", float(dt), model.substeps, model.scheme, int(model.clock.iteration == 0))

@@ -132,8 +132,9 @@ typedef enum {
     CSI_F_HSM,        /* (c,c) timestepper.Psi^-.hs */
     CSI_F_MASS_FLUX_SNOW,   /* (c,c) mass_fluxes.thermodynamics.snow (optional) */
     CSI_F_SNOWFALL_INTERCEPTED, /* (c,c) mass_fluxes.intercepted_snowfall (optional) */
-    CSI_F_TU,         /* (c,c) ice_thermodynamics.top_surface_temperature (optional output) */
-    CSI_F_TUS,        /* (c,c) snow_thermodynamics.top_surface_temperature (optional output) */
+    CSI_F_TU,         /* (c,c) ice_thermodynamics.top_surface_temperature (optional output; read-write state under
+                       * csi_heat_fluxes_set / csi_surface_solve_set, see there) */
+    CSI_F_TUS,        /* (c,c) snow_thermodynamics.top_surface_temperature (likewise) */
     CSI_F_FORCING_U,  /* (f,c) model.forcing.u given as an array: the `user_forcing` of sum_of_forcing_u
                        * (elasto_visco_plastic_rheology.jl:391-395), an acceleration in m s^-2; optional, both or neither */
     CSI_F_FORCING_V,  /* (c,f) model.forcing.v (:397-401) */
@@ -141,6 +142,14 @@ typedef enum {
     CSI_F_GV,         /* (c,f) timestepper.G^n.v */
     CSI_F_COUNT
 } csi_field_id;
+/* Further (c,c) slots of csi_field_bind: the thermodynamics' per-cell inputs (csi_heat_fluxes_set, csi_surface_solve_set).  They are
+ * numbered from CSI_F_COUNT on, so that csi_field_id and CSI_F_COUNT keep their values. */
+typedef enum {
+    CSI_F_TOP_HEAT_FLUX = CSI_F_COUNT,   /* the ARRAY term of the top heat flux, W m^-2 */
+    CSI_F_BOTTOM_HEAT_FLUX,              /* the ARRAY term of the bottom heat flux */
+    CSI_F_SNOWFALL,                      /* per-cell snowfall, kg m^-2 s^-1 (csi_surface_solve.snowfall_array) */
+    CSI_F_COUNT_ALL
+} csi_thermo_field_id;
 
 typedef enum { CSI_PRESSURE_REPLACEMENT = 0, CSI_PRESSURE_ICE_STRENGTH = 1 } csi_pressure_kind;
 
@@ -348,6 +357,58 @@ int32_t csi_slab_thermo_step(csi_context* ctx, const csi_slab_params* p, double 
 /* Make csi_time_step_fe / csi_time_step_rk3 run the slab step where the reference does (after the tracer update of
  * every stage: sea_ice_fe_step.jl:28, sea_ice_rk_substep.jl:91).  NULL removes it. */
 int32_t csi_slab_params_set(csi_context* ctx, const csi_slab_params* p);
+
+/* ---- per-cell heat fluxes, RadiativeEmission and the surface-temperature solve ---------------------------------------------
+ * External heat fluxes as the reference's getflux reads them (SeaIceThermodynamics/HeatBoundaryConditions/boundary_fluxes.jl):
+ *   CONSTANT            a Number, `value` (:8)
+ *   ARRAY               a 2-D array / Field read at [i, j] (:9-12): the (c,c) array bound to CSI_F_TOP_HEAT_FLUX / _BOTTOM_
+ *   RADIATIVE_EMISSION  RadiativeEmission(emissivity, stefan_boltzmann_constant, reference_temperature) (:98-127):
+ *                       (eps * sigma) * P at the surface temperature T, P = (T + T_r)^4 evaluated as (x * x) * (x * x) with
+ *                       x = T + T_r, uncontracted.  DEPARTURE: Julia's Float64 ^ 4 is a compensated power, so the last bit of P
+ *                       may differ from a Julia run.
+ * n terms form a Tuple, summed RIGHT-nested as getflux(::Tuple) does (:15-22): t0 + (t1 + (t2 + ...)); n = 1 is the term alone.
+ * Rules: at most one ARRAY term per side, RADIATIVE_EMISSION at the top only, n <= CSI_MAX_HEAT_FLUX_TERMS; a side with terms
+ * excludes the numeric kinds of csi_slab_params on that side (top_flux_kind 1, the frazil bottom_flux_kind 1: CSI_ERR_UNSUPPORTED).
+ * terms == NULL or n == 0 removes a side's terms: that side returns to csi_slab_params' numbers, and with no terms on either side,
+ * no per-cell temperature and no snowfall array the thermodynamic steps run exactly the kernels they run without these calls.
+ *
+ * Where the fluxes enter (thermodynamic_tendency, slab_thermodynamics_tendencies.jl:74-135; _layered_thermodynamic_time_step!,
+ * thermodynamic_time_step.jl:131-298): under MeltingConstrainedFluxBalance (top_bc_kind 1) a consolidated cell (h >= h_c) solves
+ * Qx(T) - Qi(T) = 0 for the surface temperature, Qi the slab's conductive flux (with snow: resistors in series), caps the root
+ * at Tm (the ice's melting temperature; 0 where there is snow) and WRITES it to CSI_F_TU (bare ice) / CSI_F_TUS (snow surface);
+ * an unconsolidated cell writes Tb.  Both external fluxes are then evaluated once at that temperature.
+ *   - Without an emission term Qx does not depend on T: the root is the closed form Tb - Qx R of the numeric path, Qx per cell.
+ *   - With one the secant solve of top_heat_boundary_conditions.jl:82-100, find_zero(f, SecantMethod(Tu- + 1, Tu-)), runs per
+ *     consolidated cell from Tu- = the value the bound CSI_F_TU / CSI_F_TUS holds.  RECALLED (RootSolvers is not vendored):
+ *         x0 = Tu- + 1; x1 = Tu-; y0 = f(x0); y1 = f(x1)
+ *         repeat maxiters times: dx = x1 - x0; dy = y1 - y0; x0 = x1; y0 = y1; x1 = x1 - y1 * dx / dy; y1 = f(x1);
+ *                                stop if |x1 - x0| < tol
+ *         root = x1 (also when not converged)
+ *     tol and maxiters are csi_surface_solve's (defaults 1e-3 and 1000, the recalled SolutionTolerance and maxiters).
+ * With a PrescribedTemperature top (top_bc_kind 0) and prescribed_array = 1 the surface temperature is read per cell from
+ * CSI_F_TU (bare ice) / CSI_F_TUS (snow) instead of top_temperature.  The arithmetic follows the reference's order without
+ * contraction in STRICT and FAST alike. */
+typedef enum { CSI_FLUX_CONSTANT = 0, CSI_FLUX_ARRAY = 1, CSI_FLUX_RADIATIVE_EMISSION = 2 } csi_heat_flux_kind;
+typedef enum { CSI_HEAT_TOP = 0, CSI_HEAT_BOTTOM = 1 } csi_heat_flux_side;
+#define CSI_MAX_HEAT_FLUX_TERMS 8
+typedef struct {
+    int32_t kind;                      /* csi_heat_flux_kind */
+    int32_t reserved;
+    double value;                      /* CONSTANT */
+    double emissivity;                 /* RADIATIVE_EMISSION: 1 */
+    double stefan_boltzmann_constant;  /*                     5.67e-8 */
+    double reference_temperature;      /*                     273.15 */
+} csi_heat_flux_term;
+int32_t csi_heat_fluxes_set(csi_context* ctx, int32_t side, const csi_heat_flux_term* terms, int32_t n);
+typedef struct {
+    double tol;                        /* the secant's |x1 - x0| tolerance, > 0 (1e-3) */
+    int32_t maxiters;                  /* >= 1 (1000) */
+    int32_t prescribed_array;          /* 1: PrescribedTemperature per cell, read from CSI_F_TU / CSI_F_TUS */
+    int32_t snowfall_array;            /* 1: the layered step reads snowfall per cell from CSI_F_SNOWFALL */
+    int32_t reserved;
+} csi_surface_solve;
+/* NULL restores the defaults. */
+int32_t csi_surface_solve_set(csi_context* ctx, const csi_surface_solve* p);
 
 /* ---- multi-GPU tiles (one process per GPU; RCCL point-to-point over xGMI) ----------------- */
 /* Position of this context's tile in an Rx x Ry decomposition of a global grid; the
