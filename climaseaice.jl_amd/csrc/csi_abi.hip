@@ -142,9 +142,6 @@ int32_t csi_context_create(int32_t device_id, void* hip_stream, csi_context** ou
         { const int v = env_int("CSI_TILE_SKIPPING"); if (v >= 0) c->act.enabled = v != 0; }      // A/B: the defaults of csi_set_tile_skipping / csi_set_row_constant
         { const int v = env_int("CSI_ROW_CONSTANT"); if (v >= 0) c->rc_enabled = v != 0; }
         c->tune.band_fused = env_int("CSI_BAND_FUSED"); c->tune.band_event_flags = env_int("CSI_BAND_EVENT_FLAGS");
-        c->tune.band_cus = env_int("CSI_BAND_CUS"); c->tune.band_cus_share = env_int("CSI_BAND_CUS_SHARE");
-        c->tune.exp_band_only = env_int("CSI_EXP_BAND_ONLY");
-        c->tune.exp_overlap = env_int("CSI_EXP_OVERLAP");    // timing experiment, tiles connected to themselves only (scripts/tile_overlap_dependent.py)
         c->tune.peer_kernel = env_int("CSI_PEER_KERNEL");      // 1: untiled grids run the PEER instantiation of the pair kernel (no neighbour, no waits): what the instantiation itself costs
     }
     *out = c;
@@ -155,47 +152,18 @@ int32_t csi_context_destroy(csi_context* c) {
     if (!c) return CSI_OK;
     hipSetDevice(c->device);
     hipStreamSynchronize(c->stream);
-    if (c->dev_metrics) hipFree(c->dev_metrics);
-    if (c->dev_fcor) hipFree(c->dev_fcor);
-    if (c->dev_fcor2) hipFree(c->dev_fcor2);
     peer_release(c);
-    if (c->peer.slots) hipFree(c->peer.slots);
-    if (c->peer.err) hipFree(c->peer.err);
-    if (c->peer.err_host) hipHostFree(c->peer.err_host);
-    if (c->peer.xbuf) hipFree(c->peer.xbuf);
-    if (c->dev_coef2) hipFree(c->dev_coef2);
-    if (c->dev_c2row) hipFree(c->dev_c2row);
-    if (c->dev_rcsum) hipFree(c->dev_rcsum);
-    if (c->act.flags) hipFree(c->act.flags);
-    if (c->act.list) hipFree(c->act.list);
-    if (c->act.list0) hipFree(c->act.list0);
-    if (c->act.host) hipHostFree(c->act.host);
-    if (c->host_ring) hipHostFree(c->host_ring);
     for (auto& e : c->ring_ev) if (e) hipEventDestroy(e);
-    if (c->dev_coef) hipFree(c->dev_coef);
-    for (int k = 0; k < 5; ++k) if (c->alt[k]) hipFree(c->alt[k]);
-    for (int k = 0; k < 4; ++k) if (c->adv_buf[k]) hipFree(c->adv_buf[k]);
-    for (int k = 0; k < 9; ++k) if (c->band[k]) hipFree(c->band[k]);
     if (c->band_ev_pair) hipEventDestroy(c->band_ev_pair);
     if (c->band_ev_band) hipEventDestroy(c->band_ev_band);
     if (c->band_stream) hipStreamDestroy(c->band_stream);
-    if (c->pair_stream) hipStreamDestroy(c->pair_stream);
-    for (hipEvent_t e : c->exp_ev) if (e) hipEventDestroy(e);
-    for (int k = 0; k < 2; ++k) if (c->fbar[k]) hipFree(c->fbar[k]);
-    for (int k = 0; k < 2; ++k) if (c->fbar_top[k]) hipFree(c->fbar_top[k]);
-    for (int k = 0; k < 2; ++k) if (c->fd[k]) hipFree(c->fd[k]);
-    for (int k = 0; k < 2; ++k) if (c->vis_alt[k]) hipFree(c->vis_alt[k]);
-    for (int k = 0; k < 2; ++k) if (c->xd[k]) hipFree(c->xd[k]);
-    if (c->dev_tables) hipFree(c->dev_tables);
-    if (c->sendbuf) hipFree(c->sendbuf);
-    if (c->recvbuf) hipFree(c->recvbuf);
     if (c->comm) ncclCommDestroy(c->comm);
     if (c->hostg) hostgroup_leave(c->hostg);
     for (hipEvent_t e : c->stats.ev) hipEventDestroy(e);
     if (c->ev0) hipEventDestroy(c->ev0);
     if (c->ev1) hipEventDestroy(c->ev1);
     if (c->own_stream) hipStreamDestroy(c->stream);
-    delete c;
+    delete c;               // (every array the library allocated: freed by its owner, csi_mem.h -- the stream was drained above)
     return CSI_OK;
 }
 
@@ -212,7 +180,7 @@ int32_t csi_context_destroy(csi_context* c) {
 static int32_t peer_check(csi_context* c);
 extern "C++" { namespace csi_host { int32_t peer_check_entry(csi_context* c) { return peer_check(c); } } }
 static int32_t peer_check(csi_context* c) {
-    if (c->peer.err_host && *c->peer.err_host) c->peer.aborted = true;
+    if (c->peer.err_host && *c->peer.err_host.get()) c->peer.aborted = true;
     if (c->peer.aborted)
         return fail(c, CSI_ERR_COMM, "peer halo transport: a tile waited 3 s for its neighbour's flags and gave up (or a neighbouring rank did) -- the results of "
                                      "that sub-cycle are invalid (a rank that fell behind or died) and the transport stays refused until EVERY rank has called "
@@ -231,7 +199,7 @@ int32_t csi_debug_peer_abort(csi_context* c) {
     if (!c) return CSI_ERR_INVALID_ARGUMENT;
     if (!c->peer.err_host) return fail(c, CSI_ERR_NOT_BOUND, "the peer transport has not been set up");
     HIP_TRY(c, hipStreamSynchronize(c->stream));
-    *c->peer.err_host = 1u;
+    *c->peer.err_host.get() = 1u;
     return CSI_OK;
 }
 // csi_sync on every rank + the transport's status reduced over ALL ranks (collective: every rank of the communicator calls it
@@ -240,7 +208,7 @@ int32_t csi_debug_peer_abort(csi_context* c) {
 int32_t csi_validate_all(csi_context* c) {
     if (!c) return CSI_ERR_INVALID_ARGUMENT;
     HIP_TRY(c, hipStreamSynchronize(c->stream));
-    int bad = (c->peer.aborted || (c->peer.err_host && *c->peer.err_host)) ? 1 : 0;
+    int bad = (c->peer.aborted || (c->peer.err_host && *c->peer.err_host.get())) ? 1 : 0;
     int32_t rc;
     if ((rc = comm_allreduce_max(c, &bad))) return rc;
     if (bad) c->peer.aborted = true;
@@ -308,7 +276,7 @@ int32_t csi_grid_set(csi_context* c, int32_t Nx, int32_t Ny, int32_t Hx, int32_t
     g.metric_kind = metric_kind;
     g.dx = m->dx; g.dy = m->dy;
     HIP_TRY(c, hipStreamSynchronize(c->stream));      // kernels still in flight may read the tables freed below
-    if (c->dev_metrics) { hipFree(c->dev_metrics); c->dev_metrics = nullptr; }
+    c->dev_metrics.release();
     if (metric_kind == CSI_METRIC_PER_J) {
         if (!m->dxc || !m->dxf || !m->azc || !m->azf) return fail(c, CSI_ERR_INVALID_ARGUMENT, "PER_J metrics need dxc, dxf, azc, azf");
         const size_t n = (size_t)Ny + 2 * (size_t)Hy + 1;
@@ -319,9 +287,9 @@ int32_t csi_grid_set(csi_context* c, int32_t Nx, int32_t Ny, int32_t Hx, int32_t
                 host[k * n + t] = src[k][t];
                 host[(4 + k) * n + t] = 1.0 / src[k][t];
             }
-        HIP_TRY(c, hipMalloc((void**)&c->dev_metrics, sizeof(double) * 8 * n));
-        HIP_TRY(c, hipMemcpy(c->dev_metrics, host.data(), sizeof(double) * 8 * n, hipMemcpyHostToDevice));
-        const double* base = c->dev_metrics + (Hy - 1);   // so that ptr[j] is row j
+        HIP_TRY(c, c->dev_metrics.alloc(8 * n));
+        HIP_TRY(c, hipMemcpy(c->dev_metrics.get(), host.data(), sizeof(double) * 8 * n, hipMemcpyHostToDevice));
+        const double* base = c->dev_metrics.get() + (Hy - 1);   // so that ptr[j] is row j
         g.dxc = base; g.dxf = base + n; g.azc = base + 2 * n; g.azf = base + 3 * n;
         g.rdxc = base + 4 * n; g.rdxf = base + 5 * n; g.razc = base + 6 * n; g.razf = base + 7 * n;
     }
@@ -334,9 +302,9 @@ int32_t csi_grid_set(csi_context* c, int32_t Nx, int32_t Ny, int32_t Hx, int32_t
             for (int64_t r = 0; r < nj; ++r)
                 for (int64_t q = 0; q < ni; ++q) host[(size_t)((k * nj + r) * ni + q)] = m->full[k][r * m->full_ld + q];
         }
-        HIP_TRY(c, hipMalloc((void**)&c->dev_metrics, sizeof(double) * host.size()));
-        HIP_TRY(c, hipMemcpy(c->dev_metrics, host.data(), sizeof(double) * host.size(), hipMemcpyHostToDevice));
-        g.m2 = c->dev_metrics + (Hx - 1) + (int64_t)(Hy - 1) * ni;      // so that m2[k * plane + i + j * ld] is (i, j)
+        HIP_TRY(c, c->dev_metrics.alloc(host.size()));
+        HIP_TRY(c, hipMemcpy(c->dev_metrics.get(), host.data(), sizeof(double) * host.size(), hipMemcpyHostToDevice));
+        g.m2 = origin_of(c, c->dev_metrics.get(), ni);      // so that m2[k * plane + i + j * ld] is (i, j)
         g.m2_plane = (long)(ni * nj);
         g.m2_ld = (int)ni;
         // FAST mode: per-point stencil coefficients (three-kernel path)
@@ -344,9 +312,8 @@ int32_t csi_grid_set(csi_context* c, int32_t Nx, int32_t Ny, int32_t Hx, int32_t
         const double* planes[12];
         for (int k = 0; k < 12; ++k) planes[k] = host.data() + (size_t)k * ni * nj;
         build_fast_coef_full((int)ni, (int)nj, planes, coef2);
-        if (c->dev_coef2) { hipFree(c->dev_coef2); c->dev_coef2 = nullptr; }
-        HIP_TRY(c, hipMalloc((void**)&c->dev_coef2, sizeof(double) * coef2.size()));
-        HIP_TRY(c, hipMemcpy(c->dev_coef2, coef2.data(), sizeof(double) * coef2.size(), hipMemcpyHostToDevice));
+        HIP_TRY(c, c->dev_coef2.alloc(coef2.size()));
+        HIP_TRY(c, hipMemcpy(c->dev_coef2.get(), coef2.data(), sizeof(double) * coef2.size(), hipMemcpyHostToDevice));
         c->coef2_host.swap(coef2);      // (row-constant marks: ensure_row_constant)
     } else {
         c->coef2_host.clear();
@@ -354,9 +321,9 @@ int32_t csi_grid_set(csi_context* c, int32_t Nx, int32_t Ny, int32_t Hx, int32_t
     c->fcor2_host.clear();
     c->rc_dirty = true;
     // FAST-mode stencil coefficients
-    if (c->dev_coef) { hipFree(c->dev_coef); c->dev_coef = nullptr; }
-    if (c->dev_fcor) { hipFree(c->dev_fcor); c->dev_fcor = nullptr; }
-    if (c->dev_fcor2) { hipFree(c->dev_fcor2); c->dev_fcor2 = nullptr; }
+    c->dev_coef.release();
+    c->dev_fcor.release();
+    c->dev_fcor2.release();
     c->coef_host.clear(); c->fcor_rows[0].clear(); c->fcor_rows[1].clear();
     c->cor_dirty = true;
     c->coef = FastCoef{};
@@ -364,7 +331,7 @@ int32_t csi_grid_set(csi_context* c, int32_t Nx, int32_t Ny, int32_t Hx, int32_t
     if (metric_kind == CSI_METRIC_FULL) {
         const int64_t ni = (int64_t)Nx + 2 * Hx + 1, nj = (int64_t)Ny + 2 * Hy + 1;
         c->coef.full = 1;
-        c->coef.c2 = c->dev_coef2 + (Hx - 1) + (int64_t)(Hy - 1) * ni;
+        c->coef.c2 = origin_of(c, c->dev_coef2.get(), ni);
         c->coef.c2_plane = (long)(ni * nj);
         c->coef.c2_ld = (int)ni;
     }
@@ -387,7 +354,7 @@ int32_t csi_mask_set(csi_context* c, const uint8_t* dev_mask, int64_t ld) {
     if (!c->grid_set) return fail(c, CSI_ERR_NOT_BOUND, "csi_grid_set has not been called");
     if (!dev_mask) { c->g.mask = nullptr; c->g.has_mask = 0; c->g.mask_ld = 0; return CSI_OK; }
     if (ld < c->Nx + 2 * c->Hx) return fail(c, CSI_ERR_INVALID_ARGUMENT, "mask ld too small");
-    c->g.mask = dev_mask + (c->Hx - 1) + (int64_t)(c->Hy - 1) * ld;
+    c->g.mask = origin_of(c, dev_mask, ld);
     c->g.mask_ld = (int)ld;
     c->g.has_mask = 1;
     return CSI_OK;
@@ -444,7 +411,7 @@ int32_t csi_coriolis_rows_set(csi_context* c, const double* f_u, const double* f
     HIP_TRY(c, hipSetDevice(c->device));
     HIP_TRY(c, hipStreamSynchronize(c->stream));
     c->cor_dirty = true;
-    if (c->dev_fcor) { hipFree(c->dev_fcor); c->dev_fcor = nullptr; }
+    c->dev_fcor.release();
     c->fcor_rows[0].clear(); c->fcor_rows[1].clear();
     if (!f_u) return CSI_OK;
     const int need = c->Ny + 2 * c->Hy + 1;
@@ -452,8 +419,8 @@ int32_t csi_coriolis_rows_set(csi_context* c, const double* f_u, const double* f
     c->fcor_rows[0].assign(f_u, f_u + n); c->fcor_rows[1].assign(f_v, f_v + n);
     std::vector<double> host(2 * (size_t)n);
     for (int t = 0; t < n; ++t) { host[t] = f_u[t]; host[(size_t)n + t] = f_v[t]; }
-    HIP_TRY(c, hipMalloc((void**)&c->dev_fcor, sizeof(double) * host.size()));
-    HIP_TRY(c, hipMemcpy(c->dev_fcor, host.data(), sizeof(double) * host.size(), hipMemcpyHostToDevice));
+    HIP_TRY(c, c->dev_fcor.alloc(host.size()));
+    HIP_TRY(c, hipMemcpy(c->dev_fcor.get(), host.data(), sizeof(double) * host.size(), hipMemcpyHostToDevice));
     return CSI_OK;
 }
 
@@ -463,7 +430,7 @@ int32_t csi_coriolis_points_set(csi_context* c, const double* f_u, const double*
     if ((f_u == nullptr) != (f_v == nullptr)) return fail(c, CSI_ERR_INVALID_ARGUMENT, "f_u and f_v: both or neither");
     HIP_TRY(c, hipSetDevice(c->device));
     HIP_TRY(c, hipStreamSynchronize(c->stream));
-    if (c->dev_fcor2) { hipFree(c->dev_fcor2); c->dev_fcor2 = nullptr; }
+    c->dev_fcor2.release();
     c->fcor2_host.clear();
     c->rc_dirty = true;
     if (!f_u) return CSI_OK;
@@ -474,8 +441,8 @@ int32_t csi_coriolis_points_set(csi_context* c, const double* f_u, const double*
     std::vector<double> host(2 * (size_t)ni * nj);
     for (long b = 0; b < nj; ++b)
         for (long a = 0; a < ni; ++a) { host[a + b * ni] = f_u[a + b * ld]; host[(size_t)ni * nj + a + b * ni] = f_v[a + b * ld]; }
-    HIP_TRY(c, hipMalloc((void**)&c->dev_fcor2, sizeof(double) * host.size()));
-    HIP_TRY(c, hipMemcpy(c->dev_fcor2, host.data(), sizeof(double) * host.size(), hipMemcpyHostToDevice));
+    HIP_TRY(c, c->dev_fcor2.alloc(host.size()));
+    HIP_TRY(c, hipMemcpy(c->dev_fcor2.get(), host.data(), sizeof(double) * host.size(), hipMemcpyHostToDevice));
     c->fcor2_ld = ni; c->fcor2_plane = ni * nj;
     c->fcor2_host.swap(host);
     return CSI_OK;
@@ -622,20 +589,14 @@ bool advect_stage_supported(const csi_context* c, int scheme) {
 int32_t rk3_advection_only(csi_context* c, double dt, int scheme) {
     int32_t rc;
     if ((rc = need(c, {CSI_F_U, CSI_F_V, CSI_F_H, CSI_F_A, CSI_F_GH, CSI_F_GA, CSI_F_HM, CSI_F_AM}))) return rc;
-    const int src[4] = {CSI_F_H, CSI_F_A, CSI_F_H, CSI_F_A};
-    for (int q = 0; q < 4; ++q) {
-        const Bound& b = c->f[src[q]];
-        const size_t n = (size_t)b.ld * (size_t)b.nj;
-        if (c->adv_elems[q] != n) {
-            if (c->adv_buf[q]) { HIP_TRY(c, hipStreamSynchronize(c->stream)); hipFree(c->adv_buf[q]); c->adv_buf[q] = nullptr; }
-            HIP_TRY(c, hipMalloc((void**)&c->adv_buf[q], n * sizeof(double)));
-            // beyond walls the halo holds mirror images the stores rewrite; cells nobody writes (wall corners) start as the state's
-            HIP_TRY(c, hipMemcpyAsync(c->adv_buf[q], b.p, n * sizeof(double), hipMemcpyDeviceToDevice, c->stream));
-            c->adv_elems[q] = n;
-        }
+    for (ScratchField& s : c->adv_buf) {
+        bool fresh;
+        HIP_TRY(c, s.ensure(c, nullptr, &fresh));
+        // beyond walls the halo holds mirror images the stores rewrite; cells nobody writes (wall corners) start as the state's
+        if (fresh) HIP_TRY(c, hipMemcpyAsync(s.get(), c->f[s.fid].p, s.buf.size() * sizeof(double), hipMemcpyDeviceToDevice, c->stream));
     }
-    auto buf = [&](int q) { FRef r; const Bound& b = c->f[src[q]]; r.p = c->adv_buf[q] + (c->Hx - 1) + (int64_t)(c->Hy - 1) * b.ld; r.ld = (int)b.ld; return r; };
-    const FRef H0 = ref_of(c, CSI_F_H), A0 = ref_of(c, CSI_F_A), H1 = buf(0), A1 = buf(1), H2 = buf(2), A2 = buf(3);
+    const FRef H0 = ref_of(c, CSI_F_H), A0 = ref_of(c, CSI_F_A), H1 = c->adv_buf[0].view(c), A1 = c->adv_buf[1].view(c),
+               H2 = c->adv_buf[2].view(c), A2 = c->adv_buf[3].view(c);
     const FRef hin[3] = {H0, H1, H2}, ain[3] = {A0, A1, A2}, hout[3] = {H1, H2, H0}, aout[3] = {A1, A2, A0};
     int stage = 0;
     for (int beta = 3; beta >= 1; --beta, ++stage) {
@@ -750,7 +711,7 @@ int32_t csi_tile_set(csi_context* c, int32_t rx, int32_t ry, int32_t Rx, int32_t
     c->tile.rx = rx; c->tile.ry = ry; c->tile.Rx = Rx; c->tile.Ry = Ry;
     c->tile.periodic_x = periodic_x != 0; c->tile.periodic_y = periodic_y != 0;
     c->tile.set = true;
-    peer_release(c); c->peer.failed = false; c->peer.aborted = false; if (c->peer.err_host) *c->peer.err_host = 0;           // (the neighbours may be other ranks now)
+    peer_release(c); c->peer.failed = false; c->peer.aborted = false; if (c->peer.err_host) *c->peer.err_host.get() = 0;           // (the neighbours may be other ranks now)
     return CSI_OK;
 }
 
@@ -771,7 +732,7 @@ int32_t csi_comm_init(csi_context* c, int32_t world_size, int32_t rank, const ui
     if (c->comm) { ncclCommDestroy(c->comm); c->comm = nullptr; }
     if (c->hostg) { hostgroup_leave(c->hostg); c->hostg = nullptr; }
     c->local = nullptr;
-    peer_release(c); c->peer.failed = false; c->peer.aborted = false; if (c->peer.err_host) *c->peer.err_host = 0;           // (mappings of the previous communicator's neighbours)
+    peer_release(c); c->peer.failed = false; c->peer.aborted = false; if (c->peer.err_host) *c->peer.err_host.get() = 0;           // (mappings of the previous communicator's neighbours)
     ncclUniqueId id;
     memcpy(&id, id128, 128);
     NCCL_TRY(c, ncclCommInitRank(&c->comm, world_size, id, rank));
@@ -797,7 +758,7 @@ int32_t csi_comm_init_local(csi_context* c, csi_local_group* G, int32_t rank) {
     if (rank < 0 || rank >= G->world) return fail(c, CSI_ERR_INVALID_ARGUMENT, "rank out of range for this group");
     if (c->comm) { ncclCommDestroy(c->comm); c->comm = nullptr; }
     if (c->hostg) { hostgroup_leave(c->hostg); c->hostg = nullptr; }
-    peer_release(c); c->peer.failed = false; c->peer.aborted = false; if (c->peer.err_host) *c->peer.err_host = 0;
+    peer_release(c); c->peer.failed = false; c->peer.aborted = false; if (c->peer.err_host) *c->peer.err_host.get() = 0;
     c->local = G;
     c->world = G->world; c->rank = rank;
     // The peer transport's kernels wait for flags the OTHER tiles' kernels of this process publish.  HIP maps streams onto
@@ -825,12 +786,12 @@ int32_t csi_comm_init_host(csi_context* c, const char* shm_name, int32_t world_s
     if (c->comm) { ncclCommDestroy(c->comm); c->comm = nullptr; }
     if (c->hostg) { hostgroup_leave(c->hostg); c->hostg = nullptr; }
     c->local = nullptr;
-    peer_release(c); c->peer.failed = false; c->peer.aborted = false; if (c->peer.err_host) *c->peer.err_host = 0;
+    peer_release(c); c->peer.failed = false; c->peer.aborted = false; if (c->peer.err_host) *c->peer.err_host.get() = 0;
     std::string e;
     c->hostg = hostgroup_join(shm_name, world_size, rank, &e);
     if (!c->hostg) return fail(c, CSI_ERR_COMM, e);
     c->world = world_size; c->rank = rank;
-    if (c->sendbuf && !hostgroup_set_sendbuf(c->hostg, c->sendbuf, c->buf_cap * sizeof(double), &c->err)) return CSI_ERR_COMM;
+    if (c->sendbuf && !hostgroup_set_sendbuf(c->hostg, c->sendbuf.get(), c->sendbuf.size() * sizeof(double), &c->err)) return CSI_ERR_COMM;
     return CSI_OK;
 }
 int32_t csi_comm_count(csi_context* c, int32_t* ranks) {
@@ -928,8 +889,8 @@ int32_t csi_set_halo_transport(csi_context* c, int32_t kind) {
         // aborted launches are over), the mappings go, and the next sub-cycle on the peer transport runs the collective set-up.
         HIP_TRY(c, hipStreamSynchronize(c->stream));
         peer_release(c);
-        if (c->peer.err_host) *c->peer.err_host = 0;
-        if (c->peer.err) HIP_TRY(c, hipMemset(c->peer.err, 0, sizeof(unsigned)));
+        if (c->peer.err_host) *c->peer.err_host.get() = 0;
+        if (c->peer.err) HIP_TRY(c, hipMemset(c->peer.err.get(), 0, sizeof(unsigned)));
         c->peer.aborted = false;
         c->peer.last = 0;
     }
@@ -985,7 +946,7 @@ int32_t csi_plan_pair(int32_t Nx, int32_t Ny, int32_t Hx, int32_t Hy, int32_t to
     return CSI_OK;
 }
 
-int32_t csi_plan_peer_chunks(int32_t Nx, int32_t Ny, int32_t Hx, int32_t Hy, int32_t peer_south, int32_t peer_north, int32_t cus,
+int32_t csi_plan_peer_chunks(int32_t Nx, int32_t Ny, int32_t Hx, int32_t Hy, int32_t peer_south, int32_t peer_north, int32_t /*cus*/,
                              int32_t* out8, int32_t* rows_out, int32_t max_chunks) {
     if (!out8 || !rows_out || Nx < 1 || Ny < 1 || max_chunks < 1) return CSI_ERR_INVALID_ARGUMENT;
     csi_context tmp;
@@ -997,7 +958,6 @@ int32_t csi_plan_peer_chunks(int32_t Nx, int32_t Ny, int32_t Hx, int32_t Hy, int
     for (int d = 0; d < 8; ++d) tmp.peer.sync_rank[d] = -1;
     if (peer_south) tmp.peer.sync_rank[2] = 0;
     if (peer_north) tmp.peer.sync_rank[3] = 0;
-    (void)cus;
     memset(out8, 0, 8 * sizeof(int32_t));
     if (!pair_supported(&tmp)) return CSI_OK;
     const Range dec = v_stress_range(&tmp, pair_side_v(&tmp, 2, 2));
@@ -1005,63 +965,6 @@ int32_t csi_plan_peer_chunks(int32_t Nx, int32_t Ny, int32_t Hx, int32_t Hy, int
     const PeerSets ps = peer_wait_counts(&tmp, G);
     out8[0] = 1; out8[1] = G.nstrips; out8[2] = G.nchunks; out8[3] = G.rows; out8[4] = G.elo; out8[5] = G.ehi; out8[6] = ps.nS; out8[7] = ps.nN;
     for (int q = 0; q < G.nchunks && q < max_chunks; ++q) { int ja, jb; chunk_rows(G, q, &ja, &jb); rows_out[2 * q] = ja; rows_out[2 * q + 1] = jb; }
-    return CSI_OK;
-}
-
-int32_t csi_profile_substeps(csi_context* c, double dt, int32_t substeps, double* out_ms4) {
-    if (!c || !out_ms4) return CSI_ERR_INVALID_ARGUMENT;
-    int32_t rc = need_evp(c);
-    if (rc) return rc;
-    if (substeps < 2 || substeps > 64) return fail(c, CSI_ERR_INVALID_ARGUMENT, "2 <= substeps <= 64");
-    EvpDev P = evp_dev(c, dt);
-    FastCoef fc = c->coef;
-    { const double ie = 1.0 / P.ecc; fc.em2 = ie * ie; fc.ca_dt = 0.5 * (P.ca * dt); fc.hkc = fc.ca_dt * fc.uni[FC_RAZC]; fc.hkf = fc.ca_dt * fc.uni[FC_RAZF]; fc.hk1 = 0.5 * (1.0 - ie * ie); fc.rdt = 1.0 / dt;
-      fc.Dmin2 = P.Dmin * P.Dmin; fc.rDmin = 1.0 / P.Dmin;
-      fc.amin2 = P.amin * P.amin; fc.amax2 = P.amax * P.amax; fc.ramin = 1.0 / P.amin; fc.ramax = 1.0 / P.amax; }
-    const bool fast = c->mode == CSI_MODE_FAST, tiled = is_tiled(c);
-    const Range rs = stress_range(c), rv = interior_range(c), ru1 = first_u_range(c), rv1 = first_v_range(c);
-    const ImageSpec imu = image_spec(c, CSI_F_U), imv = image_spec(c, CSI_F_V);
-    const int uv[2] = {CSI_F_U, CSI_F_V};
-    if (fast && c->fusion && fused_supported(P)) {
-        // the fused path: one launch per sub-step or per pair (csi_last_launches); bracket the whole run with two events
-        if (substeps & 1) ++substeps;                      // even count: the state ends in the caller's arrays
-        bool peer = false;
-        if ((rc = peer_decide(c, P, substeps, &peer))) return rc;
-        if ((rc = peer ? run_fused_peer(c, dt, fc, substeps, 1) : run_fused(c, P, fc, substeps, 1))) return rc;
-        HIP_TRY(c, hipStreamSynchronize(c->stream));
-        float t = 0.f;
-        HIP_TRY(c, hipEventElapsedTime(&t, c->ev0, c->ev1));
-        out_ms4[0] = t / (c->last_launches > 0 ? c->last_launches : substeps); out_ms4[1] = out_ms4[2] = out_ms4[3] = 0.0;
-        return CSI_OK;
-    }
-    std::vector<hipEvent_t> ev((size_t)substeps * 4 + 1);
-    for (auto& e : ev) HIP_TRY(c, hipEventCreate(&e));
-    if (tiled && (rc = exchange(c, uv, 2, 2))) return rc;    // sizes the buffers outside the timed part
-    size_t k = 0;
-    HIP_TRY(c, hipEventRecord(ev[k++], c->stream));
-    for (int s = 1; s <= substeps; ++s) {
-        if (fast) launch_fast_stress(P, rs, fc, c->stream);
-        else { launch_strict_visc(P, rs, c->stream); launch_strict_stress(P, rs, c->stream); }
-        HIP_TRY(c, hipEventRecord(ev[k++], c->stream));
-        // u then v on every sub-step here (the order only permutes which kernel has the ring range)
-        if (fast) launch_fast_ustep(P, ru1, imu, fc, c->stream); else launch_strict_ustep(P, ru1, imu, c->stream);
-        HIP_TRY(c, hipEventRecord(ev[k++], c->stream));
-        if (fast) launch_fast_vstep(P, rv, imv, fc, c->stream); else launch_strict_vstep(P, rv, imv, c->stream);
-        HIP_TRY(c, hipEventRecord(ev[k++], c->stream));
-        if (tiled && (rc = exchange(c, uv, 2, 2))) return rc;
-        HIP_TRY(c, hipEventRecord(ev[k++], c->stream));
-        (void)rv1;
-    }
-    HIP_TRY(c, hipStreamSynchronize(c->stream));
-    double acc[4] = {0, 0, 0, 0};
-    for (int s = 0; s < substeps; ++s)
-        for (int q = 0; q < 4; ++q) {
-            float t = 0.f;
-            HIP_TRY(c, hipEventElapsedTime(&t, ev[(size_t)s * 4 + q], ev[(size_t)s * 4 + q + 1]));
-            acc[q] += t;
-        }
-    for (int q = 0; q < 4; ++q) out_ms4[q] = acc[q] / substeps;
-    for (auto& e : ev) hipEventDestroy(e);
     return CSI_OK;
 }
 

@@ -68,7 +68,7 @@ int extra_y(const csi_context* c, int fid) { return (kLoc[fid][1] == LOC_F && c-
 FRef ref_of(const csi_context* c, int fid) {
     FRef r;
     const Bound& b = c->f[fid];
-    r.p = b.p ? b.p + (c->Hx - 1) + (int64_t)(c->Hy - 1) * b.ld : nullptr;
+    r.p = b.p ? origin_of(c, b.p, b.ld) : nullptr;
     r.ld = (int)b.ld;
     return r;
 }
@@ -126,10 +126,10 @@ int32_t sync_coriolis(csi_context* c) {
         for (int t = 0; t < n; ++t)
             for (int w = 0; w < FC_COUNT; ++w)
                 host[(size_t)(n + t) * FC_COUNT + w] = pair_coef_scale(w) * host[(size_t)t * FC_COUNT + w];
-        HIP_TRY(c, hipStreamSynchronize(c->stream));
-        if (!c->dev_coef) HIP_TRY(c, hipMalloc((void**)&c->dev_coef, sizeof(double) * host.size()));
-        HIP_TRY(c, hipMemcpy(c->dev_coef, host.data(), sizeof(double) * host.size(), hipMemcpyHostToDevice));
-        c->coef.vec = c->dev_coef + (size_t)(c->Hy - 1) * FC_COUNT;      // so that vec[j * stride + which] is row j
+        HIP_TRY(c, hipStreamSynchronize(c->stream));      // (kernels in flight read the table that is overwritten)
+        if (!c->dev_coef) HIP_TRY(c, c->dev_coef.alloc(host.size()));      // (csi_grid_set releases it: the size follows the grid)
+        HIP_TRY(c, hipMemcpy(c->dev_coef.get(), host.data(), sizeof(double) * host.size(), hipMemcpyHostToDevice));
+        c->coef.vec = c->dev_coef.get() + (size_t)(c->Hy - 1) * FC_COUNT;      // so that vec[j * stride + which] is row j
         c->coef.vec_pair = c->coef.vec + (size_t)n * FC_COUNT;
         c->coef.stride = FC_COUNT;
         c->coef.jmin = 1 - c->Hy;
@@ -156,11 +156,10 @@ EvpDev evp_dev(const csi_context* c, double dt) {
     P.rho = e.sea_ice_density; P.fcor = e.has_coriolis ? e.coriolis_f : 0.0; P.has_cor = e.has_coriolis;   // FAST kernels multiply by fcor unconditionally
     if (c->dev_fcor && e.has_coriolis) {
         const size_t n = (size_t)c->Ny + 2 * (size_t)c->Hy + 1;
-        P.fcor_u = c->dev_fcor + (c->Hy - 1); P.fcor_v = c->dev_fcor + n + (c->Hy - 1);   // ptr[j] is row j
+        P.fcor_u = c->dev_fcor.get() + (c->Hy - 1); P.fcor_v = c->dev_fcor.get() + n + (c->Hy - 1);   // ptr[j] is row j
     }
     if (c->dev_fcor2 && e.has_coriolis) {
-        const long off = (c->Hx - 1) + (long)(c->Hy - 1) * c->fcor2_ld;
-        P.fcor2_u = c->dev_fcor2 + off; P.fcor2_v = c->dev_fcor2 + c->fcor2_plane + off; P.fcor2_ld = c->fcor2_ld;
+        P.fcor2_u = origin_of(c, c->dev_fcor2.get(), c->fcor2_ld); P.fcor2_v = P.fcor2_u + c->fcor2_plane; P.fcor2_ld = c->fcor2_ld;
     }
     P.pressure_kind = e.pressure_formulation;
     P.dt = dt;
@@ -171,10 +170,7 @@ EvpDev evp_dev(const csi_context* c, double dt) {
     for (int k = 0; k < 4; ++k) { P.ibc_u[k] = c->ibc[0][k]; P.ibc_v[k] = c->ibc[1][k]; any_ibc |= (c->ibc[0][k] != 0.0) | (c->ibc[1][k] != 0.0); }
     P.extra = (P.has_forcing || (any_ibc && c->g.has_mask)) ? 1 : 0;
     P.free_drift = c->free_drift;
-    if (c->free_drift && c->fd[0] && c->fd[1]) {
-        P.ufd.p = c->fd[0] + (c->Hx - 1) + (int64_t)(c->Hy - 1) * c->f[CSI_F_U].ld; P.ufd.ld = (int)c->f[CSI_F_U].ld;
-        P.vfd.p = c->fd[1] + (c->Hx - 1) + (int64_t)(c->Hy - 1) * c->f[CSI_F_V].ld; P.vfd.ld = (int)c->f[CSI_F_V].ld;
-    }
+    if (c->free_drift && c->fd[0].get() && c->fd[1].get()) { P.ufd = c->fd[0].view(c); P.vfd = c->fd[1].view(c); }
     return P;
 }
 
@@ -241,14 +237,6 @@ int32_t do_initialize(csi_context* c) {
 
 // ---- fused sub-step path (evp_fused.hip) -----------------------------------------------------------------
 
-FRef alt_ref(const csi_context* c, int k) {
-    FRef r;
-    const Bound& b = c->f[kPing[k]];
-    r.p = c->alt[k] + (c->Hx - 1) + (int64_t)(c->Hy - 1) * b.ld;
-    r.ld = (int)b.ld;
-    return r;
-}
-
 
 FusedGeom fused_geom(const csi_context* c, int V) {
     FusedGeom G;
@@ -287,15 +275,7 @@ void velocity_ranges(const csi_context* c, bool ufirst, int V, Range& r1, Range&
 }
 
 int32_t ensure_alt(csi_context* c) {
-    for (int k = 0; k < 5; ++k) {
-        const Bound& b = c->f[kPing[k]];
-        const size_t n = (size_t)b.ld * (size_t)b.nj;
-        if (c->alt_elems[k] != n) {
-            if (c->alt[k]) { HIP_TRY(c, hipStreamSynchronize(c->stream)); hipFree(c->alt[k]); c->alt[k] = nullptr; }
-            HIP_TRY(c, hipMalloc((void**)&c->alt[k], n * sizeof(double)));
-            c->alt_elems[k] = n;
-        }
-    }
+    for (ScratchField& a : c->alt) HIP_TRY(c, a.ensure(c));
     return CSI_OK;
 }
 
@@ -406,14 +386,12 @@ int32_t ensure_row_constant(csi_context* c) {
     }
     c->rc_rows = sum[nj];
     if (c->rc_rows == 0) return CSI_OK;
-    HIP_TRY(c, hipStreamSynchronize(c->stream));
-    if (c->dev_c2row) { hipFree(c->dev_c2row); c->dev_c2row = nullptr; }
-    if (c->dev_rcsum) { hipFree(c->dev_rcsum); c->dev_rcsum = nullptr; }
-    HIP_TRY(c, hipMalloc((void**)&c->dev_c2row, sizeof(double) * rowv.size()));
-    HIP_TRY(c, hipMalloc((void**)&c->dev_rcsum, sizeof(int) * sum.size()));
-    HIP_TRY(c, hipMemcpy(c->dev_c2row, rowv.data(), sizeof(double) * rowv.size(), hipMemcpyHostToDevice));
-    HIP_TRY(c, hipMemcpy(c->dev_rcsum, sum.data(), sizeof(int) * sum.size(), hipMemcpyHostToDevice));
-    c->coef.c2row = c->dev_c2row; c->coef.c2row_n = nj; c->coef.rcsum = c->dev_rcsum;
+    HIP_TRY(c, hipStreamSynchronize(c->stream));      // (kernels in flight read the vectors replaced below)
+    HIP_TRY(c, c->dev_c2row.alloc(rowv.size()));
+    HIP_TRY(c, c->dev_rcsum.alloc(sum.size()));
+    HIP_TRY(c, hipMemcpy(c->dev_c2row.get(), rowv.data(), sizeof(double) * rowv.size(), hipMemcpyHostToDevice));
+    HIP_TRY(c, hipMemcpy(c->dev_rcsum.get(), sum.data(), sizeof(int) * sum.size(), hipMemcpyHostToDevice));
+    c->coef.c2row = c->dev_c2row.get(); c->coef.c2row_n = nj; c->coef.rcsum = c->dev_rcsum.get();
     return CSI_OK;
 }
 

@@ -3,8 +3,9 @@
 //   csi_group.hip   halo exchange: RCCL, the in-process tile group, the host-channel group (csi_hostgroup.hip)
 //   csi_peer.hip    peer halo transport: set-up (IPC mapping, flag arrays), tile sets, kernel tables
 //   csi_fold.hip    north fold: the three-kernel band beside the pair launches
-//   csi_launch.hip  launch loops: sub-cycle, finalize, time_step_momentum!, tracer steps, update_state!
+//   csi_launch.hip  launch loops: sub-cycle, finalize, time_step_momentum!, tracer steps, update_state!, csi_profile_substeps
 //   csi_abi.hip     the C ABI (include/csi.h)
+//   csi_mem.h       DeviceBuf / PinnedBuf: the owner of every allocation the library makes
 #pragma once
 #include "../../include/csi.h"
 #include "csi_dev.h"
@@ -12,6 +13,7 @@
 #include "momentum_dev.h"
 #include "csi_hostgroup.h"
 #include "csi_comm.h"
+#include "csi_mem.h"
 #include <rccl/rccl.h>
 #include <cmath>
 #include <cstdio>
@@ -60,6 +62,21 @@ static const char* const kName[CSI_F_COUNT_ALL] = {"u", "v", "h", "aice", "sigma
 
 extern std::string g_create_error;      // csi_context_create failures (no context to hold the message)
 
+// A library array that shadows the parent array of a bound field: as many elements (ld * nj), the same row stride, and a view
+// whose element (i, j) is the field's.  `zeroed`: cleared on the context's stream whenever it is (re)allocated -- for arrays with
+// cells that no kernel ever writes but some kernel reads.
+struct ScratchField {
+    int fid;
+    bool zeroed;
+    DeviceBuf<double> buf;
+    ScratchField(int field, bool zero) : fid(field), zeroed(zero) {}
+    double* get() const { return buf.get(); }
+    // sized for c->f[fid] as it is bound now (Buf::ensure: no HIP call while the size stays)
+    hipError_t ensure(const csi_context* c, hipStream_t also = nullptr, bool* fresh = nullptr);
+    FRef view(const csi_context* c) const;
+};
+constexpr bool kZeroed = true, kRaw = false;
+
 
 }  // namespace csi_host
 using namespace csi_host;
@@ -92,14 +109,14 @@ struct csi_context {
     bool grid_set = false, evp_set = false;
     int Nx = 0, Ny = 0, Hx = 0, Hy = 0, topo_x = 0, topo_y = 0, metric_kind = 0;
     GridDev g{};
-    double* dev_metrics = nullptr;   // 8 vectors of length Ny + 2Hy + 1 (PER_J) or 12 planes (FULL)
-    double* dev_coef = nullptr;      // FAST per-row stencil coefficients [Ny + 2Hy + 1][FC_COUNT]
-    double* dev_coef2 = nullptr;     // FAST per-point stencil coefficients of a CSI_METRIC_FULL grid, C2_COUNT planes
+    DeviceBuf<double> dev_metrics;   // 8 vectors of length Ny + 2Hy + 1 (PER_J) or 12 planes (FULL)
+    DeviceBuf<double> dev_coef;      // FAST per-row stencil coefficients [Ny + 2Hy + 1][FC_COUNT]
+    DeviceBuf<double> dev_coef2;     // FAST per-point stencil coefficients of a CSI_METRIC_FULL grid, C2_COUNT planes
     FastCoef coef{};
     std::vector<double> coef_host;       // host copy of the per-row table built from PER_J metrics (empty: uniform metrics)
     std::vector<double> fcor_rows[2];    // csi_coriolis_rows_set: f per row at u / v points (empty: FPlane scalar)
-    double* dev_fcor = nullptr;          // the same on the device (STRICT kernels), 2 x (Ny + 2Hy + 1)
-    double* dev_fcor2 = nullptr;         // csi_coriolis_points_set: two planes (u points, v points) of ni x nj
+    DeviceBuf<double> dev_fcor;          // the same on the device (STRICT kernels), 2 x (Ny + 2Hy + 1)
+    DeviceBuf<double> dev_fcor2;         // csi_coriolis_points_set: two planes (u points, v points) of ni x nj
     long fcor2_ld = 0, fcor2_plane = 0;
     bool cor_dirty = true;               // Coriolis columns of the FAST table need (re)building
     double cor_synced = 0.0;             // FPlane value they were built with
@@ -118,8 +135,7 @@ struct csi_context {
     csi_local_group* local = nullptr;      // in-process tile group instead of an RCCL communicator (csi_comm_init_local)
     HostGroup* hostg = nullptr;            // host-channel group of PROCESSES (shared memory + HIP IPC, csi_comm_init_host): RCCL-free runs of several ranks on one GPU
     int world = 1, rank = 0;
-    double *sendbuf = nullptr, *recvbuf = nullptr;
-    size_t buf_cap = 0;   // elements per buffer
+    DeviceBuf<double> sendbuf, recvbuf;    // pack buffers of the message exchange: they only grow, both to the same size (exchange_refs)
     int last_exchanges = 0, last_k = 1;
     // Halo transport of the two-sub-steps kernel on tiles.  "peer" (default where it can be set up): the neighbouring tiles'
     // arrays are mapped into this process (HIP IPC; xGMI peer access) and a connected side behaves like a periodic one whose halo
@@ -139,51 +155,50 @@ struct csi_context {
         int img_rank[8], sync_rank[8];       // per direction: the rank whose arrays receive this tile's images there; the neighbour to wait for (-1: none)
         void* arr[8][NARR] = {};             // that rank's arrays as this process addresses them
         unsigned long long* nbr_slots[8] = {};   // its flag array
-        unsigned long long* slots = nullptr; // this rank's flag array: 8 directions x SLOTS
-        unsigned* err = nullptr;             // device word set by a wait that timed out
-        unsigned* err_host = nullptr;        // pinned copy, refreshed after every sub-cycle
+        DeviceBuf<unsigned long long> slots; // this rank's flag array: 8 directions x SLOTS
+        DeviceBuf<unsigned> err;             // device word set by a wait that timed out
+        PinnedBuf<unsigned> err_host;        // pinned copy, refreshed after every sub-cycle
         unsigned long long seq = 0;          // launches of the flag protocol so far (the same number on every rank)
         std::vector<void*> opened;           // IPC mappings
-        uint8_t* xbuf = nullptr;             // device staging of the set-up's all-gather
+        DeviceBuf<uint8_t> xbuf;             // device staging of the set-up's all-gather (bytes; only grows)
         int last = 0;                        // the last sub-cycle used the peer transport
         int tier = -1;                       // protocol tier asked for (csi_set_peer_tier; -1: automatic -- peer_effective_tier: 1 as soon as a
                                              // neighbour lives in another process or on another device, 0 for a tile connected to itself / an in-process group)
         bool aborted = false;                // a wait of the flag protocol gave up (here or at a neighbour): the transport is refused until every rank has
                                              // called csi_set_halo_transport / csi_comm_init* again (sticky: the flags cannot recover, csi_abi.hip peer_check)
         bool local_queues_ok = true;         // in-process tile group: GPU_MAX_HW_QUEUES > tiles (csi_comm_init_local)
-        size_t xbuf_cap = 0;                 // bytes of xbuf
     } peer;
     ExPlan pending_rp;                   // the receive plan of an exchange that has been begun
     // fused sub-step kernel: ping-pong copies of u, v, sigma11, sigma22, sigma12
-    FusedTable* dev_tables = nullptr;   // uniform-input tables of the fused kernel
+    DeviceBuf<FusedTable> dev_tables;   // uniform-input tables of the fused kernel
     // pinned staging ring for their upload: the host never waits for the stream (a slot is reused after its own copy
     // has completed, four sub-cycles later)
     static constexpr int kRing = 4;
-    FusedTable* host_ring = nullptr;
+    PinnedBuf<FusedTable> host_ring;
     hipEvent_t ring_ev[kRing] = {nullptr, nullptr, nullptr, nullptr};
     bool ring_used[kRing] = {false, false, false, false};
     unsigned ring_pos = 0;
-    double* alt[5] = {nullptr, nullptr, nullptr, nullptr, nullptr};
-    double* adv_buf[4] = {nullptr, nullptr, nullptr, nullptr};      // RK stages of an advection-only model in one launch each: (h, a) x 2 rotating copies
-    size_t adv_elems[4] = {0, 0, 0, 0};
+    // (not zeroed: run_fused / run_fused_peer copy the whole parents in before the first launch wherever a cell is not rewritten by
+    //  every launch.  The neighbours of a peer-connected tile hold IPC mappings of these five: Peer::sig)
+    ScratchField alt[5] = {{CSI_F_U, kRaw}, {CSI_F_V, kRaw}, {CSI_F_S11, kRaw}, {CSI_F_S22, kRaw}, {CSI_F_S12, kRaw}};
+    // RK stages of an advection-only model in one launch each: (h, a) x 2 rotating copies.  (Not zeroed: a new array is filled with a
+    // copy of the state -- beyond walls the halo holds mirror images the stores rewrite, cells nobody writes start as the state's)
+    ScratchField adv_buf[4] = {{CSI_F_H, kRaw}, {CSI_F_A, kRaw}, {CSI_F_H, kRaw}, {CSI_F_A, kRaw}};
     // north fold (FoldBand): the band's own copies of u, v, sigma and of the four diagnostics, its stream and the two events
     // that order it against the pair launches
-    double* band[9] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
-    size_t band_elems[9] = {0, 0, 0, 0, 0, 0, 0, 0, 0};
+    // (zeroed: only the rows from M - 7 on are ever written, the band's stencils reach the cells around them -- those stay defined and
+    //  the same from run to run; used on band_stream as well as on the context's stream: ensure_band)
+    ScratchField band[9] = {{CSI_F_U, kZeroed}, {CSI_F_V, kZeroed}, {CSI_F_S11, kZeroed}, {CSI_F_S22, kZeroed}, {CSI_F_S12, kZeroed},
+                            {CSI_F_ALPHA, kZeroed}, {CSI_F_ZETA_C, kZeroed}, {CSI_F_ZETA_F, kZeroed}, {CSI_F_DELTA, kZeroed}};
     hipStream_t band_stream = nullptr;
-    hipEvent_t exp_ev[2] = {nullptr, nullptr};      // (CSI_EXP_OVERLAP: the second stream is band_stream; band_cus: order between stream and pair_stream)
-    hipStream_t pair_stream = nullptr;              // fold band with reserved CUs (tune.band_cus): the pair launches' stream, masked to the other CUs
     hipEvent_t band_ev_pair = nullptr, band_ev_band = nullptr;
-    double* fbar[2] = {nullptr, nullptr};   // ocean ubar at v points, vbar at u points (array-valued bottom drag)
-    double* fbar_top[2] = {nullptr, nullptr};   // the same of the air velocities (array-valued wind drag)
-    size_t fbar_top_elems[2] = {0, 0};
-    double* fd[2] = {nullptr, nullptr};     // free-drift velocities at u / v points (StressBalanceFreeDrift)
-    double* xd[2] = {nullptr, nullptr};     // stress divergence of the immersed flux boundary conditions at u / v points (two-sub-steps kernel)
-    size_t xd_elems[2] = {0, 0};
-    size_t fd_elems[2] = {0, 0};
+    // Forcing scratch, filled once per sub-cycle at every point whose stencil stays inside the parents.  Zeroed: those launches never
+    // write the outermost layer of the parent, which the four-point averages of the kernels that read these arrays reach.
+    ScratchField fbar[2] = {{CSI_F_V, kZeroed}, {CSI_F_U, kZeroed}};       // ocean ubar at v points, vbar at u points (array-valued bottom drag)
+    ScratchField fbar_top[2] = {{CSI_F_V, kZeroed}, {CSI_F_U, kZeroed}};   // the same of the air velocities (array-valued wind drag)
+    ScratchField fd[2] = {{CSI_F_U, kZeroed}, {CSI_F_V, kZeroed}};         // free-drift velocities at u / v points (StressBalanceFreeDrift)
+    ScratchField xd[2] = {{CSI_F_U, kZeroed}, {CSI_F_V, kZeroed}};         // stress divergence of the immersed flux boundary conditions at u / v points (two-sub-steps kernel)
     int free_drift = 0;                     // csi_free_drift_set
-    size_t fbar_elems[2] = {0, 0};
-    size_t alt_elems[5] = {0, 0, 0, 0, 0};
     bool slab_set = false;   // thermodynamic step inside csi_time_step_fe / _rk3
     SlabDev slab{};
     int vel_bc_on[2][2] = {{0, 0}, {0, 0}};          // csi_velocity_bc_set: [u | v][low | high] ValueBoundaryCondition
@@ -196,8 +211,9 @@ struct csi_context {
     int rheology = CSI_RHEOLOGY_EVP;
     double nu = 1000.0;
     int solver = CSI_SOLVER_SPLIT_EXPLICIT;
-    double* vis_alt[2] = {nullptr, nullptr};     // the viscous sub-cycle's second u / v arrays (ping-pong with the bound ones)
-    size_t vis_alt_elems[2] = {0, 0};
+    // the viscous sub-cycle's second u / v arrays (ping-pong with the bound ones).  Not zeroed: viscous_subcycle copies the parents in
+    // unless every cell is rewritten by every launch
+    ScratchField vis_alt[2] = {{CSI_F_U, kRaw}, {CSI_F_V, kRaw}};
     int fusion = 1;       // 1: use the fused sub-step kernel when the configuration allows it
     int pairing = 1;      // 1: two sub-steps per launch where supported (csi_set_fusion level 2)
     int last_launches = 0, last_substeps = 0, last_used_pairs = 0;   // kernel launches / sub-steps of the last fused sub-cycle
@@ -210,11 +226,11 @@ struct csi_context {
     struct Activity {
         static constexpr int kSamples = 4;
         int enabled = 1;                     // csi_set_tile_skipping
-        int* flags = nullptr;                // device: one int per tile
-        int* list = nullptr;                 // device: {live, tiles, the live tiles' numbers}
-        int* list0 = nullptr;                // device: the same for the first two launches (all but the tiles quiescent from the start)
-        int* host = nullptr;                 // pinned, device-visible: {seqlock, live, tiles, sample id} written by k_activity_compact
-        int* host_dev = nullptr;             // ... as the device addresses it
+        DeviceBuf<int> flags;                // device: one int per tile
+        DeviceBuf<int> list;                 // device: {live, tiles, the live tiles' numbers}
+        DeviceBuf<int> list0;                // device: the same for the first two launches (all but the tiles quiescent from the start)
+        PinnedBuf<int> host;                 // pinned, device-visible: {seqlock, live, tiles, sample id} written by k_activity_compact
+        int* host_dev = nullptr;             // ... as the device addresses it (not owned)
         double sample_scale[kSamples] = {1, 1, 1, 1};      // the geometry scale of sample id % kSamples
         unsigned seq = 0;                    // sample ids handed out
         int seen_id = -1;                    // the newest sample the host has taken
@@ -225,8 +241,8 @@ struct csi_context {
     } act;
     // CSI_METRIC_FULL: rows whose twelve coefficient planes (and per-point Coriolis planes) hold one value per row (ensure_row_constant)
     std::vector<double> coef2_host, fcor2_host;      // host copies of the planes the marks are made from
-    double* dev_c2row = nullptr;         // (C2_COUNT + 2) vectors of nj doubles
-    int* dev_rcsum = nullptr;            // nj + 1 prefix sums
+    DeviceBuf<double> dev_c2row;         // (C2_COUNT + 2) vectors of nj doubles
+    DeviceBuf<int> dev_rcsum;            // nj + 1 prefix sums
     bool rc_dirty = true;
     int rc_enabled = 1;                  // csi_set_row_constant(ctx, on, rtol)
     double rc_rtol = 0.0;                // 0: bitwise-equal columns only (results unchanged); > 0: columns within this relative distance of column 1 count as equal -- CHANGES results at that level
@@ -238,10 +254,6 @@ struct csi_context {
                     adv_nt = -1,           // CSI_ADV_NT: tracers per thread of the advection tendency kernel (1 / 2; default by grid size)
                     band_fused = -1,      // CSI_BAND_FUSED=0: the fold band on the three kernels + two copies per step (rounds 4-6a); default: six launches per step without copies, loads hoisted (csi_fold.hip band_substeps_fused)
                     band_event_flags = -1,   // CSI_BAND_EVENT_FLAGS (csi_fold.hip ensure_band)
-                    band_cus = -1,        // CSI_BAND_CUS: CUs per XCD reserved for the fold band's launches (the pair launches beside them run on the others)
-                    band_cus_share = -1,  // CSI_BAND_CUS_SHARE=1: the band may use every CU (only the pair launches are masked)
-                    exp_band_only = -1,   // TIMING EXPERIMENT (CSI_EXP_BAND_ONLY=1, wrong results): fold grids run the band's launches without the pair launches beside them
-                    exp_overlap = -1,     // EXPERIMENT (CSI_EXP_OVERLAP, profiles/r06_tile_overlap.txt): bit 0 every tile of a peer-connected launch in the sets of both sides of a connected axis, bit 1 consecutive launches on two streams
                     no_geom_sig = -1;      // debugging aid (CSI_DEBUG_NO_GEOM_SIG=1): skip the launch-geometry check of the peer set-up (tests/test_gpu_local_tiles.py)
       long adv_stage_max_cells = 1L << 40;      // advection-only models: one launch per RK stage up to this many cells (advect_stage_supported; no cut since round 6)
     } tune;
@@ -263,11 +275,22 @@ namespace csi_host {
             return fail(c, CSI_ERR_COMM, std::string(#expr) + ": " + ncclGetErrorString(r_));   \
     } while (0)
 
+// Element (0, 0) in reference indexing of a parent array with row stride ld -- (i, j) is then p[i + j * ld]: bound fields (ref_of),
+// library arrays that shadow them (ScratchField::view), the mask and the per-point metric / coefficient / Coriolis planes
+template <class T>
+static inline T* origin_of(const csi_context* c, T* parent, int64_t ld) { return parent + (c->Hx - 1) + (int64_t)(c->Hy - 1) * ld; }
+inline hipError_t ScratchField::ensure(const csi_context* c, hipStream_t also, bool* fresh) {
+    const Bound& b = c->f[fid];
+    return buf.ensure((size_t)b.ld * (size_t)b.nj, c->stream, zeroed, also, fresh);
+}
+inline FRef ScratchField::view(const csi_context* c) const { return FRef{origin_of(c, buf.get(), c->f[fid].ld), (int)c->f[fid].ld}; }
+
 static inline int nxf_of(int k) { return k > 1 ? 5 : 2; }     // sigma travels with u, v when k > 1 (see do_subcycle)
 
 struct FoldBand;
 // ---- functions shared by the translation units (definitions: see the list at the top) ----
 static const int kPing[5] = {CSI_F_U, CSI_F_V, CSI_F_S11, CSI_F_S22, CSI_F_S12};
+static const int kForcingFields[6] = {CSI_F_TOP_U, CSI_F_TOP_V, CSI_F_BOT_U, CSI_F_BOT_V, CSI_F_FORCING_U, CSI_F_FORCING_V};      // update_external_stress!
 // (elo / ehi: rows of the FIRST / LAST chunk where they differ from `rows` -- shorter tiles next to a peer-connected y side,
 //  pair_geom; elo == rows and ehi == 0: every chunk `rows` rows, the last one what is left)
 struct FusedGeom { Range rs; int nstrips, nchunks, rows; int elo = 0, ehi = 0; int wt = 0; };      // wt: write-through result stores (FI_WT)
@@ -314,7 +337,6 @@ struct FoldBand {
     ImageSpec imu, imv;
     Range rs, ru1, rv1, r2;         // the three kernels' ranges on the whole grid
 };
-static const int kBandDiag[4] = {CSI_F_ALPHA, CSI_F_ZETA_C, CSI_F_ZETA_F, CSI_F_DELTA};
 struct FoldCut {        // RAII: the tile with the band cut off (rows 1 .. M, north side "connected")
     csi_context* c; GridDev g; int Ny, band;
     FoldCut(csi_context* cc, int M) : c(cc), g(cc->g), Ny(cc->Ny), band(cc->geom_band) { c->Ny = M; c->g.Ny = M; c->g.yhi = SIDE_CONNECTED; c->geom_band = 1; }
@@ -348,7 +370,7 @@ int32_t exchange_refs(csi_context* c, const FRef* fr, int nf, int W);
 int32_t fill_halo(csi_context* c, int fid);
 int32_t copy_parent(csi_context* c, int dst, int src);
 int32_t do_initialize(csi_context* c);
-FRef alt_ref(const csi_context* c, int k);
+static inline FRef alt_ref(const csi_context* c, int k) { return c->alt[k].view(c); }
 FusedGeom fused_geom(const csi_context* c, int V);
 void velocity_ranges(const csi_context* c, bool ufirst, int V, Range& r1, Range& r1c, Range& r2);
 int32_t ensure_alt(csi_context* c);
@@ -372,7 +394,7 @@ PeerSets peer_my_sets(csi_context* c);
 int32_t peer_setup(csi_context* c, bool local_ok);
 int32_t peer_decide(csi_context* c, const EvpDev& P, int substeps, bool* use);
 int32_t peer_fill_table(csi_context* c, const FusedGeom& G, bool out_is_alt, FusedTable* t);
-FRef band_ref(const csi_context* c, int q);
+static inline FRef band_ref(const csi_context* c, int q) { return c->band[q].view(c); }
 int32_t ensure_band(csi_context* c);
 int32_t band_substep(csi_context* c, const FoldBand& bd, const FastCoef& fc, const FRef* b, const FRef* d, bool ufirst, int jlo, bool last, hipStream_t st);
 int32_t band_substeps(csi_context* c, const FoldBand& bd, const FastCoef& fc, int cur, int s, int n, bool last);
@@ -386,11 +408,15 @@ int32_t do_finalize(csi_context* c);
 int32_t need_evp(csi_context* c);
 int32_t need_dynamics_common(csi_context* c);
 int32_t do_time_step_momentum(csi_context* c, double dt, int substeps, int rk_reset);
+FastCoef fast_coef(const csi_context* c, const EvpDev& P, double dt);
 // csi_momentum.hip: the rheology / solver dispatch (EVP + split-explicit: need_evp / do_time_step_momentum, unchanged)
 int32_t momentum_config_check(csi_context* c);
 int32_t need_momentum(csi_context* c);
 int32_t do_momentum(csi_context* c, double dt, int substeps, int rk_reset);
 int32_t do_momentum_tendencies(csi_context* c, double dt);
+int32_t free_drift_fields(csi_context* c, double dt);      // (shared with the EVP sub-cycle and time_step_momentum!, csi_launch.hip)
+int32_t reset_velocities(csi_context* c);
+int32_t fill_forcing_halos(csi_context* c);
 AdvDev adv_dev(const csi_context* c, int scheme, double dt, int from_cache);
 int32_t do_update_state(csi_context* c, bool in_step = false, bool tracers_filled = false);
 int32_t do_tendencies(csi_context* c, int scheme);
@@ -403,7 +429,7 @@ Range parent_range(const csi_context* c);
 bool has_comm(const csi_context* c);
 Range v_stress_range(const csi_context* c, const SideV& v);
 Range v_second_range(const csi_context* c, const SideV& v);
-const Bound& band_bound(const csi_context* c, int q);
+static inline const Bound& band_bound(const csi_context* c, int q) { return c->f[c->band[q].fid]; }
 int32_t peer_check_entry(csi_context* c);      // (csi_abi.hip: the error word of the peer transport, checked at every entry point)
 
 }  // namespace csi_host

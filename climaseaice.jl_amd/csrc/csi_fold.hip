@@ -13,39 +13,11 @@ namespace csi_host {
 // on after the second), copy rows >= M + 1 into the other buffer -- while the pair launch reads the current buffer and stores
 // rows <= M of the other one.  Two events: a pair launch waits for the previous band (its halo rows), a band for the previous
 // pair launch (rows M - 7 .. M of its input).
-const Bound& band_bound(const csi_context* c, int q) { return c->f[q < 5 ? kPing[q] : kBandDiag[q - 5]]; }
-FRef band_ref(const csi_context* c, int q) {
-    const Bound& b = band_bound(c, q);
-    FRef r;
-    r.p = c->band[q] + (c->Hx - 1) + (int64_t)(c->Hy - 1) * b.ld;
-    r.ld = (int)b.ld;
-    return r;
-}
 int32_t ensure_band(csi_context* c) {
-    for (int q = 0; q < 9; ++q) {
-        const Bound& b = band_bound(c, q);
-        const size_t n = (size_t)b.ld * (size_t)b.nj;
-        if (c->band_elems[q] != n) {
-            if (c->band[q]) { HIP_TRY(c, hipDeviceSynchronize()); hipFree(c->band[q]); c->band[q] = nullptr; }
-            HIP_TRY(c, hipMalloc((void**)&c->band[q], n * sizeof(double)));
-            HIP_TRY(c, hipMemsetAsync(c->band[q], 0, n * sizeof(double), c->stream));
-            c->band_elems[q] = n;
-        }
-    }
+    // (the band's kernels run on band_stream: a reallocation waits for that stream as well as for the context's -- the two streams
+    //  that ever touch these arrays)
+    for (ScratchField& b : c->band) HIP_TRY(c, b.ensure(c, c->band_stream));
     if (!c->band_stream) {
-        // Reserved CUs (tune.band_cus = r per XCD): the band's launches are six dependent, latency-bound kernels per pair of sub-steps
-        // that otherwise queue for wave slots behind the pair kernel's workgroups.  Mask bit k is a CU of XCD k % 8
-        // (scripts/microbench/cu_mask_probe.hip): bits 0 .. 8 r - 1 are r CUs of every XCD.
-        const int r = c->tune.band_cus;
-        if (r > 0 && r < 16) {
-            uint32_t band_mask[8] = {0, 0, 0, 0, 0, 0, 0, 0}, pair_mask[8];
-            for (int k = 0; k < 8 * r; ++k) band_mask[k >> 5] |= 1u << (k & 31);
-            for (int w = 0; w < 8; ++w) pair_mask[w] = ~band_mask[w];
-            if (c->tune.band_cus_share > 0) for (int w = 0; w < 8; ++w) band_mask[w] = 0xffffffffu;
-            HIP_TRY(c, hipExtStreamCreateWithCUMask(&c->band_stream, 8, band_mask));
-            HIP_TRY(c, hipExtStreamCreateWithCUMask(&c->pair_stream, 8, pair_mask));
-            for (hipEvent_t& e : c->exp_ev) if (!e) HIP_TRY(c, hipEventCreateWithFlags(&e, hipEventDisableTiming));
-        } else
         HIP_TRY(c, hipStreamCreateWithFlags(&c->band_stream, hipStreamNonBlocking));
         // the two events order kernels of ONE device against each other (pair launch <-> band step), sixty times per sub-cycle each: no
         // system-scope fence (what they guard reaches the host and other devices behind the kernels that follow on the context's stream).
@@ -118,7 +90,7 @@ int32_t band_substeps_fused(csi_context* c, const FoldBand& bd, const FastCoef& 
         for (int q = 5; q < 9; ++q) {
             const Bound& bb = band_bound(c, q);
             const size_t row = (size_t)(bd.M + 1 - 1 + c->Hy), off = row * (size_t)bb.ld;
-            diag.src[diag.count] = c->band[q] + off; diag.dst[diag.count] = bb.p + off; diag.n[diag.count] = (long)(((size_t)bb.nj - row) * (size_t)bb.ld);
+            diag.src[diag.count] = c->band[q].get() + off; diag.dst[diag.count] = bb.p + off; diag.n[diag.count] = (long)(((size_t)bb.nj - row) * (size_t)bb.ld);
             ++diag.count;
         }
         launch_copy_batch(diag, st, 64);
@@ -143,8 +115,8 @@ int32_t band_substeps(csi_context* c, const FoldBand& bd, const FastCoef& fc, in
     CopyBatch in{}, out{}, diag{};
     for (int q = 0; q < 5; ++q) {
         const Bound& b = band_bound(c, q);
-        rows_from(q, bd.M - 7, cur == 0 ? b.p : c->alt[q], c->band[q], in);
-        rows_from(q, bd.M + 1, c->band[q], cur == 0 ? c->alt[q] : b.p, out);
+        rows_from(q, bd.M - 7, cur == 0 ? b.p : c->alt[q].get(), c->band[q].get(), in);
+        rows_from(q, bd.M + 1, c->band[q].get(), cur == 0 ? c->alt[q].get() : b.p, out);
     }
     launch_copy_batch(in, st, 64);
     FRef b[5], d[4];
@@ -158,7 +130,7 @@ int32_t band_substeps(csi_context* c, const FoldBand& bd, const FastCoef& fc, in
     } else if ((rc = band_substep(c, bd, fc, b, d, (s % 2) == 0, bd.M - 3, last, st))) return rc;
     launch_copy_batch(out, st, 64);
     if (last) {
-        for (int q = 5; q < 9; ++q) rows_from(q, bd.M + 1, c->band[q], band_bound(c, q).p, diag);
+        for (int q = 5; q < 9; ++q) rows_from(q, bd.M + 1, c->band[q].get(), band_bound(c, q).p, diag);
         launch_copy_batch(diag, st, 64);
     }
     HIP_TRY(c, hipEventRecord(c->band_ev_band, st));

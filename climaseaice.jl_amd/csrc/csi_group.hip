@@ -63,14 +63,14 @@ int32_t comm_allreduce_max(csi_context* c, int* v) {
     } else if (c->hostg) {
         if (!hostgroup_allgather(c->hostg, v, sizeof(int), all, &c->err)) return CSI_ERR_COMM;
     } else {
-        int* flag = nullptr;
-        HIP_TRY(c, hipMalloc((void**)&flag, sizeof(int)));
+        DeviceBuf<int> word;      // (freed on every way out)
+        HIP_TRY(c, word.alloc(1));
+        int* flag = word.get();
         hipError_t e = hipMemcpy(flag, v, sizeof(int), hipMemcpyHostToDevice);
         ncclResult_t r = ncclSuccess;
         if (e == hipSuccess) r = ncclAllReduce(flag, flag, 1, ncclInt32, ncclMax, c->comm, c->stream);
         if (e == hipSuccess && r == ncclSuccess) e = hipStreamSynchronize(c->stream);
         if (e == hipSuccess && r == ncclSuccess) e = hipMemcpy(v, flag, sizeof(int), hipMemcpyDeviceToHost);
-        hipFree(flag);
         if (r != ncclSuccess) return fail(c, CSI_ERR_COMM, std::string("ncclAllReduce: ") + ncclGetErrorString(r));
         if (e != hipSuccess) return fail(c, CSI_ERR_HIP, std::string("all-reduce of a status word: ") + hipGetErrorString(e));
         return CSI_OK;
@@ -95,7 +95,7 @@ int32_t local_sendrecv(csi_context* c, const long* soff, const long* scnt, const
         std::unique_lock<std::mutex> lk(G->mu);
         for (int k = 0; k < 8; ++k)
             if (speer[k] >= 0 && scnt[k] > 0) {
-                G->box[(size_t)c->rank * G->world + speer[k]].push_back(csi_local_group::Msg{c->sendbuf + soff[k], (size_t)scnt[k]});
+                G->box[(size_t)c->rank * G->world + speer[k]].push_back(csi_local_group::Msg{c->sendbuf.get() + soff[k], (size_t)scnt[k]});
                 ++G->posted[c->rank];
             }
         G->cv.notify_all();
@@ -107,7 +107,7 @@ int32_t local_sendrecv(csi_context* c, const long* soff, const long* scnt, const
                 const csi_local_group::Msg m = q.front();
                 q.pop_front();
                 if (m.count != (size_t)rcnt[k]) return fail(c, CSI_ERR_COMM, "in-process tile group: halo message of unexpected size (send / receive plans do not match)");
-                HIP_TRY(c, hipMemcpyAsync(c->recvbuf + roff[k], m.ptr, m.count * sizeof(double), hipMemcpyDeviceToDevice, c->stream));
+                HIP_TRY(c, hipMemcpyAsync(c->recvbuf.get() + roff[k], m.ptr, m.count * sizeof(double), hipMemcpyDeviceToDevice, c->stream));
                 from[nfrom++] = rpeer[k];
             }
     }
@@ -137,37 +137,37 @@ int32_t exchange_refs(csi_context* c, const FRef* fr, int nf, int W) {
     int32_t lrc;
     if (c->local && (lrc = local_wait_consumed(c))) return lrc;      // (before the send buffer is repacked -- or freed)
     if (c->hostg && !hostgroup_wait_consumed(c->hostg, &c->err)) return CSI_ERR_COMM;
-    if (need_elems > c->buf_cap) {
+    // (grow only, with room to spare: a host-channel group has exported the send buffer, so every new one is exported again.
+    //  recvbuf is allocated last: its size is the capacity both are known to have)
+    if (need_elems > c->recvbuf.size()) {
         HIP_TRY(c, hipStreamSynchronize(c->stream));
-        if (c->sendbuf) hipFree(c->sendbuf);
-        if (c->recvbuf) hipFree(c->recvbuf);
-        c->sendbuf = c->recvbuf = nullptr;
+        c->sendbuf.release();
+        c->recvbuf.release();
         const size_t cap = need_elems * 2;
-        HIP_TRY(c, hipMalloc((void**)&c->sendbuf, cap * sizeof(double)));
-        HIP_TRY(c, hipMalloc((void**)&c->recvbuf, cap * sizeof(double)));
-        c->buf_cap = cap;
-        if (c->hostg && !hostgroup_set_sendbuf(c->hostg, c->sendbuf, cap * sizeof(double), &c->err)) return CSI_ERR_COMM;
+        HIP_TRY(c, c->sendbuf.alloc(cap));
+        HIP_TRY(c, c->recvbuf.alloc(cap));
+        if (c->hostg && !hostgroup_set_sendbuf(c->hostg, c->sendbuf.get(), cap * sizeof(double), &c->err)) return CSI_ERR_COMM;
     }
-    launch_pack(sp, c->sendbuf, 0, c->stream);
+    launch_pack(sp, c->sendbuf.get(), 0, c->stream);
     if (c->local) {
         if ((lrc = local_sendrecv(c, soff, scnt, speer, roff, rcnt, rpeer))) return lrc;
-        launch_pack(c->pending_rp, c->recvbuf, 1, c->stream);
+        launch_pack(c->pending_rp, c->recvbuf.get(), 1, c->stream);
         HIP_TRY(c, hipGetLastError());
         return CSI_OK;
     }
     if (c->hostg) {
-        if (!hostgroup_sendrecv(c->hostg, c->stream, c->recvbuf, soff, scnt, speer, roff, rcnt, rpeer, &c->err)) return CSI_ERR_COMM;
-        launch_pack(c->pending_rp, c->recvbuf, 1, c->stream);
+        if (!hostgroup_sendrecv(c->hostg, c->stream, c->recvbuf.get(), soff, scnt, speer, roff, rcnt, rpeer, &c->err)) return CSI_ERR_COMM;
+        launch_pack(c->pending_rp, c->recvbuf.get(), 1, c->stream);
         HIP_TRY(c, hipGetLastError());
         return CSI_OK;
     }
     NCCL_TRY(c, ncclGroupStart());
     for (int k = 0; k < 8; ++k)
-        if (speer[k] >= 0 && scnt[k] > 0) NCCL_TRY(c, ncclSend(c->sendbuf + soff[k], (size_t)scnt[k], ncclDouble, speer[k], c->comm, c->stream));
+        if (speer[k] >= 0 && scnt[k] > 0) NCCL_TRY(c, ncclSend(c->sendbuf.get() + soff[k], (size_t)scnt[k], ncclDouble, speer[k], c->comm, c->stream));
     for (int k = 0; k < 8; ++k)
-        if (rpeer[k] >= 0 && rcnt[k] > 0) NCCL_TRY(c, ncclRecv(c->recvbuf + roff[k], (size_t)rcnt[k], ncclDouble, rpeer[k], c->comm, c->stream));
+        if (rpeer[k] >= 0 && rcnt[k] > 0) NCCL_TRY(c, ncclRecv(c->recvbuf.get() + roff[k], (size_t)rcnt[k], ncclDouble, rpeer[k], c->comm, c->stream));
     NCCL_TRY(c, ncclGroupEnd());
-    launch_pack(c->pending_rp, c->recvbuf, 1, c->stream);
+    launch_pack(c->pending_rp, c->recvbuf.get(), 1, c->stream);
     HIP_TRY(c, hipGetLastError());
     return CSI_OK;
 }

@@ -42,28 +42,28 @@ int32_t need_momentum(csi_context* c) {
     return CSI_OK;
 }
 
-// StressBalanceFreeDrift: the velocities of marginal ice depend on the forcing only -- once per call into library arrays (as do_subcycle)
-static int32_t free_drift_fields(csi_context* c, double dt) {
+// StressBalanceFreeDrift: the free-drift velocities of marginal ice depend on the forcing only -- once per sub-cycle (EVP: do_subcycle)
+// or step into library arrays, at every point whose four-point averages stay inside the parent arrays.  (A launch error surfaces at
+// the caller's hipGetLastError.)
+int32_t free_drift_fields(csi_context* c, double dt) {
     if (!c->free_drift) return CSI_OK;
-    const int src[2] = {CSI_F_U, CSI_F_V};
-    for (int q = 0; q < 2; ++q) {
-        const size_t n = (size_t)c->f[src[q]].ld * (size_t)c->f[src[q]].nj;
-        if (c->fd_elems[q] != n) {
-            if (c->fd[q]) { HIP_TRY(c, hipStreamSynchronize(c->stream)); hipFree(c->fd[q]); c->fd[q] = nullptr; }
-            HIP_TRY(c, hipMalloc((void**)&c->fd[q], n * sizeof(double)));
-            HIP_TRY(c, hipMemsetAsync(c->fd[q], 0, n * sizeof(double), c->stream));
-            c->fd_elems[q] = n;
-        }
-    }
+    for (ScratchField& f : c->fd) HIP_TRY(c, f.ensure(c));
     launch_free_drift(evp_dev(c, dt), Range{2 - c->Hx, c->Nx + c->Hx - 1, 2 - c->Hy, c->Ny + c->Hy - 1}, c->stream);
-    HIP_TRY(c, hipGetLastError());
     return CSI_OK;
 }
 
-// update_external_stress! (split_explicit_momentum_equations.jl:133-134): local halos of the stress / forcing arrays
-static int32_t fill_forcing_halos(csi_context* c) {
+// reset_velocities! (split_explicit_momentum_equations.jl:89-93): an RK stage starts from u^-, v^-
+int32_t reset_velocities(csi_context* c) {
     int32_t rc;
-    for (int id : {CSI_F_TOP_U, CSI_F_TOP_V, CSI_F_BOT_U, CSI_F_BOT_V, CSI_F_FORCING_U, CSI_F_FORCING_V})
+    if ((rc = need(c, {CSI_F_UM, CSI_F_VM}))) return rc;
+    if ((rc = copy_parent(c, CSI_F_U, CSI_F_UM))) return rc;
+    return copy_parent(c, CSI_F_V, CSI_F_VM);
+}
+
+// update_external_stress! (split_explicit_momentum_equations.jl:133-134): local halos of the stress / forcing arrays
+int32_t fill_forcing_halos(csi_context* c) {
+    int32_t rc;
+    for (int id : kForcingFields)
         if (c->f[id].p && (rc = fill_halo(c, id))) return rc;
     return CSI_OK;
 }
@@ -80,11 +80,7 @@ static MomDev mom_dev(const csi_context* c, double dt) {
 // ---- ViscousRheology, split-explicit (split_explicit_momentum_equations.jl:103-195 with Rheologies.jl:42-55) ----------------
 static int32_t viscous_subcycle(csi_context* c, double dt, int substeps, int rk_reset) {
     int32_t rc;
-    if (rk_reset) {                                         // reset_velocities! :89-93
-        if ((rc = need(c, {CSI_F_UM, CSI_F_VM}))) return rc;
-        if ((rc = copy_parent(c, CSI_F_U, CSI_F_UM))) return rc;
-        if ((rc = copy_parent(c, CSI_F_V, CSI_F_VM))) return rc;
-    }
+    if (rk_reset && (rc = reset_velocities(c))) return rc;
     if ((rc = fill_forcing_halos(c))) return rc;           // :133-134 (initialize_rheology!: nothing)
     {                                                       // :170-171
         HaloBatch B{};
@@ -98,31 +94,22 @@ static int32_t viscous_subcycle(csi_context* c, double dt, int substeps, int rk_
     // reaches (halos beyond walls, deeper layers of a ValueBoundaryCondition side) must agree in both arrays: copied once, unless every
     // cell is an image (doubly periodic)
     const int comp[2] = {CSI_F_U, CSI_F_V};
-    for (int q = 0; q < 2; ++q) {
-        const Bound& b = c->f[comp[q]];
-        const size_t n = (size_t)b.ld * (size_t)b.nj;
-        if (c->vis_alt_elems[q] != n) {
-            if (c->vis_alt[q]) { HIP_TRY(c, hipStreamSynchronize(c->stream)); hipFree(c->vis_alt[q]); c->vis_alt[q] = nullptr; }
-            HIP_TRY(c, hipMalloc((void**)&c->vis_alt[q], n * sizeof(double)));
-            c->vis_alt_elems[q] = n;
-        }
-    }
+    for (ScratchField& a : c->vis_alt) HIP_TRY(c, a.ensure(c));
     const bool every_cell_imaged = c->g.xlo == SIDE_PERIODIC && c->g.xhi == SIDE_PERIODIC && c->g.ylo == SIDE_PERIODIC && c->g.yhi == SIDE_PERIODIC;
     if (!every_cell_imaged && substeps > 0) {
         CopyBatch B{};
         B.aligned16 = 1;
         for (int q = 0; q < 2; ++q) {
             const Bound& b = c->f[comp[q]];
-            B.src[B.count] = b.p; B.dst[B.count] = c->vis_alt[q]; B.n[B.count] = (long)b.ld * b.nj; ++B.count;
-            if ((((uintptr_t)b.p) | ((uintptr_t)c->vis_alt[q])) & 15) B.aligned16 = 0;
+            B.src[B.count] = b.p; B.dst[B.count] = c->vis_alt[q].get(); B.n[B.count] = (long)b.ld * b.nj; ++B.count;
+            if ((((uintptr_t)b.p) | ((uintptr_t)c->vis_alt[q].get())) & 15) B.aligned16 = 0;
         }
         launch_copy_batch(B, c->stream);
     }
     FRef bound[2], alt[2];
     for (int q = 0; q < 2; ++q) {
         bound[q] = ref_of(c, comp[q]);
-        alt[q] = bound[q];
-        alt[q].p = c->vis_alt[q] + (c->Hx - 1) + (int64_t)(c->Hy - 1) * c->f[comp[q]].ld;
+        alt[q] = c->vis_alt[q].view(c);
     }
     MomDev M = mom_dev(c, dt / substeps);                   // Delta tau = Delta t / substeps (Rheologies.jl:48-49)
     const ImageSpec imu = image_spec(c, CSI_F_U), imv = image_spec(c, CSI_F_V);
@@ -149,8 +136,8 @@ static int32_t viscous_subcycle(csi_context* c, double dt, int substeps, int rk_
         for (int q = 0; q < 2; ++q)
             if (cur[q]) {
                 const Bound& b = c->f[comp[q]];
-                B.src[B.count] = c->vis_alt[q]; B.dst[B.count] = b.p; B.n[B.count] = (long)b.ld * b.nj; ++B.count;
-                if ((((uintptr_t)b.p) | ((uintptr_t)c->vis_alt[q])) & 15) B.aligned16 = 0;
+                B.src[B.count] = c->vis_alt[q].get(); B.dst[B.count] = b.p; B.n[B.count] = (long)b.ld * b.nj; ++B.count;
+                if ((((uintptr_t)b.p) | ((uintptr_t)c->vis_alt[q].get())) & 15) B.aligned16 = 0;
             }
         launch_copy_batch(B, c->stream);
     }

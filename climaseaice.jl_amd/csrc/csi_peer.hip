@@ -28,12 +28,6 @@ PeerSets peer_wait_counts(const csi_context* c, const FusedGeom& G) {
         if (ja <= reach) ++ps.nS;
         if (jb + reach > c->Ny) ++ps.nN;
     }
-    if (c->tune.exp_overlap > 0 && (c->tune.exp_overlap & 1)) {
-        // EXPERIMENT (profiles/r06_tile_overlap.txt): every tile in the sets of both sides of a connected axis -- each publishes its
-        // flag at every launch and waits before it loads anything, so that consecutive launches need no stream order between them
-        if (c->geom_peer & 4) ps.nS = ps.nN = G.nchunks;
-        if (c->geom_peer & 2) ps.nW = ps.nE = G.nstrips;
-    }
     const int sz[8] = {ps.nW * G.nchunks, ps.nE * G.nchunks, ps.nS * G.nstrips, ps.nN * G.nstrips,
                        ps.nW * ps.nS, ps.nE * ps.nS, ps.nW * ps.nN, ps.nE * ps.nN};
     for (int d = 0; d < 8; ++d) ps.size[d] = sz[d];
@@ -43,7 +37,7 @@ PeerSets peer_wait_counts(const csi_context* c, const FusedGeom& G) {
 
 // the 14 local arrays a neighbour stores images into, in Peer::arr order
 void peer_local_arrays(const csi_context* c, const void* out[csi_context::Peer::NARR]) {
-    for (int q = 0; q < 5; ++q) { out[q] = c->f[kPing[q]].p; out[5 + q] = c->alt[q]; }
+    for (int q = 0; q < 5; ++q) { out[q] = c->f[kPing[q]].p; out[5 + q] = c->alt[q].get(); }
     out[10] = c->f[CSI_F_ALPHA].p; out[11] = c->f[CSI_F_ZETA_C].p; out[12] = c->f[CSI_F_ZETA_F].p; out[13] = c->f[CSI_F_DELTA].p;
 }
 
@@ -116,25 +110,17 @@ int32_t peer_setup(csi_context* c, bool local_ok) {
     soft(hipStreamSynchronize(c->stream), "hipStreamSynchronize");
     peer_release(c);
     const int me = c->tile.ry * c->tile.Rx + c->tile.rx;
-    if (!pr.slots) {
+    // (a failed allocation leaves its owner empty: reported through the collective below, tried again by the next set-up)
+    constexpr size_t kFlags = 8 * (size_t)csi_context::Peer::SLOTS;
+    if (!pr.slots && pr.slots.alloc(kFlags, hipDeviceMallocFinegrained) != hipSuccess) {
         // fine-grained (uncached) device memory where the runtime offers it: the flags are polled while remote ranks write them
-        if (hipExtMallocWithFlags((void**)&pr.slots, sizeof(unsigned long long) * 8 * csi_context::Peer::SLOTS, hipDeviceMallocFinegrained) != hipSuccess) {
-            (void)hipGetLastError();
-            pr.slots = nullptr;
-            if (!soft(hipMalloc((void**)&pr.slots, sizeof(unsigned long long) * 8 * csi_context::Peer::SLOTS), "hipMalloc(flags)")) pr.slots = nullptr;
-        }
+        (void)hipGetLastError();
+        soft(pr.slots.alloc(kFlags), "allocating the flag array");
     }
-    if (!pr.err && !soft(hipMalloc((void**)&pr.err, sizeof(unsigned)), "hipMalloc(error word)")) pr.err = nullptr;
-    if (!pr.err_host && !soft(hipHostMalloc((void**)&pr.err_host, sizeof(unsigned), hipHostMallocDefault), "hipHostMalloc(error word)")) pr.err_host = nullptr;
-    {
-        const size_t need_x = sizeof(PeerRec) * kPeerRecs * (size_t)(c->world + 1) + 64;      // (a later csi_comm_init may have a larger world)
-        if (need_x > pr.xbuf_cap) {
-            if (pr.xbuf) hipFree(pr.xbuf);
-            pr.xbuf = nullptr; pr.xbuf_cap = 0;
-            HIP_TRY(c, hipMalloc((void**)&pr.xbuf, need_x));      // (the all-gather's own staging: the one failure this rank cannot report collectively)
-            pr.xbuf_cap = need_x;
-        }
-    }
+    if (!pr.err) soft(pr.err.alloc(1), "allocating the error word");
+    if (!pr.err_host) soft(pr.err_host.alloc(1, hipHostMallocDefault), "allocating the pinned error word");
+    const size_t need_x = sizeof(PeerRec) * kPeerRecs * (size_t)(c->world + 1) + 64;      // (a later csi_comm_init may have a larger world)
+    if (need_x > pr.xbuf.size()) HIP_TRY(c, pr.xbuf.alloc(need_x));      // (the all-gather's own staging: the one failure this rank cannot report collectively)
     if (!pr.slots || !pr.err || !pr.err_host) ok = 0;
     pr.seq = 0;
     pr.ny_below = c->Ny;
@@ -156,7 +142,7 @@ int32_t peer_setup(csi_context* c, bool local_ok) {
                                                   c->f[CSI_F_ALPHA].ld, c->f[CSI_F_ZETA_C].ld, c->f[CSI_F_ZETA_F].ld, c->f[CSI_F_DELTA].ld};
     std::vector<PeerRec> mine(kPeerRecs), all((size_t)kPeerRecs * c->world);
     for (int q = 0; q < kPeerRecs; ++q) {
-        const void* ptr = q < csi_context::Peer::NARR ? local[q] : (const void*)pr.slots;
+        const void* ptr = q < csi_context::Peer::NARR ? local[q] : (const void*)pr.slots.get();
         PeerRec& r = mine[q];
         memset(&r, 0, sizeof r);
         r.ld = q < csi_context::Peer::NARR ? lds[q] : 0;
@@ -188,10 +174,10 @@ int32_t peer_setup(csi_context* c, bool local_ok) {
     } else if (c->world > 1) {
         const size_t nb = sizeof(PeerRec) * kPeerRecs;
         // (a local copy that fails must not keep this rank out of the collectives: it takes part and votes 0 below)
-        soft(hipMemcpy(pr.xbuf, mine.data(), nb, hipMemcpyHostToDevice), "hipMemcpy(records)");
-        NCCL_TRY(c, ncclAllGather(pr.xbuf, pr.xbuf + nb, nb, ncclUint8, c->comm, c->stream));      // (an RCCL error is fatal for the communicator anyway)
+        soft(hipMemcpy(pr.xbuf.get(), mine.data(), nb, hipMemcpyHostToDevice), "hipMemcpy(records)");
+        NCCL_TRY(c, ncclAllGather(pr.xbuf.get(), pr.xbuf.get() + nb, nb, ncclUint8, c->comm, c->stream));      // (an RCCL error is fatal for the communicator anyway)
         if (!soft(hipStreamSynchronize(c->stream), "hipStreamSynchronize(all-gather)") ||
-            !soft(hipMemcpy(all.data(), pr.xbuf + nb, nb * c->world, hipMemcpyDeviceToHost), "hipMemcpy(all records)"))
+            !soft(hipMemcpy(all.data(), pr.xbuf.get() + nb, nb * c->world, hipMemcpyDeviceToHost), "hipMemcpy(all records)"))
             for (PeerRec& r : all) r.ok = 0;
     } else {
         all = mine;
@@ -200,9 +186,9 @@ int32_t peer_setup(csi_context* c, bool local_ok) {
     // raises its abort words.  NOW the flags, the abort words and the error word are cleared -- cleared before the all-gather, a
     // neighbour still finishing its last launch (or its aborted sub-cycle) could write them again behind the memset and the
     // restarted launch numbers would meet stale flags.  No rank launches before the all-reduce below has returned.
-    if (pr.slots) soft(hipMemset(pr.slots, 0, sizeof(unsigned long long) * 8 * csi_context::Peer::SLOTS), "hipMemset(flags)");
-    if (pr.err) soft(hipMemset(pr.err, 0, sizeof(unsigned)), "hipMemset(error word)");
-    if (pr.err_host) *pr.err_host = 0;
+    if (pr.slots) soft(hipMemset(pr.slots.get(), 0, sizeof(unsigned long long) * kFlags), "hipMemset(flags)");
+    if (pr.err) soft(hipMemset(pr.err.get(), 0, sizeof(unsigned)), "hipMemset(error word)");
+    if (pr.err_host) *pr.err_host.get() = 0;
     // map the neighbours' buffers (one mapping per distinct allocation)
     struct Mapped { int rank; hipIpcMemHandle_t h; void* p; };
     std::vector<Mapped> cache;
@@ -240,7 +226,7 @@ int32_t peer_setup(csi_context* c, bool local_ok) {
         pr.nbr_slots[d] = nullptr;
         pr.nbr_wait[d] = (ok && pr.sync_rank[d] >= 0) ? all[(size_t)pr.sync_rank[d] * kPeerRecs].set_size[kPeerOpp[d]] : 0;
         if (ok && pr.sync_rank[d] >= 0) {
-            void* sp = pr.slots;
+            void* sp = pr.slots.get();
             if (pr.sync_rank[d] != me && !resolve(pr.sync_rank[d], csi_context::Peer::NARR, &sp)) ok = 0;
             pr.nbr_slots[d] = (unsigned long long*)sp;
         }
@@ -253,7 +239,7 @@ int32_t peer_setup(csi_context* c, bool local_ok) {
         if (!hostgroup_allgather(c->hostg, &ok, sizeof(int), bytes, &c->err)) return CSI_ERR_COMM;
         for (int r = 0; r < c->world; ++r) { int x; memcpy(&x, bytes.data() + (size_t)r * sizeof(int), sizeof(int)); if (x < ok) ok = x; }
     } else if (c->world > 1) {                               // every rank or none
-        int* flag = (int*)pr.xbuf;
+        int* flag = (int*)pr.xbuf.get();
         // (a failing upload votes with a zeroed word: hipMemset is tried, and whatever the word holds this rank itself ends with ok = 0)
         const bool up = soft(hipMemcpy(flag, &ok, sizeof(int), hipMemcpyHostToDevice), "hipMemcpy(vote)");
         // (... and when the word can be neither written nor zeroed it still holds all-gather bytes: this rank would vote non-zero while ending
@@ -319,7 +305,7 @@ int32_t peer_fill_table(csi_context* c, const FusedGeom& G, bool out_is_alt, Fus
         }
     int mask = 0;
     for (int d = 0; d < 8; ++d) {
-        t->P[FP_SLOT_IN + d] = (unsigned long)(pr.slots + (size_t)d * csi_context::Peer::SLOTS);
+        t->P[FP_SLOT_IN + d] = (unsigned long)(pr.slots.get() + (size_t)d * csi_context::Peer::SLOTS);
         t->P[FP_SLOT_OUT + d] = pr.nbr_slots[d] ? (unsigned long)(pr.nbr_slots[d] + (size_t)kPeerOpp[d] * csi_context::Peer::SLOTS) : 0ul;
         t->I[FI_PWAIT + d] = pr.nbr_wait[d];      // (the neighbour's own set: a fold tile's launches have another geometry)
         if (pr.sync_rank[d] >= 0) mask |= 1 << d;
@@ -329,7 +315,7 @@ int32_t peer_fill_table(csi_context* c, const FusedGeom& G, bool out_is_alt, Fus
         for (int q = 0; q < 2; ++q) { t->I[FI_PDLD + d * 2 + q] = pr.dld[d][q]; any |= pr.dld[d][q] != 0; }
     t->I[FI_PHASDLD] = any;
     t->I[FI_NYLO] = c->peer.ny_below > 0 ? c->peer.ny_below : c->Ny;
-    t->P[FP_PERR] = (unsigned long)pr.err;
+    t->P[FP_PERR] = (unsigned long)pr.err.get();
     t->I[FI_PEER] = 1; t->I[FI_PMASK] = mask;
     t->I[FI_PTIER] = peer_effective_tier(c);
     t->I[FI_PSET] = ps.nW; t->I[FI_PSET + 1] = ps.nE; t->I[FI_PSET + 2] = ps.nS; t->I[FI_PSET + 3] = ps.nN;
