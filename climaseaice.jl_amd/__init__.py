@@ -7,7 +7,7 @@ contains a dot, so import it through the repo-root shim: `import climaseaice_jl_
 """
 from . import _lib
 from ._lib import Context, CsiError, LocalGroup, plan_exchange, plan_ranges
-from .dynamics import (Auxiliaries, BetaPlane, PointwiseCoriolis, ElastoViscoPlasticRheology, ExplicitSolver, FPlane, IceStrength,
+from .dynamics import (Auxiliaries, BetaPlane, FreeDriftVelocities, PointwiseCoriolis, ElastoViscoPlasticRheology, ExplicitSolver, FPlane, IceStrength,
                        ReplacementPressure, SeaIceMomentumEquation, SemiImplicitStress, SplitExplicitSolver, StressBalanceFreeDrift,
                        ViscousRheology)
 from .fields import CenterField, CornerField, Field, XFaceField, YFaceField

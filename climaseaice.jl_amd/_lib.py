@@ -18,7 +18,8 @@ FIELD_IDS = ["U", "V", "H", "A", "S11", "S22", "S12", "UN", "VN", "P", "ALPHA", 
              "GH", "GA", "HM", "AM", "UM", "VM", "TOP_U", "TOP_V", "BOT_U", "BOT_V", "MASS_FLUX",
              "HS", "GHS", "HSM", "MASS_FLUX_SNOW", "SNOWFALL_INTERCEPTED", "TU", "TUS", "FORCING_U", "FORCING_V", "GU", "GV"]
 THERMO_FIELD_IDS = ["TOP_HEAT_FLUX", "BOTTOM_HEAT_FLUX", "SNOWFALL"]     # csi_thermo_field_id: numbered from CSI_F_COUNT on
-F = {n: k for k, n in enumerate(FIELD_IDS + THERMO_FIELD_IDS)}
+FREE_DRIFT_FIELD_IDS = ["FREE_DRIFT_U", "FREE_DRIFT_V"]                  # csi_free_drift_field_id: numbered from CSI_F_COUNT_ALL on
+F = {n: k for k, n in enumerate(FIELD_IDS + THERMO_FIELD_IDS + FREE_DRIFT_FIELD_IDS)}
 STRESS_NONE, STRESS_CONST, STRESS_FIELD, STRESS_SEMI_IMPLICIT = 0, 1, 2, 3
 VEL_ZERO, VEL_CONST, VEL_FIELD = 0, 1, 2
 STRESS_TOP, STRESS_BOTTOM = 0, 1
@@ -26,6 +27,8 @@ MODE_STRICT, MODE_FAST = 0, 1
 PRESSURE_REPLACEMENT, PRESSURE_ICE_STRENGTH = 0, 1
 RHEOLOGY_EVP, RHEOLOGY_VISCOUS = 0, 1
 SOLVER_SPLIT_EXPLICIT, SOLVER_EXPLICIT = 0, 1
+FREE_DRIFT_NONE, FREE_DRIFT_STRESS_BALANCE, FREE_DRIFT_FIELDS = 0, 1, 2
+DYNAMICS_MOMENTUM_EQUATION, DYNAMICS_FREE_DRIFT = 0, 1
 FLUX_CONSTANT, FLUX_ARRAY, FLUX_RADIATIVE_EMISSION = 0, 1, 2
 HEAT_TOP, HEAT_BOTTOM = 0, 1
 MAX_HEAT_FLUX_TERMS = 8
@@ -41,7 +44,7 @@ SYMBOLS = ["csi_version", "csi_context_create", "csi_context_destroy", "csi_last
            "csi_immersed_flux_bc_set", "csi_coriolis_points_set", "csi_validate_all", "csi_debug_peer_abort", "csi_set_weno_weight_dtype", "csi_weno_weight_dtype", "csi_subcycle_stats_begin", "csi_subcycle_stats_end",
            "csi_set_tile_skipping", "csi_tile_activity", "csi_set_row_constant", "csi_row_constant_rows",
            "csi_rheology_set", "csi_momentum_solver_set", "csi_compute_momentum_tendencies",
-           "csi_heat_fluxes_set", "csi_surface_solve_set"]
+           "csi_heat_fluxes_set", "csi_surface_solve_set", "csi_dynamics_set"]
 
 
 class Metrics(C.Structure):
@@ -160,6 +163,7 @@ def load():
         "csi_subcycle_stats_end": [vp, C.POINTER(dbl), C.POINTER(i32), C.POINTER(i32)],
         "csi_rheology_set": [vp, i32, dbl], "csi_momentum_solver_set": [vp, i32], "csi_compute_momentum_tendencies": [vp, dbl],
         "csi_heat_fluxes_set": [vp, i32, C.POINTER(HeatFluxTerm), i32], "csi_surface_solve_set": [vp, C.POINTER(SurfaceSolve)],
+        "csi_dynamics_set": [vp, i32],
     }
     for name, args in sig.items():
         fn = getattr(L, name, None)

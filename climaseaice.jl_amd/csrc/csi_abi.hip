@@ -363,7 +363,7 @@ int32_t csi_mask_set(csi_context* c, const uint8_t* dev_mask, int64_t ld) {
 int32_t csi_field_bind(csi_context* c, int32_t fid, void* dev_ptr, int64_t ld, int32_t ni, int32_t nj) {
     if (!c) return CSI_ERR_INVALID_ARGUMENT;
     if (!c->grid_set) return fail(c, CSI_ERR_NOT_BOUND, "csi_grid_set has not been called");
-    if (fid < 0 || fid >= CSI_F_COUNT_ALL) return fail(c, CSI_ERR_INVALID_ARGUMENT, "unknown field id");
+    if (fid < 0 || fid >= CSI_F_COUNT_TOTAL) return fail(c, CSI_ERR_INVALID_ARGUMENT, "unknown field id");
     if (!dev_ptr) { c->f[fid] = Bound{}; return CSI_OK; }
     const int eni = c->Nx + 2 * c->Hx + extra_x(c, fid), enj = c->Ny + 2 * c->Hy + extra_y(c, fid);
     if (ni != eni || nj != enj || ld < ni) {
@@ -536,6 +536,9 @@ int32_t csi_cache_current_fields(csi_context* c) {
     return CSI_OK;
 }
 
+// the slots csi_fill_halo_local / csi_halo_exchange take: csi_field_id and the prescribed free-drift velocity fields
+static bool halo_slot(int32_t fid) { return (fid >= 0 && fid < CSI_F_COUNT) || fid == CSI_F_FREE_DRIFT_U || fid == CSI_F_FREE_DRIFT_V; }
+
 int32_t csi_update_state(csi_context* c) {
     if (!c) return CSI_ERR_INVALID_ARGUMENT;
     return do_update_state(c);
@@ -543,7 +546,7 @@ int32_t csi_update_state(csi_context* c) {
 
 int32_t csi_fill_halo_local(csi_context* c, int32_t fid) {
     if (!c) return CSI_ERR_INVALID_ARGUMENT;
-    if (fid < 0 || fid >= CSI_F_COUNT) return fail(c, CSI_ERR_INVALID_ARGUMENT, "unknown field id");
+    if (!halo_slot(fid)) return fail(c, CSI_ERR_INVALID_ARGUMENT, "unknown field id");
     int32_t rc = need(c, {fid});
     if (rc) return rc;
     return fill_halo(c, fid);
@@ -553,7 +556,7 @@ int32_t csi_time_step_fe(csi_context* c, double dt, int32_t substeps, int32_t sc
     if (!c) return CSI_ERR_INVALID_ARGUMENT;
     // dynamics = nothing (csi_evp_params_set never called): prescribed velocities, time_step_momentum! is a no-op
     // (SeaIceDynamics.jl:40) -- the advection-only models of examples/ice_advected_by_anticyclone.jl's family
-    const bool dynamics = c->evp_set;
+    const bool dynamics = has_dynamics(c);      // (or csi_dynamics_set(ctx, CSI_DYNAMICS_FREE_DRIFT))
     int32_t rc = dynamics ? need_momentum(c) : need(c, {CSI_F_H, CSI_F_A});
     if (rc) return rc;
     if (first_iteration && (rc = do_update_state(c))) return rc;          // sea_ice_fe_step.jl:16
@@ -583,7 +586,7 @@ bool advect_stage_supported(const csi_context* c, int scheme) {
     // separate update streams another 7 arrays per stage, which the fused stage never touches: no cut any more (A/B knob:
     // CSI_ADV_STAGE_MAX_CELLS)
     if ((long)c->Nx * c->Ny > c->tune.adv_stage_max_cells) return false;
-    return !c->evp_set && scheme != 0 && c->fusion && !c->slab_set && !c->g.has_mask && !is_tiled(c) &&
+    return !has_dynamics(c) && scheme != 0 && c->fusion && !c->slab_set && !c->g.has_mask && !is_tiled(c) &&
            c->f[CSI_F_HS].p == nullptr && c->f[CSI_F_H].ld == c->f[CSI_F_HM].ld && c->f[CSI_F_A].ld == c->f[CSI_F_AM].ld;
 }
 int32_t rk3_advection_only(csi_context* c, double dt, int scheme) {
@@ -614,7 +617,7 @@ int32_t rk3_advection_only(csi_context* c, double dt, int scheme) {
 
 int32_t csi_time_step_rk3(csi_context* c, double dt, int32_t substeps, int32_t scheme) {
     if (!c) return CSI_ERR_INVALID_ARGUMENT;
-    const bool dynamics = c->evp_set;                                     // see csi_time_step_fe
+    const bool dynamics = has_dynamics(c);                                // see csi_time_step_fe
     int32_t rc = dynamics ? need_momentum(c) : need(c, {CSI_F_H, CSI_F_A});
     if (rc) return rc;
     if ((rc = dynamics ? need(c, {CSI_F_HM, CSI_F_AM, CSI_F_UM, CSI_F_VM}) : need(c, {CSI_F_HM, CSI_F_AM}))) return rc;
@@ -810,7 +813,7 @@ int32_t csi_halo_exchange(csi_context* c, const int32_t* field_ids, int32_t nfie
     if (!c || !field_ids) return CSI_ERR_INVALID_ARGUMENT;
     if (!c->grid_set) return fail(c, CSI_ERR_NOT_BOUND, "csi_grid_set has not been called");
     for (int k = 0; k < nfields; ++k)
-        if (field_ids[k] < 0 || field_ids[k] >= CSI_F_COUNT) return fail(c, CSI_ERR_INVALID_ARGUMENT, "unknown field id");
+        if (!halo_slot(field_ids[k])) return fail(c, CSI_ERR_INVALID_ARGUMENT, "unknown field id");
     return exchange(c, field_ids, nfields, width);
 }
 
@@ -843,8 +846,17 @@ int32_t csi_plan_exchange(int32_t Nx, int32_t Ny, int32_t Hx, int32_t Hy, int32_
 
 int32_t csi_free_drift_set(csi_context* c, int32_t kind) {
     if (!c) return CSI_ERR_INVALID_ARGUMENT;
-    if (kind != 0 && kind != 1) return fail(c, CSI_ERR_INVALID_ARGUMENT, "free drift kind: 0 (nothing) or 1 (StressBalanceFreeDrift)");
+    if (kind != CSI_FREE_DRIFT_NONE && kind != CSI_FREE_DRIFT_STRESS_BALANCE && kind != CSI_FREE_DRIFT_FIELDS)
+        return fail(c, CSI_ERR_INVALID_ARGUMENT, "free drift kind: 0 (nothing), 1 (StressBalanceFreeDrift) or 2 (prescribed velocity fields)");
     c->free_drift = kind;
+    return CSI_OK;
+}
+
+int32_t csi_dynamics_set(csi_context* c, int32_t kind) {
+    if (!c) return CSI_ERR_INVALID_ARGUMENT;
+    if (kind != CSI_DYNAMICS_MOMENTUM_EQUATION && kind != CSI_DYNAMICS_FREE_DRIFT)
+        return fail(c, CSI_ERR_INVALID_ARGUMENT, "unknown dynamics kind: 0 (SeaIceMomentumEquation) or 1 (StressBalanceFreeDrift)");
+    c->dynamics = kind;
     return CSI_OK;
 }
 

@@ -170,7 +170,10 @@ EvpDev evp_dev(const csi_context* c, double dt) {
     for (int k = 0; k < 4; ++k) { P.ibc_u[k] = c->ibc[0][k]; P.ibc_v[k] = c->ibc[1][k]; any_ibc |= (c->ibc[0][k] != 0.0) | (c->ibc[1][k] != 0.0); }
     P.extra = (P.has_forcing || (any_ibc && c->g.has_mask)) ? 1 : 0;
     P.free_drift = c->free_drift;
-    if (c->free_drift && c->fd[0].get() && c->fd[1].get()) { P.ufd = c->fd[0].view(c); P.vfd = c->fd[1].view(c); }
+    // (P.free_drift non-zero: the kernels read P.ufd / P.vfd -- the library's arrays (kind 1, filled by free_drift_fields) or, in place,
+    //  the caller's (kind 2: need_dynamics_common has checked that both are bound))
+    if (c->free_drift == CSI_FREE_DRIFT_FIELDS) { P.ufd = ref_of(c, CSI_F_FREE_DRIFT_U); P.vfd = ref_of(c, CSI_F_FREE_DRIFT_V); }
+    else if (c->free_drift && c->fd[0].get() && c->fd[1].get()) { P.ufd = c->fd[0].view(c); P.vfd = c->fd[1].view(c); }
     return P;
 }
 
@@ -331,7 +334,7 @@ bool offsets_fit_32bit(int Nx, int Ny, int Hx, int Hy, int64_t max_ld) {
 }
 int64_t max_bound_ld(const csi_context* c) {
     int64_t m = 0;
-    for (int k = 0; k < CSI_F_COUNT_ALL; ++k) if (c->f[k].p && c->f[k].ld > m) m = c->f[k].ld;
+    for (int k = 0; k < CSI_F_COUNT_TOTAL; ++k) if (c->f[k].p && c->f[k].ld > m) m = c->f[k].ld;
     if (c->g.has_mask && c->g.mask_ld > m) m = c->g.mask_ld;
     return m;
 }

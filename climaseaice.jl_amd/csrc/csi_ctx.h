@@ -40,7 +40,7 @@ struct Bound {
 };
 
 // (x, y) location of every field slot
-static const int kLoc[CSI_F_COUNT_ALL][2] = {
+static const int kLoc[CSI_F_COUNT_TOTAL][2] = {
     {LOC_F, LOC_C}, {LOC_C, LOC_F}, {LOC_C, LOC_C}, {LOC_C, LOC_C},   // U V H A
     {LOC_C, LOC_C}, {LOC_C, LOC_C}, {LOC_F, LOC_F},                   // S11 S22 S12
     {LOC_F, LOC_C}, {LOC_C, LOC_F}, {LOC_C, LOC_C}, {LOC_C, LOC_C}, {LOC_C, LOC_C},  // UN VN P ALPHA DELTA
@@ -53,12 +53,13 @@ static const int kLoc[CSI_F_COUNT_ALL][2] = {
     {LOC_C, LOC_C}, {LOC_C, LOC_C}, {LOC_C, LOC_C}, {LOC_C, LOC_C},   // MASS_FLUX_SNOW SNOWFALL_INTERCEPTED TU TUS
     {LOC_F, LOC_C}, {LOC_C, LOC_F},                                   // FORCING_U FORCING_V
     {LOC_F, LOC_C}, {LOC_C, LOC_F},                                   // GU GV
-    {LOC_C, LOC_C}, {LOC_C, LOC_C}, {LOC_C, LOC_C}};                  // TOP_HEAT_FLUX BOTTOM_HEAT_FLUX SNOWFALL
-static const char* const kName[CSI_F_COUNT_ALL] = {"u", "v", "h", "aice", "sigma11", "sigma22", "sigma12", "un", "vn", "P", "alpha",
+    {LOC_C, LOC_C}, {LOC_C, LOC_C}, {LOC_C, LOC_C},                   // TOP_HEAT_FLUX BOTTOM_HEAT_FLUX SNOWFALL
+    {LOC_F, LOC_C}, {LOC_C, LOC_F}};                                  // FREE_DRIFT_U FREE_DRIFT_V
+static const char* const kName[CSI_F_COUNT_TOTAL] = {"u", "v", "h", "aice", "sigma11", "sigma22", "sigma12", "un", "vn", "P", "alpha",
                                   "Delta", "zeta_f", "zeta_c", "Gh", "Gaice", "h-", "aice-", "u-", "v-",
                                   "top_u", "top_v", "bottom_u", "bottom_v", "mass_flux",
                                   "hs", "Ghs", "hs-", "mass_flux_snow", "intercepted_snowfall", "Tu", "Tu_snow", "forcing_u", "forcing_v", "Gu", "Gv",
-                                  "top_heat_flux", "bottom_heat_flux", "snowfall"};
+                                  "top_heat_flux", "bottom_heat_flux", "snowfall", "free_drift_u", "free_drift_v"};
 
 extern std::string g_create_error;      // csi_context_create failures (no context to hold the message)
 
@@ -120,7 +121,7 @@ struct csi_context {
     long fcor2_ld = 0, fcor2_plane = 0;
     bool cor_dirty = true;               // Coriolis columns of the FAST table need (re)building
     double cor_synced = 0.0;             // FPlane value they were built with
-    Bound f[CSI_F_COUNT_ALL];
+    Bound f[CSI_F_COUNT_TOTAL];
     csi_evp_params evp{};
     csi_stress stress[2]{};
     int mode = CSI_MODE_STRICT;
@@ -198,7 +199,9 @@ struct csi_context {
     ScratchField fbar_top[2] = {{CSI_F_V, kZeroed}, {CSI_F_U, kZeroed}};   // the same of the air velocities (array-valued wind drag)
     ScratchField fd[2] = {{CSI_F_U, kZeroed}, {CSI_F_V, kZeroed}};         // free-drift velocities at u / v points (StressBalanceFreeDrift)
     ScratchField xd[2] = {{CSI_F_U, kZeroed}, {CSI_F_V, kZeroed}};         // stress divergence of the immersed flux boundary conditions at u / v points (two-sub-steps kernel)
-    int free_drift = 0;                     // csi_free_drift_set
+    int free_drift = 0;                     // csi_free_drift_set: csi_free_drift_kind.  Non-zero: the kernels read P.ufd / P.vfd; 1: the library
+                                            // computes them from the stresses first (fd[]); 2: they ARE the arrays bound to CSI_F_FREE_DRIFT_U / _V
+    int dynamics = CSI_DYNAMICS_MOMENTUM_EQUATION;   // csi_dynamics_set: CSI_DYNAMICS_FREE_DRIFT = StressBalanceFreeDrift as the whole dynamics
     bool slab_set = false;   // thermodynamic step inside csi_time_step_fe / _rk3
     SlabDev slab{};
     int vel_bc_on[2][2] = {{0, 0}, {0, 0}};          // csi_velocity_bc_set: [u | v][low | high] ValueBoundaryCondition
@@ -290,7 +293,9 @@ static inline int nxf_of(int k) { return k > 1 ? 5 : 2; }     // sigma travels w
 struct FoldBand;
 // ---- functions shared by the translation units (definitions: see the list at the top) ----
 static const int kPing[5] = {CSI_F_U, CSI_F_V, CSI_F_S11, CSI_F_S22, CSI_F_S12};
-static const int kForcingFields[6] = {CSI_F_TOP_U, CSI_F_TOP_V, CSI_F_BOT_U, CSI_F_BOT_V, CSI_F_FORCING_U, CSI_F_FORCING_V};      // update_external_stress!
+// update_external_stress!: the arrays at the velocity points whose halos the library fills (and exchanges between tiles) before a momentum step
+static const int kForcingFields[8] = {CSI_F_TOP_U, CSI_F_TOP_V, CSI_F_BOT_U, CSI_F_BOT_V, CSI_F_FORCING_U, CSI_F_FORCING_V,
+                                      CSI_F_FREE_DRIFT_U, CSI_F_FREE_DRIFT_V};
 // (elo / ehi: rows of the FIRST / LAST chunk where they differ from `rows` -- shorter tiles next to a peer-connected y side,
 //  pair_geom; elo == rows and ehi == 0: every chunk `rows` rows, the last one what is left)
 struct FusedGeom { Range rs; int nstrips, nchunks, rows; int elo = 0, ehi = 0; int wt = 0; };      // wt: write-through result stores (FI_WT)
@@ -417,6 +422,8 @@ int32_t do_momentum_tendencies(csi_context* c, double dt);
 int32_t free_drift_fields(csi_context* c, double dt);      // (shared with the EVP sub-cycle and time_step_momentum!, csi_launch.hip)
 int32_t reset_velocities(csi_context* c);
 int32_t fill_forcing_halos(csi_context* c);
+int32_t update_external_stress(csi_context* c);          // fill_forcing_halos + their exchange between tiles
+static inline bool has_dynamics(const csi_context* c) { return c->evp_set || c->dynamics == CSI_DYNAMICS_FREE_DRIFT; }
 AdvDev adv_dev(const csi_context* c, int scheme, double dt, int from_cache);
 int32_t do_update_state(csi_context* c, bool in_step = false, bool tracers_filled = false);
 int32_t do_tendencies(csi_context* c, int scheme);

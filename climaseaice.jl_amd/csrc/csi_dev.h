@@ -71,8 +71,9 @@ struct EvpDev {
     const double *fcor2_u, *fcor2_v; // per-point f on CSI_METRIC_FULL grids (ptr[i + j * fcor2_ld]); NULL: rows / fcor
     long fcor2_ld;
     int pressure_kind, has_cor;
-    int free_drift;           // 1: StressBalanceFreeDrift, velocities of marginal ice from ufd / vfd
-    FRef ufd, vfd;            // free-drift velocities at u / v points (library scratch, once per sub-cycle)
+    int free_drift;           // csi_free_drift_kind; non-zero: the velocities of marginal ice are read from ufd / vfd
+    FRef ufd, vfd;            // free-drift velocities at u / v points: library scratch filled once per sub-cycle (kind 1,
+                              // StressBalanceFreeDrift) or the caller's arrays, read in place (kind 2, prescribed fields)
     double dt;
     int write_diag;   // FAST: also store zeta_c, zeta_f, Delta (last sub-step only)
     // rarely used terms of the velocity tendencies (three-kernel paths only; `extra` = any of them present):
@@ -83,6 +84,15 @@ struct EvpDev {
 };
 
 struct Range { int i0, i1, j0, j1; };
+
+// StressBalanceFreeDrift's closed form (stress_balance_free_drift.jl:61-109) on gathered values: ue the external velocity component of
+// the SemiImplicitStress at the point, (tx, ty) the explicit stress there (one component read at the point, the other a four-point
+// average), own = the one of the two that belongs to the velocity component, C = rho_e * C_D.  One arithmetic for every caller
+// (k_free_drift, k_free_drift_step), in the reference's operation order.
+__device__ __forceinline__ double stress_balance_velocity(double ue, double own, double tx, double ty, double C) {
+    const double t = sqrt(tx * tx + ty * ty);
+    return ue - ((t == 0) ? t : own / sqrt(C * t));
+}
 
 // Coriolis parameter at the u / v point (i, j): per point, per row or a number
 // (one conditional load from a selected address: nested loads under nested tests were two memory round trips)
@@ -183,6 +193,9 @@ __device__ __forceinline__ int image_hi(int mode, int i, int N, int H, bool& has
     if (mode == IMG_VALUE) { has = (i == N); return N + 1; }
     has = false; return 0;
 }
+// (momentum_free_drift.hip store_point_and_images restates these stores with fixed image slots instead of the run-time lists below,
+//  which live in scratch memory: a change of the image semantics here has to be made there too.  tests/test_gpu_free_drift.py compares
+//  that kernel's parents, halos included, with the oracle's fills on every topology.)
 __device__ __forceinline__ void store_with_images(const FRef& f, const GridDev& g, const ImageSpec& im, int i, int j, double val) {
     f(i, j) = val;
     // Elements within H of an edge have halo images; the test is cheap and almost always false.

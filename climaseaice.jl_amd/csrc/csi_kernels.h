@@ -14,6 +14,8 @@ void launch_strict_vstep(const EvpDev& P, const Range& r, const ImageSpec& im, h
 
 // free-drift velocities of marginal ice (StressBalanceFreeDrift), once per sub-cycle, both modes (evp_strict.hip)
 void launch_free_drift(const EvpDev& P, const Range& r, hipStream_t s);
+// StressBalanceFreeDrift as the model's dynamics (momentum_free_drift.hip): u and v over r, each with its halo images, in one launch
+void launch_free_drift_step(const EvpDev& P, const Range& r, const ImageSpec& imu, const ImageSpec& imv, hipStream_t s);
 
 // FAST mode (evp_fast.hip): fused viscosity + stress phase, u step, v step
 void launch_fast_init(const EvpDev& P, const Range& r, hipStream_t s);
@@ -133,7 +135,7 @@ void launch_fused_pair(const FusedTable* dev_table, int metric, bool a_ufirst, b
 // stress divergence of the immersed FluxBoundaryConditions at every u / v point whose stencil stays inside the parents (evp_fast.hip)
 void launch_immersed_div(const EvpDev& P, const FRef& xd_u, const FRef& xd_v, hipStream_t s);
 // array-valued forcing the pair kernel takes: 0 none needed, 1 supported (FORCE variant), -1 not supported;
-// StressBalanceFreeDrift (P.free_drift: free-drift velocity arrays P.ufd / P.vfd) also selects the FORCE variant
+// free drift (P.free_drift non-zero -- StressBalanceFreeDrift or prescribed fields: the arrays P.ufd / P.vfd) also selects the FORCE variant
 int pair_forcing_kind(const EvpDev& P);
 bool evp_array_forcing(const EvpDev& P);
 bool evp_ring_forcing(const EvpDev& P);

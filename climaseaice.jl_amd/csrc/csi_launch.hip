@@ -551,7 +551,10 @@ int32_t need_dynamics_common(csi_context* c) {
     if ((rc = check_stress_fields(c, CSI_STRESS_TOP))) return rc;
     if ((rc = check_stress_fields(c, CSI_STRESS_BOTTOM))) return rc;
     if (c->Hx < 2 || c->Hy < 2) return fail(c, CSI_ERR_INVALID_ARGUMENT, "the momentum step needs halo >= 2");
-    if (c->free_drift) {   // stress_balance_free_drift.jl:21-35: exactly one of the two stresses is a SemiImplicitStress
+    if (c->free_drift == CSI_FREE_DRIFT_FIELDS && (!c->f[CSI_F_FREE_DRIFT_U].p || !c->f[CSI_F_FREE_DRIFT_V].p))      // free_drift = (u, v)
+        return fail(c, CSI_ERR_NOT_BOUND, std::string("prescribed free-drift velocity field not bound: ") +
+                                              kName[c->f[CSI_F_FREE_DRIFT_U].p ? CSI_F_FREE_DRIFT_V : CSI_F_FREE_DRIFT_U]);
+    if (c->free_drift == CSI_FREE_DRIFT_STRESS_BALANCE) {   // stress_balance_free_drift.jl:21-35: exactly one of the two stresses is a SemiImplicitStress
         const bool ts = c->stress[CSI_STRESS_TOP].kind == CSI_STRESS_SEMI_IMPLICIT, bs = c->stress[CSI_STRESS_BOTTOM].kind == CSI_STRESS_SEMI_IMPLICIT;
         if (ts == bs) return fail(c, CSI_ERR_INVALID_ARGUMENT, "StressBalanceFreeDrift needs exactly one SemiImplicitStress (top or bottom)");
     }
@@ -570,12 +573,8 @@ int32_t do_time_step_momentum(csi_context* c, double dt, int substeps, int rk_re
     // the step updates), so beyond a connected side the halo must hold the neighbour's values
     if ((c->f[CSI_F_FORCING_U].p != nullptr) != (c->f[CSI_F_FORCING_V].p != nullptr))
         return fail(c, CSI_ERR_NOT_BOUND, "model.forcing arrays: bind both CSI_F_FORCING_U and CSI_F_FORCING_V or neither");
-    if ((rc = fill_forcing_halos(c))) return rc;
-    if (is_tiled(c)) {
-        int ff[6], n = 0;
-        for (int id : kForcingFields) if (c->f[id].p) ff[n++] = id;
-        if (n && (rc = exchange(c, ff, n, c->Hx < c->Hy ? c->Hx : c->Hy))) return rc;
-    }
+    // (... and of prescribed free-drift velocity fields, which the same kernels read at the same points)
+    if ((rc = update_external_stress(c))) return rc;
     if ((rc = do_subcycle(c, dt, substeps, 1))) return rc;  // :170-189
     return do_finalize(c);                                  // :192
 }
@@ -602,7 +601,7 @@ int32_t do_update_state(csi_context* c, bool in_step, bool tracers_filled) {
     if ((rc = need(c, {CSI_F_H, CSI_F_A}))) return rc;
     // mask_immersed_field_xy! of every prognostic field, then their local halo fills in one batch (two launches)
     const bool snow = c->f[CSI_F_HS].p != nullptr;
-    const bool vel = c->f[CSI_F_U].p && c->f[CSI_F_V].p && (!in_step || c->evp_set);
+    const bool vel = c->f[CSI_F_U].p && c->f[CSI_F_V].p && (!in_step || has_dynamics(c));
     launch_mask_center(ref_of(c, CSI_F_H), c->g, c->stream);
     launch_mask_center(ref_of(c, CSI_F_A), c->g, c->stream);
     if (snow) launch_mask_center(ref_of(c, CSI_F_HS), c->g, c->stream);

@@ -30,7 +30,27 @@ static int32_t need_dynamics(csi_context* c) {
     return need_dynamics_common(c);
 }
 
+// StressBalanceFreeDrift as the model's dynamics (csi_dynamics_set): u, v, the grid and the two stresses -- none of the EVP slots, no
+// csi_evp_params, no rheology / solver / free-drift-kind setting
+static int32_t need_free_drift_dynamics(csi_context* c) {
+    int32_t rc = need(c, {CSI_F_U, CSI_F_V});
+    if (rc) return rc;
+    // stress_balance_free_drift.jl:24-32, the constructor's two errors
+    const bool ts = c->stress[CSI_STRESS_TOP].kind == CSI_STRESS_SEMI_IMPLICIT, bs = c->stress[CSI_STRESS_BOTTOM].kind == CSI_STRESS_SEMI_IMPLICIT;
+    if (ts && bs)
+        return fail(c, CSI_ERR_INVALID_ARGUMENT, "`StressBalanceFreeDrift` supports a `SemiImplicitStress` only for the `top_momentum_stress` or the `bottom_momentum_stress`, not both");
+    if (!ts && !bs)
+        return fail(c, CSI_ERR_INVALID_ARGUMENT, "`StressBalanceFreeDrift` requires using a `SemiImplicitStress` for either the `top_momentum_stress` or the `bottom_momentum_stress`");
+    if ((rc = check_stress_fields(c, CSI_STRESS_TOP))) return rc;
+    if ((rc = check_stress_fields(c, CSI_STRESS_BOTTOM))) return rc;
+    if (c->Hx < 1 || c->Hy < 1) return fail(c, CSI_ERR_INVALID_ARGUMENT, "the free-drift step needs halo >= 1");      // the four-point averages reach one cell
+    if (c->Nx < c->Hx || c->Ny < c->Hy) return fail(c, CSI_ERR_UNSUPPORTED, "tile smaller than its halo");
+    if (is_tiled(c) && !c->tile.set) return fail(c, CSI_ERR_NOT_BOUND, "connected topology but csi_tile_set has not been called");
+    return CSI_OK;
+}
+
 int32_t need_momentum(csi_context* c) {
+    if (c->dynamics == CSI_DYNAMICS_FREE_DRIFT) return need_free_drift_dynamics(c);
     if (c->rheology == CSI_RHEOLOGY_EVP && c->solver == CSI_SOLVER_SPLIT_EXPLICIT) return need_evp(c);
     int32_t rc = need_dynamics(c);
     if (rc) return rc;
@@ -45,8 +65,10 @@ int32_t need_momentum(csi_context* c) {
 // StressBalanceFreeDrift: the free-drift velocities of marginal ice depend on the forcing only -- once per sub-cycle (EVP: do_subcycle)
 // or step into library arrays, at every point whose four-point averages stay inside the parent arrays.  (A launch error surfaces at
 // the caller's hipGetLastError.)
+// free_drift = (u, v) (CSI_FREE_DRIFT_FIELDS): nothing to do -- evp_dev points P.ufd / P.vfd at the bound arrays, whose halos
+// update_external_stress has filled.
 int32_t free_drift_fields(csi_context* c, double dt) {
-    if (!c->free_drift) return CSI_OK;
+    if (c->free_drift != CSI_FREE_DRIFT_STRESS_BALANCE) return CSI_OK;
     for (ScratchField& f : c->fd) HIP_TRY(c, f.ensure(c));
     launch_free_drift(evp_dev(c, dt), Range{2 - c->Hx, c->Nx + c->Hx - 1, 2 - c->Hy, c->Ny + c->Hy - 1}, c->stream);
     return CSI_OK;
@@ -65,6 +87,23 @@ int32_t fill_forcing_halos(csi_context* c) {
     int32_t rc;
     for (int id : kForcingFields)
         if (c->f[id].p && (rc = fill_halo(c, id))) return rc;
+    return CSI_OK;
+}
+
+// ... and, on tiles, the neighbours' values beyond the connected sides: inside an exchange batch the velocity kernels run on ranges
+// that reach into the halo and read the forcing / free-drift value there, and the four-point averages of the stresses cross the sides
+int32_t update_external_stress(csi_context* c) {
+    int32_t rc;
+    if ((rc = fill_forcing_halos(c))) return rc;
+    if (is_tiled(c)) {
+        // (every rank binds the same slots, so every rank issues the same batches: one exchange takes at most MAX_EX_FIELDS fields,
+        //  which the six older slots fill; with the two free-drift fields on top of them a second batch follows)
+        int ff[8], n = 0;
+        for (int id : kForcingFields) if (c->f[id].p) ff[n++] = id;
+        const int W = c->Hx < c->Hy ? c->Hx : c->Hy;
+        for (int at = 0; at < n; at += MAX_EX_FIELDS)
+            if ((rc = exchange(c, ff + at, std::min(n - at, MAX_EX_FIELDS), W))) return rc;
+    }
     return CSI_OK;
 }
 
@@ -154,7 +193,7 @@ static int32_t viscous_subcycle(csi_context* c, double dt, int substeps, int rk_
 
 // ---- ExplicitSolver (explicit_momentum_equations.jl) ---------------------------------------------------------------------------
 int32_t do_momentum_tendencies(csi_context* c, double dt) {
-    if (c->solver != CSI_SOLVER_EXPLICIT) return CSI_OK;     // SplitExplicitSolver: compute_momentum_tendencies! is nothing
+    if (c->solver != CSI_SOLVER_EXPLICIT || c->dynamics == CSI_DYNAMICS_FREE_DRIFT) return CSI_OK;     // SplitExplicitSolver: compute_momentum_tendencies! is nothing
     MomDev M = mom_dev(c, dt);
     launch_explicit_tendencies(M, interior_range(c), c->rheology == CSI_RHEOLOGY_VISCOUS, c->mode == CSI_MODE_FAST, c->stream);
     HIP_TRY(c, hipGetLastError());
@@ -188,7 +227,29 @@ static int32_t explicit_step(csi_context* c, double dt, int rk_reset) {
     return CSI_OK;
 }
 
+// ---- StressBalanceFreeDrift as the dynamics (stress_balance_free_drift.jl:131-151): one launch, u and v with their halo images ------
+static int32_t free_drift_dynamics_step(csi_context* c) {
+    int32_t rc;
+    if ((rc = peer_check_entry(c))) return rc;
+    if ((rc = update_external_stress(c))) return rc;        // the stress arrays' halos: the four-point averages reach one cell
+    HIP_TRY(c, hipEventRecord(c->ev0, c->stream));
+    // the ranges and images of the EVP three-kernel velocity steps for u and v: the owned points, every side's local images
+    launch_free_drift_step(evp_dev(c, 0.0), interior_range(c), image_spec(c, CSI_F_U), image_spec(c, CSI_F_V), c->stream);
+    HIP_TRY(c, hipEventRecord(c->ev1, c->stream));
+    HIP_TRY(c, hipGetLastError());
+    c->timed = true;
+    c->last_fused = 0;
+    c->peer.last = 0;
+    c->last_launches = 1;
+    c->last_substeps = 1;
+    c->launches_per_substep = 1;
+    c->last_exchanges = 0;
+    c->last_k = 1;
+    return CSI_OK;
+}
+
 int32_t do_momentum(csi_context* c, double dt, int substeps, int rk_reset) {
+    if (c->dynamics == CSI_DYNAMICS_FREE_DRIFT) return free_drift_dynamics_step(c);      // (no dt, no sub-steps, no u^-)
     if (c->solver == CSI_SOLVER_EXPLICIT) return explicit_step(c, dt, rk_reset);
     if (c->rheology == CSI_RHEOLOGY_VISCOUS) return viscous_subcycle(c, dt, substeps, rk_reset);
     return do_time_step_momentum(c, dt, substeps, rk_reset);
@@ -222,7 +283,7 @@ int32_t csi_momentum_solver_set(csi_context* c, int32_t kind) {
 
 int32_t csi_compute_momentum_tendencies(csi_context* c, double dt) {
     if (!c) return CSI_ERR_INVALID_ARGUMENT;
-    if (c->solver != CSI_SOLVER_EXPLICIT) return CSI_OK;
+    if (c->solver != CSI_SOLVER_EXPLICIT || c->dynamics == CSI_DYNAMICS_FREE_DRIFT) return CSI_OK;      // (free-drift dynamics: SeaIceDynamics.jl:41)
     int32_t rc = need_momentum(c);
     if (rc) return rc;
     return do_momentum_tendencies(c, dt);

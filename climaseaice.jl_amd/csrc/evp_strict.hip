@@ -220,9 +220,7 @@ __device__ __forceinline__ double free_drift_u(const EvpDev& P, int i, int j) {
 #define TY_(ii, jj) explicit_tau_y(P, expl, ii, jj)
     const double ty = AVG4_FC(TY_);
 #undef TY_
-    const double t = sqrt(tx * tx + ty * ty);
-    const double C = semi.rho_e * semi.Cd;
-    return ext_ue(semi, i, j) - ((t == 0) ? t : tx / sqrt(C * t));
+    return stress_balance_velocity(ext_ue(semi, i, j), tx, tx, ty, semi.rho_e * semi.Cd);
 }
 __device__ __forceinline__ double free_drift_v(const EvpDev& P, int i, int j) {
     const StressDev& semi = P.bot.kind == 3 ? P.bot : P.top;
@@ -231,9 +229,7 @@ __device__ __forceinline__ double free_drift_v(const EvpDev& P, int i, int j) {
     const double tx = AVG4_CF(TX_);
 #undef TX_
     const double ty = explicit_tau_y(P, expl, i, j);
-    const double t = sqrt(tx * tx + ty * ty);
-    const double C = semi.rho_e * semi.Cd;
-    return ext_ve(semi, i, j) - ((t == 0) ? t : ty / sqrt(C * t));
+    return stress_balance_velocity(ext_ve(semi, i, j), ty, tx, ty, semi.rho_e * semi.Cd);
 }
 
 __device__ __forceinline__ double implicit_tau_x(const EvpDev& P, const StressDev& s, int i, int j) {

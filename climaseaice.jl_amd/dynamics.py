@@ -6,6 +6,8 @@ Auxiliaries                  :140-173 (EVP); Rheologies.jl:33 (every other rheol
 SplitExplicitSolver          SeaIceDynamics/split_explicit_momentum_equations.jl:18-46
 ExplicitSolver               SeaIceDynamics/sea_ice_momentum_equations.jl:14-15
 SemiImplicitStress           SeaIceDynamics/sea_ice_external_stress.jl:84-130
+StressBalanceFreeDrift       SeaIceDynamics/stress_balance_free_drift.jl:3-35 (free_drift of a momentum equation, or the whole dynamics :131-151)
+FreeDriftVelocities          :123-125, `free_drift = (u = ..., v = ...)`
 SeaIceMomentumEquation       SeaIceDynamics/sea_ice_momentum_equations.jl:3-12,67-94
 FPlane, BetaPlane            upstream Oceananigans.Coriolis
 """
@@ -148,13 +150,71 @@ def Auxiliaries(rheology, grid, device=None):
 
 
 class StressBalanceFreeDrift:
-    """Free-drift velocity of marginal ice from the balance of the top and bottom stresses
-    (SeaIceDynamics/stress_balance_free_drift.jl:3-121).  Exactly one of the model's two stresses must be a
-    SemiImplicitStress; the arguments are accepted for API parity and replaced by the model's stresses."""
+    """Free-drift velocity from the balance of the top and bottom stresses (SeaIceDynamics/stress_balance_free_drift.jl:3-121).
+
+    As `free_drift = StressBalanceFreeDrift()` of a SeaIceMomentumEquation: the velocity of marginal ice.  Exactly one of the
+    model's two stresses must be a SemiImplicitStress; the arguments are accepted for API parity and replaced by the model's stresses
+    (materialize_free_drift, :44-46).
+
+    As `dynamics = StressBalanceFreeDrift(top_momentum_stress = ..., bottom_momentum_stress = ...)` of a SeaIceModel: the model's whole
+    dynamics (:131-151) -- every momentum step sets u, v to the free-drift velocity at every point, no rheology, no sub-cycle.  The
+    arguments ARE the stresses then, in the forms SeaIceMomentumEquation takes: None, a number pair, a pair / dict(u, v) of arrays or
+    fields, a SemiImplicitStress.  The reference's rule -- exactly one SemiImplicitStress, :24-32 -- is checked where the object is used
+    as dynamics (check_as_dynamics), not here: StressBalanceFreeDrift() without arguments is the first form."""
 
     def __init__(self, top_momentum_stress=None, bottom_momentum_stress=None):
         self.top_momentum_stress = top_momentum_stress
         self.bottom_momentum_stress = bottom_momentum_stress
+
+    def check_as_dynamics(self):
+        """The constructor's two errors in the reference (stress_balance_free_drift.jl:24-32)."""
+        top, bottom = isinstance(self.top_momentum_stress, SemiImplicitStress), isinstance(self.bottom_momentum_stress, SemiImplicitStress)
+        if top and bottom:
+            raise ValueError("`StressBalanceFreeDrift` supports a `SemiImplicitStress` only for the `top_momentum_stress` or the "
+                             "`bottom_momentum_stress`, not both")
+        if not top and not bottom:
+            raise ValueError("`StressBalanceFreeDrift` requires using a `SemiImplicitStress` for either the `top_momentum_stress` or the "
+                             "`bottom_momentum_stress`")
+        return self
+
+
+class FreeDriftVelocities:
+    """`free_drift = (u = ..., v = ...)`: the velocity of marginal ice read from two fields (stress_balance_free_drift.jl:123-125), e.g.
+    the ocean surface velocity of a coupled model.  u lives at (Face, Center), v at (Center, Face); each is a number, an array of the
+    component's interior shape (on a TileGrid: the tile's slice) or an XFaceField / YFaceField of the grid, which is then used as it
+    is.  SeaIceModel materialises both on the device (model.free_drift_field("u" | "v")); the library fills their halos."""
+
+    def __init__(self, grid, u, v):
+        for name, val, loc in (("u", u, (Face, Center)), ("v", v, (Center, Face))):
+            if isinstance(val, Field):
+                if val.location != loc or (val.ni, val.nj) != tuple(grid.field_size(*loc)):
+                    raise ValueError(f"free_drift.{name}: a field at ({loc[0].__name__}, {loc[1].__name__}) of the dynamics' grid is needed")
+            elif isinstance(val, bool) or val is None or callable(val):
+                raise TypeError(f"free_drift.{name}: a number, an array or a field is needed, got {type(val).__name__}")
+            elif not np.isscalar(val):
+                nx, ny = grid.interior_size(*loc)
+                if np.shape(val) != (ny, nx):
+                    raise ValueError(f"free_drift.{name}: an array of the interior shape {(ny, nx)} is needed, got {np.shape(val)}")
+        self.u, self.v = u, v
+
+    def __iter__(self):
+        return iter((self.u, self.v))
+
+
+def _free_drift_of(grid, free_drift):
+    """None, StressBalanceFreeDrift() or the two prescribed fields: dict(u = ..., v = ...), an object with .u and .v, a 2-tuple."""
+    if free_drift is None or isinstance(free_drift, (StressBalanceFreeDrift, FreeDriftVelocities)):
+        return free_drift
+    if isinstance(free_drift, dict):
+        if set(free_drift) != {"u", "v"}:
+            raise ValueError(f"free_drift: a dict needs exactly the keys 'u' and 'v', got {sorted(free_drift)}")
+        return FreeDriftVelocities(grid, free_drift["u"], free_drift["v"])
+    if isinstance(free_drift, (tuple, list)) and len(free_drift) == 2:
+        return FreeDriftVelocities(grid, free_drift[0], free_drift[1])
+    if hasattr(free_drift, "u") and hasattr(free_drift, "v"):
+        return FreeDriftVelocities(grid, free_drift.u, free_drift.v)
+    raise NotImplementedError(f"free_drift: None, StressBalanceFreeDrift() or two velocity fields (dict(u=..., v=...) / a 2-tuple), got "
+                              f"{type(free_drift).__name__}")
 
 
 class SeaIceMomentumEquation:
@@ -168,11 +228,10 @@ class SeaIceMomentumEquation:
         self.solver = solver if solver is not None else SplitExplicitSolver(substeps=150)
         if not isinstance(self.solver, (SplitExplicitSolver, ExplicitSolver)):
             raise NotImplementedError("solver: SplitExplicitSolver or ExplicitSolver")
-        # free_drift: None (`nothing`: marginal ice is at rest) or StressBalanceFreeDrift(); like the reference's
-        # materialize_free_drift (stress_balance_free_drift.jl:44-46) the balance uses the model's own stresses
-        if free_drift is not None and not isinstance(free_drift, StressBalanceFreeDrift):
-            raise NotImplementedError("free_drift: None or StressBalanceFreeDrift() (prescribed free-drift velocity fields are not on the accelerated path)")
-        self.free_drift = free_drift
+        # free_drift: None (`nothing`: marginal ice is at rest), StressBalanceFreeDrift() -- like the reference's
+        # materialize_free_drift (stress_balance_free_drift.jl:44-46) the balance uses the model's own stresses -- or two prescribed
+        # velocity fields, dict(u=..., v=...) / a 2-tuple (:123-125), kept as a FreeDriftVelocities
+        self.free_drift = _free_drift_of(grid, free_drift)
         self.external_momentum_stresses = SimpleNamespace(top=top_momentum_stress, bottom=bottom_momentum_stress)
         self.minimum_concentration = float(minimum_concentration)
         self.minimum_mass = float(minimum_mass)

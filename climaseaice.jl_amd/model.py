@@ -14,8 +14,8 @@ import numpy as np
 import torch
 
 from . import _lib
-from .dynamics import (ElastoViscoPlasticRheology, ExplicitSolver, FPlane, IceStrength, SeaIceMomentumEquation, SemiImplicitStress,
-                       ViscousRheology)
+from .dynamics import (ElastoViscoPlasticRheology, ExplicitSolver, FPlane, FreeDriftVelocities, IceStrength, SeaIceMomentumEquation,
+                       SemiImplicitStress, StressBalanceFreeDrift, ViscousRheology)
 from .fields import CenterField, Field, XFaceField, YFaceField
 from .grids import (METRIC_NAMES, Bounded, Center, FullyConnected, LeftConnected, LeftConnectedRightFolded, Periodic, RightConnected,
                     RightFolded, TileGrid)
@@ -259,6 +259,12 @@ class SeaIceModel:
                  boundary_conditions=None, forcing=None, device="cuda:0", mode="fast", stream=None, top_heat_flux=None,
                  bottom_heat_flux=None):
         self.grid = grid
+        # dynamics: None (prescribed velocities), a SeaIceMomentumEquation, or StressBalanceFreeDrift(top_momentum_stress = ...,
+        # bottom_momentum_stress = ...) as the whole dynamics (stress_balance_free_drift.jl:131-151)
+        if isinstance(dynamics, StressBalanceFreeDrift):
+            dynamics.check_as_dynamics()
+        elif dynamics is not None and not isinstance(dynamics, SeaIceMomentumEquation):
+            raise NotImplementedError("dynamics: None, a SeaIceMomentumEquation or a StressBalanceFreeDrift")
         self.dynamics = dynamics
         self.advection = advection
         self.ice_thermodynamics = ice_thermodynamics
@@ -289,7 +295,7 @@ class SeaIceModel:
         # TimeStepper(timestepper, grid, prognostic_fields): G^n for both, Psi^- for RK (:235)
         Gn = SimpleNamespace(h=CenterField(grid, dev, "Gh"), aice=CenterField(grid, dev, "Gaice"))
         self.timestepper = SimpleNamespace(Gn=Gn, Psi_minus=None)
-        if dynamics is not None and isinstance(dynamics.solver, ExplicitSolver):
+        if isinstance(dynamics, SeaIceMomentumEquation) and isinstance(dynamics.solver, ExplicitSolver):
             # the ExplicitSolver's velocity tendencies (explicit_momentum_equations.jl:103-104)
             Gn.u, Gn.v = XFaceField(grid, dev, "Gu"), YFaceField(grid, dev, "Gv")
         if timestepper == "SplitRungeKutta3":
@@ -311,6 +317,7 @@ class SeaIceModel:
         self.clock = SimpleNamespace(time=0.0, iteration=0)
         self._keep = []
         self._stress_fields = {}
+        self._free_drift_fields = {}
         self.ctx = _lib.Context(dev.index or 0, stream)
         self._configure()
         self.set_mode(mode)
@@ -396,6 +403,12 @@ class SeaIceModel:
         d = self.dynamics
         if d is None:
             return
+        if isinstance(d, StressBalanceFreeDrift):
+            # the free-drift velocity as the whole dynamics: the two stresses and the dynamics kind; nothing of a momentum equation
+            self._set_stress(_lib.STRESS_TOP, d.top_momentum_stress, "TOP")
+            self._set_stress(_lib.STRESS_BOTTOM, d.bottom_momentum_stress, "BOT")
+            self.ctx.call("csi_dynamics_set", _lib.DYNAMICS_FREE_DRIFT)
+            return
         if d.grid is not g:
             raise ValueError("dynamics was built on a different grid")
         f = d.auxiliaries.fields
@@ -430,7 +443,15 @@ class SeaIceModel:
             self.ctx.call("csi_coriolis_rows_set", None, None, 0)
         self._set_stress(_lib.STRESS_TOP, d.external_momentum_stresses.top, "TOP")
         self._set_stress(_lib.STRESS_BOTTOM, d.external_momentum_stresses.bottom, "BOT")
-        self.ctx.call("csi_free_drift_set", 1 if d.free_drift is not None else 0)
+        if isinstance(d.free_drift, FreeDriftVelocities):      # free_drift = (u, v): the kernels read the two fields in place
+            for comp, value in (("U", d.free_drift.u), ("V", d.free_drift.v)):
+                self._free_drift_field(comp, value)
+            self.ctx.call("csi_free_drift_set", _lib.FREE_DRIFT_FIELDS)
+            torch.cuda.synchronize(self.device)
+            for comp in ("U", "V"):                    # (csi_time_step_momentum fills them again at every step)
+                self.ctx.call("csi_fill_halo_local", _lib.F[f"FREE_DRIFT_{comp}"])
+        else:
+            self.ctx.call("csi_free_drift_set", _lib.FREE_DRIFT_STRESS_BALANCE if d.free_drift is not None else _lib.FREE_DRIFT_NONE)
 
     def _cell_field(self, value, name):
         """A (Center, Center) field on the model grid from a CenterField (used as it is: writes into it reach the next step) or an
@@ -596,6 +617,26 @@ class SeaIceModel:
     def external_stress_field(self, slot, comp):
         return self._stress_fields[f"{slot}_{comp}"]
 
+    def _free_drift_field(self, comp, value):
+        """One component of `free_drift = (u, v)` on the device, like _stress_field: a field of the grid is used as it is, a number or
+        an interior-shaped array fills a new one.  The library fills the halos at every momentum step."""
+        mk = XFaceField if comp == "U" else YFaceField
+        if isinstance(value, Field):
+            fld = value
+            if fld.data.device != self.device:
+                fld.data = fld.data.to(self.device)
+        else:
+            fld = mk(self.grid, self.device, f"free_drift_{comp}".lower())
+            fld.set(value)
+        self._free_drift_fields[comp] = fld
+        self._bind(f"FREE_DRIFT_{comp}", fld)
+        return fld
+
+    def free_drift_field(self, comp):
+        """The device field of a prescribed free-drift velocity component ("u" / "v"): write into its interior between steps (then
+        torch.cuda.synchronize) to update it in place."""
+        return self._free_drift_fields[comp.upper()]
+
     def set_mode(self, mode):
         self.mode = mode
         self.ctx.call("csi_set_mode", _lib.MODE_FAST if mode == "fast" else _lib.MODE_STRICT)
@@ -674,7 +715,8 @@ class SeaIceModel:
     # ---- convenience ----------------------------------------------------------------------------
     @property
     def substeps(self):
-        return 0 if self.dynamics is None else getattr(self.dynamics.solver, "substeps", 0)      # (ExplicitSolver: none)
+        # (ExplicitSolver, StressBalanceFreeDrift as the dynamics: none)
+        return 0 if self.dynamics is None else getattr(getattr(self.dynamics, "solver", None), "substeps", 0)
 
     @property
     def scheme(self):
@@ -724,7 +766,7 @@ def _state_fields(model):
     if model.timestepper.Psi_minus is not None:
         for k, f in vars(model.timestepper.Psi_minus).items():
             out["Psi_minus." + k] = f
-    if model.dynamics is not None:
+    if isinstance(model.dynamics, SeaIceMomentumEquation):      # (StressBalanceFreeDrift as the dynamics: no fields, :46)
         for k, f in vars(model.dynamics.auxiliaries.fields).items():
             out["dynamics." + k] = f
     if model.mass_fluxes is not None:
@@ -769,7 +811,9 @@ def restore_prognostic_state(model, state):
 def time_step_momentum(model, dt, rk_reset=False):
     """time_step_momentum!(model, model.dynamics, dt): split_explicit_momentum_equations.jl:103-195 (EVP or viscous sub-cycle;
     rk_reset: reset_velocities! from Psi^-) or explicit_momentum_equations.jl:8-38 (ExplicitSolver: u^- = Psi^-.u when rk_reset,
-    the current velocities otherwise; G^n from compute_momentum_tendencies)."""
+    the current velocities otherwise; G^n from compute_momentum_tendencies) or, with StressBalanceFreeDrift as the dynamics,
+    stress_balance_free_drift.jl:132-143: u, v = the free-drift velocity at every point (dt and rk_reset are not read; model.substeps
+    is 0 and the fusion / tile-skipping switches are accepted and ignored: there is no sub-cycle)."""
     model.ctx.call("csi_time_step_momentum", float(dt), model.substeps, int(rk_reset))
 
 

@@ -150,6 +150,13 @@ typedef enum {
     CSI_F_SNOWFALL,                      /* per-cell snowfall, kg m^-2 s^-1 (csi_surface_solve.snowfall_array) */
     CSI_F_COUNT_ALL
 } csi_thermo_field_id;
+/* Further slots of csi_field_bind: the prescribed free-drift velocity fields of csi_free_drift_set(ctx, 2).  Numbered from
+ * CSI_F_COUNT_ALL on, so that csi_field_id, csi_thermo_field_id, CSI_F_COUNT and CSI_F_COUNT_ALL keep their values. */
+typedef enum {
+    CSI_F_FREE_DRIFT_U = CSI_F_COUNT_ALL,   /* (f,c) free_drift.u of `free_drift = (u = ..., v = ...)` (stress_balance_free_drift.jl:123-125) */
+    CSI_F_FREE_DRIFT_V,                     /* (c,f) free_drift.v */
+    CSI_F_COUNT_TOTAL                       /* every slot csi_field_bind takes */
+} csi_free_drift_field_id;
 
 typedef enum { CSI_PRESSURE_REPLACEMENT = 0, CSI_PRESSURE_ICE_STRENGTH = 1 } csi_pressure_kind;
 
@@ -302,11 +309,12 @@ int32_t csi_dynamic_step_tracers(csi_context* ctx, double dt, int32_t from_cache
 int32_t csi_cache_current_fields(csi_context* ctx);
 /* update_state!(model), sea_ice_model.jl:379-394: immersed masking + local halo fill of h, aice, u, v */
 int32_t csi_update_state(csi_context* ctx);
-/* fill_halo_regions!(field; only_local_halos = true) for one bound field */
+/* fill_halo_regions!(field; only_local_halos = true) for one bound field (a csi_field_id slot or CSI_F_FREE_DRIFT_U / _V; so
+ * csi_halo_exchange) */
 int32_t csi_fill_halo_local(csi_context* ctx, int32_t field_id);
 /* Whole model steps: FE (sea_ice_fe_step.jl:13-34) and the SplitRungeKutta3 stage loop around rk_substep!
- * (sea_ice_rk_substep.jl:81-94).  Without csi_evp_params_set (dynamics = nothing) the velocities are prescribed and
- * the momentum step is skipped: advection-only models.  Thermodynamics: csi_slab_params_set / csi_snow_params_set. */
+ * (sea_ice_rk_substep.jl:81-94).  Without csi_evp_params_set and without csi_dynamics_set(ctx, CSI_DYNAMICS_FREE_DRIFT)
+ * (dynamics = nothing) the velocities are prescribed and the momentum step is skipped: advection-only models.  Thermodynamics: csi_slab_params_set / csi_snow_params_set. */
 int32_t csi_time_step_fe(csi_context* ctx, double dt, int32_t substeps, int32_t scheme, int32_t first_iteration);
 int32_t csi_time_step_rk3(csi_context* ctx, double dt, int32_t substeps, int32_t scheme);
 
@@ -449,17 +457,52 @@ int32_t csi_comm_init_host(csi_context* ctx, const char* shm_name, int32_t world
 int32_t csi_halo_exchange(csi_context* ctx, const int32_t* field_ids, int32_t nfields, int32_t width);
 
 /* Velocity of marginal ice (0 < mass, concentration below minimum_mass / minimum_concentration;
- * split_explicit_momentum_equations.jl:219-228).  kind 0 (default): `free_drift = nothing`, zero.  kind 1:
- * StressBalanceFreeDrift built on the model's own top / bottom stresses (stress_balance_free_drift.jl:61-121,
- * materialize_free_drift :44-46): exactly one of them must be a SemiImplicitStress, U = U_e - tau / sqrt(C |tau|).
- * Evaluated once per sub-cycle into library-owned arrays (it depends on the forcing only); the three-kernel paths and
- * the two-sub-steps-per-launch kernel read them. */
+ * split_explicit_momentum_equations.jl:219-228).
+ * CSI_FREE_DRIFT_NONE (0, default): `free_drift = nothing`, zero (stress_balance_free_drift.jl:128-129).
+ * CSI_FREE_DRIFT_STRESS_BALANCE (1): StressBalanceFreeDrift built on the model's own top / bottom stresses (:61-121,
+ *   materialize_free_drift :44-46): exactly one of them must be a SemiImplicitStress, U = U_e - tau / sqrt(C |tau|).
+ *   Evaluated once per sub-cycle (or explicit step) into library-owned arrays (it depends on the forcing only).
+ * CSI_FREE_DRIFT_FIELDS (2): `free_drift = (u = ..., v = ...)`, the velocity of marginal ice read from two arrays (:123-125; e.g. the
+ *   ocean surface velocity of a coupled model): the (f,c) array bound to CSI_F_FREE_DRIFT_U and the (c,f) array bound to
+ *   CSI_F_FREE_DRIFT_V, which the kernels read in place (nothing is evaluated or copied per sub-cycle).  Both must be bound when a
+ *   momentum step runs (CSI_ERR_NOT_BOUND, by name); no SemiImplicitStress is needed.  Their halos are the library's to fill, like
+ *   those of the stress arrays at the same locations: csi_time_step_momentum fills them locally (periodic wrap, walls, the north
+ *   fold with the sign change of a vector component) and exchanges them between tiles before the velocities are stepped
+ *   (csi_evp_subcycle called on its own does not, as for the stress arrays: csi_fill_halo_local / csi_halo_exchange first).
+ * Every momentum path reads the same two arrays: the EVP three-kernel paths, the fused kernels, the fold band, tiles on either
+ * transport, the viscous sub-cycle and the ExplicitSolver. */
+typedef enum { CSI_FREE_DRIFT_NONE = 0, CSI_FREE_DRIFT_STRESS_BALANCE = 1, CSI_FREE_DRIFT_FIELDS = 2 } csi_free_drift_kind;
 int32_t csi_free_drift_set(csi_context* ctx, int32_t kind);
+
+/* The model's dynamics.
+ * CSI_DYNAMICS_MOMENTUM_EQUATION (0, default): a SeaIceMomentumEquation -- rheology, solver and free drift as set by the calls
+ *   above and below; nothing changes.
+ * CSI_DYNAMICS_FREE_DRIFT (1): `dynamics = StressBalanceFreeDrift(top_momentum_stress, bottom_momentum_stress)`, the free-drift
+ *   velocity as the model's WHOLE dynamics (AbstractFreeDriftDynamics, stress_balance_free_drift.jl:131-151).  A momentum step is
+ *   ONE launch over i = 1 .. Nx, j = 1 .. Ny that sets u[i, j] = free_drift_u, v[i, j] = free_drift_v (:61-109) at EVERY point:
+ *   no mass or concentration select, no `* active` factor, no dependence on the current u, v, on dt, on substeps or on rk_reset;
+ *   the stores also write the local halo images of u and v (periodic wrap, no-flux mirror, ValueBoundaryCondition, north fold), so
+ *   no fill launch follows.  STRICT and FAST run the same arithmetic (the reference's operation order) and are bit-identical.
+ *   Needs CSI_F_U, CSI_F_V, the grid (halo >= 1) and the two csi_stress_set stresses: exactly one of them a SemiImplicitStress
+ *   (rho_e, C_D, u_e / v_e zero, numbers or the bound arrays), the other one nothing, a number pair or the two bound arrays;
+ *   otherwise CSI_ERR_INVALID_ARGUMENT with the reference's wording (:24-32).  NOT read: the ten EVP slots, h, aice, CSI_F_GU /
+ *   CSI_F_GV, csi_evp_params_set (not needed at all here: such a model has dynamics without it), csi_rheology_set,
+ *   csi_momentum_solver_set, csi_free_drift_set, csi_set_fusion.  csi_time_step_momentum, csi_time_step_fe, csi_time_step_rk3,
+ *   csi_update_state and csi_compute_momentum_tendencies (a no-op: SeaIceDynamics.jl:41) work; u and v are prognostic (Psi^- copies
+ *   under RK3, masked and halo-filled by update_state! as for any dynamics).  Runs on tiles (the stress arrays' halos are exchanged
+ *   first, the step itself needs no exchange: its four-point averages reach one cell; u, v beyond a connected side are
+ *   update_state!'s to exchange, as in the reference, whose free-drift step fills no halos at all -- csi_time_step_fe / _rk3 do so at
+ *   the end of every stage, after csi_time_step_momentum called on its own call csi_update_state) and on the north fold.
+ *   Wall faces and immersed faces are written like any other point, as by the ExplicitSolver's velocity launches; the values the
+ *   local fill and update_state! then leave there are recalled fill semantics, not pinned. */
+typedef enum { CSI_DYNAMICS_MOMENTUM_EQUATION = 0, CSI_DYNAMICS_FREE_DRIFT = 1 } csi_dynamics_kind;
+int32_t csi_dynamics_set(csi_context* ctx, int32_t kind);
 
 /* ---- rheology and momentum solver (SeaIceMomentumEquation(grid; rheology, solver), sea_ice_momentum_equations.jl:67-94) ------------
  * Defaults: CSI_RHEOLOGY_EVP with CSI_SOLVER_SPLIT_EXPLICIT -- the library's EVP path, unchanged by these calls.  The scalars both
  * rheologies share (minimum mass / concentration, sea_ice_density, FPlane f) still come from csi_evp_params_set, which marks the model
- * as having dynamics; the EVP fields of that struct are ignored by a viscous model.
+ * as having dynamics; the EVP fields of that struct are ignored by a viscous model.  (csi_dynamics_set(ctx, CSI_DYNAMICS_FREE_DRIFT)
+ * needs none of it.)
  *
  * CSI_RHEOLOGY_VISCOUS: ViscousRheology(nu) with a Number nu (Rheologies/viscous_rheology.jl:1-22): stresses nu * delta u computed
  *   inline from the velocities, no auxiliary fields (the ten EVP slots need not be bound), sub-step Delta t / substeps, sum_of_forcing_*

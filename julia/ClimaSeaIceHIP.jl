@@ -49,7 +49,9 @@ end
 const F = (U=0, V=1, H=2, A=3, S11=4, S22=5, S12=6, UN=7, VN=8, P=9, ALPHA=10, DELTA=11, ZETA_F=12, ZETA_C=13,
            GH=14, GA=15, HM=16, AM=17, UM=18, VM=19, TOP_U=20, TOP_V=21, BOT_U=22, BOT_V=23, MASS_FLUX=24,
            HS=25, GHS=26, HSM=27, MASS_FLUX_SNOW=28, SNOWFALL_INTERCEPTED=29, TU=30, TUS=31, FORCING_U=32, FORCING_V=33,
-           GU=34, GV=35)
+           GU=34, GV=35,
+           # csi_thermo_field_id (from CSI_F_COUNT on) and csi_free_drift_field_id (from CSI_F_COUNT_ALL on)
+           TOP_HEAT_FLUX=36, BOTTOM_HEAT_FLUX=37, SNOWFALL=38, FREE_DRIFT_U=39, FREE_DRIFT_V=40)
 
 mutable struct Context
     handle::Ptr{Cvoid}
@@ -173,6 +175,25 @@ function stress_struct(τ::SemiImplicitStress)
     return CsiStress(3, kind(τ.uₑ), kind(τ.vₑ), 0, 0, 0, val(τ.uₑ), val(τ.vₑ), τ.ρₑ, τ.Cᴰ)
 end
 
+# csi_free_drift_set (include/csi.h): the velocity of marginal ice.
+#   nothing                          CSI_FREE_DRIFT_NONE (0): zero (stress_balance_free_drift.jl:128-129)
+#   StressBalanceFreeDrift(...)      CSI_FREE_DRIFT_STRESS_BALANCE (1): the library rebuilds the balance on the model's own stresses,
+#                                    like materialize_free_drift (:44-46)
+#   (u = Field, v = Field)           CSI_FREE_DRIFT_FIELDS (2): read from the two fields (:123-125), bound to CSI_F_FREE_DRIFT_U / _V;
+#                                    the library fills their halos
+# Anything else is an error by name: it must not run silently with marginal ice at rest.
+set_free_drift_kind!(ctx, kind) = check(ctx, ccall((:csi_free_drift_set, libcsi), Int32, (Ptr{Cvoid}, Int32), ctx.handle, kind))
+set_free_drift!(ctx, ::Nothing) = set_free_drift_kind!(ctx, 0)
+set_free_drift!(ctx, ::StressBalanceFreeDrift) = set_free_drift_kind!(ctx, 1)
+function set_free_drift!(ctx, fd::NamedTuple)
+    (haskey(fd, :u) && haskey(fd, :v) && fd.u isa Field && fd.v isa Field) ||
+        error("ClimaSeaIceHIP: free_drift = (u = ..., v = ...) needs two Fields at (Face, Center) and (Center, Face), got $(typeof(fd))")
+    bind!(ctx, F.FREE_DRIFT_U, fd.u); bind!(ctx, F.FREE_DRIFT_V, fd.v)
+    return set_free_drift_kind!(ctx, 2)
+end
+set_free_drift!(ctx, fd) = error("ClimaSeaIceHIP: free_drift of type $(typeof(fd)) is not supported: nothing, a StressBalanceFreeDrift " *
+                                 "or a NamedTuple (u = Field, v = Field)")
+
 """
     attach!(model) -> Context
 
@@ -244,10 +265,7 @@ function attach!(model::SeaIceModel)
             bind!(ctx, side == 0 ? F.TOP_V : F.BOT_V, τ.v)
         end
     end
-    # free_drift = StressBalanceFreeDrift(...): the library rebuilds the balance on the model's own stresses, like
-    # materialize_free_drift (stress_balance_free_drift.jl:44-46)
-    check(ctx, ccall((:csi_free_drift_set, libcsi), Int32, (Ptr{Cvoid}, Int32), ctx.handle,
-                     dyn.free_drift isa StressBalanceFreeDrift ? 1 : 0))
+    set_free_drift!(ctx, dyn.free_drift)
     # model.forcing.u / .v given as Fields (arrays): the user forcing of sum_of_forcing_u / _v (elasto_visco_plastic_rheology.jl:391-401);
     # closures cannot cross a C ABI and keep the model on the Julia kernels
     if model.forcing.u isa Field && model.forcing.v isa Field
@@ -385,6 +403,41 @@ function ClimaSeaIce.SeaIceDynamics.time_step_momentum!(model, dynamics::HIPMome
     GC.@preserve model begin
         check(ctx, ccall((:csi_time_step_momentum, libcsi), Int32, (Ptr{Cvoid}, Cdouble, Int32, Int32),
                          ctx.handle, Δt, dynamics.solver.substeps, rk ? 1 : 0))
+    end
+    return nothing
+end
+
+# ---- StressBalanceFreeDrift as the model's dynamics (stress_balance_free_drift.jl:131-151) ---------------------------------------
+# `SeaIceModel(grid; dynamics = StressBalanceFreeDrift(top_momentum_stress = ..., bottom_momentum_stress = ...))`: every momentum step
+# is one launch that sets u, v to the free-drift velocity at every point (csi_dynamics_set(ctx, CSI_DYNAMICS_FREE_DRIFT), include/csi.h).
+# Only the momentum step is taken over (the reference's own tracer, thermodynamic and update_state! methods go on as they are), so
+# the context holds u, v, the grid and the two stresses -- nothing of a momentum equation.
+function attach_free_drift!(model, dynamics::StressBalanceFreeDrift)
+    ctx = Context()
+    grid = model.velocities.u.grid
+    set_grid!(ctx, grid)
+    bind!(ctx, F.U, model.velocities.u); bind!(ctx, F.V, model.velocities.v)
+    for (side, τ) in ((0, dynamics.top_momentum_stress), (1, dynamics.bottom_momentum_stress))
+        s = Ref(stress_struct(τ))
+        check(ctx, ccall((:csi_stress_set, libcsi), Int32, (Ptr{Cvoid}, Int32, Ref{CsiStress}), ctx.handle, side, s))
+        if τ isa SemiImplicitStress
+            τ.uₑ isa Field && bind!(ctx, side == 0 ? F.TOP_U : F.BOT_U, τ.uₑ)
+            τ.vₑ isa Field && bind!(ctx, side == 0 ? F.TOP_V : F.BOT_V, τ.vₑ)
+        elseif τ isa NamedTuple && τ.u isa Field
+            bind!(ctx, side == 0 ? F.TOP_U : F.BOT_U, τ.u)
+            bind!(ctx, side == 0 ? F.TOP_V : F.BOT_V, τ.v)
+        end
+    end
+    arch = architecture(grid)
+    arch isa Distributed && attach_tiles!(ctx, arch, grid)
+    check(ctx, ccall((:csi_dynamics_set, libcsi), Int32, (Ptr{Cvoid}, Int32), ctx.handle, 1))      # CSI_DYNAMICS_FREE_DRIFT
+    return ctx
+end
+
+function ClimaSeaIce.SeaIceDynamics.time_step_momentum!(model, dynamics::StressBalanceFreeDrift, Δt)
+    ctx = get!(() -> attach_free_drift!(model, dynamics), CONTEXTS, model)
+    GC.@preserve model begin
+        check(ctx, ccall((:csi_time_step_momentum, libcsi), Int32, (Ptr{Cvoid}, Cdouble, Int32, Int32), ctx.handle, Δt, 0, 0))
     end
     return nothing
 end
