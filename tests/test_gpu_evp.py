@@ -746,10 +746,8 @@ def test_masked_tile_self_exchange_bitwise(k):
         assert np.array_equal(a, b), f
 
 
-@pytest.mark.parametrize("seed", range(24))
-def test_fused_paths_fuzz_bitwise(seed):
-    """Randomised geometry / topology / halo / sub-step count / forcing / mask: the fused paths (whatever the library
-    picks at level 2) equal the three-kernel path bit for bit on u, v, sigma (interior of sigma12 next to walls)."""
+def fuzz_config(seed):
+    """(make_case keywords, sub-step count) of one fuzz seed (also drawn from by tests/test_gpu_pair_ufirst.py, on seeds of its own)"""
     rng = np.random.default_rng(1000 + seed)
     topo = (("periodic", "bounded")[rng.integers(2)], ("periodic", "bounded")[rng.integers(2)])
     H = int(rng.integers(4, 9))
@@ -782,6 +780,19 @@ def test_fused_paths_fuzz_bitwise(seed):
         elif r == 2 and not kw["field_forcing"]:
             kw["bottom"] = "arrays"
             kw.pop("free_drift", None)
+    return kw, nsub
+
+
+def fuzz_unfused(kw):
+    """no instantiation of the two-sub-steps kernel takes both families of arrays: such a configuration runs the three kernels"""
+    return bool((kw.get("wind_drag") == "arrays" or kw.get("bottom") == "arrays") and (kw.get("free_drift") or kw.get("user_forcing") or kw.get("immersed_bc")))
+
+
+@pytest.mark.parametrize("seed", range(24))
+def test_fused_paths_fuzz_bitwise(seed):
+    """Randomised geometry / topology / halo / sub-step count / forcing / mask: the fused paths (whatever the library
+    picks at level 2) equal the three-kernel path bit for bit on u, v, sigma (interior of sigma12 next to walls)."""
+    kw, nsub = fuzz_config(seed)
     c = cases.make_case(substeps=nsub, **kw)
     out = {}
     lvl = {}
@@ -793,8 +804,7 @@ def test_fused_paths_fuzz_bitwise(seed):
         out[fusion] = {k: cmp_region(c, k, EVP_FIELDS[k](m).numpy()).copy() for k in ("u", "v", "s11", "s22", "s12")}
         out[fusion]["alpha"] = EVP_FIELDS["alpha"](m).interior_numpy().copy()
         lvl[fusion] = m.ctx.last_path()["level"]
-    unfused = (kw.get("wind_drag") == "arrays" or kw.get("bottom") == "arrays") and (kw.get("free_drift") or kw.get("user_forcing") or kw.get("immersed_bc"))
-    assert (lvl[2] == 0) if unfused else (lvl[2] == 2), (kw, nsub, lvl)   # (no instantiation with both families of arrays)
+    assert (lvl[2] == 0) if fuzz_unfused(kw) else (lvl[2] == 2), (kw, nsub, lvl)   # (no instantiation with both families of arrays)
     for fusion in (2,):
         for k in out[0]:
             a, b = out[0][k], out[fusion][k]
