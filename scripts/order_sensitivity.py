@@ -7,9 +7,14 @@ comparison with the oracle detects it only where the oracle's two answers differ
 
   * for every case of test_even_start_two_substeps_vs_oracle: oracle sub-steps (2, 3) against (1, 2) from the initial state;
   * for every case of test_even_start_along_the_oracle_cycle: the SMALLEST such difference over the states s = 2, 4, .. 118 of the
-    120-sub-step cycle (sub-steps (s, s + 1) against (s + 1, s + 2) from the same state).
+    120-sub-step cycle (sub-steps (s, s + 1) against (s + 1, s + 2) from the same state);
+  * for every case of tests/pair_matrix.py (tests/test_gpu_pair_matrix.py): the distance between the two orders, and the distance between
+    the oracle's answer and its answer with the case's distinguishing ingredient removed (pair_matrix.ingredient_removed: ocean
+    velocity -> 0, ice_strength -> replacement, arrays -> numbers, free drift off, model.forcing off, ...) -- what tells a CF1 kernel from
+    one that ignores the ocean velocity, or a force_w kernel from one that ignores the wind arrays.  A matrix case at or below 1e-10
+    of max|u, v| on either distance makes the script fail.
 
-No GPU is needed:  python scripts/order_sensitivity.py [--markdown]
+No GPU is needed:  python scripts/order_sensitivity.py [--markdown] [--matrix]      (--matrix: the last table only)
 """
 import os
 import sys
@@ -64,9 +69,44 @@ def along_the_cycle(name):
     return least
 
 
+def two_substeps(kw, first):
+    c = cases.make_case(substeps=2, **kw)
+    p = cases.oracle_problem(c)
+    p.initialize_rheology()
+    p.L.ora_fill_halo_u(p.ptr); p.L.ora_fill_halo_v(p.ptr)
+    p.subcycle(c["dt"], first, first + 1)
+    assert all(np.all(np.isfinite(p.f[k])) for k in STATE), kw
+    return p
+
+
+def matrix_table(md):
+    """tests/pair_matrix.py: per case and first sub-step, the distance between the oracle's two orders and the distance between the oracle's
+    answer and its answer without the case's distinguishing ingredient (du, dv relative to max|u, v|: the larger of the two)"""
+    import pair_matrix as pm
+    print("the case matrix (tests/pair_matrix.py), two oracle sub-steps from the initial state, max(du, dv) / max|u,v|:\n"
+          "other order; ingredient removed, first = 1; ingredient removed, first = 2; which ingredient")
+    if md:
+        print("\n| case | instantiation (untiled, v-first) | other order | ingredient removed, first = 1 | first = 2 | ingredient |\n|---|---|---|---|---|---|")
+    blind = []
+    for name, kw in pm.MATRIX.items():
+        what, without = pm.ingredient_removed(kw)
+        p1, p2 = two_substeps(kw, 1), two_substeps(kw, 2)
+        order = max(rel_diff(p2, p1)[:2])
+        gone = [max(rel_diff(p, two_substeps(without, first))[:2]) for first, p in ((1, p1), (2, p2))]
+        if min(order, *gone) <= 1e-10:
+            blind.append(name)
+        key = pm.expected_key(kw)
+        print(f"| {name} | `{key}` | {order:.1e} | {gone[0]:.1e} | {gone[1]:.1e} | {what} |" if md else
+              f"{name:26s} {key:38s} {order:9.1e} {gone[0]:9.1e} {gone[1]:9.1e}  {what}")
+    print("matrix cases at or below 1e-10 on one of the distances (they must be changed or dropped):", blind or "none")
+    return blind
+
+
 def main():
     oracle.build()
     md = "--markdown" in sys.argv
+    if "--matrix" in sys.argv:
+        return 1 if matrix_table(md) else 0
     row = (lambda n, d: f"| {n} | {d[0]:.1e} | {d[1]:.1e} | {d[2]:.1e} |") if md else (lambda n, d: f"{n:34s} {d[0]:9.1e} {d[1]:9.1e} {d[2]:9.1e}")
     blind = []
     print("two oracle sub-steps from first = 2 against first = 1, initial state: du / max|u,v|, dv / max|u,v|, dsigma / max|sigma|")
@@ -82,7 +122,7 @@ def main():
             blind.append(name + " (cycle)")
         print(row(name, d))
     print("cases whose two orders agree within 1e-10 on the velocities (they cannot detect a swapped order there):", blind or "none")
-    return 0
+    return 1 if matrix_table(md) else 0
 
 
 if __name__ == "__main__":

@@ -12,6 +12,12 @@ grouped by the template argument that no traced case selects and with what the s
     python scripts/pair_instantiation_coverage.py OUT_BEFORE                       # one run
     python scripts/pair_instantiation_coverage.py OUT_BEFORE --with OUT_NEW        # a second set of runs on top of the first
     ... --markdown                                                                  # tables for profiles/*.md
+    ... --expected                                                                  # tests/pair_matrix.py against the LAST set of runs
+
+--expected: every key the selection rule of tests/pair_matrix.py (expected_key over MATRIX x transports x first sub-step, as
+tests/test_gpu_pair_matrix.py runs them) names, against the keys the last set of statistics executed.  Expected but not executed: a
+mistake in the mirror rule or a fall-back of the library -- to be explained or fixed; executed but not expected: launches the rule
+does not describe (the trailing single sub-step of an odd count has the other order; other test files).
 
 A measurement, not a gate: no test reads its result.
 """
@@ -116,9 +122,37 @@ def summary(title, calls, table, md):
     return ran
 
 
+def expected_by_the_table():
+    """{key: [(case, transport, first sub-step)]} of tests/pair_matrix.py, and its UNREACHABLE dict"""
+    sys.path.insert(0, os.path.join(ROOT, "tests"))
+    import pair_matrix as pm
+    return pm.selected(), pm.UNREACHABLE, set(pm.TARGETS)
+
+
+def compare_expected(calls, table, md):
+    expected, unreachable, targets = expected_by_the_table()
+    ran = {k for k in table if calls.get(k)}
+    print(f"\nexpected by the table: {len(expected)} keys; executed in the trace: {len(ran)}; both: {len(ran & set(expected))}; "
+          f"targets (never executed before) executed: {len(ran & targets)} of {len(targets)}")
+    missing = sorted(set(expected) - ran)
+    print(f"expected but NOT executed: {len(missing)}")
+    for k in missing:
+        who = ", ".join(f"{n} ({t}, first = {f})" for n, t, f in expected[k][:3])
+        print(f"| `{k}` | {who} |" if md else f"  {k:44s} {who}")
+    beyond = sorted(ran - set(expected))
+    print(f"executed but not expected: {len(beyond)}")
+    for k in beyond:
+        print(f"| `{k}` | {calls[k]} |" if md else f"  {k:44s} {calls[k]:8d}")
+    print(f"listed as unreachable (the library refuses the configuration on tiles): {len(unreachable)}")
+    for k, why in unreachable.items():
+        print(f"| `{k}` | {why} | {'EXECUTED' if k in ran else 'not executed'} |" if md else f"  {k:44s} {why}")
+    return 1 if missing else 0
+
+
 def main(argv):
     md = "--markdown" in argv
-    argv = [a for a in argv if a != "--markdown"]
+    want_expected = "--expected" in argv
+    argv = [a for a in argv if a not in ("--markdown", "--expected")]
     extra = []
     if "--with" in argv:
         i = argv.index("--with")
@@ -151,6 +185,8 @@ def main(argv):
         print(f"\n{len(rows)} instantiations -- {WHY[group]}\n" + ("\n| instantiation | | measured beside it |\n|---|---|---|" if md else ""))
         for k, beside in rows:
             print(f"| `{k}` | {describe(k)} | {beside} |" if md else f"  {k:44s} {describe(k)}; {beside}")
+    if want_expected:
+        return compare_expected(more if extra else before, table, md)
     return 0
 
 
