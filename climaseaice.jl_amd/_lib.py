@@ -7,6 +7,8 @@ point raises `CsiError` when there is no HIP device.
 import ctypes as C
 import os
 
+import numpy as np
+
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("CSI_HIP_LIBRARY", os.path.join(_HERE, "libcsi_hip.so"))   # override: A/B runs of two builds
 
@@ -32,6 +34,11 @@ DYNAMICS_MOMENTUM_EQUATION, DYNAMICS_FREE_DRIFT = 0, 1
 FLUX_CONSTANT, FLUX_ARRAY, FLUX_RADIATIVE_EMISSION = 0, 1, 2
 HEAT_TOP, HEAT_BOTTOM = 0, 1
 MAX_HEAT_FLUX_TERMS = 8
+TIME_CLAMP, TIME_CYCLICAL, TIME_LINEAR = 0, 1, 2
+SERIES_DEVICE, SERIES_HOST = 0, 1
+# the eleven slots a time series may drive (csi_time_series_set)
+SERIES_SLOTS = ["TOP_U", "TOP_V", "BOT_U", "BOT_V", "FORCING_U", "FORCING_V", "FREE_DRIFT_U", "FREE_DRIFT_V",
+                "TOP_HEAT_FLUX", "BOTTOM_HEAT_FLUX", "SNOWFALL"]
 
 # every symbol include/csi.h declares (checked by tests/test_abi.py against the header text)
 SYMBOLS = ["csi_version", "csi_context_create", "csi_context_destroy", "csi_last_error", "csi_sync", "csi_set_mode",
@@ -44,7 +51,8 @@ SYMBOLS = ["csi_version", "csi_context_create", "csi_context_destroy", "csi_last
            "csi_immersed_flux_bc_set", "csi_coriolis_points_set", "csi_validate_all", "csi_debug_peer_abort", "csi_set_weno_weight_dtype", "csi_weno_weight_dtype", "csi_subcycle_stats_begin", "csi_subcycle_stats_end",
            "csi_set_tile_skipping", "csi_tile_activity", "csi_set_row_constant", "csi_row_constant_rows",
            "csi_rheology_set", "csi_momentum_solver_set", "csi_compute_momentum_tendencies",
-           "csi_heat_fluxes_set", "csi_surface_solve_set", "csi_dynamics_set"]
+           "csi_heat_fluxes_set", "csi_surface_solve_set", "csi_dynamics_set",
+           "csi_time_series_plan", "csi_time_series_set", "csi_time_series_update", "csi_time_series_status"]
 
 
 class Metrics(C.Structure):
@@ -93,6 +101,11 @@ class HeatFluxTerm(C.Structure):
 class SurfaceSolve(C.Structure):
     _fields_ = [("tol", C.c_double), ("maxiters", C.c_int32), ("prescribed_array", C.c_int32), ("snowfall_array", C.c_int32),
                 ("reserved", C.c_int32)]
+
+
+class TimeSeries(C.Structure):
+    _fields_ = [("nt", C.c_int32), ("indexing", C.c_int32), ("backend", C.c_int32), ("window", C.c_int32), ("period", C.c_double),
+                ("times", C.POINTER(C.c_double)), ("data", C.c_void_p), ("ld", C.c_int64), ("slice_stride", C.c_int64)]
 
 
 class CsiError(RuntimeError):
@@ -164,6 +177,9 @@ def load():
         "csi_rheology_set": [vp, i32, dbl], "csi_momentum_solver_set": [vp, i32], "csi_compute_momentum_tendencies": [vp, dbl],
         "csi_heat_fluxes_set": [vp, i32, C.POINTER(HeatFluxTerm), i32], "csi_surface_solve_set": [vp, C.POINTER(SurfaceSolve)],
         "csi_dynamics_set": [vp, i32],
+        "csi_time_series_plan": [C.POINTER(dbl), i32, i32, dbl, dbl, C.POINTER(i32), C.POINTER(i32), C.POINTER(dbl)],
+        "csi_time_series_set": [vp, i32, C.POINTER(TimeSeries)], "csi_time_series_update": [vp, dbl],
+        "csi_time_series_status": [vp, i32, C.POINTER(i32), C.POINTER(i64)],
     }
     for name, args in sig.items():
         fn = getattr(L, name, None)
@@ -201,6 +217,17 @@ def plan_pair(Nx, Ny, Hx, Hy, topo_x, topo_y, k=1, m=0):
     r = lambda q: tuple(out[4 + 4 * q: 8 + 4 * q])
     return dict(nstrips=out[1], nchunks=out[2], rows=out[3], first_compute=r(0), second_compute=r(1), store_sigma=r(2),
                 store_first_u=r(3), store_first_v=r(4), store_second=r(5), walls=bool(out[28]))
+
+
+def time_series_plan(times, indexing, period, t):
+    """csi_time_series_plan: (n1, n2, weight) of a time series at time t (pure host function; CsiError on invalid input)."""
+    a = np.ascontiguousarray(times, dtype=np.float64)
+    n1, n2, frac = C.c_int32(), C.c_int32(), C.c_double()
+    rc = load().csi_time_series_plan(a.ctypes.data_as(C.POINTER(C.c_double)), a.size, int(indexing), float(period), float(t),
+                                     C.byref(n1), C.byref(n2), C.byref(frac))
+    if rc != OK:
+        raise CsiError(rc, "csi_time_series_plan: invalid input")
+    return n1.value, n2.value, frac.value
 
 
 def plan_peer_chunks(Nx, Ny, Hx, Hy, peer_south=True, peer_north=True):
@@ -329,3 +356,13 @@ class Context:
         v = C.c_int32()
         self.call("csi_launches_per_substep", C.byref(v))
         return v.value
+
+    def time_series_update(self, time):
+        """csi_time_series_update: every series-driven slot interpolated at `time`, one launch (none without series)."""
+        self.call("csi_time_series_update", float(time))
+
+    def time_series_status(self, slot, window):
+        """(slices the ring slots of a HOST series hold, -1: none; slice uploads since csi_time_series_set)."""
+        res, up = (C.c_int32 * max(int(window), 1))(*([-1] * max(int(window), 1))), C.c_int64()
+        self.call("csi_time_series_status", F[slot], res, C.byref(up))
+        return list(res)[:int(window)], up.value

@@ -153,6 +153,7 @@ int32_t csi_context_destroy(csi_context* c) {
     hipSetDevice(c->device);
     hipStreamSynchronize(c->stream);
     peer_release(c);
+    series_release(c);
     for (auto& e : c->ring_ev) if (e) hipEventDestroy(e);
     if (c->band_ev_pair) hipEventDestroy(c->band_ev_pair);
     if (c->band_ev_band) hipEventDestroy(c->band_ev_band);
@@ -187,6 +188,13 @@ static int32_t peer_check(csi_context* c) {
                                      "csi_set_halo_transport again (CSI_TRANSPORT_PEER: a new collective set-up at the next sub-cycle; CSI_TRANSPORT_RCCL: the "
                                      "message exchange)");
     return CSI_OK;
+}
+// the end of an entry point that advances the model: its launches are queued, so the host has time for the look-ahead uploads of the
+// forcing time series (csi_time_series.hip); then the transport's status
+static int32_t finish_step(csi_context* c, int32_t rc) {
+    if (rc) return rc;
+    if ((rc = series_prefetch(c))) return rc;
+    return peer_check(c);
 }
 int32_t csi_sync(csi_context* c) {
     if (!c) return CSI_ERR_INVALID_ARGUMENT;
@@ -496,7 +504,7 @@ int32_t csi_time_step_momentum(csi_context* c, double dt, int32_t substeps, int3
     if (rc) return rc;
     if (substeps < 0) return fail(c, CSI_ERR_INVALID_ARGUMENT, "substeps >= 0 required");
     rc = do_momentum(c, dt, substeps, rk_reset);       // (EVP + split-explicit: do_time_step_momentum)
-    return rc ? rc : peer_check(c);
+    return finish_step(c, rc);
 }
 
 int32_t csi_compute_tracer_tendencies(csi_context* c, int32_t scheme) {
@@ -541,7 +549,8 @@ static bool halo_slot(int32_t fid) { return (fid >= 0 && fid < CSI_F_COUNT) || f
 
 int32_t csi_update_state(csi_context* c) {
     if (!c) return CSI_ERR_INVALID_ARGUMENT;
-    return do_update_state(c);
+    const int32_t rc = do_update_state(c);
+    return rc ? rc : series_prefetch(c);      // (forcing time series: the look-ahead uploads, if an update has left any)
 }
 
 int32_t csi_fill_halo_local(csi_context* c, int32_t fid) {
@@ -568,7 +577,7 @@ int32_t csi_time_step_fe(csi_context* c, double dt, int32_t substeps, int32_t sc
     if ((rc = do_tracer_step(c, dt, 0, fused_fill))) return rc;           // :25
     if ((rc = do_thermo(c, dt))) return rc;                               // :28 thermodynamic_time_step!
     if ((rc = do_update_state(c, true, fused_fill))) return rc;           // :31
-    return peer_check(c);
+    return finish_step(c, CSI_OK);
 }
 
 // An RK3 step of an advection-only model (prescribed velocities: examples/ice_advected_by_anticyclone.jl's family, BASELINE
@@ -626,7 +635,7 @@ int32_t csi_time_step_rk3(csi_context* c, double dt, int32_t substeps, int32_t s
         const int need_h = scheme == CSI_ADVECT_WENO7 ? 4 : (scheme == CSI_ADVECT_UPWIND1 ? 1 : (third ? 2 : 3));
         if (c->Hx >= need_h && c->Hy >= need_h &&
             (scheme == CSI_ADVECT_UPWIND1 || scheme == CSI_ADVECT_WENO5 || scheme == CSI_ADVECT_WENO7 || scheme == CSI_ADVECT_UPWIND5 || third))
-            return rk3_advection_only(c, dt, scheme);
+            return finish_step(c, rk3_advection_only(c, dt, scheme));
     }
     if ((rc = csi_cache_current_fields(c))) return rc;                    // sea_ice_rk_substep.jl:29-42
     for (int beta = 3; beta >= 1; --beta) {                               // upstream stage loop
@@ -639,7 +648,7 @@ int32_t csi_time_step_rk3(csi_context* c, double dt, int32_t substeps, int32_t s
         if ((rc = do_thermo(c, dtau))) return rc;                         // :91 thermodynamic_time_step!
         if ((rc = do_update_state(c, true, fused_fill))) return rc;
     }
-    return peer_check(c);
+    return finish_step(c, CSI_OK);
 }
 
 int32_t csi_slab_thermo_step(csi_context* c, const csi_slab_params* p, double dt) {

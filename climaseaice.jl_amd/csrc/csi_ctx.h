@@ -5,6 +5,7 @@
 //   csi_fold.hip    north fold: the three-kernel band beside the pair launches
 //   csi_launch.hip  launch loops: sub-cycle, finalize, time_step_momentum!, tracer steps, update_state!, csi_profile_substeps
 //   csi_abi.hip     the C ABI (include/csi.h)
+//   csi_time_series.hip   forcing time series: time indexing, the device ring of a host-resident series, the interpolation launch
 //   csi_mem.h       DeviceBuf / PinnedBuf: the owner of every allocation the library makes
 #pragma once
 #include "../../include/csi.h"
@@ -100,6 +101,32 @@ struct csi_local_group {
     long arrived = 0, generation = 0;
     int joined = 0;
     std::vector<int> device;                       // per rank: the HIP device of its context (-1: not joined); peer_effective_tier
+};
+
+// One forcing time series (csi_time_series_set): the caller's description, and for the HOST backend the device ring with its slot table.
+struct TimeSeries {
+    int fid = -1;
+    int nt = 0, indexing = 0, backend = 0, window = 0;
+    double period = 0.0;
+    std::vector<double> times;           // copied: the caller's array need not outlive the call
+    const double* data = nullptr;        // device (DEVICE) / host (HOST) pointer to all nt slices, the caller's
+    int64_t ld = 0, slice_stride = 0;    // doubles between rows / slices of `data`
+    int nx = 0, ny = 0;                  // slice shape: the interior of the bound field
+    // ---- HOST backend
+    DeviceBuf<double> ring;              // `window` slices, rows ring_ld apart, slices ring_stride apart, first element at ring_off
+    int64_t ring_ld = 0, ring_stride = 0, ring_off = 0;
+    bool data_pinned = false;            // the caller's host memory is page-locked: slices are copied from it directly
+    PinnedBuf<double> stage;             // else: one packed nx * ny staging slice per ring slot
+    struct Slot {
+        int slice = -1;                  // the slice the slot holds (-1: none)
+        long used = 0;                   // the update that last read it (eviction: least recently used)
+        hipEvent_t uploaded = nullptr;   // recorded on the copy stream behind the slot's upload
+        bool pending = false;            // the context's stream has not yet been made to wait for `uploaded`
+        bool staged = false;             // the slot's staging slice has been the source of a copy (wait for `uploaded` before rewriting it)
+    };
+    std::vector<Slot> slots;
+    int64_t uploads = 0;                 // slice uploads since csi_time_series_set
+    int cur[2] = {-1, -1}, next = -1;    // the newest update's pair and the slice wanted after it (series_prefetch)
 };
 
 struct csi_context {
@@ -209,6 +236,14 @@ struct csi_context {
     bool snow_set = false;   // layered (snow + ice) step instead of the bare-ice one
     SnowDev snow{};
     HeatFluxDev heat{};      // csi_heat_fluxes_set / csi_surface_solve_set (thermo_flux.hip); heat.top.n = heat.bot.n = 0: numbers only
+    // csi_time_series_set / _update (csi_time_series.hip): at most one series per eligible slot; the copy stream of the HOST backend's
+    // uploads and the event recorded behind every interpolation launch (an upload into a ring slot waits for it), both made once
+    std::vector<TimeSeries> series;
+    hipStream_t series_stream = nullptr;
+    hipEvent_t series_launched = nullptr;
+    bool series_launched_valid = false;
+    bool series_prefetch_pending = false;    // the newest update's look-ahead uploads have not been issued yet
+    long series_updates = 0;
     int weno_w32 = 0;     // csi_set_weno_weight_dtype: 1 = WENO weights in single precision (upstream's FT2 = Float32, recalled)
     // csi_rheology_set / csi_momentum_solver_set (csi_momentum.hip): ViscousRheology, ExplicitSolver
     int rheology = CSI_RHEOLOGY_EVP;
@@ -437,6 +472,8 @@ bool has_comm(const csi_context* c);
 Range v_stress_range(const csi_context* c, const SideV& v);
 Range v_second_range(const csi_context* c, const SideV& v);
 static inline const Bound& band_bound(const csi_context* c, int q) { return c->f[c->band[q].fid]; }
+int32_t series_prefetch(csi_context* c);                 // ... the look-ahead uploads of the newest csi_time_series_update, once (no-op otherwise)
+void series_release(csi_context* c);                     // csi_time_series.hip: events, copy stream, rings (the streams have been drained)
 int32_t peer_check_entry(csi_context* c);      // (csi_abi.hip: the error word of the peer transport, checked at every entry point)
 
 }  // namespace csi_host

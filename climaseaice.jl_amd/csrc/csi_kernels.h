@@ -220,4 +220,20 @@ void launch_slab_flux_step(const SlabDev& S, const HeatFluxDev& F, const FluxFie
 void launch_layered_flux_step(const SlabDev& S, const SnowDev& W, const HeatFluxDev& F, const FluxFields& ff, const GridDev& g,
                               const FRef& h, const FRef& a, const FRef& hs, const LayeredOut& o, double dt, hipStream_t s);
 
+// forcing time series interpolated at the model clock (time_series.hip; include/csi.h csi_time_series_update): every series-driven
+// slot in ONE launch.  A descriptor: the two slices around the clock (a: psi_1, b: psi_2; b == a where n1 == n2), the interior of the
+// bound array, row strides in doubles, the interior extents and the weights w2 = n~, w1 = 1 - n~ (formed on the host, in double).
+constexpr int kMaxSeries = 11;
+struct SeriesDesc {
+    const double *a, *b;
+    double* dst;
+    long lda, ldb, ldd;
+    int nx, ny;
+    double w1, w2;
+    int same;                  // n1 == n2: dst = psi_1, bit for bit
+    int pad_;
+};
+struct SeriesTable { int n; int pad_; SeriesDesc d[kMaxSeries]; };
+void launch_time_series(const SeriesTable& T, hipStream_t s);
+
 }  // namespace csi

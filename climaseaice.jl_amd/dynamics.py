@@ -19,6 +19,7 @@ from types import SimpleNamespace
 
 from .fields import CenterField, CornerField, Field, XFaceField, YFaceField
 from .grids import Center, Face
+from .time_series import FieldTimeSeries
 
 
 class ReplacementPressure:
@@ -189,6 +190,11 @@ class FreeDriftVelocities:
             if isinstance(val, Field):
                 if val.location != loc or (val.ni, val.nj) != tuple(grid.field_size(*loc)):
                     raise ValueError(f"free_drift.{name}: a field at ({loc[0].__name__}, {loc[1].__name__}) of the dynamics' grid is needed")
+            elif isinstance(val, FieldTimeSeries):
+                nx, ny = grid.interior_size(*loc)
+                if val.location != loc or val.interior_shape != (ny, nx):
+                    raise ValueError(f"free_drift.{name}: a FieldTimeSeries at ({loc[0].__name__}, {loc[1].__name__}) with slices of the "
+                                     f"interior shape {(ny, nx)} is needed")
             elif isinstance(val, bool) or val is None or callable(val):
                 raise TypeError(f"free_drift.{name}: a number, an array or a field is needed, got {type(val).__name__}")
             elif not np.isscalar(val):

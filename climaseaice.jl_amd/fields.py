@@ -41,6 +41,8 @@ class Field:
         """set!(field, value): a number, an (ny, nx) array, or a function f(x, y) of the field's nodes."""
         g = self.grid
         dst = self.interior()
+        from .time_series import refuse_series
+        refuse_series(value, f"set!({self.name or 'field'})")
         if callable(value):
             x = g.xnodes(self.LX)
             y = g.ynodes(self.LY)

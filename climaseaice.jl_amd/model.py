@@ -17,6 +17,7 @@ from . import _lib
 from .dynamics import (ElastoViscoPlasticRheology, ExplicitSolver, FPlane, FreeDriftVelocities, IceStrength, SeaIceMomentumEquation,
                        SemiImplicitStress, StressBalanceFreeDrift, ViscousRheology)
 from .fields import CenterField, Field, XFaceField, YFaceField
+from .time_series import FieldTimeSeries, refuse_series
 from .grids import (METRIC_NAMES, Bounded, Center, FullyConnected, LeftConnected, LeftConnectedRightFolded, Periodic, RightConnected,
                     RightFolded, TileGrid)
 
@@ -28,6 +29,8 @@ def _cell_shape_ok(value, grid):
     """An (Ny, Nx) array of the grid (on a TileGrid also of the global grid) or a CenterField of the grid."""
     if isinstance(value, Field):
         return value.location == (Center, Center) and (value.ni, value.nj) == tuple(grid.field_size(Center, Center))
+    if isinstance(value, FieldTimeSeries):      # (cut to the tile when it was built)
+        return value.location == (Center, Center) and value.interior_shape == (grid.Ny, grid.Nx)
     shape = np.shape(value)
     if isinstance(grid, TileGrid) and shape == (grid.global_grid.Ny, grid.global_grid.Nx):
         return True
@@ -49,7 +52,7 @@ def check_heat_flux(spec, side, grid):
         if isinstance(x, RadiativeEmission):
             if side != "top":
                 raise NotImplementedError("RadiativeEmission is a top heat flux only")
-        elif isinstance(x, (Field, np.ndarray, list)):
+        elif isinstance(x, (Field, np.ndarray, list, FieldTimeSeries)):
             arrays += 1
             if arrays > 1:
                 raise NotImplementedError(f"{side}_heat_flux: at most one array / CenterField term (sum the arrays into one)")
@@ -72,6 +75,7 @@ def check_heat_fluxes(grid, ice, top_heat_flux, bottom_heat_flux, snowfall=None)
         raise ValueError("bottom_heat_flux is given both to SeaIceModel and to SlabThermodynamics")
     check_heat_flux(top_heat_flux if top_heat_flux is not None else ice.top_heat_flux, "top", grid)
     check_heat_flux(bottom_heat_flux if bottom_heat_flux is not None else ice.bottom_heat_flux, "bottom", grid)
+    refuse_series(ice.prescribed, "PrescribedTemperature (the per-cell temperature is also state)")
     for name, value in (("snowfall", snowfall), ("PrescribedTemperature", ice.prescribed)):
         if value is not None and not _is_number(value) and not _cell_shape_ok(value, grid):
             raise ValueError(f"{name}: an array of shape (Ny, Nx) = {(grid.Ny, grid.Nx)} or a CenterField of the grid is needed")
@@ -128,6 +132,7 @@ class PrescribedTemperature:
     (slab_sea_ice_thermodynamics.jl:83-100)."""
 
     def __init__(self, temperature):
+        refuse_series(temperature, "PrescribedTemperature (the per-cell temperature is also state)")
         self.per_cell = not _is_number(temperature)
         self.temperature = temperature if self.per_cell else float(temperature)
 
@@ -318,8 +323,10 @@ class SeaIceModel:
         self._keep = []
         self._stress_fields = {}
         self._free_drift_fields = {}
+        self._series, self._pending_series = {}, []     # slot name -> what csi_time_series_set was given (kept alive)
         self.ctx = _lib.Context(dev.index or 0, stream)
         self._configure()
+        self._attach_pending_series()
         self.set_mode(mode)
         self.ctx.call("csi_set_weno_weight_dtype", 1 if getattr(advection, "weight_dtype", "f64") == "f32" else 0)
         torch.cuda.synchronize(self.device)   # field initialisation ran on torch's stream
@@ -394,7 +401,11 @@ class SeaIceModel:
         if self.forcing is not None:
             fu, fv = self.forcing["u"], self.forcing["v"]
             self.forcing_fields = SimpleNamespace(u=XFaceField(g, self.device, "forcing_u"), v=YFaceField(g, self.device, "forcing_v"))
-            self.forcing_fields.u.set(fu); self.forcing_fields.v.set(fv)
+            for fld, val, slot in ((self.forcing_fields.u, fu, "FORCING_U"), (self.forcing_fields.v, fv, "FORCING_V")):
+                if isinstance(val, FieldTimeSeries):
+                    self._pending_series.append((slot, val, fld))
+                else:
+                    fld.set(val)
             self._bind("FORCING_U", self.forcing_fields.u)
             self._bind("FORCING_V", self.forcing_fields.v)
             torch.cuda.synchronize(self.device)
@@ -463,6 +474,11 @@ class SeaIceModel:
             if value.data.device != self.device:
                 value.data = value.data.to(self.device)
             return value
+        if isinstance(value, FieldTimeSeries):      # the series writes into a new field (bound by the caller, registered after it)
+            fld = CenterField(g, self.device, name)
+            self._pending_series.append(({"top_heat_flux": "TOP_HEAT_FLUX", "bottom_heat_flux": "BOTTOM_HEAT_FLUX",
+                                          "snowfall": "SNOWFALL"}[name], value, fld))
+            return fld
         arr = np.asarray(value, dtype=np.float64)
         if isinstance(g, TileGrid) and arr.shape == (g.global_grid.Ny, g.global_grid.Nx):
             arr = arr[g.j_off:g.j_off + g.Ny, g.i_off:g.i_off + g.Nx]
@@ -580,6 +596,9 @@ class SeaIceModel:
             fld = value
             if fld.data.device != self.device:
                 fld.data = fld.data.to(self.device)
+        elif isinstance(value, FieldTimeSeries):
+            fld = mk(self.grid, self.device, f"{slot}_{comp}".lower())
+            self._pending_series.append((f"{slot}_{comp}", value, fld))
         else:
             fld = mk(self.grid, self.device, f"{slot}_{comp}".lower())
             fld.set(value)
@@ -625,6 +644,9 @@ class SeaIceModel:
             fld = value
             if fld.data.device != self.device:
                 fld.data = fld.data.to(self.device)
+        elif isinstance(value, FieldTimeSeries):
+            fld = mk(self.grid, self.device, f"free_drift_{comp}".lower())
+            self._pending_series.append((f"FREE_DRIFT_{comp}", value, fld))
         else:
             fld = mk(self.grid, self.device, f"free_drift_{comp}".lower())
             fld.set(value)
@@ -636,6 +658,49 @@ class SeaIceModel:
         """The device field of a prescribed free-drift velocity component ("u" / "v"): write into its interior between steps (then
         torch.cuda.synchronize) to update it in place."""
         return self._free_drift_fields[comp.upper()]
+
+    # ---- forcing time series (include/csi.h, csi_time_series_set) -----------------------------------------------------------------
+    def _set_series(self, slot):
+        self.ctx.call("csi_time_series_set", _lib.F[slot], C.byref(self._series[slot].struct))
+
+    def _attach_pending_series(self):
+        """Register the series met while the model was described (their fields are bound by now), interpolate them at the clock and
+        fill the halos the library fills for plain arrays at construction."""
+        for slot, fts, fld in self._pending_series:
+            if fts.location != fld.location or fts.interior_shape != tuple(reversed(self.grid.interior_size(*fld.location))):
+                raise ValueError(f"{slot.lower()}: a FieldTimeSeries at ({fld.LX.__name__}, {fld.LY.__name__}) with slices of the "
+                                 f"interior shape {tuple(reversed(self.grid.interior_size(*fld.location)))} is needed, got one at "
+                                 f"({fts.location[0].__name__}, {fts.location[1].__name__}) with {fts.interior_shape}")
+            if slot in self._series:
+                raise ValueError(f"{slot.lower()}: two time series for one array")
+            nt, (ny, nx) = len(fts), fts.interior_shape
+            host = fts.backend.chunk_size is not None
+            keep = fts.data if host else torch.from_numpy(fts.data).to(self.device)      # (the caller's array: the library reads it)
+            ptr = keep.ctypes.data if host else keep.data_ptr()
+            st = _lib.TimeSeries(nt, fts.time_indexing.kind, _lib.SERIES_HOST if host else _lib.SERIES_DEVICE,
+                                 fts.backend.chunk_size or 0, fts.time_indexing.period, _dptr(fts.times), C.c_void_p(ptr), nx, nx * ny)
+            self._series[slot] = SimpleNamespace(series=fts, field=fld, struct=st, keep=keep, window=fts.backend.chunk_size or 0)
+        self._pending_series = []
+        if not self._series:
+            return
+        torch.cuda.synchronize(self.device)
+        for slot in self._series:
+            self._set_series(slot)
+        self.update_time_series()
+        for slot in self._series:
+            if self._series[slot].field.location != (Center, Center):
+                self.ctx.call("csi_fill_halo_local", _lib.F[slot])
+
+    def update_time_series(self):
+        """csi_time_series_update at the model clock (time_step, time_step_momentum, compute_momentum_tendencies and update_state call
+        it first); nothing is called for a model without series."""
+        if self._series:
+            self.ctx.time_series_update(self.clock.time)
+
+    def time_series_status(self, slot):
+        """(slices resident in the device window of a host-resident series, -1: none; slice uploads so far) of the series on `slot`,
+        e.g. "TOP_U", "SNOWFALL"."""
+        return self.ctx.time_series_status(slot, self._series[slot].window)
 
     def set_mode(self, mode):
         self.mode = mode
@@ -750,6 +815,7 @@ def set_(model, **kw):
 
 
 def update_state(model):
+    model.update_time_series()
     model.ctx.call("csi_update_state")
 
 
@@ -814,17 +880,21 @@ def time_step_momentum(model, dt, rk_reset=False):
     the current velocities otherwise; G^n from compute_momentum_tendencies) or, with StressBalanceFreeDrift as the dynamics,
     stress_balance_free_drift.jl:132-143: u, v = the free-drift velocity at every point (dt and rk_reset are not read; model.substeps
     is 0 and the fusion / tile-skipping switches are accepted and ignored: there is no sub-cycle)."""
+    model.update_time_series()
     model.ctx.call("csi_time_step_momentum", float(dt), model.substeps, int(rk_reset))
 
 
 def compute_momentum_tendencies(model, dt):
     """compute_momentum_tendencies!(model, model.dynamics, dt): G^n.u / G^n.v of the ExplicitSolver (explicit_momentum_equations.jl:
     85-113); nothing for the split-explicit solver."""
+    model.update_time_series()
     model.ctx.call("csi_compute_momentum_tendencies", float(dt))
 
 
 def time_step(model, dt):
-    """time_step!(model, dt)."""
+    """time_step!(model, dt).  Forcing time series are interpolated at the time the step starts from: every stage reads the same
+    forcing, as in the reference, whose tick! follows the stages."""
+    model.update_time_series()
     if model.dynamics is None and model.scheme in (0, None):
         # dynamics = nothing, advection = nothing: the step is the thermodynamic update alone
         # (sea_ice_fe_step.jl:13-34 with time_step_momentum!, compute_tendencies! and dynamic_time_step! no-ops)

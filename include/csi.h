@@ -498,6 +498,69 @@ int32_t csi_free_drift_set(csi_context* ctx, int32_t kind);
 typedef enum { CSI_DYNAMICS_MOMENTUM_EQUATION = 0, CSI_DYNAMICS_FREE_DRIFT = 1 } csi_dynamics_kind;
 int32_t csi_dynamics_set(csi_context* ctx, int32_t kind);
 
+/* ---- forcing time series interpolated at the model clock ---------------------------------------------------------------------------
+ * The reference treats time-dependent forcing as part of the model: update_state! ends with update_model_field_time_series!(model,
+ * clock) (sea_ice_model.jl:391-408) and its kernels read a FieldTimeSeries at Time(clock.time) (thermodynamic_time_step.jl:326-329).
+ * Here a series drives one of ELEVEN slots of csi_field_bind: CSI_F_TOP_U / _V, CSI_F_BOT_U / _V (stress arrays or external
+ * velocities), CSI_F_FORCING_U / _V, CSI_F_FREE_DRIFT_U / _V, CSI_F_TOP_HEAT_FLUX, CSI_F_BOTTOM_HEAT_FLUX, CSI_F_SNOWFALL.
+ * csi_time_series_update(ctx, t) interpolates every series in ONE launch, in place, into the INTERIOR of the arrays bound to those
+ * slots -- the arrays the momentum and thermodynamic kernels already read; no kernel of theirs changes.  The halos of the
+ * velocity-point slots stay the library's to fill where it fills them for plain arrays (csi_time_step_momentum; csi_free_drift_set).
+ *
+ * Time indexing (csi_time_series_plan; pure host function, no context, no GPU).  times: strictly increasing, nt >= 2.  Output: 0-based
+ * slice indices n1, n2 and the weight frac; the interpolated value is
+ *     psi = (n1 == n2) ? psi_1 : psi_2 * frac + psi_1 * (1 - frac)          (two products, one sum, uncontracted; STRICT and FAST alike)
+ *   CSI_TIME_CLAMP:    t <= times[0] / t >= times[nt-1]: the end slice (n1 == n2, frac 0).  Inside: n1 the last node at or below t,
+ *                      n2 = n1 + 1, frac = (t - times[n1]) / (times[n2] - times[n1]); at a node n1 == n2, frac 0.
+ *   CSI_TIME_LINEAR:   as CLAMP inside and at the two end nodes; beyond them it extrapolates from the first (0, 1) / last (nt-2, nt-1)
+ *                      two slices with the same formula, so frac < 0 / frac > 1.
+ *   CSI_TIME_CYCLICAL: period <= 0 means "infer": times[nt-1] - times[0] + (times[nt-1] - times[nt-2]); a given period must exceed
+ *                      times[nt-1] - times[0].  t' = times[0] + r, r = fmod(t - times[0], period), plus period if r < 0.  t' inside
+ *                      the nodes: as CLAMP.  In the gap behind the last node: n1 = nt-1, n2 = 0,
+ *                      frac = (t' - times[nt-1]) / (period - (times[nt-1] - times[0])).
+ * Invalid input (nt < 2, times not strictly increasing, an unknown kind, a period that is too short, a time that is not finite):
+ * CSI_ERR_INVALID_ARGUMENT.  STATUS: Oceananigans is not vendored; these rules (its Clamp / Cyclical / Linear time indexing), the
+ * inferred period and the interpolation formula are RECALLED, like the fold and the secant solve above.  This statement is the
+ * definition; tests/time_series_ref.py restates it and tests/test_time_series_plan.py pins the library to it bit for bit. */
+typedef enum { CSI_TIME_CLAMP = 0, CSI_TIME_CYCLICAL = 1, CSI_TIME_LINEAR = 2 } csi_time_indexing;
+int32_t csi_time_series_plan(const double* times, int32_t nt, int32_t indexing, double period, double t,
+                             int32_t* n1, int32_t* n2, double* frac);
+/* CSI_SERIES_DEVICE: `data` is a DEVICE pointer to all nt slices; the caller keeps it alive; nothing is copied.
+ * CSI_SERIES_HOST:   `data` is a HOST pointer to all nt slices (pageable or page-locked), which the caller keeps alive.  The library
+ *   keeps `window` slices (>= 2; 0 selects the default, 3) in a device ring of its own and uploads slices on a copy stream of its own:
+ *   the two an update needs if they are not resident, and the slice that time moving forward needs next.  That look-ahead is issued
+ *   at the END of the next entry point that advances the model (csi_time_step_momentum, csi_time_step_fe / _rk3, csi_update_state),
+ *   once its launches are queued -- by the next csi_time_series_update or _status at the latest --, so that the host's staging copy
+ *   and the transfer both run under that step.  Residency is a table (ring slot -> slice); a slot is evicted only if
+ *   neither current index uses it.  Any time is legal: jumps forward or backward (a restored checkpoint), a first call in the middle.
+ *   No call waits for the device; the host copies a PAGEABLE slice into page-locked staging memory first (one staging slice per ring
+ *   slot, rewritten only after the copy that last read it has completed).
+ * Slices have the shape of the slot's field's INTERIOR: parent extents minus halos (so a Face field on a Bounded side is one wider);
+ * rows are `ld` doubles apart, slices `slice_stride` doubles apart.  `times` is copied. */
+typedef enum { CSI_SERIES_DEVICE = 0, CSI_SERIES_HOST = 1 } csi_series_backend;
+typedef struct {
+    int32_t nt;              /* slices, >= 2 */
+    int32_t indexing;        /* csi_time_indexing */
+    int32_t backend;         /* csi_series_backend */
+    int32_t window;          /* HOST: slices of the device ring */
+    double period;           /* CYCLICAL: <= 0 infers it */
+    const double* times;     /* host, nt values */
+    const void* data;        /* nt slices: device (DEVICE) or host (HOST) memory */
+    int64_t ld;              /* doubles between rows */
+    int64_t slice_stride;    /* doubles between slices */
+} csi_time_series;
+/* Set (or, ts == NULL, remove) the series of one slot.  Any slot but the eleven: CSI_ERR_INVALID_ARGUMENT.  The slot's field must be
+ * bound (CSI_ERR_NOT_BOUND): the series writes into that array.  Setting a slot again replaces its series (empty window, zero uploads). */
+int32_t csi_time_series_set(csi_context* ctx, int32_t field_id, const csi_time_series* ts);
+/* Interpolate every series at `time` into its bound array, one launch on the context's stream (no series: nothing is launched, CSI_OK).
+ * The Python / Julia front ends call it with the model clock at the start of time_step!, time_step_momentum!,
+ * compute_momentum_tendencies! and update_state!: all stages of a step read the forcing at the time the step starts from, as in the
+ * reference, whose tick! follows the stages. */
+int32_t csi_time_series_update(csi_context* ctx, double time);
+/* For tests and profiles: resident[k] = the slice ring slot k holds (-1: none), k < window (HOST; DEVICE: nothing is written), and the
+ * slice uploads since csi_time_series_set.  Either pointer may be NULL. */
+int32_t csi_time_series_status(csi_context* ctx, int32_t field_id, int32_t* resident, int64_t* uploads);
+
 /* ---- rheology and momentum solver (SeaIceMomentumEquation(grid; rheology, solver), sea_ice_momentum_equations.jl:67-94) ------------
  * Defaults: CSI_RHEOLOGY_EVP with CSI_SOLVER_SPLIT_EXPLICIT -- the library's EVP path, unchanged by these calls.  The scalars both
  * rheologies share (minimum mass / concentration, sea_ice_density, FPlane f) still come from csi_evp_params_set, which marks the model

@@ -17,6 +17,7 @@ using Oceananigans.BoundaryConditions: FluxBoundaryCondition, getbc
 using Oceananigans.Coriolis: FPlane, BetaPlane
 using Oceananigans.DistributedComputations: Distributed
 using Oceananigans.Fields: Field, ZeroField, ConstantField
+using Oceananigans.OutputReaders: FieldTimeSeries
 using Oceananigans.Grids: topology, halo_size, Periodic, Bounded, Center, Face, RectilinearGrid, LatitudeLongitudeGrid,
                           OrthogonalSphericalShellGrid, ynode, inactive_cell
 using Oceananigans.ImmersedBoundaries: ImmersedBoundaryGrid, ImmersedBoundaryCondition
@@ -44,6 +45,12 @@ struct CsiStress
     kind::Int32; ue_kind::Int32; ve_kind::Int32; reserved::Int32
     tau_u::Cdouble; tau_v::Cdouble; ue::Cdouble; ve::Cdouble; rho_e::Cdouble; Cd::Cdouble
 end
+struct CsiTimeSeries
+    nt::Int32; indexing::Int32; backend::Int32; window::Int32
+    period::Cdouble
+    times::Ptr{Cdouble}; data::Ptr{Cvoid}
+    ld::Int64; slice_stride::Int64
+end
 
 # field slots, in the order of csi_field_id
 const F = (U=0, V=1, H=2, A=3, S11=4, S22=5, S12=6, UN=7, VN=8, P=9, ALPHA=10, DELTA=11, ZETA_F=12, ZETA_C=13,
@@ -57,7 +64,8 @@ mutable struct Context
     handle::Ptr{Cvoid}
     mask::Any            # UInt8 activity mask of an immersed grid (owned here so that it outlives the library's pointer)
     validated_iteration::Int      # Distributed grids: the clock iteration whose state csi_validate_all has last checked on every rank
-    Context(handle) = new(handle, nothing, -1)
+    series::Vector{Any}  # forcing time series: the series, their target fields and host arrays (kept alive: the library holds pointers)
+    Context(handle) = new(handle, nothing, -1, Any[])
 end
 
 function check(ctx, rc)
@@ -170,6 +178,7 @@ stress_struct(τ::NamedTuple{(:u, :v), <:Tuple{Number, Number}}) = CsiStress(1, 
 # CSI_STRESS_FIELD; the arrays are bound to CSI_F_TOP_U / _V or CSI_F_BOT_U / _V in attach!
 stress_struct(τ::NamedTuple{(:u, :v), <:Tuple{Field, Field}}) = CsiStress(2, 0, 0, 0, 0, 0, 0, 0, 0, 0)
 function stress_struct(τ::SemiImplicitStress)
+    # (2: a Field, or a FieldTimeSeries interpolated into one)
     kind(x) = x isa Oceananigans.Fields.ZeroField ? Int32(0) : x isa Oceananigans.Fields.ConstantField ? Int32(1) : Int32(2)
     val(x) = x isa Oceananigans.Fields.ConstantField ? Float64(x.constant) : 0.0
     return CsiStress(3, kind(τ.uₑ), kind(τ.vₑ), 0, 0, 0, val(τ.uₑ), val(τ.vₑ), τ.ρₑ, τ.Cᴰ)
@@ -186,13 +195,89 @@ set_free_drift_kind!(ctx, kind) = check(ctx, ccall((:csi_free_drift_set, libcsi)
 set_free_drift!(ctx, ::Nothing) = set_free_drift_kind!(ctx, 0)
 set_free_drift!(ctx, ::StressBalanceFreeDrift) = set_free_drift_kind!(ctx, 1)
 function set_free_drift!(ctx, fd::NamedTuple)
-    (haskey(fd, :u) && haskey(fd, :v) && fd.u isa Field && fd.v isa Field) ||
-        error("ClimaSeaIceHIP: free_drift = (u = ..., v = ...) needs two Fields at (Face, Center) and (Center, Face), got $(typeof(fd))")
-    bind!(ctx, F.FREE_DRIFT_U, fd.u); bind!(ctx, F.FREE_DRIFT_V, fd.v)
+    (haskey(fd, :u) && haskey(fd, :v) && fd.u isa Union{Field, FieldTimeSeries} && fd.v isa Union{Field, FieldTimeSeries}) ||
+        error("ClimaSeaIceHIP: free_drift = (u = ..., v = ...) needs two Fields (or FieldTimeSeries) at (Face, Center) and (Center, Face), got $(typeof(fd))")
+    bind_forcing!(ctx, F.FREE_DRIFT_U, fd.u); bind_forcing!(ctx, F.FREE_DRIFT_V, fd.v)
     return set_free_drift_kind!(ctx, 2)
 end
 set_free_drift!(ctx, fd) = error("ClimaSeaIceHIP: free_drift of type $(typeof(fd)) is not supported: nothing, a StressBalanceFreeDrift " *
                                  "or a NamedTuple (u = Field, v = Field)")
+
+# ---- forcing time series (include/csi.h: csi_time_series_set / _update / _status) ---------------------------------------------------
+# A FieldTimeSeries in one of the eleven places below is interpolated by the library at the model clock, in one launch per update, into
+# a Field the stub allocates and binds to the slot -- the momentum kernels read that Field like any array.
+#   top / bottom stress (u = fts, v = fts)              TOP_U, TOP_V / BOT_U, BOT_V
+#   SemiImplicitStress(uₑ = fts, vₑ = fts)              TOP_U, TOP_V / BOT_U, BOT_V
+#   model.forcing.u / .v                                FORCING_U, FORCING_V
+#   free_drift = (u = fts, v = fts)                     FREE_DRIFT_U, FREE_DRIFT_V
+#   top / bottom heat flux array term, snowfall         TOP_HEAT_FLUX, BOTTOM_HEAT_FLUX, SNOWFALL (for callers that run the
+#                                                       library's thermodynamic step; this stub leaves that step to Julia)
+# time indexing: csi_time_indexing (RECALLED rules, stated in include/csi.h)
+time_indexing_code(::Oceananigans.OutputReaders.Clamp) = (Int32(0), 0.0)
+time_indexing_code(ti::Oceananigans.OutputReaders.Cyclical) = (Int32(1), isnothing(ti.period) ? 0.0 : Float64(ti.period))
+time_indexing_code(::Oceananigans.OutputReaders.Linear) = (Int32(2), 0.0)
+time_indexing_code(ti) = error("ClimaSeaIceHIP: time indexing $(typeof(ti)) is not supported: Clamp, Cyclical or Linear")
+
+series_target(fts) = Field{Oceananigans.Fields.location(fts)[1], Oceananigans.Fields.location(fts)[2], Nothing}(fts.grid)
+
+# a totally-in-memory FieldTimeSeries: CSI_SERIES_DEVICE over parent(fts.data), (ni, nj, 1, Nt) with halos -- rows ni apart, slices
+# ni * nj apart, the first interior element Hx + Hy * ni elements in.  Returns the Field the series writes into.
+function attach_series!(ctx, slot, fts::FieldTimeSeries)
+    fts.backend isa Oceananigans.OutputReaders.InMemory && isnothing(fts.backend.length) ||
+        error("ClimaSeaIceHIP: FieldTimeSeries backend $(typeof(fts.backend)) is not supported in attach!: only a totally-in-memory " *
+              "series maps to the DEVICE backend; for a partly-in-memory or on-disk series load the slices into a host array and " *
+              "call attach_time_series!(ctx, slot, times, host_array; window, time_indexing)")
+    target = series_target(fts)
+    bind!(ctx, slot, target)
+    p = parent(fts.data)
+    ni, nj = size(p, 1), size(p, 2)
+    Hx, Hy, _ = halo_size(fts.grid)
+    times = Float64.(collect(fts.times))
+    kind, period = time_indexing_code(fts.time_indexing)
+    GC.@preserve times begin
+        ts = Ref(CsiTimeSeries(length(times), kind, 0, 0, period, pointer(times), Ptr{Cvoid}(pointer(p) + 8 * (Hx + Hy * ni)),
+                               ni, ni * nj * size(p, 3)))
+        check(ctx, ccall((:csi_time_series_set, libcsi), Int32, (Ptr{Cvoid}, Int32, Ptr{CsiTimeSeries}), ctx.handle, slot, ts))
+    end
+    push!(ctx.series, (fts, target))
+    return target
+end
+
+"""
+    attach_time_series!(ctx, slot, times, host_array; window = 3, time_indexing = Linear(), target)
+
+CSI_SERIES_HOST: `host_array` is an `Array{Float64, 3}` of size (nx, ny, Nt) holding the INTERIOR slices of the slot's field; the library
+keeps `window` of them on the device and uploads ahead of use.  `target` is the Field bound to `slot` (bound here if given).
+"""
+function attach_time_series!(ctx, slot, times, host_array; window = 3, time_indexing = Oceananigans.OutputReaders.Linear(), target = nothing)
+    isnothing(target) || bind!(ctx, slot, target)
+    nx, ny = size(host_array, 1), size(host_array, 2)
+    t = Float64.(collect(times))
+    kind, period = time_indexing_code(time_indexing)
+    GC.@preserve t host_array begin
+        ts = Ref(CsiTimeSeries(length(t), kind, 1, window, period, pointer(t), Ptr{Cvoid}(pointer(host_array)), nx, nx * ny))
+        check(ctx, ccall((:csi_time_series_set, libcsi), Int32, (Ptr{Cvoid}, Int32, Ptr{CsiTimeSeries}), ctx.handle, slot, ts))
+    end
+    push!(ctx.series, (host_array, target))
+    return nothing
+end
+
+# csi_time_series_update at the model clock: the first thing update_state! and the step entries do (nothing is launched without series)
+update_time_series!(ctx, clock) =
+    check(ctx, ccall((:csi_time_series_update, libcsi), Int32, (Ptr{Cvoid}, Cdouble), ctx.handle, Float64(clock.time)))
+
+# (slices the device window of a HOST series holds, -1: none; slice uploads so far) -- for tests and profiles
+function time_series_status(ctx, slot, window)
+    resident = fill(Int32(-1), max(window, 1)); uploads = Ref{Int64}(0)
+    check(ctx, ccall((:csi_time_series_status, libcsi), Int32, (Ptr{Cvoid}, Int32, Ptr{Int32}, Ptr{Int64}), ctx.handle, slot, resident, uploads))
+    return resident[1:window], uploads[]
+end
+
+# a Field is bound as it is, a FieldTimeSeries through the Field it writes into
+bind_forcing!(ctx, slot, f::Field) = bind!(ctx, slot, f)
+bind_forcing!(ctx, slot, f::FieldTimeSeries) = attach_series!(ctx, slot, f)
+const ArrayLike = Union{Field, FieldTimeSeries}
+stress_struct(τ::NamedTuple{(:u, :v), <:Tuple{ArrayLike, ArrayLike}}) = CsiStress(2, 0, 0, 0, 0, 0, 0, 0, 0, 0)
 
 """
     attach!(model) -> Context
@@ -258,18 +343,18 @@ function attach!(model::SeaIceModel)
         s = Ref(stress_struct(τ))
         check(ctx, ccall((:csi_stress_set, libcsi), Int32, (Ptr{Cvoid}, Int32, Ref{CsiStress}), ctx.handle, side, s))
         if τ isa SemiImplicitStress    # field-valued external velocities
-            τ.uₑ isa Field && bind!(ctx, side == 0 ? F.TOP_U : F.BOT_U, τ.uₑ)
-            τ.vₑ isa Field && bind!(ctx, side == 0 ? F.TOP_V : F.BOT_V, τ.vₑ)
-        elseif τ isa NamedTuple && τ.u isa Field      # stress arrays
-            bind!(ctx, side == 0 ? F.TOP_U : F.BOT_U, τ.u)
-            bind!(ctx, side == 0 ? F.TOP_V : F.BOT_V, τ.v)
+            τ.uₑ isa ArrayLike && bind_forcing!(ctx, side == 0 ? F.TOP_U : F.BOT_U, τ.uₑ)
+            τ.vₑ isa ArrayLike && bind_forcing!(ctx, side == 0 ? F.TOP_V : F.BOT_V, τ.vₑ)
+        elseif τ isa NamedTuple && τ.u isa ArrayLike      # stress arrays or series of them
+            bind_forcing!(ctx, side == 0 ? F.TOP_U : F.BOT_U, τ.u)
+            bind_forcing!(ctx, side == 0 ? F.TOP_V : F.BOT_V, τ.v)
         end
     end
     set_free_drift!(ctx, dyn.free_drift)
     # model.forcing.u / .v given as Fields (arrays): the user forcing of sum_of_forcing_u / _v (elasto_visco_plastic_rheology.jl:391-401);
     # closures cannot cross a C ABI and keep the model on the Julia kernels
-    if model.forcing.u isa Field && model.forcing.v isa Field
-        bind!(ctx, F.FORCING_U, model.forcing.u); bind!(ctx, F.FORCING_V, model.forcing.v)
+    if model.forcing.u isa ArrayLike && model.forcing.v isa ArrayLike
+        bind_forcing!(ctx, F.FORCING_U, model.forcing.u); bind_forcing!(ctx, F.FORCING_V, model.forcing.v)
     end
     # immersed FluxBoundaryConditions of u and v with number values (ice_stress_divergence.jl:65-123)
     for (slot, f) in ((F.U, model.velocities.u), (F.V, model.velocities.v))
@@ -399,6 +484,7 @@ const HIPRKSeaIceModel = SeaIceModel{<:Any, <:Any, <:Any, <:HIPMomentumEquation,
 function ClimaSeaIce.SeaIceDynamics.time_step_momentum!(model, dynamics::HIPMomentumEquation, Δt)
     ctx = context(model)
     rk = model.timestepper isa SplitRungeKuttaTimeStepper
+    update_time_series!(ctx, model.clock)
     # GC.@preserve exactly as the reference does around its own loop (:150)
     GC.@preserve model begin
         check(ctx, ccall((:csi_time_step_momentum, libcsi), Int32, (Ptr{Cvoid}, Cdouble, Int32, Int32),
@@ -421,11 +507,11 @@ function attach_free_drift!(model, dynamics::StressBalanceFreeDrift)
         s = Ref(stress_struct(τ))
         check(ctx, ccall((:csi_stress_set, libcsi), Int32, (Ptr{Cvoid}, Int32, Ref{CsiStress}), ctx.handle, side, s))
         if τ isa SemiImplicitStress
-            τ.uₑ isa Field && bind!(ctx, side == 0 ? F.TOP_U : F.BOT_U, τ.uₑ)
-            τ.vₑ isa Field && bind!(ctx, side == 0 ? F.TOP_V : F.BOT_V, τ.vₑ)
-        elseif τ isa NamedTuple && τ.u isa Field
-            bind!(ctx, side == 0 ? F.TOP_U : F.BOT_U, τ.u)
-            bind!(ctx, side == 0 ? F.TOP_V : F.BOT_V, τ.v)
+            τ.uₑ isa ArrayLike && bind_forcing!(ctx, side == 0 ? F.TOP_U : F.BOT_U, τ.uₑ)
+            τ.vₑ isa ArrayLike && bind_forcing!(ctx, side == 0 ? F.TOP_V : F.BOT_V, τ.vₑ)
+        elseif τ isa NamedTuple && τ.u isa ArrayLike
+            bind_forcing!(ctx, side == 0 ? F.TOP_U : F.BOT_U, τ.u)
+            bind_forcing!(ctx, side == 0 ? F.TOP_V : F.BOT_V, τ.v)
         end
     end
     arch = architecture(grid)
@@ -436,6 +522,7 @@ end
 
 function ClimaSeaIce.SeaIceDynamics.time_step_momentum!(model, dynamics::StressBalanceFreeDrift, Δt)
     ctx = get!(() -> attach_free_drift!(model, dynamics), CONTEXTS, model)
+    update_time_series!(ctx, model.clock)
     GC.@preserve model begin
         check(ctx, ccall((:csi_time_step_momentum, libcsi), Int32, (Ptr{Cvoid}, Cdouble, Int32, Int32), ctx.handle, Δt, 0, 0))
     end
@@ -469,6 +556,7 @@ end
 # compute_momentum_tendencies!, explicit_momentum_equations.jl:85-113 (called by compute_tendencies! before the momentum step)
 function ClimaSeaIce.SeaIceDynamics.compute_momentum_tendencies!(model, dynamics::HIPExplicitMomentumEquation, Δt)
     ctx = context(model)
+    update_time_series!(ctx, model.clock)
     check(ctx, ccall((:csi_compute_momentum_tendencies, libcsi), Int32, (Ptr{Cvoid}, Cdouble), ctx.handle, Δt))
     return nothing
 end
@@ -477,6 +565,7 @@ end
 function ClimaSeaIce.SeaIceDynamics.time_step_momentum!(model, dynamics::HIPExplicitMomentumEquation, Δt)
     ctx = context(model)
     rk = model.timestepper isa SplitRungeKuttaTimeStepper
+    update_time_series!(ctx, model.clock)
     check(ctx, ccall((:csi_time_step_momentum, libcsi), Int32, (Ptr{Cvoid}, Cdouble, Int32, Int32), ctx.handle, Δt, 0, rk ? 1 : 0))
     return nothing
 end
@@ -525,6 +614,7 @@ ClimaSeaIce.dynamic_time_step!(model::HIPRKSeaIceModel, Δt) = hip_dynamic_time_
 # halo width -- the hand-off Oceananigans' MPI halo pass would do.
 function Oceananigans.TimeSteppers.update_state!(model::HIPSeaIceModel, callbacks = [])
     ctx = context(model)
+    update_time_series!(ctx, model.clock)      # the series the library drives (the rest: update_model_field_time_series! below)
     GC.@preserve model check(ctx, ccall((:csi_update_state, libcsi), Int32, (Ptr{Cvoid},), ctx.handle))
     # No host synchronisation here (round 5; the round-4 stub drained the stream after every RK stage on Distributed grids, which
     # cost the host / device overlap of a whole stage and still proved nothing about ranks that are not direct neighbours: a
