@@ -47,7 +47,7 @@ SYMBOLS = ["csi_version", "csi_context_create", "csi_context_destroy", "csi_last
            "csi_compute_tracer_tendencies", "csi_dynamic_step_tracers", "csi_cache_current_fields",
            "csi_update_state", "csi_fill_halo_local", "csi_time_step_fe", "csi_time_step_rk3",
            "csi_slab_thermo_step", "csi_slab_params_set", "csi_layered_thermo_step", "csi_snow_params_set", "csi_tile_set", "csi_comm_unique_id", "csi_comm_init", "csi_comm_count", "csi_local_group_create", "csi_local_group_destroy", "csi_comm_init_local", "csi_comm_init_host", "csi_halo_exchange",
-           "csi_plan_exchange", "csi_set_fusion", "csi_set_exchange_interval", "csi_set_halo_transport", "csi_halo_transport", "csi_set_peer_tier", "csi_peer_tier", "csi_plan_ranges", "csi_profile_substeps", "csi_last_path", "csi_last_subcycle_ms", "csi_launches_per_substep", "csi_last_launches", "csi_plan_pair", "csi_plan_peer_chunks", "csi_free_drift_set", "csi_coriolis_rows_set", "csi_velocity_bc_set",
+           "csi_plan_exchange", "csi_set_fusion", "csi_set_exchange_interval", "csi_set_halo_transport", "csi_halo_transport", "csi_set_peer_tier", "csi_peer_tier", "csi_plan_ranges", "csi_profile_substeps", "csi_last_path", "csi_last_advection", "csi_last_subcycle_ms", "csi_launches_per_substep", "csi_last_launches", "csi_plan_pair", "csi_plan_peer_chunks", "csi_free_drift_set", "csi_coriolis_rows_set", "csi_velocity_bc_set",
            "csi_immersed_flux_bc_set", "csi_coriolis_points_set", "csi_validate_all", "csi_debug_peer_abort", "csi_set_weno_weight_dtype", "csi_weno_weight_dtype", "csi_subcycle_stats_begin", "csi_subcycle_stats_end",
            "csi_set_tile_skipping", "csi_tile_activity", "csi_set_row_constant", "csi_row_constant_rows",
            "csi_rheology_set", "csi_momentum_solver_set", "csi_compute_momentum_tendencies",
@@ -170,6 +170,7 @@ def load():
         "csi_plan_exchange": [i32] * 14 + [C.POINTER(i32)],
         "csi_profile_substeps": [vp, dbl, i32, C.POINTER(dbl)],
         "csi_last_path": [vp, C.POINTER(i32), C.POINTER(i32), C.POINTER(i32)],
+        "csi_last_advection": [vp, C.POINTER(i32), C.POINTER(i32), C.POINTER(i32), C.POINTER(i32)],
         "csi_last_subcycle_ms": [vp, C.POINTER(dbl)], "csi_launches_per_substep": [vp, C.POINTER(i32)],
         "csi_last_launches": [vp, C.POINTER(i32), C.POINTER(i32)],
         "csi_validate_all": [vp], "csi_debug_peer_abort": [vp], "csi_set_weno_weight_dtype": [vp, i32], "csi_weno_weight_dtype": [vp, C.POINTER(i32)], "csi_subcycle_stats_begin": [vp],
@@ -327,6 +328,12 @@ class Context:
         f, k, n = C.c_int32(), C.c_int32(), C.c_int32()
         self.call("csi_last_path", C.byref(f), C.byref(k), C.byref(n))
         return dict(fused=bool(f.value), level=f.value, exchange_interval=k.value, exchanges=n.value)
+
+    def last_advection(self):
+        """csi_last_advection: the layout of the last advection launch (all zero before the first one)."""
+        nt, tx, ty, st = C.c_int32(), C.c_int32(), C.c_int32(), C.c_int32()
+        self.call("csi_last_advection", C.byref(nt), C.byref(tx), C.byref(ty), C.byref(st))
+        return dict(tracers_per_thread=nt.value, tile_x=tx.value, tile_y=ty.value, stage_fused=st.value)
 
     def comm_count(self):
         """ranks of the RCCL communicator (ncclCommCount); 0 without one"""

@@ -521,11 +521,12 @@ static bool adv_two_tracers(const AdvDev& A) {
 // monotonic in anything simple (wave quantisation of the block, blocks per CU, redundant face rows), so: the best measured shape per size
 enum { SHAPE_64x8 = 0, SHAPE_63x7 = 1, SHAPE_63x11 = 2 };
 static int adv_shape(const AdvDev& A) {
+    if (A.shape > 0) return A.shape - 1;         // tuning aid / tests (CSI_ADV_SHAPE, read when the context is created)
     const long cells = (long)A.g.Nx * (long)A.g.Ny;
     return cells < 600000L ? SHAPE_64x8 : (cells < 2500000L ? SHAPE_63x7 : SHAPE_63x11);
 }
 template <bool FAST, bool W32>
-static void launch_tendencies_mode(const AdvDev& A, hipStream_t s) {
+static AdvLayout launch_tendencies_mode(const AdvDev& A, hipStream_t s) {
     const bool two = adv_two_tracers(A);
     const int shape = adv_shape(A);
     const int tx = two ? (shape == SHAPE_64x8 ? 64 : 63) : adv::TX;
@@ -546,14 +547,15 @@ static void launch_tendencies_mode(const AdvDev& A, hipStream_t s) {
         default: CSI_ADV_LAUNCH(7, W32); break;
     }
 #undef CSI_ADV_LAUNCH
+    return AdvLayout{two ? 2 : 1, tx, ty};
 }
 // mode: CSI_MODE_STRICT (0) the oracle's arithmetic, bit for bit; CSI_MODE_FAST (1) reciprocals and contraction (header)
-void launch_tracer_tendencies(const AdvDev& A, int mode, hipStream_t s) {
-    if (A.w32) { if (mode == 1) launch_tendencies_mode<true, true>(A, s); else launch_tendencies_mode<false, true>(A, s); }
-    else { if (mode == 1) launch_tendencies_mode<true, false>(A, s); else launch_tendencies_mode<false, false>(A, s); }
+AdvLayout launch_tracer_tendencies(const AdvDev& A, int mode, hipStream_t s) {
+    if (A.w32) return mode == 1 ? launch_tendencies_mode<true, true>(A, s) : launch_tendencies_mode<false, true>(A, s);
+    return mode == 1 ? launch_tendencies_mode<true, false>(A, s) : launch_tendencies_mode<false, false>(A, s);
 }
 template <bool FAST, bool W32>
-static void launch_stage_mode(const AdvDev& A, hipStream_t s) {
+static AdvLayout launch_stage_mode(const AdvDev& A, hipStream_t s) {
     const bool two = adv_two_tracers(A);
     const int shape = adv_shape(A);
     const int tx = two ? (shape == SHAPE_64x8 ? 64 : 63) : adv::TX;
@@ -573,11 +575,12 @@ static void launch_stage_mode(const AdvDev& A, hipStream_t s) {
         default: CSI_ADV_STAGE(7, W32); break;
     }
 #undef CSI_ADV_STAGE
+    return AdvLayout{two ? 2 : 1, tx, ty};
 }
 // one RK stage of an advection-only model without snow: tendencies of (A.h, A.a), update A.hb + dt G -> A.ho (A.ab, A.ao)
-void launch_advect_stage(const AdvDev& A, int mode, hipStream_t s) {
-    if (A.w32) { if (mode == 1) launch_stage_mode<true, true>(A, s); else launch_stage_mode<false, true>(A, s); }
-    else { if (mode == 1) launch_stage_mode<true, false>(A, s); else launch_stage_mode<false, false>(A, s); }
+AdvLayout launch_advect_stage(const AdvDev& A, int mode, hipStream_t s) {
+    if (A.w32) return mode == 1 ? launch_stage_mode<true, true>(A, s) : launch_stage_mode<false, true>(A, s);
+    return mode == 1 ? launch_stage_mode<true, false>(A, s) : launch_stage_mode<false, false>(A, s);
 }
 void launch_tracer_step(const AdvDev& A, hipStream_t s) {
     dim3 b(64, 4);

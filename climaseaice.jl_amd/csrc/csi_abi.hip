@@ -116,6 +116,14 @@ int32_t csi_context_create(int32_t device_id, void* hip_stream, csi_context** ou
         return fail(nullptr, CSI_ERR_NO_DEVICE, "no HIP device visible (libcsi_hip has no CPU fallback)");
     if (device_id < 0 || device_id >= n) return fail(nullptr, CSI_ERR_INVALID_ARGUMENT, "device_id out of range");
     HIP_TRY(nullptr, hipSetDevice(device_id));
+    int adv_shape = -1;
+    if (const char* e = getenv("CSI_ADV_SHAPE"); e && *e) {
+        char* end = nullptr;
+        const long v = strtol(e, &end, 10);
+        if (*end || v < 0 || v > 3)
+            return fail(nullptr, CSI_ERR_INVALID_ARGUMENT, std::string("CSI_ADV_SHAPE=") + e + ": 0 (by grid size), 1 (64 x 8), 2 (63 x 7) or 3 (63 x 11)");
+        adv_shape = (int)v;
+    }
     csi_context* c = new csi_context();
     c->device = device_id;
     if (hip_stream) {
@@ -137,6 +145,7 @@ int32_t csi_context_create(int32_t device_id, void* hip_stream, csi_context** ou
         c->tune.peer_edge = env_int("CSI_PEER_EDGE");          // rows the chunks next to a peer-connected y side are shorter by (default 4; 0: uniform chunks)
         c->tune.write_through = env_int("CSI_WRITE_THROUGH");  // 0 / 1: never / always store the pair kernel's results write-through (default: by grid size)
         c->tune.adv_nt = env_int("CSI_ADV_NT"); c->tune.pair_target = env_int("CSI_PAIR_TARGET");
+        c->tune.adv_shape = adv_shape;                         // block shape of the advection kernel's two-tracer layout (checked above)
         { const char* e = getenv("CSI_ADV_STAGE_MAX_CELLS"); if (e && *e) c->tune.adv_stage_max_cells = atol(e); }      // A/B: largest grid that takes one launch per RK stage
         { const int v = env_int("CSI_ROW_TARGET_1024"); if (v >= 0) c->tune.row_target_1024 = v; }      // 0: per-row coefficients keep 1536 tiles (rounds 3-5a)
         { const int v = env_int("CSI_TILE_SKIPPING"); if (v >= 0) c->act.enabled = v != 0; }      // A/B: the defaults of csi_set_tile_skipping / csi_set_row_constant
@@ -618,7 +627,8 @@ int32_t rk3_advection_only(csi_context* c, double dt, int scheme) {
         A.ho = hout[stage]; A.ao = aout[stage];
         A.write_cache = stage == 0;
         A.fill_images = 1;
-        launch_advect_stage(A, c->mode, c->stream);
+        c->last_adv = launch_advect_stage(A, c->mode, c->stream);
+        c->last_adv_stage = 1;
         HIP_TRY(c, hipGetLastError());
     }
     return CSI_OK;
@@ -1027,6 +1037,15 @@ int32_t csi_last_path(csi_context* c, int32_t* fused, int32_t* exchange_interval
     if (fused) *fused = c->last_fused;
     if (exchange_interval) *exchange_interval = c->last_k;
     if (exchanges) *exchanges = c->last_exchanges;
+    return CSI_OK;
+}
+
+int32_t csi_last_advection(csi_context* c, int32_t* tracers_per_thread, int32_t* tile_x, int32_t* tile_y, int32_t* stage_fused) {
+    if (!c) return CSI_ERR_INVALID_ARGUMENT;
+    if (tracers_per_thread) *tracers_per_thread = c->last_adv.nt;
+    if (tile_x) *tile_x = c->last_adv.tx;
+    if (tile_y) *tile_y = c->last_adv.ty;
+    if (stage_fused) *stage_fused = c->last_adv_stage;
     return CSI_OK;
 }
 

@@ -256,6 +256,8 @@ struct csi_context {
     int pairing = 1;      // 1: two sub-steps per launch where supported (csi_set_fusion level 2)
     int last_launches = 0, last_substeps = 0, last_used_pairs = 0;   // kernel launches / sub-steps of the last fused sub-cycle
     int last_fused = 0;
+    AdvLayout last_adv{0, 0, 0};     // csi_last_advection: what the last tendency / stage launch of k_tendencies used (0: none yet)
+    int last_adv_stage = 0;          // ... and whether it was a whole RK stage in one launch
     double ibc[2][4] = {{0, 0, 0, 0}, {0, 0, 0, 0}};   // csi_immersed_flux_bc_set: [u | v][west, east, south, north]
     int exch_k = 0;       // sub-steps per halo exchange (0 = auto: the largest k with 2k <= halo, at most 4)
     // Tile activity (csi_activity.hip, run_fused): the live-tile list of the current sub-cycle and, read back asynchronously, how many
@@ -290,6 +292,7 @@ struct csi_context {
     // tuning aids (A/B runs), read from the environment ONCE, when the context is created; -1 = not set
     struct Tuning { int fused_rows = -1, pair_tiles = -1, pair_target = -1, row_target_1024 = 0, pair_minrows = -1, pair_rows = -1, pair_common = -1, peer_kernel = -1, peer_edge = -1, write_through = -1,
                     adv_nt = -1,           // CSI_ADV_NT: tracers per thread of the advection tendency kernel (1 / 2; default by grid size)
+                    adv_shape = -1,        // CSI_ADV_SHAPE: block shape where two tracers share a thread (1 / 2 / 3: 64 x 8 / 63 x 7 / 63 x 11; default by grid size)
                     band_fused = -1,      // CSI_BAND_FUSED=0: the fold band on the three kernels + two copies per step (rounds 4-6a); default: six launches per step without copies, loads hoisted (csi_fold.hip band_substeps_fused)
                     band_event_flags = -1,   // CSI_BAND_EVENT_FLAGS (csi_fold.hip ensure_band)
                     no_geom_sig = -1;      // debugging aid (CSI_DEBUG_NO_GEOM_SIG=1): skip the launch-geometry check of the peer set-up (tests/test_gpu_local_tiles.py)

@@ -174,10 +174,13 @@ struct AdvDev {
     int write_cache;        // first stage: also store the base values into hm, am (cache_current_fields!, with halo images)
     int nt;                 // tracers per thread of the tendency kernel: 0 by grid size, 1 / 2 forced (CSI_ADV_NT)
     int w32;                // WENO schemes: smoothness indicators / weights in single precision (csi_set_weno_weight_dtype; advect.hip)
+    int shape;              // block shape of the two-tracers-per-thread layout: 0 by grid size, 1 / 2 / 3 forced to 64 x 8 / 63 x 7 / 63 x 11 (CSI_ADV_SHAPE)
 };
-void launch_tracer_tendencies(const AdvDev& A, int mode, hipStream_t s);
+// what a tendency / stage launch used: tracers per thread and the cells of a flux tile (csi_last_advection)
+struct AdvLayout { int nt, tx, ty; };
+AdvLayout launch_tracer_tendencies(const AdvDev& A, int mode, hipStream_t s);
 void launch_tracer_step(const AdvDev& A, hipStream_t s);
-void launch_advect_stage(const AdvDev& A, int mode, hipStream_t s);
+AdvLayout launch_advect_stage(const AdvDev& A, int mode, hipStream_t s);
 
 // slab thermodynamics (thermo.hip)
 struct SlabDev {

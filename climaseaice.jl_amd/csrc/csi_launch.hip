@@ -589,6 +589,7 @@ AdvDev adv_dev(const csi_context* c, int scheme, double dt, int from_cache) {
     A.scheme = scheme; A.dt = dt; A.from_cache = from_cache;
     A.w32 = c->weno_w32;
     A.nt = c->tune.adv_nt > 0 ? c->tune.adv_nt : 0;
+    A.shape = c->tune.adv_shape > 0 ? c->tune.adv_shape : 0;
     A.fill_images = 0; A.im = image_spec(c, CSI_F_H);
     return A;
 }
@@ -637,7 +638,8 @@ int32_t do_tendencies(csi_context* c, int scheme) {
     if (scheme != CSI_ADVECT_UPWIND1 && scheme != CSI_ADVECT_WENO5 && scheme != CSI_ADVECT_WENO7 && scheme != CSI_ADVECT_UPWIND5 && !third)
         return fail(c, CSI_ERR_INVALID_ARGUMENT, "unknown advection scheme");
     if (c->Hx < need_h || c->Hy < need_h) return fail(c, CSI_ERR_INVALID_ARGUMENT, "halo too small for the advection scheme");
-    launch_tracer_tendencies(adv_dev(c, scheme, 0.0, 0), c->mode, c->stream);
+    c->last_adv = launch_tracer_tendencies(adv_dev(c, scheme, 0.0, 0), c->mode, c->stream);
+    c->last_adv_stage = 0;
     HIP_TRY(c, hipGetLastError());
     return CSI_OK;
 }

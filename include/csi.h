@@ -737,6 +737,11 @@ int32_t csi_profile_substeps(csi_context* ctx, double dt, int32_t substeps, doub
 /* Which path the last sub-cycle took: three kernels (0), fused kernel (1), fused pairs of sub-steps (2); the
  * halo-exchange interval k and the number of exchanges issued.  Any pointer may be NULL. */
 int32_t csi_last_path(csi_context* ctx, int32_t* fused, int32_t* exchange_interval, int32_t* exchanges);
+/* The layout of the last advection launch (csi_compute_tracer_tendencies, a time step with advection): tracers per thread (1 / 2),
+ * the cells of a flux tile in x and y -- the block has one more thread each way, for the tile's east / north faces --, and whether
+ * the launch was a whole RK stage of an advection-only model (tendencies + tracer update, 1) or the tendencies alone (0).  What the
+ * launch code used, recorded when it launched; all zero before the first one.  Any pointer may be NULL. */
+int32_t csi_last_advection(csi_context* ctx, int32_t* tracers_per_thread, int32_t* tile_x, int32_t* tile_y, int32_t* stage_fused);
 /* Kernel launches and sub-steps of the last fused sub-cycle (sub-steps / launches = sub-steps per launch). */
 int32_t csi_last_launches(csi_context* ctx, int32_t* launches, int32_t* substeps);
 /* Number of kernel launches issued for one sub-step in the current configuration (upper bound). */

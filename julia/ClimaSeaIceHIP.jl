@@ -420,6 +420,13 @@ function tile_activity(ctx)
     check(ctx, ccall((:csi_tile_activity, libcsi), Int32, (Ptr{Cvoid}, Ref{Int32}, Ref{Int32}, Ref{Int32}), ctx.handle, t, l, u))
     return (tiles = t[], live = l[], used = u[] != 0)
 end
+# The layout of the last advection launch (include/csi.h: csi_last_advection): tracers per thread, the cells of a flux tile, and
+# whether the launch was a whole RK stage of an advection-only model
+function last_advection(ctx)
+    nt, tx, ty, st = Ref{Int32}(0), Ref{Int32}(0), Ref{Int32}(0), Ref{Int32}(0)
+    check(ctx, ccall((:csi_last_advection, libcsi), Int32, (Ptr{Cvoid}, Ref{Int32}, Ref{Int32}, Ref{Int32}, Ref{Int32}), ctx.handle, nt, tx, ty, st))
+    return (tracers_per_thread = Int(nt[]), tile_x = Int(tx[]), tile_y = Int(ty[]), stage_fused = st[] != 0)
+end
 set_row_constant!(ctx, on::Bool, rtol::Real = 0.0) =
     check(ctx, ccall((:csi_set_row_constant, libcsi), Int32, (Ptr{Cvoid}, Int32, Cdouble), ctx.handle, on ? 1 : 0, rtol))
 function row_constant_rows(ctx)
