@@ -52,7 +52,9 @@ SYMBOLS = ["csi_version", "csi_context_create", "csi_context_destroy", "csi_last
            "csi_set_tile_skipping", "csi_tile_activity", "csi_set_row_constant", "csi_row_constant_rows",
            "csi_rheology_set", "csi_momentum_solver_set", "csi_compute_momentum_tendencies",
            "csi_heat_fluxes_set", "csi_surface_solve_set", "csi_dynamics_set",
-           "csi_time_series_plan", "csi_time_series_set", "csi_time_series_update", "csi_time_series_status"]
+           "csi_time_series_plan", "csi_time_series_set", "csi_time_series_update", "csi_time_series_status",
+           "csi_diagnostics_compute"]
+DIAG_VELOCITY, DIAG_TRACERS, DIAG_ALL = 1, 2, 3
 
 
 class Metrics(C.Structure):
@@ -106,6 +108,17 @@ class SurfaceSolve(C.Structure):
 class TimeSeries(C.Structure):
     _fields_ = [("nt", C.c_int32), ("indexing", C.c_int32), ("backend", C.c_int32), ("window", C.c_int32), ("period", C.c_double),
                 ("times", C.POINTER(C.c_double)), ("data", C.c_void_p), ("ld", C.c_int64), ("slice_stride", C.c_int64)]
+
+
+class Diagnostics(C.Structure):
+    """csi_diagnostics (include/csi.h): "not computed" members hold NaN (doubles) / -1 (counts)."""
+    _fields_ = ([("what", C.c_int32), ("has_snow", C.c_int32)] +
+                [(n, C.c_double) for n in ("advection_timescale", "inv_timescale_max", "max_abs_u", "max_abs_v")] +
+                [(n, C.c_int64) for n in ("nonfinite_u", "nonfinite_v", "nan_u", "nan_v")] +
+                [(n, C.c_double) for n in ("ice_volume", "ice_area", "ice_extent", "snow_volume", "active_area",
+                                           "min_h", "max_h", "min_aice", "max_aice", "max_hs")] +
+                [(n, C.c_int64) for n in ("nonfinite_h", "nonfinite_aice", "nonfinite_hs", "active_cells")] +
+                [("extent_threshold", C.c_double)])
 
 
 class CsiError(RuntimeError):
@@ -181,6 +194,7 @@ def load():
         "csi_time_series_plan": [C.POINTER(dbl), i32, i32, dbl, dbl, C.POINTER(i32), C.POINTER(i32), C.POINTER(dbl)],
         "csi_time_series_set": [vp, i32, C.POINTER(TimeSeries)], "csi_time_series_update": [vp, dbl],
         "csi_time_series_status": [vp, i32, C.POINTER(i32), C.POINTER(i64)],
+        "csi_diagnostics_compute": [vp, i32, dbl, C.POINTER(Diagnostics)],
     }
     for name, args in sig.items():
         fn = getattr(L, name, None)
@@ -363,6 +377,13 @@ class Context:
         v = C.c_int32()
         self.call("csi_launches_per_substep", C.byref(v))
         return v.value
+
+    def diagnostics_compute(self, what, extent_threshold):
+        """csi_diagnostics_compute: the filled csi_diagnostics (two launches and one small copy; waits for the context's stream;
+        collective on a tiled context)."""
+        d = Diagnostics()
+        self.call("csi_diagnostics_compute", int(what), float(extent_threshold), C.byref(d))
+        return d
 
     def time_series_update(self, time):
         """csi_time_series_update: every series-driven slot interpolated at `time`, one launch (none without series)."""

@@ -6,6 +6,7 @@
 //   csi_launch.hip  launch loops: sub-cycle, finalize, time_step_momentum!, tracer steps, update_state!, csi_profile_substeps
 //   csi_abi.hip     the C ABI (include/csi.h)
 //   csi_time_series.hip   forcing time series: time indexing, the device ring of a host-resident series, the interpolation launch
+//   csi_diagnostics.hip   device diagnostics: the two launches, the result copy, the combine over the ranks of a decomposition
 //   csi_mem.h       DeviceBuf / PinnedBuf: the owner of every allocation the library makes
 #pragma once
 #include "../../include/csi.h"
@@ -244,6 +245,11 @@ struct csi_context {
     bool series_launched_valid = false;
     bool series_prefetch_pending = false;    // the newest update's look-ahead uploads have not been issued yet
     long series_updates = 0;
+    // csi_diagnostics_compute (csi_diagnostics.hip): the partial records followed by the DQ_COUNT result slots (sized at first use, for
+    // the grid), the page-locked copy of the result, and the device staging of an all-gather over an RCCL communicator (only grows)
+    DeviceBuf<double> diag_part;
+    PinnedBuf<double> diag_host;
+    DeviceBuf<uint8_t> gather_buf;
     int weno_w32 = 0;     // csi_set_weno_weight_dtype: 1 = WENO weights in single precision (upstream's FT2 = Float32, recalled)
     // csi_rheology_set / csi_momentum_solver_set (csi_momentum.hip): ViscousRheology, ExplicitSolver
     int rheology = CSI_RHEOLOGY_EVP;
@@ -405,6 +411,8 @@ bool is_tiled(const csi_context* c);
 int32_t exchange(csi_context* c, const int* fids, int nf, int W);
 int32_t local_allgather(csi_context* c, const void* mine, size_t nb, std::vector<uint8_t>& out);
 int32_t local_allreduce_min(csi_context* c, int* v);
+// rank r's `nb` bytes end up in out[r * nb ...] on every rank, over whatever joins the ranks; no communicator: out = mine
+int32_t comm_allgather(csi_context* c, const void* mine, size_t nb, std::vector<uint8_t>& out);
 int32_t comm_allreduce_max(csi_context* c, int* v);      // over whatever joins the ranks (RCCL communicator, in-process group, host-channel group)
 int peer_effective_tier(const csi_context* c);
 int32_t local_wait_consumed(csi_context* c);

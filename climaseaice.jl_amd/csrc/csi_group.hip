@@ -52,6 +52,34 @@ int32_t local_allreduce_min(csi_context* c, int* v) {
     for (int r = 0; r < c->world; ++r) { int x; memcpy(&x, all.data() + (size_t)r * sizeof(int), sizeof(int)); if (x < *v) *v = x; }
     return CSI_OK;
 }
+// All-gather of `nb` bytes per rank over whatever joins the ranks -- the in-process group, the host-channel group or the RCCL
+// communicator, also one of a single rank (no communicator: out = mine).  Host-synchronous; on the RCCL path the bytes are staged through a
+// context-owned device buffer on the context's stream.  Collective: every rank calls it, also one that has failed locally.
+int32_t comm_allgather(csi_context* c, const void* mine, size_t nb, std::vector<uint8_t>& out) {
+    if (!has_comm(c)) {
+        out.assign((const uint8_t*)mine, (const uint8_t*)mine + nb);
+        return CSI_OK;
+    }
+    if (c->local) return local_allgather(c, mine, nb, out);
+    if (c->hostg) return hostgroup_allgather(c->hostg, mine, nb, out, &c->err) ? CSI_OK : CSI_ERR_COMM;
+    const size_t total = nb * (size_t)(c->world + 1);
+    if (c->gather_buf.size() < total) {
+        HIP_TRY(c, hipStreamSynchronize(c->stream));
+        HIP_TRY(c, c->gather_buf.alloc(total));
+    }
+    uint8_t* buf = c->gather_buf.get();
+    // (a local copy that fails must not keep this rank out of the collective: it takes part and reports afterwards)
+    hipError_t e = hipMemcpyAsync(buf, mine, nb, hipMemcpyHostToDevice, c->stream);
+    if (e == hipSuccess) e = hipStreamSynchronize(c->stream);      // (`mine` may be pageable: the copy has left it)
+    const ncclResult_t r = ncclAllGather(buf, buf + nb, nb, ncclUint8, c->comm, c->stream);
+    if (r != ncclSuccess) return fail(c, CSI_ERR_COMM, std::string("ncclAllGather: ") + ncclGetErrorString(r));
+    out.resize(nb * (size_t)c->world);
+    if (e == hipSuccess) e = hipMemcpyAsync(out.data(), buf + nb, nb * (size_t)c->world, hipMemcpyDeviceToHost, c->stream);
+    const hipError_t e2 = hipStreamSynchronize(c->stream);
+    if (e == hipSuccess) e = e2;
+    if (e != hipSuccess) return fail(c, CSI_ERR_HIP, std::string("all-gather staging: ") + hipGetErrorString(e));
+    return CSI_OK;
+}
 // max of one int over all ranks of whatever joins them: the in-process group, the host-channel group or the RCCL communicator
 // (one rank: nothing to do).  Host-synchronous on the RCCL path (a 4-byte all-reduce on the context's stream).
 int32_t comm_allreduce_max(csi_context* c, int* v) {

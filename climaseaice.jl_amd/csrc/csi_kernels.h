@@ -239,4 +239,25 @@ struct SeriesDesc {
 struct SeriesTable { int n; int pad_; SeriesDesc d[kMaxSeries]; };
 void launch_time_series(const SeriesTable& T, hipStream_t s);
 
+// device diagnostics (diagnostics.hip; include/csi.h csi_diagnostics_compute).  One 8-byte slot per quantity, in this order, in every
+// partial record and in the result; the counts are int64 bit patterns in their slots.  Slots below DQ_VOLUME: CSI_DIAG_VELOCITY,
+// from DQ_VOLUME on: CSI_DIAG_TRACERS.
+enum : int { DQ_INV_TIMESCALE = 0, DQ_MAX_ABS_U, DQ_MAX_ABS_V, DQ_NONFINITE_U, DQ_NONFINITE_V, DQ_NAN_U, DQ_NAN_V,
+             DQ_VOLUME, DQ_AREA, DQ_EXTENT, DQ_SNOW_VOLUME, DQ_ACTIVE_AREA, DQ_MIN_H, DQ_MAX_H, DQ_MIN_AICE, DQ_MAX_AICE, DQ_MAX_HS,
+             DQ_NONFINITE_H, DQ_NONFINITE_AICE, DQ_NONFINITE_HS, DQ_ACTIVE_CELLS, DQ_COUNT };
+struct DiagDev {
+    GridDev g;
+    FRef u, v, h, a, hs;       // (a group that is not requested: unused)
+    int exu, eyv;              // 1: u has the faces i = Nx + 1 / v the faces j = Ny + 1 (Bounded direction; a tile: its east / north wall)
+    int has_hs;
+    int pad_;
+    double threshold;          // ice_extent counts cells with aice >= threshold
+    double* part;              // partial records, one slot after the other: slot q of record r at part[q * nrec + r]
+    long nrec;                 // records = blocks of the first launch (diag_geometry)
+};
+// blocks of 64 x 64 cells over i = 1 .. Nx, j = 1 .. Ny: a function of (Nx, Ny) alone -- the summation order depends on nothing else
+void diag_geometry(int Nx, int Ny, int* nbx, int* nby);
+// the two launches: partial records into D.part, the folded result into out[DQ_COUNT] (device memory; only the requested groups' slots are written)
+void launch_diagnostics(const DiagDev& D, bool vel, bool trc, double* out, hipStream_t s);
+
 }  // namespace csi

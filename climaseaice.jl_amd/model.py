@@ -787,6 +787,13 @@ class SeaIceModel:
     def scheme(self):
         return 0 if self.advection is None else self.advection.scheme
 
+    def diagnostics(self, what="all", extent_threshold=0.15):
+        """Advection timescale, max|u|, max|v|, area-weighted volume / area / extent sums, extrema and non-finite counts computed on
+        the device (diagnostics.py, include/csi.h csi_diagnostics_compute): what = "all", "velocity" or "tracers".  Waits for the
+        library's stream; collective on a tiled model.  Returns an immutable Diagnostics record."""
+        from .diagnostics import diagnostics
+        return diagnostics(self, what, extent_threshold)
+
     def synchronize(self):
         """Wait for the library's stream (call before reading fields with torch / numpy)."""
         self.ctx.call("csi_sync")

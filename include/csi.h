@@ -561,6 +561,74 @@ int32_t csi_time_series_update(csi_context* ctx, double time);
  * slice uploads since csi_time_series_set.  Either pointer may be NULL. */
 int32_t csi_time_series_status(csi_context* ctx, int32_t field_id, int32_t* resident, int64_t* uploads);
 
+/* ---- device diagnostics: advection timescale, integrals, extrema, finite check ------------------------------------------------------
+ * Scalars computed from the bound fields ON THE DEVICE, in two launches on the context's stream (a pass over the interior that
+ * leaves one partial record per block of 64 x 64 cells, and one block that folds the records), followed by a copy of the 21 result
+ * slots to page-locked host memory and a wait for the stream: no field crosses the bus.  Stands where the reference's root module has
+ * cell_advection_timescale(model::SeaIceModel) (src/ClimaSeaIce.jl:63-69) and where its tests and validation scripts reduce fields on
+ * the host (maximum(u), volume closure, progress lines).  No atomics, no flags, no hand-off between workgroups inside a launch: the
+ * results -- the sums included -- are the same bits from call to call, in STRICT and in FAST mode (one code, compiled without
+ * contraction), on every device.
+ *
+ * `what` is a mask of the groups below; only the arrays of a requested group are read, and each of them once, at i = 1 .. Nx,
+ * j = 1 .. Ny (halo elements are never read, so whatever they hold -- NaN, stale images -- changes nothing).
+ *
+ * CSI_DIAG_VELOCITY (needs CSI_F_U, CSI_F_V; 16 B per cell):
+ *   inv_timescale_max   max over i = 1 .. Nx, j = 1 .. Ny of (|u[i, j]| / dx^fc(i, j)) + (|v[i, j]| / dy^cf(i, j)): Oceananigans'
+ *                       cell_advection_timescale^ccc with w = ZeroField, before its reciprocal.  STATUS: the formula is RECALLED --
+ *                       Oceananigans is not vendored; this statement is the definition.
+ *   advection_timescale 1 / inv_timescale_max, one division on the host: equal to the minimum over the cells of the per-cell
+ *                       reciprocals (IEEE division is monotone); +Inf for ice at rest; 0 when a velocity of some cell is infinite; NaN
+ *                       if and only if nan_u + nan_v > 0, as Julia's `minimum` propagates NaN (the device maxima themselves skip NaN).
+ *   max_abs_u, max_abs_v  over each field's OWN interior: a Bounded x direction has Nx + 1 u faces, a Bounded y direction Ny + 1 v
+ *                       faces.  (Those last faces enter the maxima and the counts; they belong to no cell's timescale.)
+ *   nonfinite_u, nonfinite_v   elements of that interior that are NaN or +-Inf;  nan_u, nan_v: those that are NaN.
+ * CSI_DIAG_TRACERS (needs CSI_F_H, CSI_F_A; reads CSI_F_HS if bound and the mask if set):
+ *   over ACTIVE cells (every interior cell without a mask; mask byte != 0 with one):
+ *   ice_volume = sum (h * aice) * Az     ice_area = sum aice * Az     ice_extent = sum Az over cells with aice >= extent_threshold
+ *   snow_volume = sum (hs * aice) * Az   active_area = sum Az         (Az = Az^cc; products in the order written, uncontracted)
+ *   min_h, max_h, min_aice, max_aice, max_hs   (no active cell: +Inf for a minimum, -Inf for a maximum; NaN elements are skipped;
+ *                                               -0.0 and +0.0 compare equal and either may be returned when both occur)
+ *   active_cells        their number
+ *   over ALL interior cells, land included:  nonfinite_h, nonfinite_aice, nonfinite_hs.
+ * Members of a group that was not requested -- and snow_volume, max_hs, nonfinite_hs without a bound CSI_F_HS (has_snow = 0) -- hold
+ * the "not computed" values: NaN for a double, -1 for a count.
+ *
+ * SUMMATION ORDER (part of the interface; a function of (Nx, Ny) alone).  Blocks: nbx = ceil(Nx / 64), nby = ceil(Ny / 64); block
+ * (bx, by) owns columns 64 bx + 1 .. 64 bx + 64 and rows 64 by + 1 .. 64 by + 64; a cell beyond Nx or Ny, and an inactive cell,
+ * contributes the term +0.0.  With t(tx, row) the term of the block's column tx (0 .. 63) and row (0 .. 63):
+ *   1. thread (tx, ty), ty = 0 .. 3:  s = +0.0; s = s + t(tx, ty); s = s + t(tx, ty + 4); ...; s = s + t(tx, ty + 60)   (sixteen rows, ascending)
+ *   2. wave ty (its 64 threads, lane = tx): for off = 32, 16, 8, 4, 2, 1: s[lane] = s[lane] + s[lane xor off], all lanes at once
+ *   3. block: S = s_wave0; S = S + s_wave1; S = S + s_wave2; S = S + s_wave3.  This is record r = by * nbx + bx.
+ *   4. finishing block, thread t = 0 .. 255: s = +0.0; s = s + record[t]; s = s + record[t + 256]; ... (ascending, while < nbx * nby);
+ *      then step 2 within each of its four waves (lane = t mod 64, wave = t / 64) and step 3.
+ * Maxima, minima and counts take the same route with max, min and integer addition in place of +.
+ *
+ * Tiled contexts: the call is COLLECTIVE -- every rank of the decomposition calls it between the same two steps, with the same
+ * arguments.  Each rank reduces its own interior (the interiors partition the global grid; the easternmost tile of a Bounded x
+ * direction owns the faces i = Nx + 1, the northernmost of a Bounded y direction the faces j = Ny + 1), the ranks all-gather their
+ * 21 slots over whatever joins them (RCCL communicator, in-process group, host-channel group) and EVERY rank combines them on the
+ * host in rank order: a sum is S = slot_rank0; S = S + slot_rank1; ..., maxima / minima by max / min, counts added -- all ranks
+ * return the same bits.  A rank that fails locally still takes part in the all-gather; then every rank returns an error.  Sums of a
+ * tiled run differ from the untiled run's by rounding only (another tree over the same terms).
+ *
+ * Errors: CSI_ERR_NOT_BOUND naming the missing field of a requested group (u, v; h, aice); CSI_ERR_INVALID_ARGUMENT for what == 0 or
+ * an unknown bit of `what`, and for an extent_threshold that is negative or not finite. */
+#define CSI_DIAG_VELOCITY 1
+#define CSI_DIAG_TRACERS 2
+#define CSI_DIAG_ALL 3
+typedef struct {
+    int32_t what;                  /* echo of the request */
+    int32_t has_snow;              /* 1: CSI_F_HS was bound and read */
+    double advection_timescale, inv_timescale_max, max_abs_u, max_abs_v;
+    int64_t nonfinite_u, nonfinite_v, nan_u, nan_v;
+    double ice_volume, ice_area, ice_extent, snow_volume, active_area;
+    double min_h, max_h, min_aice, max_aice, max_hs;
+    int64_t nonfinite_h, nonfinite_aice, nonfinite_hs, active_cells;
+    double extent_threshold;       /* echo */
+} csi_diagnostics;
+int32_t csi_diagnostics_compute(csi_context* ctx, int32_t what, double extent_threshold, csi_diagnostics* out);
+
 /* ---- rheology and momentum solver (SeaIceMomentumEquation(grid; rheology, solver), sea_ice_momentum_equations.jl:67-94) ------------
  * Defaults: CSI_RHEOLOGY_EVP with CSI_SOLVER_SPLIT_EXPLICIT -- the library's EVP path, unchanged by these calls.  The scalars both
  * rheologies share (minimum mass / concentration, sea_ice_density, FPlane f) still come from csi_evp_params_set, which marks the model

@@ -51,6 +51,15 @@ struct CsiTimeSeries
     times::Ptr{Cdouble}; data::Ptr{Cvoid}
     ld::Int64; slice_stride::Int64
 end
+struct CsiDiagnostics
+    what::Int32; has_snow::Int32
+    advection_timescale::Cdouble; inv_timescale_max::Cdouble; max_abs_u::Cdouble; max_abs_v::Cdouble
+    nonfinite_u::Int64; nonfinite_v::Int64; nan_u::Int64; nan_v::Int64
+    ice_volume::Cdouble; ice_area::Cdouble; ice_extent::Cdouble; snow_volume::Cdouble; active_area::Cdouble
+    min_h::Cdouble; max_h::Cdouble; min_aice::Cdouble; max_aice::Cdouble; max_hs::Cdouble
+    nonfinite_h::Int64; nonfinite_aice::Int64; nonfinite_hs::Int64; active_cells::Int64
+    extent_threshold::Cdouble
+end
 
 # field slots, in the order of csi_field_id
 const F = (U=0, V=1, H=2, A=3, S11=4, S22=5, S12=6, UN=7, VN=8, P=9, ALPHA=10, DELTA=11, ZETA_F=12, ZETA_C=13,
@@ -650,6 +659,22 @@ function validate_state!(model::HIPSeaIceModel)
     GC.@preserve model check(ctx, ccall((:csi_validate_all, libcsi), Int32, (Ptr{Cvoid},), ctx.handle))
     return nothing
 end
+
+# ---- device diagnostics (include/csi.h: csi_diagnostics_compute) ---------------------------------------------------------------------
+# Two launches and a 168-byte copy on the context's stream instead of copying fields to the host.  `what`: 1 the velocity group
+# (u, v: the advection timescale, max |u|, max |v|, non-finite counts), 2 the tracer group (h, aice, hs: area-weighted sums, extrema,
+# counts), 3 both.  Members that were not computed hold NaN / -1.  COLLECTIVE on a Distributed grid: every rank calls it between the
+# same two steps and gets the same bits.
+function diagnostics(model::HIPSeaIceModel; what = 3, extent_threshold = 0.15)
+    ctx = context(model)
+    out = Ref{CsiDiagnostics}()
+    GC.@preserve model check(ctx, ccall((:csi_diagnostics_compute, libcsi), Int32, (Ptr{Cvoid}, Int32, Cdouble, Ptr{CsiDiagnostics}),
+                                        ctx.handle, Int32(what), Float64(extent_threshold), out))
+    return out[]
+end
+
+# cell_advection_timescale(model::SeaIceModel), src/ClimaSeaIce.jl:63-69 -- what a TimeStepWizard calls: the velocity group alone
+Oceananigans.Advection.cell_advection_timescale(model::HIPSeaIceModel) = diagnostics(model; what = 1).advection_timescale
 
 # Checkpointing (sea_ice_model.jl:414-445: prognostic_state / restore_prognostic_state!) needs nothing from the library: the
 # state lives in the Oceananigans Fields, restore writes into the same parents, and the library holds pointers only.  If a
