@@ -53,8 +53,12 @@ SYMBOLS = ["csi_version", "csi_context_create", "csi_context_destroy", "csi_last
            "csi_rheology_set", "csi_momentum_solver_set", "csi_compute_momentum_tendencies",
            "csi_heat_fluxes_set", "csi_surface_solve_set", "csi_dynamics_set",
            "csi_time_series_plan", "csi_time_series_set", "csi_time_series_update", "csi_time_series_status",
-           "csi_diagnostics_compute"]
+           "csi_diagnostics_compute",
+           "csi_output_plan_layout", "csi_output_create", "csi_output_layout", "csi_output_record_bytes", "csi_output_accumulate",
+           "csi_output_snapshot", "csi_output_test", "csi_output_wait", "csi_output_release", "csi_output_destroy"]
 DIAG_VELOCITY, DIAG_TRACERS, DIAG_ALL = 1, 2, 3
+OUT_F64, OUT_F32 = 0, 1
+OUTPUT_MAX_FIELDS, OUTPUT_MAX_SETS, OUTPUT_MAX_SLOTS = 16, 4, 64
 
 
 class Metrics(C.Structure):
@@ -119,6 +123,12 @@ class Diagnostics(C.Structure):
                                            "min_h", "max_h", "min_aice", "max_aice", "max_hs")] +
                 [(n, C.c_int64) for n in ("nonfinite_h", "nonfinite_aice", "nonfinite_hs", "active_cells")] +
                 [("extent_threshold", C.c_double)])
+
+
+class OutputField(C.Structure):
+    """csi_output_field (include/csi.h): one field of an output set."""
+    _fields_ = [("field_id", C.c_int32), ("dtype", C.c_int32), ("averaged", C.c_int32), ("masked", C.c_int32),
+                ("fill_value", C.c_double)]
 
 
 class CsiError(RuntimeError):
@@ -195,6 +205,13 @@ def load():
         "csi_time_series_set": [vp, i32, C.POINTER(TimeSeries)], "csi_time_series_update": [vp, dbl],
         "csi_time_series_status": [vp, i32, C.POINTER(i32), C.POINTER(i64)],
         "csi_diagnostics_compute": [vp, i32, dbl, C.POINTER(Diagnostics)],
+        "csi_output_plan_layout": [C.POINTER(i32), C.POINTER(i32), C.POINTER(i32), i32, C.POINTER(i64), C.POINTER(i64)],
+        "csi_output_create": [vp, C.POINTER(OutputField), i32, i32, C.POINTER(i32)],
+        "csi_output_layout": [vp, i32, i32, C.POINTER(i64), C.POINTER(i32), C.POINTER(i32)],
+        "csi_output_record_bytes": [vp, i32, C.POINTER(i64)],
+        "csi_output_accumulate": [vp, i32, dbl], "csi_output_snapshot": [vp, i32, C.POINTER(i32)],
+        "csi_output_test": [vp, i32, i32, C.POINTER(i32)], "csi_output_wait": [vp, i32, i32, C.POINTER(vp)],
+        "csi_output_release": [vp, i32, i32], "csi_output_destroy": [vp, i32],
     }
     for name, args in sig.items():
         fn = getattr(L, name, None)
@@ -243,6 +260,20 @@ def time_series_plan(times, indexing, period, t):
     if rc != OK:
         raise CsiError(rc, "csi_time_series_plan: invalid input")
     return n1.value, n2.value, frac.value
+
+
+def output_plan_layout(shapes, dtypes):
+    """csi_output_plan_layout: (byte offsets, record bytes) of a record whose field k is a dense (ny, nx) = shapes[k] array of
+    dtypes[k] (OUT_F64 / OUT_F32).  Pure host function; CsiError on invalid input."""
+    n = len(shapes)
+    nx = (C.c_int32 * max(n, 1))(*[int(s[1]) for s in shapes])
+    ny = (C.c_int32 * max(n, 1))(*[int(s[0]) for s in shapes])
+    dt = (C.c_int32 * max(n, 1))(*[int(d) for d in dtypes])
+    off, total = (C.c_int64 * max(n, 1))(), C.c_int64()
+    rc = load().csi_output_plan_layout(nx, ny, dt, n, off, C.byref(total))
+    if rc != OK:
+        raise CsiError(rc, "csi_output_plan_layout: invalid input")
+    return list(off)[:n], total.value
 
 
 def plan_peer_chunks(Nx, Ny, Hx, Hy, peer_south=True, peer_north=True):
@@ -394,3 +425,50 @@ class Context:
         res, up = (C.c_int32 * max(int(window), 1))(*([-1] * max(int(window), 1))), C.c_int64()
         self.call("csi_time_series_status", F[slot], res, C.byref(up))
         return list(res)[:int(window)], up.value
+
+    # ---- device-side output (include/csi.h, csi_output_*) -------------------------------------------------------------------------
+    def output_create(self, fields, slots):
+        """csi_output_create: fields = [(slot name, OUT_F64 | OUT_F32, averaged, masked, fill_value), ...]; returns the handle."""
+        arr = (OutputField * max(len(fields), 1))(*[OutputField(F[n], int(d), int(a), int(m), float(v)) for n, d, a, m, v in fields])
+        h = C.c_int32()
+        self.call("csi_output_create", arr, len(fields), int(slots), C.byref(h))
+        return h.value
+
+    def output_layout(self, handle, k):
+        """(byte offset, ny, nx) of field k in a record of the set"""
+        off, nx, ny = C.c_int64(), C.c_int32(), C.c_int32()
+        self.call("csi_output_layout", int(handle), int(k), C.byref(off), C.byref(nx), C.byref(ny))
+        return off.value, ny.value, nx.value
+
+    def output_record_bytes(self, handle):
+        v = C.c_int64()
+        self.call("csi_output_record_bytes", int(handle), C.byref(v))
+        return v.value
+
+    def output_accumulate(self, handle, w):
+        self.call("csi_output_accumulate", int(handle), float(w))
+
+    def output_snapshot(self, handle):
+        """csi_output_snapshot: queues the pack launch and the copy, returns the slot without waiting for the device."""
+        v = C.c_int32()
+        self.call("csi_output_snapshot", int(handle), C.byref(v))
+        return v.value
+
+    def output_test(self, handle, slot):
+        v = C.c_int32()
+        self.call("csi_output_test", int(handle), int(slot), C.byref(v))
+        return bool(v.value)
+
+    def output_wait(self, handle, slot):
+        """csi_output_wait: waits for that slot's copy only; the record as a uint8 view of the page-locked slot (valid until
+        output_release)."""
+        p = C.c_void_p()
+        self.call("csi_output_wait", int(handle), int(slot), C.byref(p))
+        n = self.output_record_bytes(handle)
+        return np.ctypeslib.as_array(C.cast(p, C.POINTER(C.c_uint8)), shape=(n,))
+
+    def output_release(self, handle, slot):
+        self.call("csi_output_release", int(handle), int(slot))
+
+    def output_destroy(self, handle):
+        self.call("csi_output_destroy", int(handle))

@@ -7,6 +7,7 @@
 //   csi_abi.hip     the C ABI (include/csi.h)
 //   csi_time_series.hip   forcing time series: time indexing, the device ring of a host-resident series, the interpolation launch
 //   csi_diagnostics.hip   device diagnostics: the two launches, the result copy, the combine over the ranks of a decomposition
+//   csi_output.hip        device-side output: output sets, their staging slots, the copy stream and the slot events
 //   csi_mem.h       DeviceBuf / PinnedBuf: the owner of every allocation the library makes
 #pragma once
 #include "../../include/csi.h"
@@ -130,6 +131,29 @@ struct TimeSeries {
     int cur[2] = {-1, -1}, next = -1;    // the newest update's pair and the slice wanted after it (series_prefetch)
 };
 
+// One output set (csi_output_create): the caller's field list, what the fields were bound to then, the record layout, the averaged
+// fields' accumulators and the staging slots on both sides of the bus.
+struct OutputSet {
+    bool live = false;
+    int n = 0, slots = 0;
+    csi_output_field f[kMaxOutputFields];
+    Bound sig[kMaxOutputFields];         // the binding of each field at creation: another one since invalidates the set
+    long grid_gen = 0;                   // ... and the csi_grid_set count then
+    int nx[kMaxOutputFields], ny[kMaxOutputFields];
+    int64_t off[kMaxOutputFields];       // byte offset of field k in a record (a multiple of 256)
+    int64_t record_bytes = 0;            // a multiple of 256
+    int64_t acc_off[kMaxOutputFields];   // averaged fields: first element of the accumulator in `acc` (doubles, even)
+    DeviceBuf<double> acc;               // zeroed at creation and by every pack launch
+    DeviceBuf<uint8_t> stage;            // slots records
+    PinnedBuf<uint8_t> host;             // slots records, page-locked
+    std::vector<hipEvent_t> packed;      // per slot: recorded on the context's stream behind the pack launch
+    std::vector<hipEvent_t> done;        // per slot: recorded on the copy stream behind the copy to `host`
+    std::vector<int> in_flight;          // per slot: 0 free, 1 from csi_output_snapshot to csi_output_release
+    double W = 0.0;                      // sum of the weights since the last snapshot
+    bool any_averaged = false;
+};
+constexpr int kMaxOutputSets = 4;
+
 struct csi_context {
     int device = 0;
     hipStream_t stream = nullptr;
@@ -250,6 +274,10 @@ struct csi_context {
     DeviceBuf<double> diag_part;
     PinnedBuf<double> diag_host;
     DeviceBuf<uint8_t> gather_buf;
+    // csi_output_* (csi_output.hip): the sets and the copy stream their records leave on, made at the first csi_output_create
+    OutputSet out_sets[kMaxOutputSets];
+    hipStream_t out_stream = nullptr;
+    long grid_gen = 0;                   // csi_grid_set calls so far
     int weno_w32 = 0;     // csi_set_weno_weight_dtype: 1 = WENO weights in single precision (upstream's FT2 = Float32, recalled)
     // csi_rheology_set / csi_momentum_solver_set (csi_momentum.hip): ViscousRheology, ExplicitSolver
     int rheology = CSI_RHEOLOGY_EVP;
@@ -485,6 +513,7 @@ Range v_second_range(const csi_context* c, const SideV& v);
 static inline const Bound& band_bound(const csi_context* c, int q) { return c->f[c->band[q].fid]; }
 int32_t series_prefetch(csi_context* c);                 // ... the look-ahead uploads of the newest csi_time_series_update, once (no-op otherwise)
 void series_release(csi_context* c);                     // csi_time_series.hip: events, copy stream, rings (the streams have been drained)
+void output_release(csi_context* c);                     // csi_output.hip: every set, the copy stream (the context's stream has been drained)
 int32_t peer_check_entry(csi_context* c);      // (csi_abi.hip: the error word of the peer transport, checked at every entry point)
 
 }  // namespace csi_host

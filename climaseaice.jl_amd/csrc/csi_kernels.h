@@ -260,4 +260,23 @@ void diag_geometry(int Nx, int Ny, int* nbx, int* nby);
 // the two launches: partial records into D.part, the folded result into out[DQ_COUNT] (device memory; only the requested groups' slots are written)
 void launch_diagnostics(const DiagDev& D, bool vel, bool trc, double* out, hipStream_t s);
 
+// device-side output (output.hip; include/csi.h csi_output_accumulate / csi_output_snapshot): every field of a set in ONE launch.  A
+// descriptor: the first INTERIOR element of the bound array and its row stride in doubles, the dense (ny, nx) accumulator of an
+// averaged field, the field's place in the staging slot, the interior extents.  accumulate: w = the weight, the table holds the
+// averaged fields only; pack: w = W, the sum of the weights; mask = the byte of cell (1, 1) (null: no mask set), rows mask_ld apart.
+constexpr int kMaxOutputFields = 16;
+struct OutputDesc {
+    const double* src;
+    double* acc;
+    void* dst;
+    long lds;
+    int nx, ny;
+    int f32, averaged, masked;
+    int pad_;
+    double fill;
+};
+struct OutputTable { int n; int mask_ld; double w; const unsigned char* mask; OutputDesc d[kMaxOutputFields]; };
+void launch_output_accumulate(const OutputTable& T, hipStream_t s);
+void launch_output_pack(const OutputTable& T, hipStream_t s);
+
 }  // namespace csi

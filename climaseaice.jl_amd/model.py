@@ -8,6 +8,7 @@ time_step!        sea_ice_fe_step.jl:13-34 (ForwardEuler) / upstream SplitRungeK
 update_state!     sea_ice_model.jl:379-394
 """
 import ctypes as C
+from collections import OrderedDict
 from types import SimpleNamespace
 
 import numpy as np
@@ -320,6 +321,7 @@ class SeaIceModel:
             self.snow_top_temperature = CenterField(grid, dev, "Tu_snow")
             self.ice_top_temperature = CenterField(grid, dev, "Tu")
         self.clock = SimpleNamespace(time=0.0, iteration=0)
+        self.output_writers = OrderedDict()      # key -> output.OutputWriter, driven by time_step (empty: nothing is called)
         self._keep = []
         self._stress_fields = {}
         self._free_drift_fields = {}
@@ -900,7 +902,10 @@ def compute_momentum_tendencies(model, dt):
 
 def time_step(model, dt):
     """time_step!(model, dt).  Forcing time series are interpolated at the time the step starts from: every stage reads the same
-    forcing, as in the reference, whose tick! follows the stages."""
+    forcing, as in the reference, whose tick! follows the stages.  Output writers (model.output_writers) write their initial record
+    before the first step and are driven at the end of every step, once the clock has advanced and a tiled model has been validated."""
+    for writer in model.output_writers.values():
+        writer.begin(model)
     model.update_time_series()
     if model.dynamics is None and model.scheme in (0, None):
         # dynamics = nothing, advection = nothing: the step is the thermodynamic update alone
@@ -922,3 +927,5 @@ def time_step(model, dt):
     # it -- what the Julia stub does in the update_state! that ends time_step! (julia/ClimaSeaIceHIP.jl)
     if isinstance(model.grid, TileGrid):
         model.ctx.validate_all()
+    for writer in model.output_writers.values():
+        writer.after_step(model, float(dt))

@@ -629,6 +629,81 @@ typedef struct {
 } csi_diagnostics;
 int32_t csi_diagnostics_compute(csi_context* ctx, int32_t what, double extent_threshold, csi_diagnostics* out);
 
+/* ---- device-side output: packed snapshots, time averages, asynchronous copies ----------------------------------------------------------
+ * Stands where the reference attaches an output writer to a Simulation (examples/ice_advected_by_anticyclone.jl:161-163: JLD2Writer
+ * with IterationInterval(5); test/distributed_tests_utils.jl:159; test/test_netcdf_writer.jl).  An OUTPUT SET is a list of up to
+ * CSI_OUTPUT_MAX_FIELDS bound fields (any slot of csi_field_bind).  csi_output_snapshot packs the INTERIOR of every field of the set
+ * into one record in device memory with ONE launch on the context's stream and copies the record to page-locked host memory on a
+ * copy stream of the library's own; it returns without waiting for the device, and the stepping goes on while the record crosses
+ * the bus.  csi_output_accumulate adds the fields marked `averaged` into accumulators the library owns, so that a time average
+ * never leaves the device before it is complete.  Nothing of this changes any other entry point: a context without output sets runs
+ * exactly the launches it ran before.
+ *
+ * RECORD LAYOUT (a function of the field list and the grid alone; csi_output_plan_layout is the same rule as a pure host function).
+ *   Field k of the set is a dense row-major (ny_k, nx_k) array of its OWN interior: nx_k = ni - 2Hx, ny_k = nj - 2Hy of the bound
+ *   parent, i.e. Nx x Ny, one more column for a Face-in-x field whose high x side is Bounded, one more row for a Face-in-y field whose
+ *   high y side is Bounded.  Halos are not part of it and are never read.  On a tile this is the ownership rule of the diagnostics:
+ *   only the easternmost / northernmost tile of a Bounded direction has (and writes) the last face, and the interiors of the tiles
+ *   partition the global field.  Element (i, j) of the field (1-based) sits at row j - 1, column i - 1.
+ *   Elements are 8 bytes (CSI_OUT_F64) or 4 bytes (CSI_OUT_F32).  byte_offset_0 = 0; byte_offset_{k+1} = byte_offset_k + the bytes of
+ *   field k, rounded up to a multiple of 256; record_bytes = the same expression behind the last field.  Padding bytes are undefined.
+ * ELEMENTS.
+ *   snapshot field   x, the array's element
+ *   averaged field   acc / W: one IEEE division (no reciprocal) of the accumulator by the sum of the weights W = ((w_1 + w_2) + ...)
+ *                    formed on the host in double; acc = ((+0.0 + (x_1 * w_1)) + (x_2 * w_2)) + ..., each product rounded before it
+ *                    is added (no contraction).  The pack launch sets acc back to +0.0 and the call sets W back to 0.
+ *   masked           a field with masked != 0 takes fill_value in the cells whose mask byte is 0, if a mask is set (csi_mask_set) at
+ *                    the time of the snapshot.  (Center, Center) fields only; any other location: CSI_ERR_INVALID_ARGUMENT.
+ *   CSI_OUT_F32      the value above converted to fp32, round to nearest even: overflow gives +-Inf, subnormal results are kept, the
+ *                    sign of zero is kept, NaN stays NaN (its payload is not specified).
+ * One code serves STRICT and FAST, compiled without contraction: both modes give the same bits.
+ *
+ * SLOTS.  A set has `slots` staging records on the device and as many in page-locked host memory.  csi_output_snapshot takes the free
+ * slot with the lowest number (free -> in flight), queues the pack launch on the context's stream, records an event, makes the copy
+ * stream wait for it, queues ONE device-to-host copy of the record and records the slot's event behind it.  Steps queued after the call
+ * may overwrite the fields: the record is the state at the point of the call.  csi_output_test / csi_output_wait look at / wait for
+ * that slot's event ONLY -- never for the context's stream --; after csi_output_wait, host_ptr points to record_bytes bytes that stay
+ * valid until csi_output_release (in flight -> free).  With no free slot csi_output_snapshot fails (CSI_ERR_INVALID_ARGUMENT, "no
+ * free slot"), changes nothing -- accumulators and W included -- and never overwrites a record that has not been released.  A slot is
+ * reused only after its release, which follows its wait, so no further ordering between a pack launch and the previous copy out of
+ * the same slot is needed.
+ *
+ * Errors: CSI_ERR_NOT_BOUND naming the field of the list that is not bound; CSI_ERR_INVALID_ARGUMENT for an unknown dtype or field id,
+ * n outside 1 .. CSI_OUTPUT_MAX_FIELDS, slots outside 1 .. CSI_OUTPUT_MAX_SLOTS, a fifth set on a context, a bad handle, field
+ * index or slot, a slot that is not in flight, a weight that is not finite and > 0, and csi_output_snapshot of a set with averaged
+ * fields while W == 0.  Binding another array (or shape) to a field of a set, or calling csi_grid_set, after csi_output_create
+ * INVALIDATES the set: every later call on it but csi_output_destroy fails with CSI_ERR_INVALID_ARGUMENT and says so.
+ * csi_context_destroy frees the sets.  Tiled contexts: nothing here communicates; every rank packs its own interior. */
+#define CSI_OUT_F64 0
+#define CSI_OUT_F32 1
+#define CSI_OUTPUT_MAX_FIELDS 16
+#define CSI_OUTPUT_MAX_SETS 4
+#define CSI_OUTPUT_MAX_SLOTS 64
+typedef struct {
+    int32_t field_id;              /* a slot of csi_field_bind */
+    int32_t dtype;                 /* CSI_OUT_F64 | CSI_OUT_F32 */
+    int32_t averaged;              /* 0: snapshot of the field, 1: time average (csi_output_accumulate) */
+    int32_t masked;                /* 1: fill_value in inactive cells ((Center, Center) fields only) */
+    double fill_value;
+} csi_output_field;
+/* The layout rule above for n fields of interior extents nx[k] x ny[k] and dtypes dtype[k]: byte_offsets[k] and *record_bytes.  Pure
+ * host function (no context, no GPU).  Either output pointer may be NULL. */
+int32_t csi_output_plan_layout(const int32_t* nx, const int32_t* ny, const int32_t* dtype, int32_t n, int64_t* byte_offsets,
+                               int64_t* record_bytes);
+/* handle: 1 .. CSI_OUTPUT_MAX_SETS.  Allocates the staging slots, the accumulators (zeroed) and, the first time on a context, the
+ * copy stream. */
+int32_t csi_output_create(csi_context* ctx, const csi_output_field* fields, int32_t n, int32_t slots, int32_t* handle);
+int32_t csi_output_layout(csi_context* ctx, int32_t handle, int32_t k, int64_t* byte_offset, int32_t* nx, int32_t* ny);
+int32_t csi_output_record_bytes(csi_context* ctx, int32_t handle, int64_t* bytes);
+/* acc = acc + (x * w) for every averaged field, one launch on the context's stream (none if no field is averaged); W = W + w. */
+int32_t csi_output_accumulate(csi_context* ctx, int32_t handle, double w);
+int32_t csi_output_snapshot(csi_context* ctx, int32_t handle, int32_t* slot);
+int32_t csi_output_test(csi_context* ctx, int32_t handle, int32_t slot, int32_t* done);
+int32_t csi_output_wait(csi_context* ctx, int32_t handle, int32_t slot, void** host_ptr);
+int32_t csi_output_release(csi_context* ctx, int32_t handle, int32_t slot);
+/* Waits for the context's stream and the copy stream, then frees the set; its handle may be handed out again. */
+int32_t csi_output_destroy(csi_context* ctx, int32_t handle);
+
 /* ---- rheology and momentum solver (SeaIceMomentumEquation(grid; rheology, solver), sea_ice_momentum_equations.jl:67-94) ------------
  * Defaults: CSI_RHEOLOGY_EVP with CSI_SOLVER_SPLIT_EXPLICIT -- the library's EVP path, unchanged by these calls.  The scalars both
  * rheologies share (minimum mass / concentration, sea_ice_density, FPlane f) still come from csi_evp_params_set, which marks the model

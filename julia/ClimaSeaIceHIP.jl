@@ -61,6 +61,12 @@ struct CsiDiagnostics
     extent_threshold::Cdouble
 end
 
+# csi_output_field (include/csi.h): one field of an output set
+struct CsiOutputField
+    field_id::Int32; dtype::Int32; averaged::Int32; masked::Int32
+    fill_value::Cdouble
+end
+
 # field slots, in the order of csi_field_id
 const F = (U=0, V=1, H=2, A=3, S11=4, S22=5, S12=6, UN=7, VN=8, P=9, ALPHA=10, DELTA=11, ZETA_F=12, ZETA_C=13,
            GH=14, GA=15, HM=16, AM=17, UM=18, VM=19, TOP_U=20, TOP_V=21, BOT_U=22, BOT_V=23, MASS_FLUX=24,
@@ -675,6 +681,75 @@ end
 
 # cell_advection_timescale(model::SeaIceModel), src/ClimaSeaIce.jl:63-69 -- what a TimeStepWizard calls: the velocity group alone
 Oceananigans.Advection.cell_advection_timescale(model::HIPSeaIceModel) = diagnostics(model; what = 1).advection_timescale
+
+# ---- device-side output (include/csi.h: csi_output_*) ---------------------------------------------------------------------------------
+# Stands where a Simulation carries a JLD2Writer (examples/ice_advected_by_anticyclone.jl:161-163).  An OutputSet packs the interiors of
+# up to 16 bound fields into one record with ONE launch and copies it to page-locked host memory on the library's copy stream; nothing
+# here waits for the device except wait_output.  `fields`: a vector of (slot, dtype, averaged, masked, fill_value) with slot a member of
+# F, dtype 0 (Float64) / 1 (Float32).  write_output! is what a Callback calls: it drains the oldest record through `sink(record, layout)`
+# when no slot is free, then takes the next snapshot.  On a Distributed grid every rank writes its own interior: no communication.
+mutable struct OutputSet
+    handle::Int32
+    slots::Int32
+    layout::Vector{NTuple{3, Int64}}      # (byte offset, nx, ny) of every field in a record
+    record_bytes::Int64
+    pending::Vector{Int32}                # slots in flight, oldest first
+end
+
+function OutputSet(model::HIPSeaIceModel, fields::Vector{CsiOutputField}; slots = 2)
+    ctx = context(model)
+    handle = Ref{Int32}(0)
+    GC.@preserve model fields check(ctx, ccall((:csi_output_create, libcsi), Int32, (Ptr{Cvoid}, Ptr{CsiOutputField}, Int32, Int32, Ptr{Int32}),
+                                               ctx.handle, fields, Int32(length(fields)), Int32(slots), handle))
+    layout = NTuple{3, Int64}[]
+    for k in 0:length(fields)-1
+        off = Ref{Int64}(0); nx = Ref{Int32}(0); ny = Ref{Int32}(0)
+        check(ctx, ccall((:csi_output_layout, libcsi), Int32, (Ptr{Cvoid}, Int32, Int32, Ptr{Int64}, Ptr{Int32}, Ptr{Int32}),
+                         ctx.handle, handle[], Int32(k), off, nx, ny))
+        push!(layout, (off[], Int64(nx[]), Int64(ny[])))
+    end
+    bytes = Ref{Int64}(0)
+    check(ctx, ccall((:csi_output_record_bytes, libcsi), Int32, (Ptr{Cvoid}, Int32, Ptr{Int64}), ctx.handle, handle[], bytes))
+    return OutputSet(handle[], Int32(slots), layout, bytes[], Int32[])
+end
+
+# acc = acc + (x * w) for the averaged fields of the set (one launch; a Callback calls it after every step with the step's weight)
+function accumulate_output!(model::HIPSeaIceModel, set::OutputSet, w)
+    ctx = context(model)
+    GC.@preserve model check(ctx, ccall((:csi_output_accumulate, libcsi), Int32, (Ptr{Cvoid}, Int32, Cdouble), ctx.handle, set.handle, Float64(w)))
+    return nothing
+end
+
+# the oldest record in flight as a Vector{UInt8} view of the page-locked slot, handed to `sink`; then the slot is released
+function drain_output!(sink, model::HIPSeaIceModel, set::OutputSet)
+    ctx = context(model)
+    slot = popfirst!(set.pending)
+    ptr = Ref{Ptr{Cvoid}}(C_NULL)
+    check(ctx, ccall((:csi_output_wait, libcsi), Int32, (Ptr{Cvoid}, Int32, Int32, Ptr{Ptr{Cvoid}}), ctx.handle, set.handle, slot, ptr))
+    sink(unsafe_wrap(Array, Ptr{UInt8}(ptr[]), set.record_bytes), set.layout)
+    check(ctx, ccall((:csi_output_release, libcsi), Int32, (Ptr{Cvoid}, Int32, Int32), ctx.handle, set.handle, slot))
+    return nothing
+end
+
+# What a Callback calls: Callback(sim -> write_output!(sink, sim.model, set), IterationInterval(5)).  Returns without waiting for the
+# device unless every slot is in flight.
+function write_output!(sink, model::HIPSeaIceModel, set::OutputSet)
+    ctx = context(model)
+    length(set.pending) >= set.slots && drain_output!(sink, model, set)
+    slot = Ref{Int32}(0)
+    GC.@preserve model check(ctx, ccall((:csi_output_snapshot, libcsi), Int32, (Ptr{Cvoid}, Int32, Ptr{Int32}), ctx.handle, set.handle, slot))
+    push!(set.pending, slot[])
+    return nothing
+end
+
+function close_output!(sink, model::HIPSeaIceModel, set::OutputSet)
+    ctx = context(model)
+    while !isempty(set.pending)
+        drain_output!(sink, model, set)
+    end
+    check(ctx, ccall((:csi_output_destroy, libcsi), Int32, (Ptr{Cvoid}, Int32), ctx.handle, set.handle))
+    return nothing
+end
 
 # Checkpointing (sea_ice_model.jl:414-445: prognostic_state / restore_prognostic_state!) needs nothing from the library: the
 # state lives in the Oceananigans Fields, restore writes into the same parents, and the library holds pointers only.  If a
