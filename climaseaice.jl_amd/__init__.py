@@ -15,6 +15,7 @@ from .grids import (Bounded, Center, Face, Flat, FullyConnected, LatitudeLongitu
                     OrthogonalCurvilinearGrid, Periodic, LeftConnectedRightFolded, RightFolded, fold_north,
                     RectilinearGrid, RightConnected, TileGrid, TripolarGrid)
 from .diagnostics import Diagnostics, TimeStepWizard, assert_finite, cell_advection_timescale, new_time_step
+from .derived import DERIVED_NAMES, EnergyBudget
 from .output import (AveragedTimeInterval, IterationInterval, OutputWriter, TimeInterval, aligned_time_step, bound_fields,
                      load_output)
 from .time_series import Clamp, Cyclical, FieldTimeSeries, InMemory, Linear

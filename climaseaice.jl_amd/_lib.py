@@ -22,6 +22,16 @@ FIELD_IDS = ["U", "V", "H", "A", "S11", "S22", "S12", "UN", "VN", "P", "ALPHA", 
 THERMO_FIELD_IDS = ["TOP_HEAT_FLUX", "BOTTOM_HEAT_FLUX", "SNOWFALL"]     # csi_thermo_field_id: numbered from CSI_F_COUNT on
 FREE_DRIFT_FIELD_IDS = ["FREE_DRIFT_U", "FREE_DRIFT_V"]                  # csi_free_drift_field_id: numbered from CSI_F_COUNT_ALL on
 F = {n: k for k, n in enumerate(FIELD_IDS + THERMO_FIELD_IDS + FREE_DRIFT_FIELD_IDS)}
+# csi_derived_field_id: the seven derived (c,c) fields, numbered from CSI_F_COUNT_TOTAL = len(F) on (F itself keeps its extent)
+DERIVED_FIELD_IDS = ["D_DIVERGENCE", "D_SHEAR", "D_DEFORMATION", "D_SPEED", "D_SIGMA_I", "D_SIGMA_II", "D_STRESS_POWER"]
+F_DERIVED = {n: len(F) + k for k, n in enumerate(DERIVED_FIELD_IDS)}
+
+
+def slot_id(name):
+    """The number of a csi_field_bind slot by name: F, or one of the derived fields' slots."""
+    return F[name] if name in F else F_DERIVED[name]
+
+
 STRESS_NONE, STRESS_CONST, STRESS_FIELD, STRESS_SEMI_IMPLICIT = 0, 1, 2, 3
 VEL_ZERO, VEL_CONST, VEL_FIELD = 0, 1, 2
 STRESS_TOP, STRESS_BOTTOM = 0, 1
@@ -55,9 +65,12 @@ SYMBOLS = ["csi_version", "csi_context_create", "csi_context_destroy", "csi_last
            "csi_time_series_plan", "csi_time_series_set", "csi_time_series_update", "csi_time_series_status",
            "csi_diagnostics_compute",
            "csi_output_plan_layout", "csi_output_create", "csi_output_layout", "csi_output_record_bytes", "csi_output_accumulate",
-           "csi_output_snapshot", "csi_output_test", "csi_output_wait", "csi_output_release", "csi_output_destroy"]
+           "csi_output_snapshot", "csi_output_test", "csi_output_wait", "csi_output_release", "csi_output_destroy",
+           "csi_derived_compute", "csi_budget_compute", "csi_derived_stats"]
 DIAG_VELOCITY, DIAG_TRACERS, DIAG_ALL = 1, 2, 3
 OUT_F64, OUT_F32 = 0, 1
+DERIVED_ALL = 127
+BUDGET_STRESS, BUDGET_KINETIC, BUDGET_ALL = 1, 2, 3
 OUTPUT_MAX_FIELDS, OUTPUT_MAX_SETS, OUTPUT_MAX_SLOTS = 16, 4, 64
 
 
@@ -123,6 +136,12 @@ class Diagnostics(C.Structure):
                                            "min_h", "max_h", "min_aice", "max_aice", "max_hs")] +
                 [(n, C.c_int64) for n in ("nonfinite_h", "nonfinite_aice", "nonfinite_hs", "active_cells")] +
                 [("extent_threshold", C.c_double)])
+
+
+class Budget(C.Structure):
+    """csi_budget (include/csi.h): members of a group that was not requested hold NaN."""
+    _fields_ = [("what", C.c_int32), ("reserved", C.c_int32), ("internal_work", C.c_double), ("stress_power", C.c_double),
+                ("kinetic_energy", C.c_double)]
 
 
 class OutputField(C.Structure):
@@ -212,6 +231,8 @@ def load():
         "csi_output_accumulate": [vp, i32, dbl], "csi_output_snapshot": [vp, i32, C.POINTER(i32)],
         "csi_output_test": [vp, i32, i32, C.POINTER(i32)], "csi_output_wait": [vp, i32, i32, C.POINTER(vp)],
         "csi_output_release": [vp, i32, i32], "csi_output_destroy": [vp, i32],
+        "csi_derived_compute": [vp, i32], "csi_budget_compute": [vp, i32, C.POINTER(Budget)],
+        "csi_derived_stats": [vp, C.POINTER(i64), C.POINTER(i64)],
     }
     for name, args in sig.items():
         fn = getattr(L, name, None)
@@ -426,10 +447,28 @@ class Context:
         self.call("csi_time_series_status", F[slot], res, C.byref(up))
         return list(res)[:int(window)], up.value
 
+    # ---- derived fields and energy budget integrals (include/csi.h) ---------------------------------------------------------------
+    def derived_compute(self, mask):
+        """csi_derived_compute: every requested derived field in ONE launch on the context's stream (nothing is waited for)."""
+        self.call("csi_derived_compute", int(mask))
+
+    def budget_compute(self, what):
+        """csi_budget_compute: the filled csi_budget (two launches and one small copy; waits for the context's stream; collective on a
+        tiled context)."""
+        b = Budget()
+        self.call("csi_budget_compute", int(what), C.byref(b))
+        return b
+
+    def derived_stats(self):
+        """(launches of the derived-field kernel, budget calls) made on this context so far."""
+        a, b = C.c_int64(), C.c_int64()
+        self.call("csi_derived_stats", C.byref(a), C.byref(b))
+        return a.value, b.value
+
     # ---- device-side output (include/csi.h, csi_output_*) -------------------------------------------------------------------------
     def output_create(self, fields, slots):
         """csi_output_create: fields = [(slot name, OUT_F64 | OUT_F32, averaged, masked, fill_value), ...]; returns the handle."""
-        arr = (OutputField * max(len(fields), 1))(*[OutputField(F[n], int(d), int(a), int(m), float(v)) for n, d, a, m, v in fields])
+        arr = (OutputField * max(len(fields), 1))(*[OutputField(slot_id(n), int(d), int(a), int(m), float(v)) for n, d, a, m, v in fields])
         h = C.c_int32()
         self.call("csi_output_create", arr, len(fields), int(slots), C.byref(h))
         return h.value

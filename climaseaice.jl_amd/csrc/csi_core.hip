@@ -334,7 +334,7 @@ bool offsets_fit_32bit(int Nx, int Ny, int Hx, int Hy, int64_t max_ld) {
 }
 int64_t max_bound_ld(const csi_context* c) {
     int64_t m = 0;
-    for (int k = 0; k < CSI_F_COUNT_TOTAL; ++k) if (c->f[k].p && c->f[k].ld > m) m = c->f[k].ld;
+    for (int k = 0; k < CSI_F_COUNT_DERIVED; ++k) if (c->f[k].p && c->f[k].ld > m) m = c->f[k].ld;
     if (c->g.has_mask && c->g.mask_ld > m) m = c->g.mask_ld;
     return m;
 }

@@ -8,6 +8,7 @@
 //   csi_time_series.hip   forcing time series: time indexing, the device ring of a host-resident series, the interpolation launch
 //   csi_diagnostics.hip   device diagnostics: the two launches, the result copy, the combine over the ranks of a decomposition
 //   csi_output.hip        device-side output: output sets, their staging slots, the copy stream and the slot events
+//   csi_derived.hip       derived fields and energy budget integrals: binding checks, the launches, the budget's combine over the ranks
 //   csi_mem.h       DeviceBuf / PinnedBuf: the owner of every allocation the library makes
 #pragma once
 #include "../../include/csi.h"
@@ -43,7 +44,7 @@ struct Bound {
 };
 
 // (x, y) location of every field slot
-static const int kLoc[CSI_F_COUNT_TOTAL][2] = {
+static const int kLoc[CSI_F_COUNT_DERIVED][2] = {
     {LOC_F, LOC_C}, {LOC_C, LOC_F}, {LOC_C, LOC_C}, {LOC_C, LOC_C},   // U V H A
     {LOC_C, LOC_C}, {LOC_C, LOC_C}, {LOC_F, LOC_F},                   // S11 S22 S12
     {LOC_F, LOC_C}, {LOC_C, LOC_F}, {LOC_C, LOC_C}, {LOC_C, LOC_C}, {LOC_C, LOC_C},  // UN VN P ALPHA DELTA
@@ -57,12 +58,14 @@ static const int kLoc[CSI_F_COUNT_TOTAL][2] = {
     {LOC_F, LOC_C}, {LOC_C, LOC_F},                                   // FORCING_U FORCING_V
     {LOC_F, LOC_C}, {LOC_C, LOC_F},                                   // GU GV
     {LOC_C, LOC_C}, {LOC_C, LOC_C}, {LOC_C, LOC_C},                   // TOP_HEAT_FLUX BOTTOM_HEAT_FLUX SNOWFALL
-    {LOC_F, LOC_C}, {LOC_C, LOC_F}};                                  // FREE_DRIFT_U FREE_DRIFT_V
-static const char* const kName[CSI_F_COUNT_TOTAL] = {"u", "v", "h", "aice", "sigma11", "sigma22", "sigma12", "un", "vn", "P", "alpha",
+    {LOC_F, LOC_C}, {LOC_C, LOC_F},                                   // FREE_DRIFT_U FREE_DRIFT_V
+    {LOC_C, LOC_C}, {LOC_C, LOC_C}, {LOC_C, LOC_C}, {LOC_C, LOC_C}, {LOC_C, LOC_C}, {LOC_C, LOC_C}, {LOC_C, LOC_C}};   // the seven derived fields
+static const char* const kName[CSI_F_COUNT_DERIVED] = {"u", "v", "h", "aice", "sigma11", "sigma22", "sigma12", "un", "vn", "P", "alpha",
                                   "Delta", "zeta_f", "zeta_c", "Gh", "Gaice", "h-", "aice-", "u-", "v-",
                                   "top_u", "top_v", "bottom_u", "bottom_v", "mass_flux",
                                   "hs", "Ghs", "hs-", "mass_flux_snow", "intercepted_snowfall", "Tu", "Tu_snow", "forcing_u", "forcing_v", "Gu", "Gv",
-                                  "top_heat_flux", "bottom_heat_flux", "snowfall", "free_drift_u", "free_drift_v"};
+                                  "top_heat_flux", "bottom_heat_flux", "snowfall", "free_drift_u", "free_drift_v",
+                                  "divergence", "shear", "deformation", "speed", "sigma_I", "sigma_II", "stress_power"};
 
 extern std::string g_create_error;      // csi_context_create failures (no context to hold the message)
 
@@ -173,7 +176,7 @@ struct csi_context {
     long fcor2_ld = 0, fcor2_plane = 0;
     bool cor_dirty = true;               // Coriolis columns of the FAST table need (re)building
     double cor_synced = 0.0;             // FPlane value they were built with
-    Bound f[CSI_F_COUNT_TOTAL];
+    Bound f[CSI_F_COUNT_DERIVED];
     csi_evp_params evp{};
     csi_stress stress[2]{};
     int mode = CSI_MODE_STRICT;
@@ -274,6 +277,11 @@ struct csi_context {
     DeviceBuf<double> diag_part;
     PinnedBuf<double> diag_host;
     DeviceBuf<uint8_t> gather_buf;
+    // csi_derived_compute / csi_budget_compute (csi_derived.hip): the budget's partial records followed by its BQ_COUNT result slots, their
+    // page-locked copy, and the calls made so far (csi_derived_stats)
+    DeviceBuf<double> budget_part;
+    PinnedBuf<double> budget_host;
+    int64_t derived_launches = 0, budget_calls = 0;
     // csi_output_* (csi_output.hip): the sets and the copy stream their records leave on, made at the first csi_output_create
     OutputSet out_sets[kMaxOutputSets];
     hipStream_t out_stream = nullptr;

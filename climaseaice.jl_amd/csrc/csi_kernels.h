@@ -260,6 +260,28 @@ void diag_geometry(int Nx, int Ny, int* nbx, int* nby);
 // the two launches: partial records into D.part, the folded result into out[DQ_COUNT] (device memory; only the requested groups' slots are written)
 void launch_diagnostics(const DiagDev& D, bool vel, bool trc, double* out, hipStream_t s);
 
+// derived fields (derived.hip; include/csi.h csi_derived_compute): every requested field in ONE launch.  out[k]: the array bound to slot
+// CSI_F_D_DIVERGENCE + k as a (0, 0)-offset reference, p == nullptr where the field is not requested.
+enum : int { DV_DIVERGENCE = 0, DV_SHEAR, DV_DEFORMATION, DV_SPEED, DV_SIGMA_I, DV_SIGMA_II, DV_STRESS_POWER, DV_COUNT };
+struct DerivedDev {
+    GridDev g;
+    FRef u, v, s11, s22, s12, P;      // (the stress group's four: unused without it)
+    FRef out[DV_COUNT];
+};
+void launch_derived(const DerivedDev& D, bool stress, hipStream_t s);
+
+// energy budget integrals (budget.hip; include/csi.h csi_budget_compute): the diagnostics' two launches and record layout (slot q of
+// record r at part[q * nrec + r], diag_geometry blocks) with three sums.  Slots below BQ_KINETIC: CSI_BUDGET_STRESS.
+enum : int { BQ_WORK = 0, BQ_POWER, BQ_KINETIC, BQ_COUNT };
+struct BudgetDev {
+    GridDev g;
+    FRef u, v, s11, s22, s12, h, a;
+    double rho;
+    double* part;
+    long nrec;
+};
+void launch_budget(const BudgetDev& D, bool stress, bool kin, double* out, hipStream_t s);
+
 // device-side output (output.hip; include/csi.h csi_output_accumulate / csi_output_snapshot): every field of a set in ONE launch.  A
 // descriptor: the first INTERIOR element of the bound array and its row stride in doubles, the dense (ny, nx) accumulator of an
 // averaged field, the field's place in the staging slot, the interior extents.  accumulate: w = the weight, the table holds the

@@ -325,6 +325,7 @@ class SeaIceModel:
         self._keep = []
         self._stress_fields = {}
         self._free_drift_fields = {}
+        self._derived_fields = {}           # name -> CenterField of the derived fields asked for so far (derived_field)
         self._series, self._pending_series = {}, []     # slot name -> what csi_time_series_set was given (kept alive)
         self.ctx = _lib.Context(dev.index or 0, stream)
         self._configure()
@@ -335,7 +336,7 @@ class SeaIceModel:
 
     # ---- plumbing: describe the problem to the library -----------------------------------------
     def _bind(self, name, fld):
-        self.ctx.call("csi_field_bind", _lib.F[name], C.c_void_p(fld.data.data_ptr()), fld.ni, fld.ni, fld.nj)
+        self.ctx.call("csi_field_bind", _lib.slot_id(name), C.c_void_p(fld.data.data_ptr()), fld.ni, fld.ni, fld.nj)
 
     def _configure(self):
         g = self.grid
@@ -795,6 +796,36 @@ class SeaIceModel:
         library's stream; collective on a tiled model.  Returns an immutable Diagnostics record."""
         from .diagnostics import diagnostics
         return diagnostics(self, what, extent_threshold)
+
+    # ---- derived fields and energy budget integrals (derived.py; include/csi.h csi_derived_compute / csi_budget_compute) ----------
+    def derived_field(self, name):
+        """The (Center, Center) field of a derived quantity -- "divergence", "shear", "deformation", "speed", "sigma_I", "sigma_II",
+        "stress_power" --, allocated and bound to its slot the first time it is asked for.  compute_derived fills its interior."""
+        from .derived import slot_of
+        if name not in self._derived_fields:
+            slot = slot_of(name)
+            fld = CenterField(self.grid, self.device, name)
+            torch.cuda.synchronize(self.device)      # (the zero fill ran on torch's stream)
+            self._bind(slot, fld)
+            self._derived_fields[name] = fld
+        return self._derived_fields[name]
+
+    def compute_derived(self, *names):
+        """Fill the named derived fields from the current state, all in ONE launch on the library's stream (no copy, no wait: an
+        output writer's pack launch, queued next, reads them; synchronize() before reading them with torch / numpy).  Returns the
+        fields in the order of the names.  The stress group needs an ElastoViscoPlasticRheology (CsiError naming sigma11 otherwise)."""
+        from .derived import mask_of
+        mask = mask_of(names)
+        fields = [self.derived_field(n) for n in names]
+        self.ctx.derived_compute(mask)
+        return fields
+
+    def energy_budget(self, what="all"):
+        """Work of the stress divergence, stress power, their relative imbalance and the kinetic energy, summed on the device in the
+        diagnostics' order (derived.py): what = "all", "stress" or "kinetic".  Waits for the library's stream; collective on a tiled
+        model.  Returns an immutable EnergyBudget record."""
+        from .derived import energy_budget
+        return energy_budget(self, what)
 
     def synchronize(self):
         """Wait for the library's stream (call before reading fields with torch / numpy)."""

@@ -196,6 +196,9 @@ def bound_fields(model):
             out[f"{side}_heat_flux"] = (f, slot)
     if isinstance(model.snowfall, Field):
         out["snowfall"] = (model.snowfall, "SNOWFALL")
+    from .derived import slot_of
+    for name, f in getattr(model, "_derived_fields", {}).items():      # derived fields, once allocated (model.derived_field)
+        out[name] = (f, slot_of(name))
     return out
 
 
@@ -268,7 +271,8 @@ class OutputWriter:
     """OutputWriter(model, outputs, schedule, dir, dtype = "f32", mask = False, fill_value = nan, slots = 2, overwrite_existing = False).
 
     outputs   a dict name -> Field, or a list of names, of fields the model has bound to its context (bound_fields(model)); anything
-              else is refused by name
+              else is refused by name.  The names of the derived fields ("shear", "divergence", ...: derived.py) may appear in a list:
+              they are allocated here and computed on the device immediately before every accumulate and snapshot
     schedule  IterationInterval, TimeInterval (snapshots) or AveragedTimeInterval (every output is a time average)
     dtype     "f32" (round to nearest even on the device) or "f64"
     mask      True: (Center, Center) outputs take fill_value in the inactive cells of the model's mask
@@ -286,6 +290,11 @@ class OutputWriter:
         if int(slots) < 1:
             raise ValueError("OutputWriter: slots >= 1")
         recorder = recorder or DeviceRecorder
+        from .derived import DERIVED_NAMES, name_of_slot
+        if not isinstance(outputs, dict) and hasattr(model, "derived_field"):
+            for name in outputs:                     # a derived field named in a list is allocated and bound here
+                if name in DERIVED_NAMES:
+                    model.derived_field(name)
         bound = recorder.bound_fields(model)
         if isinstance(outputs, dict):
             items = []
@@ -311,6 +320,9 @@ class OutputWriter:
         g = model.grid
         self.schedule, self.dtype, self.slots = schedule, dtype, int(slots)
         self.names = [n for n, _, _ in items]
+        # derived outputs: computed (model.compute_derived, one launch) immediately before every accumulate and snapshot; a writer
+        # without them makes no such call
+        self.derived = tuple(name_of_slot(slot) for _, _, slot in items if name_of_slot(slot) is not None)
         self.dir = os.path.join(dir, f"rank_{g.rank}") if isinstance(g, TileGrid) else dir
         if os.path.exists(self.dir):
             if not overwrite_existing:
@@ -357,6 +369,8 @@ class OutputWriter:
         self.begin(model)
         for action, value in self.schedule.after_step(model.clock, dt):
             if action == "accumulate":
+                if self.derived:
+                    model.compute_derived(*self.derived)
                 self.recorder.accumulate(value)
             else:
                 self._record(model, value)
@@ -377,6 +391,8 @@ class OutputWriter:
     def _record(self, model, time):
         if len(self.pending) >= self.slots:
             self._drain_one()
+        if self.derived:
+            model.compute_derived(*self.derived)
         slot = self.recorder.snapshot()
         self.pending.append((slot, float(time), int(model.clock.iteration)))
 

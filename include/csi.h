@@ -704,6 +704,94 @@ int32_t csi_output_release(csi_context* ctx, int32_t handle, int32_t slot);
 /* Waits for the context's stream and the copy stream, then frees the set; its handle may be handed out again. */
 int32_t csi_output_destroy(csi_context* ctx, int32_t handle);
 
+/* ---- derived fields and energy budget integrals ---------------------------------------------------------------------------------------
+ * What sea-ice dynamics runs are looked at through, computed on the device from the bound state: deformation maps (divergence, shear,
+ * total deformation -- the strain-rate invariants _compute_evp_viscosities! forms and drops, elasto_visco_plastic_rheology.jl:247-260),
+ * the ice speed, the stress state relative to the yield curve, the stress power, and the three sums of the reference's discrete energy
+ * budget (test/test_rheology_energy_budget.jl:77-88).  Nothing here changes another entry point: a context that never makes these
+ * calls launches exactly what it launched before.  One code serves STRICT and FAST, compiled without contraction, IEEE division and
+ * square root: both modes give the same bits (tests/derived_ref.py restates every formula below in NumPy).
+ *
+ * DERIVED FIELDS.  Seven further (c,c) slots of csi_field_bind, numbered from CSI_F_COUNT_TOTAL on so that every older id and count keeps
+ * its value.  The caller binds (Center, Center) parents to the slots it wants; csi_derived_compute(ctx, mask) fills the INTERIOR
+ * i = 1 .. Nx, j = 1 .. Ny of every requested one in ONE launch on the context's stream (no atomics, no flags, no wait; their halos are
+ * never written).  mask: bit (slot - CSI_F_D_DIVERGENCE), i.e. the CSI_DERIVED_* values.  With the reference's operators, in the
+ * operation order of the library's strict-order kernels (csrc/evp_strict.hip; oracle/csi_oracle.c):
+ *   e11 = strain_rate_xx(i, j), e22 = strain_rate_yy(i, j)              (elasto_visco_plastic_rheology.jl:365-375)
+ *   e12(p, q) = strain_rate_xy at the corner (p, q), p = i, i + 1, q = j, j + 1
+ *   Ixy(f) = ((f(i, j) + f(i + 1, j)) / 2 + (f(i, j + 1) + f(i + 1, j + 1)) / 2) / 2      (the order of epsilon12^ccc, :250)
+ *   DIVERGENCE   = e11 + e22
+ *   SHEAR        = sqrt((e11 - e22) * (e11 - e22) + 4 * (e12c * e12c)),  e12c = Ixy(e12)      (the reference's s^ccc, :259)
+ *   DEFORMATION  = sqrt(DIVERGENCE * DIVERGENCE + SHEAR * SHEAR)      (defined here: NOT the reference's Delta, which carries e^-2 and a floor)
+ *   SPEED        = sqrt(uc * uc + vc * vc),  uc = (u[i, j] + u[i + 1, j]) / 2,  vc = (v[i, j] + v[i, j + 1]) / 2
+ *   stress group (needs CSI_F_S11, CSI_F_S22, CSI_F_S12, CSI_F_P: an EVP model; otherwise CSI_ERR_NOT_BOUND naming sigma11):
+ *   SIGMA_I      = ((sigma11 + sigma22) / 2) / P
+ *   SIGMA_II     = sqrt(((sigma11 - sigma22) / 2) * ((sigma11 - sigma22) / 2) + s12c * s12c) / P,  s12c = Ixy(sigma12)
+ *                  P is the bound CSI_F_P as it stands -- the strength the stresses were relaxed against at the last momentum step --,
+ *                  not recomputed from h and aice.  Where P == 0 both are +0.0.
+ *   STRESS_POWER = (sigma11 * e11 + sigma22 * e22) + 2 * Ixy(sigma12 * e12)      (each corner's product rounded before the average)
+ *   sigma12 is read as stored (no immersed conditional).  With a mask set (csi_mask_set) inactive centres receive +0.0 in every field.
+ * HALO ELEMENTS READ (the entry point fills none): u at columns 1 .. Nx + 1, rows 0 .. Ny + 1; v at columns 0 .. Nx + 1, rows
+ * 1 .. Ny + 1; sigma12 at columns 1 .. Nx + 1, rows 1 .. Ny + 1; sigma11, sigma22, P at the interior only; the mask at the interior
+ * only.  On a Bounded high side column Nx + 1 / row Ny + 1 of a Face field is its last face, elsewhere the first halo element.  Nothing
+ * else outside the interior is read, whatever it holds.  csi_update_state and every step entry point (csi_time_step_fe / _rk3, which end
+ * each stage with update_state!; csi_time_step_momentum, whose velocity launches store their halo images and whose finalize_rheology!
+ * fills sigma's locally and exchanges them between tiles, csrc/csi_launch.hip do_finalize) leave these elements valid: locally filled on
+ * periodic, wall and fold sides, exchanged on connected sides.  (On a tiled context csi_time_step_momentum called on its own is followed
+ * by csi_update_state, as everywhere: the velocities beyond a connected side are update_state!'s to exchange.)
+ * Tiled contexts: the call is rank-local, no communication; on a north fold the halo images already carry the sign.
+ * Errors: CSI_ERR_INVALID_ARGUMENT for mask == 0 or an unknown bit and for a grid without halo; CSI_ERR_NOT_BOUND naming u, v, sigma11
+ * ..., or the derived slot ("divergence", "shear", "deformation", "speed", "sigma_I", "sigma_II", "stress_power") that is requested but
+ * not bound.
+ *
+ * ENERGY BUDGET.  csi_budget_compute(ctx, what, out): sums over i = 1 .. Nx, j = 1 .. Ny, by the two-launch scheme of the device
+ * diagnostics and in its SUMMATION ORDER (stated above; one term per cell and sum, formed as written here), followed by a copy of the
+ * three slots to page-locked memory and a wait for the stream.
+ * CSI_BUDGET_STRESS (needs u, v, sigma11, sigma22, sigma12):
+ *   internal_work = sum ((u * d1) * Az^fc + (v * d2) * Az^cf),  d1 = d_j sigma_1j(i, j), d2 = d_j sigma_2j(i, j) of
+ *                   ice_stress_divergence.jl:39-51 with its immersed conditionals (a stress at an immersed peripheral node counts as 0)
+ *   stress_power  = sum (((sigma11 * e11) * Az^cc + (sigma22 * e22) * Az^cc) + ((2 * sigma12) * e12(i, j)) * Az^ff)
+ *   On grids without a mask, with fields that vanish on and beyond the walls (or periodic ones), internal_work = -stress_power to
+ *   rounding: the reference's adjoint identity (its test asserts |W + D| / max(|W|, |D|) < 1e-10).  With land it does not close.
+ * CSI_BUDGET_KINETIC (needs u, v, h, aice; the density is csi_evp_params.sea_ice_density, 900 before csi_evp_params_set):
+ *   kinetic_energy = sum (((0.5 * mu) * (u * u)) * Az^fc + ((0.5 * mv) * (v * v)) * Az^cf),  mu = (m[i - 1, j] + m[i, j]) / 2,
+ *                    mv = (m[i, j - 1] + m[i, j]) / 2,  m = h * rho * aice as the velocity kernels form it (ClimaSeaIce.jl:42)
+ * Members of a group that was not requested hold NaN.  Elements read outside the interior: u row 0, v column 0, sigma11 / sigma22 / h /
+ * aice column 0 and row 0, sigma12 column Nx + 1 and row Ny + 1, the mask one element around (the same guarantee as above).
+ * The work of the external stresses is not computed.  Tiled contexts: COLLECTIVE, all-gathered and added in rank order exactly as the
+ * diagnostics' sums; all ranks return the same bits.  Errors by name as for the diagnostics.
+ * csi_derived_stats: launches of the derived-field kernel and budget calls made on the context so far (tests; either pointer may be NULL). */
+typedef enum {
+    CSI_F_D_DIVERGENCE = CSI_F_COUNT_TOTAL,
+    CSI_F_D_SHEAR,
+    CSI_F_D_DEFORMATION,
+    CSI_F_D_SPEED,
+    CSI_F_D_SIGMA_I,
+    CSI_F_D_SIGMA_II,
+    CSI_F_D_STRESS_POWER,
+    CSI_F_COUNT_DERIVED                     /* every slot csi_field_bind takes, the derived ones included */
+} csi_derived_field_id;
+#define CSI_DERIVED_DIVERGENCE 1
+#define CSI_DERIVED_SHEAR 2
+#define CSI_DERIVED_DEFORMATION 4
+#define CSI_DERIVED_SPEED 8
+#define CSI_DERIVED_SIGMA_I 16
+#define CSI_DERIVED_SIGMA_II 32
+#define CSI_DERIVED_STRESS_POWER 64
+#define CSI_DERIVED_ALL 127
+int32_t csi_derived_compute(csi_context* ctx, int32_t mask);
+#define CSI_BUDGET_STRESS 1
+#define CSI_BUDGET_KINETIC 2
+#define CSI_BUDGET_ALL 3
+typedef struct {
+    int32_t what;                  /* echo of the request */
+    int32_t reserved;
+    double internal_work, stress_power;   /* CSI_BUDGET_STRESS */
+    double kinetic_energy;                /* CSI_BUDGET_KINETIC */
+} csi_budget;
+int32_t csi_budget_compute(csi_context* ctx, int32_t what, csi_budget* out);
+int32_t csi_derived_stats(csi_context* ctx, int64_t* derived_launches, int64_t* budget_calls);
+
 /* ---- rheology and momentum solver (SeaIceMomentumEquation(grid; rheology, solver), sea_ice_momentum_equations.jl:67-94) ------------
  * Defaults: CSI_RHEOLOGY_EVP with CSI_SOLVER_SPLIT_EXPLICIT -- the library's EVP path, unchanged by these calls.  The scalars both
  * rheologies share (minimum mass / concentration, sea_ice_density, FPlane f) still come from csi_evp_params_set, which marks the model

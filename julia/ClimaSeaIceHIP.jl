@@ -61,6 +61,13 @@ struct CsiDiagnostics
     extent_threshold::Cdouble
 end
 
+# csi_budget (include/csi.h): the energy budget integrals; members of a group that was not requested hold NaN
+struct CsiBudget
+    what::Int32; reserved::Int32
+    internal_work::Cdouble; stress_power::Cdouble
+    kinetic_energy::Cdouble
+end
+
 # csi_output_field (include/csi.h): one field of an output set
 struct CsiOutputField
     field_id::Int32; dtype::Int32; averaged::Int32; masked::Int32
@@ -74,6 +81,9 @@ const F = (U=0, V=1, H=2, A=3, S11=4, S22=5, S12=6, UN=7, VN=8, P=9, ALPHA=10, D
            GU=34, GV=35,
            # csi_thermo_field_id (from CSI_F_COUNT on) and csi_free_drift_field_id (from CSI_F_COUNT_ALL on)
            TOP_HEAT_FLUX=36, BOTTOM_HEAT_FLUX=37, SNOWFALL=38, FREE_DRIFT_U=39, FREE_DRIFT_V=40)
+
+# csi_derived_field_id (from CSI_F_COUNT_TOTAL on): the derived (Center, Center) fields; bit k of csi_derived_compute's mask is slot 41 + k
+const DERIVED = (divergence=41, shear=42, deformation=43, speed=44, sigma_I=45, sigma_II=46, stress_power=47)
 
 mutable struct Context
     handle::Ptr{Cvoid}
@@ -681,6 +691,47 @@ end
 
 # cell_advection_timescale(model::SeaIceModel), src/ClimaSeaIce.jl:63-69 -- what a TimeStepWizard calls: the velocity group alone
 Oceananigans.Advection.cell_advection_timescale(model::HIPSeaIceModel) = diagnostics(model; what = 1).advection_timescale
+
+# ---- derived fields and energy budget integrals (include/csi.h: csi_derived_compute, csi_budget_compute) ------------------------------
+# derived!(model, :shear, :divergence, ...) fills the named (Center, Center) fields -- allocated on the model's grid and bound to their
+# slots the first time they are asked for, kept in DERIVED_FIELDS -- with ONE launch on the context's stream: the strain-rate invariants
+# that _compute_evp_viscosities! forms and drops (elasto_visco_plastic_rheology.jl:247-260), the ice speed and, for an EVP model, the
+# stress state relative to the strength of the last momentum step and the stress power.  Nothing is copied or waited for.  Returns the
+# fields in the order of the names.  Rank-local on a Distributed grid.
+const DERIVED_FIELDS = IdDict{Any, Dict{Symbol, Any}}()
+
+function derived_field!(model::HIPSeaIceModel, name::Symbol)
+    haskey(DERIVED, name) || error("derived field: one of $(keys(DERIVED)) is needed, got $name")
+    fields = get!(DERIVED_FIELDS, model, Dict{Symbol, Any}())
+    return get!(fields, name) do
+        f = CenterField(model.grid)
+        bind!(context(model), Int32(DERIVED[name]), f)
+        f
+    end
+end
+
+function derived!(model::HIPSeaIceModel, names::Symbol...)
+    isempty(names) && error("derived!: name at least one of $(keys(DERIVED))")
+    ctx = context(model)
+    fields = [derived_field!(model, n) for n in names]
+    mask = Int32(0)
+    for n in names
+        mask |= Int32(1) << (DERIVED[n] - DERIVED.divergence)
+    end
+    GC.@preserve model fields check(ctx, ccall((:csi_derived_compute, libcsi), Int32, (Ptr{Cvoid}, Int32), ctx.handle, mask))
+    return fields
+end
+
+# The three sums of test/test_rheology_energy_budget.jl:77-88 and the kinetic energy on the device, in the diagnostics' summation order:
+# `what` 1 the stress group (internal_work, stress_power), 2 the kinetic energy, 3 both.  COLLECTIVE on a Distributed grid.
+function energy_budget(model::HIPSeaIceModel; what = 3)
+    ctx = context(model)
+    out = Ref{CsiBudget}()
+    GC.@preserve model check(ctx, ccall((:csi_budget_compute, libcsi), Int32, (Ptr{Cvoid}, Int32, Ptr{CsiBudget}), ctx.handle, Int32(what), out))
+    b = out[]
+    W, D = b.internal_work, b.stress_power
+    return (; internal_work = W, stress_power = D, imbalance = abs(W + D) / max(abs(W), abs(D)), kinetic_energy = b.kinetic_energy)
+end
 
 # ---- device-side output (include/csi.h: csi_output_*) ---------------------------------------------------------------------------------
 # Stands where a Simulation carries a JLD2Writer (examples/ice_advected_by_anticyclone.jl:161-163).  An OutputSet packs the interiors of
