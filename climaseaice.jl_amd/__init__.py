@@ -16,6 +16,7 @@ from .grids import (Bounded, Center, Face, Flat, FullyConnected, LatitudeLongitu
                     RectilinearGrid, RightConnected, TileGrid, TripolarGrid)
 from .diagnostics import Diagnostics, TimeStepWizard, assert_finite, cell_advection_timescale, new_time_step
 from .derived import DERIVED_NAMES, EnergyBudget
+from .momentum_terms import MOMENTUM_TERMS, TERM_FIELD_NAMES, MomentumBudget
 from .output import (AveragedTimeInterval, IterationInterval, OutputWriter, TimeInterval, aligned_time_step, bound_fields,
                      load_output)
 from .time_series import Clamp, Cyclical, FieldTimeSeries, InMemory, Linear

@@ -25,11 +25,18 @@ F = {n: k for k, n in enumerate(FIELD_IDS + THERMO_FIELD_IDS + FREE_DRIFT_FIELD_
 # csi_derived_field_id: the seven derived (c,c) fields, numbered from CSI_F_COUNT_TOTAL = len(F) on (F itself keeps its extent)
 DERIVED_FIELD_IDS = ["D_DIVERGENCE", "D_SHEAR", "D_DEFORMATION", "D_SPEED", "D_SIGMA_I", "D_SIGMA_II", "D_STRESS_POWER"]
 F_DERIVED = {n: len(F) + k for k, n in enumerate(DERIVED_FIELD_IDS)}
+# csi_momentum_term_field_id: the ten momentum term fields, _X / _Y of each term, numbered from CSI_F_COUNT_DERIVED on
+MOMENTUM_TERM_FIELD_IDS = ["M_CORIOLIS_X", "M_CORIOLIS_Y", "M_TOP_X", "M_TOP_Y", "M_BOTTOM_X", "M_BOTTOM_Y", "M_INTERNAL_X", "M_INTERNAL_Y",
+                           "M_FORCING_X", "M_FORCING_Y"]
+F_MOMENTUM_TERMS = {n: len(F) + len(F_DERIVED) + k for k, n in enumerate(MOMENTUM_TERM_FIELD_IDS)}
+F_COUNT_BINDABLE = len(F) + len(F_DERIVED) + len(F_MOMENTUM_TERMS)
 
 
 def slot_id(name):
-    """The number of a csi_field_bind slot by name: F, or one of the derived fields' slots."""
-    return F[name] if name in F else F_DERIVED[name]
+    """The number of a csi_field_bind slot by name: F, or one of the derived fields' or momentum term fields' slots."""
+    if name in F:
+        return F[name]
+    return F_DERIVED[name] if name in F_DERIVED else F_MOMENTUM_TERMS[name]
 
 
 STRESS_NONE, STRESS_CONST, STRESS_FIELD, STRESS_SEMI_IMPLICIT = 0, 1, 2, 3
@@ -66,11 +73,14 @@ SYMBOLS = ["csi_version", "csi_context_create", "csi_context_destroy", "csi_last
            "csi_diagnostics_compute",
            "csi_output_plan_layout", "csi_output_create", "csi_output_layout", "csi_output_record_bytes", "csi_output_accumulate",
            "csi_output_snapshot", "csi_output_test", "csi_output_wait", "csi_output_release", "csi_output_destroy",
-           "csi_derived_compute", "csi_budget_compute", "csi_derived_stats"]
+           "csi_derived_compute", "csi_budget_compute", "csi_derived_stats",
+           "csi_momentum_terms_compute", "csi_momentum_budget_compute", "csi_momentum_terms_stats"]
 DIAG_VELOCITY, DIAG_TRACERS, DIAG_ALL = 1, 2, 3
 OUT_F64, OUT_F32 = 0, 1
 DERIVED_ALL = 127
 BUDGET_STRESS, BUDGET_KINETIC, BUDGET_ALL = 1, 2, 3
+MTERM_CORIOLIS, MTERM_TOP, MTERM_BOTTOM, MTERM_INTERNAL, MTERM_FORCING, MTERM_ALL, MTERM_RAW_STRESS = 1, 2, 4, 8, 16, 31, 32
+MBUDGET_EXTERNAL, MBUDGET_BODY, MBUDGET_INTERNAL, MBUDGET_ALL = 1, 2, 4, 7
 OUTPUT_MAX_FIELDS, OUTPUT_MAX_SETS, OUTPUT_MAX_SLOTS = 16, 4, 64
 
 
@@ -142,6 +152,12 @@ class Budget(C.Structure):
     """csi_budget (include/csi.h): members of a group that was not requested hold NaN."""
     _fields_ = [("what", C.c_int32), ("reserved", C.c_int32), ("internal_work", C.c_double), ("stress_power", C.c_double),
                 ("kinetic_energy", C.c_double)]
+
+
+class MomentumBudget(C.Structure):
+    """csi_momentum_budget (include/csi.h): members of a group that was not requested hold NaN."""
+    _fields_ = [("what", C.c_int32), ("reserved", C.c_int32), ("coriolis", C.c_double), ("top", C.c_double), ("bottom", C.c_double),
+                ("internal", C.c_double), ("forcing", C.c_double)]
 
 
 class OutputField(C.Structure):
@@ -233,6 +249,8 @@ def load():
         "csi_output_release": [vp, i32, i32], "csi_output_destroy": [vp, i32],
         "csi_derived_compute": [vp, i32], "csi_budget_compute": [vp, i32, C.POINTER(Budget)],
         "csi_derived_stats": [vp, C.POINTER(i64), C.POINTER(i64)],
+        "csi_momentum_terms_compute": [vp, i32], "csi_momentum_budget_compute": [vp, i32, C.POINTER(MomentumBudget)],
+        "csi_momentum_terms_stats": [vp, C.POINTER(i64), C.POINTER(i64)],
     }
     for name, args in sig.items():
         fn = getattr(L, name, None)
@@ -463,6 +481,24 @@ class Context:
         """(launches of the derived-field kernel, budget calls) made on this context so far."""
         a, b = C.c_int64(), C.c_int64()
         self.call("csi_derived_stats", C.byref(a), C.byref(b))
+        return a.value, b.value
+
+    # ---- momentum balance terms, interface stresses and their power (include/csi.h) ------------------------------------------------
+    def momentum_terms_compute(self, mask):
+        """csi_momentum_terms_compute: every requested term field in ONE launch on the context's stream (nothing is waited for)."""
+        self.call("csi_momentum_terms_compute", int(mask))
+
+    def momentum_budget_compute(self, what):
+        """csi_momentum_budget_compute: the filled csi_momentum_budget (two launches and one small copy; waits for the context's stream;
+        collective on a tiled context)."""
+        b = MomentumBudget()
+        self.call("csi_momentum_budget_compute", int(what), C.byref(b))
+        return b
+
+    def momentum_terms_stats(self):
+        """(launches of the term kernel, power calls) made on this context so far."""
+        a, b = C.c_int64(), C.c_int64()
+        self.call("csi_momentum_terms_stats", C.byref(a), C.byref(b))
         return a.value, b.value
 
     # ---- device-side output (include/csi.h, csi_output_*) -------------------------------------------------------------------------

@@ -9,6 +9,7 @@
 //   csi_diagnostics.hip   device diagnostics: the two launches, the result copy, the combine over the ranks of a decomposition
 //   csi_output.hip        device-side output: output sets, their staging slots, the copy stream and the slot events
 //   csi_derived.hip       derived fields and energy budget integrals: binding checks, the launches, the budget's combine over the ranks
+//   csi_momentum_terms.hip   momentum balance terms and their power: binding checks, the launches, the power sums' combine over the ranks
 //   csi_mem.h       DeviceBuf / PinnedBuf: the owner of every allocation the library makes
 #pragma once
 #include "../../include/csi.h"
@@ -44,7 +45,7 @@ struct Bound {
 };
 
 // (x, y) location of every field slot
-static const int kLoc[CSI_F_COUNT_DERIVED][2] = {
+static const int kLoc[CSI_F_COUNT_BINDABLE][2] = {
     {LOC_F, LOC_C}, {LOC_C, LOC_F}, {LOC_C, LOC_C}, {LOC_C, LOC_C},   // U V H A
     {LOC_C, LOC_C}, {LOC_C, LOC_C}, {LOC_F, LOC_F},                   // S11 S22 S12
     {LOC_F, LOC_C}, {LOC_C, LOC_F}, {LOC_C, LOC_C}, {LOC_C, LOC_C}, {LOC_C, LOC_C},  // UN VN P ALPHA DELTA
@@ -59,13 +60,17 @@ static const int kLoc[CSI_F_COUNT_DERIVED][2] = {
     {LOC_F, LOC_C}, {LOC_C, LOC_F},                                   // GU GV
     {LOC_C, LOC_C}, {LOC_C, LOC_C}, {LOC_C, LOC_C},                   // TOP_HEAT_FLUX BOTTOM_HEAT_FLUX SNOWFALL
     {LOC_F, LOC_C}, {LOC_C, LOC_F},                                   // FREE_DRIFT_U FREE_DRIFT_V
-    {LOC_C, LOC_C}, {LOC_C, LOC_C}, {LOC_C, LOC_C}, {LOC_C, LOC_C}, {LOC_C, LOC_C}, {LOC_C, LOC_C}, {LOC_C, LOC_C}};   // the seven derived fields
-static const char* const kName[CSI_F_COUNT_DERIVED] = {"u", "v", "h", "aice", "sigma11", "sigma22", "sigma12", "un", "vn", "P", "alpha",
+    {LOC_C, LOC_C}, {LOC_C, LOC_C}, {LOC_C, LOC_C}, {LOC_C, LOC_C}, {LOC_C, LOC_C}, {LOC_C, LOC_C}, {LOC_C, LOC_C},    // the seven derived fields
+    {LOC_F, LOC_C}, {LOC_C, LOC_F}, {LOC_F, LOC_C}, {LOC_C, LOC_F}, {LOC_F, LOC_C}, {LOC_C, LOC_F}, {LOC_F, LOC_C}, {LOC_C, LOC_F},
+    {LOC_F, LOC_C}, {LOC_C, LOC_F}};                                  // the ten momentum term fields: _X, _Y of each term
+static const char* const kName[CSI_F_COUNT_BINDABLE] = {"u", "v", "h", "aice", "sigma11", "sigma22", "sigma12", "un", "vn", "P", "alpha",
                                   "Delta", "zeta_f", "zeta_c", "Gh", "Gaice", "h-", "aice-", "u-", "v-",
                                   "top_u", "top_v", "bottom_u", "bottom_v", "mass_flux",
                                   "hs", "Ghs", "hs-", "mass_flux_snow", "intercepted_snowfall", "Tu", "Tu_snow", "forcing_u", "forcing_v", "Gu", "Gv",
                                   "top_heat_flux", "bottom_heat_flux", "snowfall", "free_drift_u", "free_drift_v",
-                                  "divergence", "shear", "deformation", "speed", "sigma_I", "sigma_II", "stress_power"};
+                                  "divergence", "shear", "deformation", "speed", "sigma_I", "sigma_II", "stress_power",
+                                  "coriolis_x", "coriolis_y", "top_x", "top_y", "bottom_x", "bottom_y", "internal_x", "internal_y",
+                                  "forcing_x", "forcing_y"};
 
 extern std::string g_create_error;      // csi_context_create failures (no context to hold the message)
 
@@ -176,7 +181,7 @@ struct csi_context {
     long fcor2_ld = 0, fcor2_plane = 0;
     bool cor_dirty = true;               // Coriolis columns of the FAST table need (re)building
     double cor_synced = 0.0;             // FPlane value they were built with
-    Bound f[CSI_F_COUNT_DERIVED];
+    Bound f[CSI_F_COUNT_BINDABLE];
     csi_evp_params evp{};
     csi_stress stress[2]{};
     int mode = CSI_MODE_STRICT;
@@ -282,6 +287,11 @@ struct csi_context {
     DeviceBuf<double> budget_part;
     PinnedBuf<double> budget_host;
     int64_t derived_launches = 0, budget_calls = 0;
+    // csi_momentum_terms_compute / csi_momentum_budget_compute (csi_momentum_terms.hip): the power sums' partial records followed by
+    // their MQ_COUNT result slots, the page-locked copy, and the calls made so far (csi_momentum_terms_stats)
+    DeviceBuf<double> mterm_part;
+    PinnedBuf<double> mterm_host;
+    int64_t mterm_launches = 0, mterm_budget_calls = 0;
     // csi_output_* (csi_output.hip): the sets and the copy stream their records leave on, made at the first csi_output_create
     OutputSet out_sets[kMaxOutputSets];
     hipStream_t out_stream = nullptr;

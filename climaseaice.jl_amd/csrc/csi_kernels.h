@@ -282,6 +282,24 @@ struct BudgetDev {
 };
 void launch_budget(const BudgetDev& D, bool stress, bool kin, double* out, hipStream_t s);
 
+// momentum balance terms and their power (momentum_terms.hip; include/csi.h csi_momentum_terms_compute / csi_momentum_budget_compute).
+// out[2 * t] / out[2 * t + 1]: the arrays bound to the _X / _Y slot of term t as (0, 0)-offset references, p == nullptr where the slot is
+// not requested.  The power sums: the diagnostics' two launches and record layout (slot q of record r at part[q * nrec + r]).
+enum : int { MQ_CORIOLIS = 0, MQ_TOP, MQ_BOTTOM, MQ_INTERNAL, MQ_FORCING, MQ_COUNT };
+struct MomTermsDev {
+    EvpDev P;                  // grid, u, v, h, aice, sigma (unused by the viscous instantiation), stresses, Coriolis, forcing, rho
+    double nu;                 // ViscousRheology(nu)
+    FRef out[2 * MQ_COUNT];
+    int exu, eyv;              // 1: u has the faces i = Nx + 1 / v the faces j = Ny + 1 (the high side is a wall)
+    int no_internal;           // the internal term is +0.0: free-drift dynamics (no rheology), or the term is not requested
+    int raw_stress;            // TOP / BOTTOM receive tau itself
+    double* part;              // power: partial records
+    long nrec;
+};
+// visc: sigma = nu * delta u inline and no load of the stored stresses (also chosen where the internal term is off)
+void launch_momentum_terms(const MomTermsDev& T, bool visc, hipStream_t s);
+void launch_momentum_power(const MomTermsDev& T, bool visc, double* out, hipStream_t s);
+
 // device-side output (output.hip; include/csi.h csi_output_accumulate / csi_output_snapshot): every field of a set in ONE launch.  A
 // descriptor: the first INTERIOR element of the bound array and its row stride in doubles, the dense (ny, nx) accumulator of an
 // averaged field, the field's place in the staging slot, the interior extents.  accumulate: w = the weight, the table holds the

@@ -326,6 +326,7 @@ class SeaIceModel:
         self._stress_fields = {}
         self._free_drift_fields = {}
         self._derived_fields = {}           # name -> CenterField of the derived fields asked for so far (derived_field)
+        self._momentum_term_fields = {}     # name -> XFaceField / YFaceField of the momentum term fields asked for so far (momentum_term)
         self._series, self._pending_series = {}, []     # slot name -> what csi_time_series_set was given (kept alive)
         self.ctx = _lib.Context(dev.index or 0, stream)
         self._configure()
@@ -826,6 +827,48 @@ class SeaIceModel:
         model.  Returns an immutable EnergyBudget record."""
         from .derived import energy_budget
         return energy_budget(self, what)
+
+    # ---- momentum balance terms, interface stresses and their power (momentum_terms.py; include/csi.h) -----------------------------
+    def momentum_term(self, name):
+        """The field of one component of a momentum balance term -- "coriolis_x", "top_y", "bottom_x", "internal_y", "forcing_x", ...: a
+        force per unit area at the u (_x) or v (_y) points --, allocated and bound to its slot the first time it is asked for.
+        compute_momentum_terms fills its interior."""
+        from .momentum_terms import location_of, slot_of
+        if name not in self._momentum_term_fields:
+            slot = slot_of(name)
+            fld = Field(location_of(name), self.grid, self.device, name)
+            torch.cuda.synchronize(self.device)      # (the zero fill ran on torch's stream)
+            self._bind(slot, fld)
+            self._momentum_term_fields[name] = fld
+        return self._momentum_term_fields[name]
+
+    def compute_momentum_terms(self, *names):
+        """Fill the named term fields from the current state, all in ONE launch on the library's stream (no copy, no wait;
+        synchronize() before reading them with torch / numpy).  A term's name without a component ("top") stands for both.  Returns
+        the fields in the order of the names, x before y."""
+        from .momentum_terms import expand, mask_of, terms_of
+        mask = mask_of(names)
+        fields = [self.momentum_term(n) for n in expand(names)]
+        for n in expand(terms_of(mask)):              # a bit selects both components: both slots are bound
+            self.momentum_term(n)
+        self.ctx.momentum_terms_compute(mask)
+        return fields
+
+    def interface_stress(self, side):
+        """(tau_x, tau_y) of side = "top" (air-ice) or "bottom" (ocean-ice): the reference's x_momentum_stress / y_momentum_stress
+        (explicit - implicit * u) at the u / v points, in N m^-2.  The device computes them as the TOP / BOTTOM term slots without
+        the interpolated-concentration factor and the sign, by a flag of the same launch: the fields returned ARE model.momentum_term
+        (side + "_x" / "_y") and hold the stresses until the next compute_momentum_terms of that term.  The ocean receives
+        -compute_momentum_terms("bottom"), the area-weighted force, not this bare stress."""
+        from .momentum_terms import interface_stress
+        return interface_stress(self, side)
+
+    def momentum_budget(self, what="all"):
+        """The power of each term of the momentum balance, sum u F_x Az + v F_y Az, summed on the device in the diagnostics' order
+        (momentum_terms.py): what = "all", "external", "body", "internal" or a tuple.  Waits for the library's stream; collective on a
+        tiled model.  Returns an immutable MomentumBudget record."""
+        from .momentum_terms import momentum_budget
+        return momentum_budget(self, what)
 
     def synchronize(self):
         """Wait for the library's stream (call before reading fields with torch / numpy)."""

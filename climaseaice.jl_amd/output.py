@@ -199,6 +199,9 @@ def bound_fields(model):
     from .derived import slot_of
     for name, f in getattr(model, "_derived_fields", {}).items():      # derived fields, once allocated (model.derived_field)
         out[name] = (f, slot_of(name))
+    from .momentum_terms import slot_of as term_slot_of
+    for name, f in getattr(model, "_momentum_term_fields", {}).items():      # momentum term fields, once allocated (model.momentum_term)
+        out[name] = (f, term_slot_of(name))
     return out
 
 
@@ -272,7 +275,8 @@ class OutputWriter:
 
     outputs   a dict name -> Field, or a list of names, of fields the model has bound to its context (bound_fields(model)); anything
               else is refused by name.  The names of the derived fields ("shear", "divergence", ...: derived.py) may appear in a list:
-              they are allocated here and computed on the device immediately before every accumulate and snapshot
+              they are allocated here and computed on the device immediately before every accumulate and snapshot; so are
+              the momentum term fields ("top_x", "internal_y", ...: momentum_terms.py)
     schedule  IterationInterval, TimeInterval (snapshots) or AveragedTimeInterval (every output is a time average)
     dtype     "f32" (round to nearest even on the device) or "f64"
     mask      True: (Center, Center) outputs take fill_value in the inactive cells of the model's mask
@@ -295,6 +299,11 @@ class OutputWriter:
             for name in outputs:                     # a derived field named in a list is allocated and bound here
                 if name in DERIVED_NAMES:
                     model.derived_field(name)
+        from .momentum_terms import TERM_FIELD_NAMES, name_of_slot as term_name_of_slot
+        if not isinstance(outputs, dict) and hasattr(model, "momentum_term"):
+            for name in outputs:                     # ... and so is a momentum term field
+                if name in TERM_FIELD_NAMES:
+                    model.momentum_term(name)
         bound = recorder.bound_fields(model)
         if isinstance(outputs, dict):
             items = []
@@ -323,6 +332,8 @@ class OutputWriter:
         # derived outputs: computed (model.compute_derived, one launch) immediately before every accumulate and snapshot; a writer
         # without them makes no such call
         self.derived = tuple(name_of_slot(slot) for _, _, slot in items if name_of_slot(slot) is not None)
+        # momentum term outputs likewise (model.compute_momentum_terms, one launch for all of them)
+        self.momentum_terms = tuple(term_name_of_slot(slot) for _, _, slot in items if term_name_of_slot(slot) is not None)
         self.dir = os.path.join(dir, f"rank_{g.rank}") if isinstance(g, TileGrid) else dir
         if os.path.exists(self.dir):
             if not overwrite_existing:
@@ -371,6 +382,8 @@ class OutputWriter:
             if action == "accumulate":
                 if self.derived:
                     model.compute_derived(*self.derived)
+                if self.momentum_terms:
+                    model.compute_momentum_terms(*self.momentum_terms)
                 self.recorder.accumulate(value)
             else:
                 self._record(model, value)
@@ -393,6 +406,8 @@ class OutputWriter:
             self._drain_one()
         if self.derived:
             model.compute_derived(*self.derived)
+        if self.momentum_terms:
+            model.compute_momentum_terms(*self.momentum_terms)
         slot = self.recorder.snapshot()
         self.pending.append((slot, float(time), int(model.clock.iteration)))
 

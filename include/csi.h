@@ -792,6 +792,93 @@ typedef struct {
 int32_t csi_budget_compute(csi_context* ctx, int32_t what, csi_budget* out);
 int32_t csi_derived_stats(csi_context* ctx, int64_t* derived_launches, int64_t* budget_calls);
 
+/* ---- momentum balance terms, interface stresses and their power ------------------------------------------------------------------------
+ * Which forces balance where, and what stress the ice puts on the ocean: every term of u_velocity_tendency / v_velocity_tendency
+ * (SeaIceDynamics/momentum_tendencies_kernel_functions.jl:11-74) kept as a force per unit area (N m^-2) at its velocity point, the
+ * reference's coupler-facing x_momentum_stress / y_momentum_stress (sea_ice_external_stress.jl:33-37, 162-174), and the power of each
+ * term.  Nothing here changes another entry point: a context that never makes these calls launches exactly what it launched before.
+ * One code serves STRICT and FAST, compiled without contraction, IEEE division and square root: both modes give the same bits
+ * (tests/momentum_terms_ref.py restates every formula below in NumPy).  Every dynamics configuration the library steps is served:
+ * EVP and ViscousRheology with either solver, free-drift dynamics (csi_dynamics_set), tiles and north folds.
+ *
+ * TERM FIELDS.  Ten further slots of csi_field_bind, numbered from CSI_F_COUNT_DERIVED on so that every older id and count keeps its
+ * value: five per component, the _X slots at (Face, Center) with parent extents like u, the _Y slots at (Center, Face) like v.
+ * csi_momentum_terms_compute(ctx, mask) fills the INTERIOR of every requested, bound slot -- i = 1 .. Nx (+ 1: the last face of a
+ * Bounded x side), j = 1 .. Ny for _X; i = 1 .. Nx, j = 1 .. Ny (+ 1) for _Y -- in ONE launch on the context's stream (no atomics, no
+ * flags, no wait; halos are never written).  mask: CSI_MTERM_* bits, a bit selects both components.  At the u point (i, j), in this
+ * order (the v point analogous with j - 1 for i - 1, y_f_cross_U = f * Ixy(u) and the _2j operators):
+ *   m_i  = (h[i-1, j] * rho * aice[i-1, j] + h[i, j] * rho * aice[i, j]) / 2          (u_velocity_tendency:28; rho: csi_evp_params
+ *   a_i  = (aice[i-1, j] + aice[i, j]) / 2                                    (:29)     .sea_ice_density, 900 before csi_evp_params_set)
+ *   Ixy(v) = ((v[i-1, j] + v[i, j]) / 2 + (v[i-1, j+1] + v[i, j+1]) / 2) / 2
+ *   CORIOLIS_X = m_i * (-x_f_cross_U),  x_f_cross_U = -f * Ixy(v)      (the term with the sign it has in G^U; +0.0 without Coriolis)
+ *   TOP_X      = -(a_i * tau_top)
+ *   BOTTOM_X   = a_i * tau_bottom            (its negative is the stress the ocean receives)
+ *   INTERNAL_X = d_j sigma_1j + immersed_d_j sigma_1j      (ice_stress_divergence.jl:36-44, 65-92: conditional fluxes and immersed flux
+ *                boundary conditions as in the tendency; ViscousRheology: sigma = nu * delta u; free-drift dynamics: +0.0)
+ *   (free-drift dynamics, csi_dynamics_set(ctx, CSI_DYNAMICS_FREE_DRIFT): StressBalanceFreeDrift carries neither a rheology nor a
+ *    Coriolis term -- INTERNAL and CORIOLIS are +0.0 there, whatever csi_evp_params_set was given)
+ *   FORCING_X  = m_i * model.forcing.u[i, j]      (CSI_F_FORCING_U, the user array only -- not the pseudo-time term of the EVP
+ *                sum_of_forcing_u; +0.0 without arrays)
+ *   tau = x_momentum_stress of the stress kind: CSI_STRESS_NONE 0; CSI_STRESS_CONST the number; CSI_STRESS_FIELD the array at the
+ *         point; CSI_STRESS_SEMI_IMPLICIT ((rho_e * C_D) * sqrt(du * du + dv * dv)) * du, du = u_e[i, j] - u[i, j],
+ *         dv = Ixy(v_e) - Ixy(v)      (:162-174: explicit - implicit * u in one product)
+ *   Every slot is +0.0 where m_i <= 0 and at a peripheral velocity node (a wall face, a face next to land, the last face of a Bounded
+ *   side).  With CSI_MTERM_RAW_STRESS in the mask the TOP and BOTTOM slots receive tau_top and tau_bottom themselves -- the interface
+ *   stresses x_momentum_stress / y_momentum_stress, without the a_i factor and the sign, zero at the same points -- in the same launch.
+ *   Output arrays never alias inputs.
+ * HALO ELEMENTS READ (the entry point fills none): ONE RING around the own interior of u, v, h, aice, of sigma11, sigma22, sigma12
+ * (INTERNAL on an EVP model), of the stress / external-velocity arrays (CSI_F_TOP_U .. CSI_F_BOT_V) and of the forcing arrays, and of the
+ * mask; nothing beyond it, whatever it holds.  The step entry points (csi_time_step_fe / _rk3, free-drift dynamics included) and
+ * csi_update_state after csi_time_step_momentum leave these elements valid, as for csi_derived_compute; the stress and forcing arrays'
+ * rings are filled by every momentum step (update_external_stress!) or by csi_fill_halo_local.
+ * Required: u, v, h, aice; with INTERNAL on an EVP model sigma11, sigma22, sigma12; the arrays the stresses name.  Errors:
+ * CSI_ERR_NOT_BOUND naming the field, or the requested slot ("coriolis_x", ..., "forcing_y") that has no array;
+ * CSI_ERR_INVALID_ARGUMENT for mask == 0, a mask without a term bit, unknown bits and a grid with halo < 1.
+ * Tiled contexts: rank-local, no communication; on a north fold the halo images already carry the sign.
+ *
+ * POWER.  csi_momentum_budget_compute(ctx, what, out): for each term F the sum of (u * F_X) * Az^fc + (v * F_Y) * Az^cf over
+ * i = 1 .. Nx, j = 1 .. Ny (the last face of a Bounded side is a peripheral node: its terms are 0 and it is not added), the terms
+ * formed on the fly exactly as above (no slot needs to be bound; TOP and BOTTOM with the a_i factor and the sign).  The two-launch
+ * scheme and the SUMMATION ORDER of the device diagnostics and of csi_budget_compute: records of 64 x 64 cells, then a single-block
+ * fold -- a function of (Nx, Ny) alone.  what: CSI_MBUDGET_EXTERNAL (top, bottom), CSI_MBUDGET_BODY (coriolis, forcing),
+ * CSI_MBUDGET_INTERNAL (the only group that loads sigma); members of a group that was not requested hold NaN.  The sum of the five is
+ * the rate of change of kinetic energy the terms imply (no inertia term; an EVP sub-cycle does not close it per step).
+ * Requirements and errors as above, INTERNAL meaning the group.  Tiled contexts: COLLECTIVE, all-gathered and added in rank order
+ * exactly as csi_budget_compute; all ranks return the same bits; a rank that fails locally still reaches the all-gather.
+ * csi_momentum_terms_stats: launches of the term kernel and power calls made on the context so far (either pointer may be NULL). */
+typedef enum {
+    CSI_F_M_CORIOLIS_X = CSI_F_COUNT_DERIVED,
+    CSI_F_M_CORIOLIS_Y,
+    CSI_F_M_TOP_X,
+    CSI_F_M_TOP_Y,
+    CSI_F_M_BOTTOM_X,
+    CSI_F_M_BOTTOM_Y,
+    CSI_F_M_INTERNAL_X,
+    CSI_F_M_INTERNAL_Y,
+    CSI_F_M_FORCING_X,
+    CSI_F_M_FORCING_Y,
+    CSI_F_COUNT_BINDABLE                    /* every slot csi_field_bind takes */
+} csi_momentum_term_field_id;
+#define CSI_MTERM_CORIOLIS 1
+#define CSI_MTERM_TOP 2
+#define CSI_MTERM_BOTTOM 4
+#define CSI_MTERM_INTERNAL 8
+#define CSI_MTERM_FORCING 16
+#define CSI_MTERM_ALL 31
+#define CSI_MTERM_RAW_STRESS 32             /* flag: TOP / BOTTOM receive the interface stresses tau_top / tau_bottom */
+int32_t csi_momentum_terms_compute(csi_context* ctx, int32_t mask);
+#define CSI_MBUDGET_EXTERNAL 1
+#define CSI_MBUDGET_BODY 2
+#define CSI_MBUDGET_INTERNAL 4
+#define CSI_MBUDGET_ALL 7
+typedef struct {
+    int32_t what;                  /* echo of the request */
+    int32_t reserved;
+    double coriolis, top, bottom, internal, forcing;      /* W: BODY, EXTERNAL, EXTERNAL, INTERNAL, BODY */
+} csi_momentum_budget;
+int32_t csi_momentum_budget_compute(csi_context* ctx, int32_t what, csi_momentum_budget* out);
+int32_t csi_momentum_terms_stats(csi_context* ctx, int64_t* launches, int64_t* budget_calls);
+
 /* ---- rheology and momentum solver (SeaIceMomentumEquation(grid; rheology, solver), sea_ice_momentum_equations.jl:67-94) ------------
  * Defaults: CSI_RHEOLOGY_EVP with CSI_SOLVER_SPLIT_EXPLICIT -- the library's EVP path, unchanged by these calls.  The scalars both
  * rheologies share (minimum mass / concentration, sea_ice_density, FPlane f) still come from csi_evp_params_set, which marks the model

@@ -68,6 +68,12 @@ struct CsiBudget
     kinetic_energy::Cdouble
 end
 
+# csi_momentum_budget (include/csi.h): the power of each term of the momentum balance; members of a group that was not requested hold NaN
+struct CsiMomentumBudget
+    what::Int32; reserved::Int32
+    coriolis::Cdouble; top::Cdouble; bottom::Cdouble; internal::Cdouble; forcing::Cdouble
+end
+
 # csi_output_field (include/csi.h): one field of an output set
 struct CsiOutputField
     field_id::Int32; dtype::Int32; averaged::Int32; masked::Int32
@@ -84,6 +90,11 @@ const F = (U=0, V=1, H=2, A=3, S11=4, S22=5, S12=6, UN=7, VN=8, P=9, ALPHA=10, D
 
 # csi_derived_field_id (from CSI_F_COUNT_TOTAL on): the derived (Center, Center) fields; bit k of csi_derived_compute's mask is slot 41 + k
 const DERIVED = (divergence=41, shear=42, deformation=43, speed=44, sigma_I=45, sigma_II=46, stress_power=47)
+
+# csi_momentum_term_field_id (from CSI_F_COUNT_DERIVED on): the momentum term fields, _x at (Face, Center), _y at (Center, Face); bit k of
+# csi_momentum_terms_compute's mask selects the slots 48 + 2k and 49 + 2k
+const MOMENTUM_TERMS = (coriolis_x=48, coriolis_y=49, top_x=50, top_y=51, bottom_x=52, bottom_y=53, internal_x=54, internal_y=55, forcing_x=56, forcing_y=57)
+const MOMENTUM_TERM_BITS = (coriolis=1, top=2, bottom=4, internal=8, forcing=16)
 
 mutable struct Context
     handle::Ptr{Cvoid}
@@ -731,6 +742,50 @@ function energy_budget(model::HIPSeaIceModel; what = 3)
     b = out[]
     W, D = b.internal_work, b.stress_power
     return (; internal_work = W, stress_power = D, imbalance = abs(W + D) / max(abs(W), abs(D)), kinetic_energy = b.kinetic_energy)
+end
+
+# ---- momentum balance terms, interface stresses and their power (include/csi.h: csi_momentum_terms_compute, csi_momentum_budget_compute) ----
+# momentum_terms!(model, :top, :bottom, ...) fills both components of the named terms -- forces per unit area in N m^-2 at the u and v
+# points, every term of u_velocity_tendency / v_velocity_tendency kept apart; XFaceField / YFaceField allocated on the model's grid and
+# bound to their slots the first time they are asked for, kept in MOMENTUM_TERM_FIELDS -- with ONE launch on the context's stream.
+# raw_stress = true: the top / bottom fields receive x_momentum_stress / y_momentum_stress (sea_ice_external_stress.jl:33-37, 162-174)
+# themselves, without the interpolated concentration and the sign.  Nothing is copied or waited for.  Returns a NamedTuple term => (x, y).
+# For coupling: call after time_step!, before the ocean reads -bottom.  Rank-local on a Distributed grid.
+const MOMENTUM_TERM_FIELDS = IdDict{Any, Dict{Symbol, Any}}()
+
+function momentum_term_field!(model::HIPSeaIceModel, name::Symbol)
+    haskey(MOMENTUM_TERMS, name) || error("momentum term field: one of $(keys(MOMENTUM_TERMS)) is needed, got $name")
+    fields = get!(MOMENTUM_TERM_FIELDS, model, Dict{Symbol, Any}())
+    return get!(fields, name) do
+        f = endswith(String(name), "_x") ? XFaceField(model.grid) : YFaceField(model.grid)
+        bind!(context(model), Int32(MOMENTUM_TERMS[name]), f)
+        f
+    end
+end
+
+function momentum_terms!(model::HIPSeaIceModel, terms::Symbol...; raw_stress = false)
+    isempty(terms) && error("momentum_terms!: name at least one of $(keys(MOMENTUM_TERM_BITS))")
+    ctx = context(model)
+    mask = raw_stress ? Int32(32) : Int32(0)
+    pairs = map(terms) do t
+        haskey(MOMENTUM_TERM_BITS, t) || error("momentum_terms!: one of $(keys(MOMENTUM_TERM_BITS)) is needed, got $t")
+        mask |= Int32(MOMENTUM_TERM_BITS[t])
+        (momentum_term_field!(model, Symbol(t, :_x)), momentum_term_field!(model, Symbol(t, :_y)))
+    end
+    GC.@preserve model pairs check(ctx, ccall((:csi_momentum_terms_compute, libcsi), Int32, (Ptr{Cvoid}, Int32), ctx.handle, mask))
+    return NamedTuple{terms}(pairs)
+end
+
+# The power of each term, sum u F_x Az + v F_y Az, on the device in the diagnostics' summation order: `what` 1 external (top, bottom),
+# 2 body (coriolis, forcing), 4 internal, 7 all.  residual: the sum of the five, the rate of change of kinetic energy the terms imply.
+# COLLECTIVE on a Distributed grid.
+function momentum_budget(model::HIPSeaIceModel; what = 7)
+    ctx = context(model)
+    out = Ref{CsiMomentumBudget}()
+    GC.@preserve model check(ctx, ccall((:csi_momentum_budget_compute, libcsi), Int32, (Ptr{Cvoid}, Int32, Ptr{CsiMomentumBudget}), ctx.handle, Int32(what), out))
+    b = out[]
+    return (; coriolis = b.coriolis, top = b.top, bottom = b.bottom, internal = b.internal, forcing = b.forcing,
+            residual = b.coriolis + b.top + b.bottom + b.internal + b.forcing)
 end
 
 # ---- device-side output (include/csi.h: csi_output_*) ---------------------------------------------------------------------------------
