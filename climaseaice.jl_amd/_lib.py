@@ -30,13 +30,20 @@ MOMENTUM_TERM_FIELD_IDS = ["M_CORIOLIS_X", "M_CORIOLIS_Y", "M_TOP_X", "M_TOP_Y",
                            "M_FORCING_X", "M_FORCING_Y"]
 F_MOMENTUM_TERMS = {n: len(F) + len(F_DERIVED) + k for k, n in enumerate(MOMENTUM_TERM_FIELD_IDS)}
 F_COUNT_BINDABLE = len(F) + len(F_DERIVED) + len(F_MOMENTUM_TERMS)
+# csi_thermo_linear_field_id: the LINEAR term's per-cell K and Ta, the per-cell bottom salinity and the two used-flux outputs, numbered
+# from CSI_F_COUNT_BINDABLE on
+THERMO_LINEAR_FIELD_IDS = ["FLUX_COEFFICIENT", "FLUX_REFERENCE_TEMPERATURE", "BOTTOM_SALINITY", "TOP_HEAT_FLUX_USED",
+                           "BOTTOM_HEAT_FLUX_USED"]
+F_THERMO_LINEAR = {n: F_COUNT_BINDABLE + k for k, n in enumerate(THERMO_LINEAR_FIELD_IDS)}
+F_COUNT_THERMO = F_COUNT_BINDABLE + len(F_THERMO_LINEAR)
 
 
 def slot_id(name):
-    """The number of a csi_field_bind slot by name: F, or one of the derived fields' or momentum term fields' slots."""
-    if name in F:
-        return F[name]
-    return F_DERIVED[name] if name in F_DERIVED else F_MOMENTUM_TERMS[name]
+    """The number of a csi_field_bind slot by name: F, or one of the derived fields', momentum term fields' or thermodynamic slots."""
+    for table in (F, F_DERIVED, F_MOMENTUM_TERMS):
+        if name in table:
+            return table[name]
+    return F_THERMO_LINEAR[name]
 
 
 STRESS_NONE, STRESS_CONST, STRESS_FIELD, STRESS_SEMI_IMPLICIT = 0, 1, 2, 3
@@ -48,7 +55,10 @@ RHEOLOGY_EVP, RHEOLOGY_VISCOUS = 0, 1
 SOLVER_SPLIT_EXPLICIT, SOLVER_EXPLICIT = 0, 1
 FREE_DRIFT_NONE, FREE_DRIFT_STRESS_BALANCE, FREE_DRIFT_FIELDS = 0, 1, 2
 DYNAMICS_MOMENTUM_EQUATION, DYNAMICS_FREE_DRIFT = 0, 1
-FLUX_CONSTANT, FLUX_ARRAY, FLUX_RADIATIVE_EMISSION = 0, 1, 2
+FLUX_CONSTANT, FLUX_ARRAY, FLUX_RADIATIVE_EMISSION, FLUX_LINEAR = 0, 1, 2, 3
+WEIGHT_NONE, WEIGHT_CONCENTRATION, WEIGHT_ICE_PRESENT = 0, 1, 2
+LINEAR_WEIGHT_MASK, LINEAR_COEFFICIENT_ARRAY, LINEAR_REFERENCE_ARRAY = 3, 4, 8      # csi_heat_flux_term.reserved of a LINEAR term
+SOLVE_BOTTOM_SALINITY_ARRAY = 1                                                     # csi_surface_solve.reserved
 HEAT_TOP, HEAT_BOTTOM = 0, 1
 MAX_HEAT_FLUX_TERMS = 8
 TIME_CLAMP, TIME_CYCLICAL, TIME_LINEAR = 0, 1, 2
@@ -56,6 +66,8 @@ SERIES_DEVICE, SERIES_HOST = 0, 1
 # the eleven slots a time series may drive (csi_time_series_set)
 SERIES_SLOTS = ["TOP_U", "TOP_V", "BOT_U", "BOT_V", "FORCING_U", "FORCING_V", "FREE_DRIFT_U", "FREE_DRIFT_V",
                 "TOP_HEAT_FLUX", "BOTTOM_HEAT_FLUX", "SNOWFALL"]
+# ... and the three thermodynamic inputs that joined them (slot_id names them): fourteen in all
+THERMO_SERIES_SLOTS = ["FLUX_COEFFICIENT", "FLUX_REFERENCE_TEMPERATURE", "BOTTOM_SALINITY"]
 
 # every symbol include/csi.h declares (checked by tests/test_abi.py against the header text)
 SYMBOLS = ["csi_version", "csi_context_create", "csi_context_destroy", "csi_last_error", "csi_sync", "csi_set_mode",
@@ -462,7 +474,7 @@ class Context:
     def time_series_status(self, slot, window):
         """(slices the ring slots of a HOST series hold, -1: none; slice uploads since csi_time_series_set)."""
         res, up = (C.c_int32 * max(int(window), 1))(*([-1] * max(int(window), 1))), C.c_int64()
-        self.call("csi_time_series_status", F[slot], res, C.byref(up))
+        self.call("csi_time_series_status", slot_id(slot), res, C.byref(up))
         return list(res)[:int(window)], up.value
 
     # ---- derived fields and energy budget integrals (include/csi.h) ---------------------------------------------------------------

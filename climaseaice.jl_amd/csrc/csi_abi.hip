@@ -24,11 +24,12 @@ static SnowDev snow_dev(const csi_snow_params* p) {
     W.k = p->conductivity; W.rho = p->snow_density; W.snowfall = p->snowfall; W.Tu = p->top_temperature; W.top_bc_kind = p->top_bc_kind;
     return W;
 }
-// The flux-term path (thermo_flux.hip) runs once a side has terms, the prescribed temperature is an array or snowfall is; its
-// arrays are checked here.  `tu_id`: the surface whose temperature is solved / prescribed (CSI_F_TU bare ice, CSI_F_TUS snow).
+// The flux-term path (thermo_flux.hip) runs once a side has terms, the prescribed temperature, the snowfall or the bottom salinity is
+// an array, or a used-flux output is bound; its arrays are checked here.  `tu_id`: the surface whose temperature is solved / prescribed (CSI_F_TU bare ice, CSI_F_TUS snow).
 static bool flux_path(const csi_context* c, bool snow) {
     const HeatFluxDev& F = c->heat;
-    return F.top.n > 0 || F.bot.n > 0 || F.prescribed_array || (snow && F.snowfall_array);
+    return F.top.n > 0 || F.bot.n > 0 || F.prescribed_array || (snow && F.snowfall_array) || F.bottom_salinity_array ||
+           c->f[CSI_F_TOP_HEAT_FLUX_USED].p || c->f[CSI_F_BOTTOM_HEAT_FLUX_USED].p;
 }
 static bool has_array_term(const FluxTermsDev& t) {
     for (int k = 0; k < t.n; ++k)
@@ -48,13 +49,19 @@ static int32_t flux_fields(csi_context* c, const SlabDev& S, int top_bc_kind, in
     if (has_array_term(F.top)) { ids.push_back(CSI_F_TOP_HEAT_FLUX); ff.qtop = ref_of(c, CSI_F_TOP_HEAT_FLUX); }
     if (has_array_term(F.bot)) { ids.push_back(CSI_F_BOTTOM_HEAT_FLUX); ff.qbot = ref_of(c, CSI_F_BOTTOM_HEAT_FLUX); }
     if (snow && F.snowfall_array) { ids.push_back(CSI_F_SNOWFALL); ff.snowfall = ref_of(c, CSI_F_SNOWFALL); }
+    if (F.lin == LIN_ARRAYS) {
+        ids.push_back(CSI_F_FLUX_COEFFICIENT); ff.lin_k = ref_of(c, CSI_F_FLUX_COEFFICIENT);
+        ids.push_back(CSI_F_FLUX_REFERENCE_TEMPERATURE); ff.lin_ta = ref_of(c, CSI_F_FLUX_REFERENCE_TEMPERATURE);
+    }
+    if (F.bottom_salinity_array) { ids.push_back(CSI_F_BOTTOM_SALINITY); ff.sbot = ref_of(c, CSI_F_BOTTOM_SALINITY); }
     // the surface temperature: read per cell (prescribed, Tu- of the secant), written by the flux balance
-    if (F.prescribed_array || (top_bc_kind == 1 && flux_has_emission(F.top))) ids.push_back(tu_id);
+    if (F.prescribed_array || (top_bc_kind == 1 && (flux_has_emission(F.top) || F.lin != LIN_NONE))) ids.push_back(tu_id);
     for (int id : ids) {
         int32_t rc = need(c, {id});
         if (rc) return rc;
     }
     ff.tu = ref_of(c, tu_id);
+    ff.qtop_used = ref_of(c, CSI_F_TOP_HEAT_FLUX_USED); ff.qbot_used = ref_of(c, CSI_F_BOTTOM_HEAT_FLUX_USED);      // (unbound: p == nullptr)
     return CSI_OK;
 }
 static int32_t do_layered(csi_context* c, const SlabDev& S, const SnowDev& W, double dt) {
@@ -382,7 +389,7 @@ int32_t csi_mask_set(csi_context* c, const uint8_t* dev_mask, int64_t ld) {
 int32_t csi_field_bind(csi_context* c, int32_t fid, void* dev_ptr, int64_t ld, int32_t ni, int32_t nj) {
     if (!c) return CSI_ERR_INVALID_ARGUMENT;
     if (!c->grid_set) return fail(c, CSI_ERR_NOT_BOUND, "csi_grid_set has not been called");
-    if (fid < 0 || fid >= CSI_F_COUNT_BINDABLE) return fail(c, CSI_ERR_INVALID_ARGUMENT, "unknown field id");
+    if (fid < 0 || fid >= CSI_F_COUNT_THERMO) return fail(c, CSI_ERR_INVALID_ARGUMENT, "unknown field id");
     if (!dev_ptr) { c->f[fid] = Bound{}; return CSI_OK; }
     const int eni = c->Nx + 2 * c->Hx + extra_x(c, fid), enj = c->Ny + 2 * c->Hy + extra_y(c, fid);
     if (ni != eni || nj != enj || ld < ni) {
@@ -697,21 +704,35 @@ int32_t csi_heat_fluxes_set(csi_context* c, int32_t side, const csi_heat_flux_te
     if (n > CSI_MAX_HEAT_FLUX_TERMS)
         return fail(c, CSI_ERR_UNSUPPORTED, "more than CSI_MAX_HEAT_FLUX_TERMS heat-flux terms on one side");
     FluxTermsDev t{};
-    int arrays = 0;
+    int arrays = 0, lin = LIN_NONE, lin_weight = WEIGHT_NONE;
     for (int k = 0; k < n; ++k) {
         const csi_heat_flux_term& q = terms[k];
-        if (q.kind != CSI_FLUX_CONSTANT && q.kind != CSI_FLUX_ARRAY && q.kind != CSI_FLUX_RADIATIVE_EMISSION)
+        if (q.kind != CSI_FLUX_CONSTANT && q.kind != CSI_FLUX_ARRAY && q.kind != CSI_FLUX_RADIATIVE_EMISSION && q.kind != CSI_FLUX_LINEAR)
             return fail(c, CSI_ERR_INVALID_ARGUMENT, "unknown heat-flux term kind");
+        if (q.kind == CSI_FLUX_LINEAR) {
+            if (side != CSI_HEAT_TOP) return fail(c, CSI_ERR_UNSUPPORTED, "LinearHeatFlux is a top heat flux only");
+            if (lin != LIN_NONE) return fail(c, CSI_ERR_UNSUPPORTED, "at most one LinearHeatFlux term per model (sum the coefficients into one)");
+            const int per_cell = q.reserved & (CSI_LINEAR_COEFFICIENT_ARRAY | CSI_LINEAR_REFERENCE_ARRAY);
+            lin_weight = q.reserved & CSI_LINEAR_WEIGHT_MASK;
+            if ((q.reserved & ~(CSI_LINEAR_WEIGHT_MASK | CSI_LINEAR_COEFFICIENT_ARRAY | CSI_LINEAR_REFERENCE_ARRAY)) || lin_weight > CSI_WEIGHT_ICE_PRESENT)
+                return fail(c, CSI_ERR_INVALID_ARGUMENT, "LinearHeatFlux: unknown weighting or flag in csi_heat_flux_term.reserved");
+            if (per_cell != 0 && per_cell != (CSI_LINEAR_COEFFICIENT_ARRAY | CSI_LINEAR_REFERENCE_ARRAY))
+                return fail(c, CSI_ERR_UNSUPPORTED, "LinearHeatFlux: the coefficient and the reference temperature are both numbers or both per cell "
+                                                    "(broadcast the number into an array)");
+            lin = per_cell ? LIN_ARRAYS : LIN_NUMBERS;
+        }
         if (q.kind == CSI_FLUX_ARRAY && ++arrays > 1)
             return fail(c, CSI_ERR_UNSUPPORTED, "at most one ARRAY heat-flux term per side (sum the arrays into one)");
         if (q.kind == CSI_FLUX_RADIATIVE_EMISSION && side != CSI_HEAT_TOP)
             return fail(c, CSI_ERR_UNSUPPORTED, "RadiativeEmission is a top heat flux only");
-        t.kind[k] = q.kind == CSI_FLUX_ARRAY ? FLUX_ARRAY : (q.kind == CSI_FLUX_RADIATIVE_EMISSION ? FLUX_EMISSION : FLUX_CONST);
+        t.kind[k] = q.kind == CSI_FLUX_ARRAY ? FLUX_ARRAY : (q.kind == CSI_FLUX_RADIATIVE_EMISSION ? FLUX_EMISSION :
+                    (q.kind == CSI_FLUX_LINEAR ? FLUX_LINEAR : FLUX_CONST));
         t.value[k] = q.value;
         t.eps[k] = q.emissivity; t.sigma[k] = q.stefan_boltzmann_constant; t.Tr[k] = q.reference_temperature;
     }
     t.n = n;
     (side == CSI_HEAT_TOP ? c->heat.top : c->heat.bot) = t;
+    if (side == CSI_HEAT_TOP) { c->heat.lin = lin; c->heat.lin_weight = lin_weight; }
     return CSI_OK;
 }
 
@@ -720,12 +741,14 @@ int32_t csi_surface_solve_set(csi_context* c, const csi_surface_solve* p) {
     const HeatFluxDev defaults{};
     if (!p) {
         c->heat.tol = defaults.tol; c->heat.maxiters = defaults.maxiters;
-        c->heat.prescribed_array = 0; c->heat.snowfall_array = 0;
+        c->heat.prescribed_array = 0; c->heat.snowfall_array = 0; c->heat.bottom_salinity_array = 0;
         return CSI_OK;
     }
     if (!(p->tol > 0) || p->maxiters < 1) return fail(c, CSI_ERR_INVALID_ARGUMENT, "the surface solve needs tol > 0 and maxiters >= 1");
     c->heat.tol = p->tol; c->heat.maxiters = p->maxiters;
+    if (p->reserved & ~CSI_SOLVE_BOTTOM_SALINITY_ARRAY) return fail(c, CSI_ERR_INVALID_ARGUMENT, "csi_surface_solve.reserved: unknown flag");
     c->heat.prescribed_array = p->prescribed_array != 0; c->heat.snowfall_array = p->snowfall_array != 0;
+    c->heat.bottom_salinity_array = (p->reserved & CSI_SOLVE_BOTTOM_SALINITY_ARRAY) != 0;
     return CSI_OK;
 }
 

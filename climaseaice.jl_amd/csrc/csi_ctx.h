@@ -45,7 +45,7 @@ struct Bound {
 };
 
 // (x, y) location of every field slot
-static const int kLoc[CSI_F_COUNT_BINDABLE][2] = {
+static const int kLoc[CSI_F_COUNT_THERMO][2] = {
     {LOC_F, LOC_C}, {LOC_C, LOC_F}, {LOC_C, LOC_C}, {LOC_C, LOC_C},   // U V H A
     {LOC_C, LOC_C}, {LOC_C, LOC_C}, {LOC_F, LOC_F},                   // S11 S22 S12
     {LOC_F, LOC_C}, {LOC_C, LOC_F}, {LOC_C, LOC_C}, {LOC_C, LOC_C}, {LOC_C, LOC_C},  // UN VN P ALPHA DELTA
@@ -62,15 +62,18 @@ static const int kLoc[CSI_F_COUNT_BINDABLE][2] = {
     {LOC_F, LOC_C}, {LOC_C, LOC_F},                                   // FREE_DRIFT_U FREE_DRIFT_V
     {LOC_C, LOC_C}, {LOC_C, LOC_C}, {LOC_C, LOC_C}, {LOC_C, LOC_C}, {LOC_C, LOC_C}, {LOC_C, LOC_C}, {LOC_C, LOC_C},    // the seven derived fields
     {LOC_F, LOC_C}, {LOC_C, LOC_F}, {LOC_F, LOC_C}, {LOC_C, LOC_F}, {LOC_F, LOC_C}, {LOC_C, LOC_F}, {LOC_F, LOC_C}, {LOC_C, LOC_F},
-    {LOC_F, LOC_C}, {LOC_C, LOC_F}};                                  // the ten momentum term fields: _X, _Y of each term
-static const char* const kName[CSI_F_COUNT_BINDABLE] = {"u", "v", "h", "aice", "sigma11", "sigma22", "sigma12", "un", "vn", "P", "alpha",
+    {LOC_F, LOC_C}, {LOC_C, LOC_F},                                   // the ten momentum term fields: _X, _Y of each term
+    {LOC_C, LOC_C}, {LOC_C, LOC_C}, {LOC_C, LOC_C}, {LOC_C, LOC_C}, {LOC_C, LOC_C}};   // FLUX_COEFFICIENT .. BOTTOM_HEAT_FLUX_USED
+static const char* const kName[CSI_F_COUNT_THERMO] = {"u", "v", "h", "aice", "sigma11", "sigma22", "sigma12", "un", "vn", "P", "alpha",
                                   "Delta", "zeta_f", "zeta_c", "Gh", "Gaice", "h-", "aice-", "u-", "v-",
                                   "top_u", "top_v", "bottom_u", "bottom_v", "mass_flux",
                                   "hs", "Ghs", "hs-", "mass_flux_snow", "intercepted_snowfall", "Tu", "Tu_snow", "forcing_u", "forcing_v", "Gu", "Gv",
                                   "top_heat_flux", "bottom_heat_flux", "snowfall", "free_drift_u", "free_drift_v",
                                   "divergence", "shear", "deformation", "speed", "sigma_I", "sigma_II", "stress_power",
                                   "coriolis_x", "coriolis_y", "top_x", "top_y", "bottom_x", "bottom_y", "internal_x", "internal_y",
-                                  "forcing_x", "forcing_y"};
+                                  "forcing_x", "forcing_y",
+                                  "flux_coefficient", "flux_reference_temperature", "bottom_salinity", "top_heat_flux_used",
+                                  "bottom_heat_flux_used"};
 
 extern std::string g_create_error;      // csi_context_create failures (no context to hold the message)
 
@@ -181,7 +184,7 @@ struct csi_context {
     long fcor2_ld = 0, fcor2_plane = 0;
     bool cor_dirty = true;               // Coriolis columns of the FAST table need (re)building
     double cor_synced = 0.0;             // FPlane value they were built with
-    Bound f[CSI_F_COUNT_BINDABLE];
+    Bound f[CSI_F_COUNT_THERMO];
     csi_evp_params evp{};
     csi_stress stress[2]{};
     int mode = CSI_MODE_STRICT;

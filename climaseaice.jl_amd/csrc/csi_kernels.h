@@ -201,11 +201,13 @@ void launch_slab_step(const SlabDev& S, const GridDev& g, const FRef& h, const F
 
 // per-cell heat fluxes, RadiativeEmission, the surface-temperature solve (thermo_flux.hip; include/csi.h csi_heat_fluxes_set)
 constexpr int kMaxFluxTerms = 8;
-enum : int { FLUX_CONST = 0, FLUX_ARRAY = 1, FLUX_EMISSION = 2 };
+enum : int { FLUX_CONST = 0, FLUX_ARRAY = 1, FLUX_EMISSION = 2, FLUX_LINEAR = 3 };
+enum : int { LIN_NONE = 0, LIN_NUMBERS = 1, LIN_ARRAYS = 2 };                 // the top's LINEAR term: absent, K and Ta numbers, both per cell
+enum : int { WEIGHT_NONE = 0, WEIGHT_CONCENTRATION = 1, WEIGHT_ICE_PRESENT = 2 };
 struct FluxTermsDev {
     int n;                     // 0: the side takes SlabDev's number (Qu / Qb with top_flux_kind / bot_flux_kind)
     int kind[kMaxFluxTerms];
-    double value[kMaxFluxTerms], eps[kMaxFluxTerms], sigma[kMaxFluxTerms], Tr[kMaxFluxTerms];
+    double value[kMaxFluxTerms], eps[kMaxFluxTerms], sigma[kMaxFluxTerms], Tr[kMaxFluxTerms];   // (LINEAR: value = K, Tr = Ta)
 };
 struct HeatFluxDev {
     FluxTermsDev top, bot;
@@ -213,10 +215,14 @@ struct HeatFluxDev {
     int maxiters = 1000;
     int prescribed_array = 0;  // PrescribedTemperature read per cell from the surface's temperature field
     int snowfall_array = 0;
+    int lin = LIN_NONE;        // the top's LINEAR term (at most one)
+    int lin_weight = WEIGHT_NONE;
+    int bottom_salinity_array = 0;      // Tb per cell from FluxFields.sbot
 };
 // qtop / qbot: the ARRAY terms' fields; snowfall: per-cell snowfall; tu: the solved surface's temperature field (CSI_F_TU for the
-// bare-ice step, CSI_F_TUS for the layered one) -- Tu- of the secant, the prescribed per-cell value, and the output
-struct FluxFields { FRef qtop, qbot, snowfall, tu; };
+// bare-ice step, CSI_F_TUS for the layered one) -- Tu- of the secant, the prescribed per-cell value, and the output; lin_k / lin_ta:
+// the LINEAR term's per-cell K and Ta; sbot: the per-cell bottom salinity; qtop_used / qbot_used: optional outputs (p == nullptr: absent)
+struct FluxFields { FRef qtop, qbot, snowfall, tu, lin_k, lin_ta, sbot, qtop_used, qbot_used; };
 bool flux_has_emission(const FluxTermsDev& t);
 void launch_slab_flux_step(const SlabDev& S, const HeatFluxDev& F, const FluxFields& ff, const GridDev& g, const FRef& h, const FRef& a,
                            const FRef& mf, int has_mf, double dt, hipStream_t s);
@@ -226,7 +232,7 @@ void launch_layered_flux_step(const SlabDev& S, const SnowDev& W, const HeatFlux
 // forcing time series interpolated at the model clock (time_series.hip; include/csi.h csi_time_series_update): every series-driven
 // slot in ONE launch.  A descriptor: the two slices around the clock (a: psi_1, b: psi_2; b == a where n1 == n2), the interior of the
 // bound array, row strides in doubles, the interior extents and the weights w2 = n~, w1 = 1 - n~ (formed on the host, in double).
-constexpr int kMaxSeries = 11;
+constexpr int kMaxSeries = 14;
 struct SeriesDesc {
     const double *a, *b;
     double* dst;

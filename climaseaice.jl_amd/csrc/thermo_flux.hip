@@ -1,6 +1,7 @@
-// thermo_flux.hip -- the slab and layered thermodynamic steps with per-cell heat fluxes, RadiativeEmission and the
-// surface-temperature solve (include/csi.h, csi_heat_fluxes_set).  The numeric configuration keeps k_slab / k_layered
-// (thermo.hip); these kernels run once a side has flux terms, the prescribed temperature is an array or snowfall is.
+// thermo_flux.hip -- the slab and layered thermodynamic steps with per-cell heat fluxes, RadiativeEmission, the LINEAR top term, the
+// surface-temperature solve, a per-cell bottom salinity and the used-flux outputs (include/csi.h, csi_heat_fluxes_set).  The numeric
+// configuration keeps k_slab / k_layered (thermo.hip); these kernels run once a side has flux terms, the prescribed temperature, the
+// snowfall or the bottom salinity is an array, or a used-flux output is bound.
 //
 //   getflux of a Number / array / Tuple / RadiativeEmission   HeatBoundaryConditions/boundary_fluxes.jl:8-22, 98-127
 //   thermodynamic_tendency with the surface solve            slab_thermodynamics_tendencies.jl:74-135
@@ -23,22 +24,37 @@ __device__ __forceinline__ double pow4(double x) {
     return x2 * x2;
 }
 
-// getflux of one term at surface temperature T; q: the cell's value of the side's ARRAY term
-template <bool EMIT>
-__device__ __forceinline__ double flux_term(const FluxTermsDev& t, int k, double q, double T) {
+// what the LINEAR term reads of a cell: K and Ta (LIN_ARRAYS; the term's numbers otherwise), the concentration the step starts from
+// and the weighting
+struct LinCell {
+    double K, Ta, a;
+    int w;
+};
+
+// getflux of one term at surface temperature T; q: the cell's value of the side's ARRAY term.  EMIT / LIN: the side has a term that
+// depends on T -- RadiativeEmission / the LINEAR term (K * (T - Ta)) * w, in this order
+template <bool EMIT, int LIN>
+__device__ __forceinline__ double flux_term(const FluxTermsDev& t, int k, double q, double T, const LinCell& lc) {
     if (EMIT && t.kind[k] == FLUX_EMISSION) return t.eps[k] * t.sigma[k] * pow4(T + t.Tr[k]);
+    if (LIN != LIN_NONE && t.kind[k] == FLUX_LINEAR) {
+        const double K = (LIN == LIN_ARRAYS) ? lc.K : t.value[k], Ta = (LIN == LIN_ARRAYS) ? lc.Ta : t.Tr[k];
+        const double v = K * (T - Ta);
+        if (lc.w == WEIGHT_CONCENTRATION) return v * lc.a;
+        if (lc.w == WEIGHT_ICE_PRESENT) return (lc.a == 0) ? 0.0 : v;
+        return v;
+    }
     return t.kind[k] == FLUX_ARRAY ? q : t.value[k];
 }
 
 // getflux of the side's Tuple: t0 + (t1 + (... + t_{n-1})), right-nested (boundary_fluxes.jl:15-22); n >= 1.  Unrolled over the
 // fixed capacity so that every term index is a constant (no dynamically indexed kernel argument).
-template <bool EMIT>
-__device__ __forceinline__ double flux_sum(const FluxTermsDev& t, double q, double T) {
+template <bool EMIT, int LIN>
+__device__ __forceinline__ double flux_sum(const FluxTermsDev& t, double q, double T, const LinCell& lc) {
     double acc = 0.0;
 #pragma unroll
     for (int k = kMaxFluxTerms - 1; k >= 0; --k) {
         if (k < t.n) {
-            const double v = flux_term<EMIT>(t, k, q, T);
+            const double v = flux_term<EMIT, LIN>(t, k, q, T, lc);
             acc = (k == t.n - 1) ? v : v + acc;
         }
     }
@@ -63,8 +79,9 @@ __device__ __forceinline__ double secant_root(const Fn& f, double Tu_prev, doubl
 }
 
 // QT / QB: the top / bottom side has an ARRAY term; EMIT: the top has a RadiativeEmission term; LTU: the cell's surface temperature
-// is read (Tu- of the secant, or the prescribed per-cell value)
-template <bool QT, bool QB, bool EMIT, bool LTU>
+// is read (Tu- of the secant, or the prescribed per-cell value); LIN: the top's LINEAR term (LIN_NONE / LIN_NUMBERS / LIN_ARRAYS);
+// SB: the bottom salinity is read per cell.  The last two default to "off": those instantiations are the kernels of before.
+template <bool QT, bool QB, bool EMIT, bool LTU, int LIN = LIN_NONE, bool SB = false>
 __global__ void __launch_bounds__(256) k_slab_flux(SlabDev s, HeatFluxDev F, FluxFields ff, GridDev g, FRef h, FRef a, FRef mf, int has_mf,
                                                    double dt) {
     const int i = 1 + blockIdx.x * blockDim.x + threadIdx.x, j = 1 + blockIdx.y * blockDim.y + threadIdx.y;
@@ -73,16 +90,18 @@ __global__ void __launch_bounds__(256) k_slab_flux(SlabDev s, HeatFluxDev F, Flu
     const double tum = LTU ? ff.tu(i, j) : 0.0;
     const double qt = QT ? ff.qtop(i, j) : 0.0;
     const double qb = QB ? ff.qbot(i, j) : 0.0;
+    const LinCell lc{LIN == LIN_ARRAYS ? ff.lin_k(i, j) : 0.0, LIN == LIN_ARRAYS ? ff.lin_ta(i, j) : 0.0, an, F.lin_weight};
+    const double Sb = SB ? ff.sbot(i, j) : s.S;
     const double hc = s.hc;
     const bool consolidated = hn >= hc;
-    const double Tb = s.liq_T0 - s.liq_slope * s.S;
-    auto Qx = [&](double T) { return F.top.n ? flux_sum<EMIT>(F.top, qt, T) : s.Qu; };
+    const double Tb = s.liq_T0 - s.liq_slope * Sb;
+    auto Qx = [&](double T) { return F.top.n ? flux_sum<EMIT, LIN>(F.top, qt, T, lc) : s.Qu; };
     double Tu = s.Tu;
     if (s.top_bc_kind == 1) {      // MeltingConstrainedFluxBalance: root of Qx - Qi(T), capped at Tm(S_ice); thin slab: Tb
         const double Tm = s.liq_T0 - s.liq_slope * s.ice_salinity;
         double root = Tb;
         if (consolidated) {
-            if (EMIT && LTU) {      // (the host sets LTU whenever the flux balance has an emission term)
+            if ((EMIT || LIN != LIN_NONE) && LTU) {      // (the host sets LTU whenever the flux balance has a term that depends on T)
                 auto f = [&](double T) { return Qx(T) - ((hn <= 0) ? 0.0 : -s.k * (T - Tb) / hn); };
                 root = secant_root(f, tum, F.tol, F.maxiters);
             } else {
@@ -97,7 +116,7 @@ __global__ void __launch_bounds__(256) k_slab_flux(SlabDev s, HeatFluxDev F, Flu
     const double Eu = s.rho_bulk * latent_heat(s, Tu);
     const double Qi_fun = (hn <= 0) ? 0.0 : -s.k * (Tu - Tb) / hn;
     const double Qu = (s.top_flux_kind == 1) ? Qi_fun : Qx(Tu);
-    const double Qb = (s.bot_flux_kind == 1) ? (-(1 - an)) * s.Qb : (F.bot.n ? flux_sum<false>(F.bot, qb, Tu) : s.Qb);
+    const double Qb = (s.bot_flux_kind == 1) ? (-(1 - an)) * s.Qb : (F.bot.n ? flux_sum<false, LIN_NONE>(F.bot, qb, Tu, lc) : s.Qb);
     const double Qi = consolidated ? Qi_fun : 0.0;
     const double wu = (Qu - Qi) / Eu;
     const double wb = (Qi - Qb) / Eb;
@@ -107,10 +126,12 @@ __global__ void __launch_bounds__(256) k_slab_flux(SlabDev s, HeatFluxDev F, Flu
     h(i, j) = h1;
     if (has_mf) mf(i, j) = s.rho_bulk * (h1 * a1 - hn * an) / dt;
     if (s.top_bc_kind == 1 && ff.tu.p) ff.tu(i, j) = Tu;
+    if (ff.qtop_used.p) ff.qtop_used(i, j) = Qu;
+    if (ff.qbot_used.p) ff.qbot_used(i, j) = Qb;
 }
 
 // PS: per-cell snowfall
-template <bool QT, bool QB, bool EMIT, bool LTU, bool PS>
+template <bool QT, bool QB, bool EMIT, bool LTU, bool PS, int LIN = LIN_NONE, bool SB = false>
 __global__ void __launch_bounds__(256) k_layered_flux(SlabDev s, SnowDev w, HeatFluxDev F, FluxFields ff, GridDev g, FRef h, FRef a, FRef hs,
                                                       LayeredOut o, double dt) {
     const int i = 1 + blockIdx.x * blockDim.x + threadIdx.x, j = 1 + blockIdx.y * blockDim.y + threadIdx.y;
@@ -121,20 +142,22 @@ __global__ void __launch_bounds__(256) k_layered_flux(SlabDev s, SnowDev w, Heat
     const double qt = QT ? ff.qtop(i, j) : 0.0;
     const double qb = QB ? ff.qbot(i, j) : 0.0;
     const double Ps = PS ? ff.snowfall(i, j) : w.snowfall;
+    const LinCell lc{LIN == LIN_ARRAYS ? ff.lin_k(i, j) : 0.0, LIN == LIN_ARRAYS ? ff.lin_ta(i, j) : 0.0, an, F.lin_weight};
+    const double Sb = SB ? ff.sbot(i, j) : s.S;
     const double hc = s.hc;
     const double Vin = hin * an, Vsn = hsn * an;
     const bool consolidated = hin >= hc;
-    const double Tb = s.liq_T0 - s.liq_slope * s.S;
+    const double Tb = s.liq_T0 - s.liq_slope * Sb;
     double Tm = s.liq_T0 - s.liq_slope * s.ice_salinity;
     const double ks = w.k, ki = s.k;
-    auto Qx = [&](double T) { return F.top.n ? flux_sum<EMIT>(F.top, qt, T) : s.Qu; };
+    auto Qx = [&](double T) { return F.top.n ? flux_sum<EMIT, LIN>(F.top, qt, T, lc) : s.Qu; };
     Tm = (hsn > 0) ? 0.0 : Tm;
     const double R = hsn / ks + hin / ki;
     double Tus = w.Tu;
     if (w.top_bc_kind == 1) {
         double root = Tb;
         if (consolidated) {
-            if (EMIT && LTU) {      // (the host sets LTU whenever the flux balance has an emission term)
+            if ((EMIT || LIN != LIN_NONE) && LTU) {      // (the host sets LTU whenever the flux balance has a term that depends on T)
                 auto f = [&](double T) { return Qx(T) - ((R <= 0) ? 0.0 : (Tb - T) / R); };
                 root = secant_root(f, tum, F.tol, F.maxiters);
             } else {
@@ -158,7 +181,7 @@ __global__ void __launch_bounds__(256) k_layered_flux(SlabDev s, SnowDev w, Heat
     const double Qs = jmin(melt_energy, cap);
     const double Gsm = Qs / (rs * Ls);
     const double ri = s.rho_bulk, riL = ri * Ls;
-    const double Qbi = (s.bot_flux_kind == 1) ? (-(1 - an)) * s.Qb : (F.bot.n ? flux_sum<false>(F.bot, qb, Tus) : s.Qb);
+    const double Qbi = (s.bot_flux_kind == 1) ? (-(1 - an)) * s.Qb : (F.bot.n ? flux_sum<false, LIN_NONE>(F.bot, qb, Tus, lc) : s.Qb);
     const double alpha = (Qui - Qbi) / riL, beta = Qs / riL;
     const double Cm = (hin > 0) ? an / (2 * hin) : 0.0;
     const double Cf = (hc > 0) ? (1 - an) / hc : 0.0;
@@ -198,6 +221,8 @@ __global__ void __launch_bounds__(256) k_layered_flux(SlabDev s, SnowDev w, Heat
     if (o.mf_int.p) o.mf_int(i, j) = Pabs;
     if (o.tu_ice.p) o.tu_ice(i, j) = Tsi;
     if (o.tu_snow.p) o.tu_snow(i, j) = Tus;
+    if (ff.qtop_used.p) ff.qtop_used(i, j) = Qui;
+    if (ff.qbot_used.p) ff.qbot_used(i, j) = Qbi;
 }
 
 bool flux_has_emission(const FluxTermsDev& t) {
@@ -215,8 +240,8 @@ using SlabFn = void (*)(const SlabDev&, const HeatFluxDev&, const FluxFields&, c
 template <int B>
 void slab_inst(const SlabDev& S, const HeatFluxDev& F, const FluxFields& ff, const GridDev& g, const FRef& h, const FRef& a, const FRef& mf,
                int has_mf, double dt, hipStream_t st) {
-    hipLaunchKernelGGL((k_slab_flux<(B & 1) != 0, (B & 2) != 0, (B & 4) != 0, (B & 8) != 0>), cells(g), dim3(kBlockX, kBlockY), 0, st,
-                       S, F, ff, g, h, a, mf, has_mf, dt);
+    hipLaunchKernelGGL((k_slab_flux<(B & 1) != 0, (B & 2) != 0, (B & 4) != 0, (B & 8) != 0, (B / 16) % 3, (B / 48) != 0>), cells(g),
+                       dim3(kBlockX, kBlockY), 0, st, S, F, ff, g, h, a, mf, has_mf, dt);
 }
 template <int... B>
 constexpr SlabFn slab_table_entry(int b, std::integer_sequence<int, B...>) {
@@ -229,8 +254,8 @@ using LayeredFn = void (*)(const SlabDev&, const SnowDev&, const HeatFluxDev&, c
 template <int B>
 void layered_inst(const SlabDev& S, const SnowDev& W, const HeatFluxDev& F, const FluxFields& ff, const GridDev& g, const FRef& h,
                   const FRef& a, const FRef& hs, const LayeredOut& o, double dt, hipStream_t st) {
-    hipLaunchKernelGGL((k_layered_flux<(B & 1) != 0, (B & 2) != 0, (B & 4) != 0, (B & 8) != 0, (B & 16) != 0>), cells(g),
-                       dim3(kBlockX, kBlockY), 0, st, S, W, F, ff, g, h, a, hs, o, dt);
+    hipLaunchKernelGGL((k_layered_flux<(B & 1) != 0, (B & 2) != 0, (B & 4) != 0, (B & 8) != 0, (B & 16) != 0, (B / 32) % 3, (B / 96) != 0>),
+                       cells(g), dim3(kBlockX, kBlockY), 0, st, S, W, F, ff, g, h, a, hs, o, dt);
 }
 template <int... B>
 constexpr LayeredFn layered_table_entry(int b, std::integer_sequence<int, B...>) {
@@ -241,20 +266,23 @@ constexpr LayeredFn layered_table_entry(int b, std::integer_sequence<int, B...>)
 // template bits shared by both steps: which per-cell arrays a configuration reads
 int flux_bits(const HeatFluxDev& F, const FluxFields& ff, int top_bc_kind) {
     const bool emit = flux_has_emission(F.top);
-    const bool ltu = (top_bc_kind == 0 && F.prescribed_array) || (top_bc_kind == 1 && emit);
+    const bool ltu = (top_bc_kind == 0 && F.prescribed_array) || (top_bc_kind == 1 && (emit || F.lin != LIN_NONE));
     return (ff.qtop.p ? 1 : 0) | (ff.qbot.p ? 2 : 0) | (emit ? 4 : 0) | (ltu ? 8 : 0);
 }
+// the variants beyond them: the LINEAR term's three states, times the per-cell bottom salinity (6 per combination of bits)
+int flux_variant(const HeatFluxDev& F) { return F.lin + 3 * (F.bottom_salinity_array ? 1 : 0); }
 }  // namespace
 
 void launch_slab_flux_step(const SlabDev& S, const HeatFluxDev& F, const FluxFields& ff, const GridDev& g, const FRef& h, const FRef& a,
                            const FRef& mf, int has_mf, double dt, hipStream_t s) {
-    slab_table_entry(flux_bits(F, ff, S.top_bc_kind), std::make_integer_sequence<int, 16>{})(S, F, ff, g, h, a, mf, has_mf, dt, s);
+    const int b = flux_bits(F, ff, S.top_bc_kind) + 16 * flux_variant(F);
+    slab_table_entry(b, std::make_integer_sequence<int, 16 * 6>{})(S, F, ff, g, h, a, mf, has_mf, dt, s);
 }
 
 void launch_layered_flux_step(const SlabDev& S, const SnowDev& W, const HeatFluxDev& F, const FluxFields& ff, const GridDev& g,
                               const FRef& h, const FRef& a, const FRef& hs, const LayeredOut& o, double dt, hipStream_t s) {
-    const int b = flux_bits(F, ff, W.top_bc_kind) | (F.snowfall_array ? 16 : 0);
-    layered_table_entry(b, std::make_integer_sequence<int, 32>{})(S, W, F, ff, g, h, a, hs, o, dt, s);
+    const int b = (flux_bits(F, ff, W.top_bc_kind) | (F.snowfall_array ? 16 : 0)) + 32 * flux_variant(F);
+    layered_table_entry(b, std::make_integer_sequence<int, 32 * 6>{})(S, W, F, ff, g, h, a, hs, o, dt, s);
 }
 
 }  // namespace csi

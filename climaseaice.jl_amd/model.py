@@ -39,20 +39,30 @@ def _cell_shape_ok(value, grid):
 
 
 def check_heat_flux(spec, side, grid):
-    """Refuse, by name, what the C ABI cannot take: closures (FluxFunction, callables), RadiativeEmission at the bottom, more than
-    one array per side, arrays of the wrong shape (ValueError)."""
+    """Refuse, by name, what the C ABI cannot take: closures (FluxFunction, callables), RadiativeEmission or LinearHeatFlux at the
+    bottom, more than one array or LinearHeatFlux per side, arrays of the wrong shape (ValueError)."""
     if spec is None or _is_number(spec) or (side == "bottom" and isinstance(spec, str) and spec == "frazil"):
         return
     items = spec if isinstance(spec, tuple) else (spec,)
     if len(items) > _lib.MAX_HEAT_FLUX_TERMS:
         raise NotImplementedError(f"{side}_heat_flux: at most {_lib.MAX_HEAT_FLUX_TERMS} terms")
-    arrays = 0
+    arrays = linear = 0
     for x in items:
         if _is_number(x):
             continue
         if isinstance(x, RadiativeEmission):
             if side != "top":
                 raise NotImplementedError("RadiativeEmission is a top heat flux only")
+        elif isinstance(x, LinearHeatFlux):
+            if side != "top":
+                raise NotImplementedError("LinearHeatFlux is a top heat flux only")
+            linear += 1
+            if linear > 1:
+                raise NotImplementedError("top_heat_flux: at most one LinearHeatFlux term (sum the coefficients into one)")
+            for name, value in (("coefficient", x.coefficient), ("reference_temperature", x.reference_temperature)):
+                if not _is_number(value) and not _cell_shape_ok(value, grid):
+                    raise ValueError(f"LinearHeatFlux.{name}: a number, an array of shape (Ny, Nx) = {(grid.Ny, grid.Nx)} or a "
+                                     "CenterField of the grid is needed")
         elif isinstance(x, (Field, np.ndarray, list, FieldTimeSeries)):
             arrays += 1
             if arrays > 1:
@@ -63,7 +73,7 @@ def check_heat_flux(spec, side, grid):
         elif callable(x) or type(x).__name__ == "FluxFunction":
             raise NotImplementedError(f"{side}_heat_flux: {type(x).__name__} is not supported -- FluxFunction and other callables "
                                       "cannot cross the C ABI; give numbers, (Ny, Nx) arrays, CenterFields, RadiativeEmission "
-                                      "or a tuple of them")
+                                      "or a tuple of them; a bulk flux K (T - Ta) is data: LinearHeatFlux")
         else:
             raise TypeError(f"{side}_heat_flux: unsupported term {type(x).__name__}")
 
@@ -77,7 +87,7 @@ def check_heat_fluxes(grid, ice, top_heat_flux, bottom_heat_flux, snowfall=None)
     check_heat_flux(top_heat_flux if top_heat_flux is not None else ice.top_heat_flux, "top", grid)
     check_heat_flux(bottom_heat_flux if bottom_heat_flux is not None else ice.bottom_heat_flux, "bottom", grid)
     refuse_series(ice.prescribed, "PrescribedTemperature (the per-cell temperature is also state)")
-    for name, value in (("snowfall", snowfall), ("PrescribedTemperature", ice.prescribed)):
+    for name, value in (("snowfall", snowfall), ("PrescribedTemperature", ice.prescribed), ("bottom_salinity", ice.bottom_salinity)):
         if value is not None and not _is_number(value) and not _cell_shape_ok(value, grid):
             raise ValueError(f"{name}: an array of shape (Ny, Nx) = {(grid.Ny, grid.Nx)} or a CenterField of the grid is needed")
 
@@ -149,11 +159,44 @@ class RadiativeEmission:
         self.reference_temperature = float(reference_temperature)
 
 
+_WEIGHTINGS = {None: _lib.WEIGHT_NONE, "concentration": _lib.WEIGHT_CONCENTRATION, "ice_present": _lib.WEIGHT_ICE_PRESENT}
+
+
+class LinearHeatFlux:
+    """The bulk form the reference's users write into a FluxFunction closure (examples/melting_in_spring.jl:64-73,
+    test/test_energy_conservation.jl:8-13), as data: Q(T) = (K * (T - Ta)) * w at the surface temperature T, in this order.
+    coefficient K (W m^-2 K^-1) and reference_temperature Ta: a number, an (Ny, Nx) array, a CenterField or a FieldTimeSeries.
+    area_weighting: "concentration" (w = aice at the start of the step), "ice_present" (Q = 0 where aice == 0, no product) or None.
+    A term of top_heat_flux, alone or in a tuple, at most one; with MeltingConstrainedFluxBalance the surface temperature is solved
+    per cell by the secant method, as with RadiativeEmission (include/csi.h, csi_heat_fluxes_set)."""
+
+    def __init__(self, coefficient, reference_temperature, area_weighting="concentration"):
+        if area_weighting not in _WEIGHTINGS:
+            raise ValueError('LinearHeatFlux.area_weighting: "concentration", "ice_present" or None')
+        self.coefficient = float(coefficient) if _is_number(coefficient) else coefficient
+        self.reference_temperature = float(reference_temperature) if _is_number(reference_temperature) else reference_temperature
+        self.area_weighting = area_weighting
+
+    @property
+    def per_cell(self):
+        return not (_is_number(self.coefficient) and _is_number(self.reference_temperature))
+
+
+def bulk_sensible_heat_flux(transfer_coefficient, atmosphere_density, atmosphere_heat_capacity, atmosphere_wind_speed,
+                            atmosphere_temperature, area_weighting="concentration"):
+    """The bulk sensible heat flux Cs rho_a c_a u_a (Tu - Ta) as a LinearHeatFlux: K = ((Cs * rho_a) * c_a) * u_a formed in this order
+    in fp64 from numbers or arrays (examples/melting_in_spring.jl:64-73), Ta = atmosphere_temperature."""
+    parts = [x if _is_number(x) else np.asarray(x, dtype=np.float64)
+             for x in (transfer_coefficient, atmosphere_density, atmosphere_heat_capacity, atmosphere_wind_speed)]
+    K = ((np.float64(parts[0]) * parts[1]) * parts[2]) * parts[3]
+    return LinearHeatFlux(float(K) if np.ndim(K) == 0 else K, atmosphere_temperature, area_weighting)
+
+
 class MeltingConstrainedFluxBalance:
     """HeatBoundaryConditions.MeltingConstrainedFluxBalance (top_heat_boundary_conditions.jl:5-52): the top temperature
     balances the external and conductive fluxes, capped at the melting temperature.  On the accelerated path the
-    external flux does not depend on the temperature unless it has a RadiativeEmission term: then the reference's secant solve
-    runs per cell, otherwise its closed-form root is used (include/csi.h)."""
+    external flux does not depend on the temperature unless it has a RadiativeEmission or LinearHeatFlux term: then the reference's
+    secant solve runs per cell, otherwise its closed-form root is used (include/csi.h)."""
 
 
 class SlabThermodynamics:
@@ -161,7 +204,8 @@ class SlabThermodynamics:
     MeltingConstrainedFluxBalance (top_heat_boundary_condition) top boundary condition and IceWaterThermalEquilibrium
     at the bottom (SeaIceThermodynamics/slab_sea_ice_thermodynamics.jl:82-109); PhaseTransitions defaults
     (SeaIceThermodynamics.jl:106-124).  Heat fluxes: a number, an (Ny, Nx) array, a CenterField, RadiativeEmission (top only) or
-    a tuple of them (summed as the reference's getflux does), here or in SeaIceModel (not both); top_heat_flux=None is the
+    a tuple of them (summed as the reference's getflux does), here or in SeaIceModel (not both); bottom_salinity: a number or, per
+    cell, an (Ny, Nx) array, a CenterField or a FieldTimeSeries (the ocean's surface salinity: Tb = Tm(S(i, j))); top_heat_flux=None is the
     reference's default: for a prescribed temperature the external flux in equilibrium with the internal conductive flux,
     otherwise 0 (sea_ice_model.jl:243-256); bottom_heat_flux=None is 0 and "frazil" the -(1 - aice) W m^-2 flux of
     examples/freezing_bucket.jl:79-81.  top_surface_temperature: the CenterField the model binds when the step reads or writes
@@ -193,7 +237,8 @@ class SlabThermodynamics:
         equilibrium = top is None and not self.flux_balance and not snow     # sea_ice_model.jl:245-256
         return _lib.SlabParams(self.conductivity, sea_ice_density, self.density, self.liquid_density, self.liquid_heat_capacity,
                                self.heat_capacity, self.reference_latent_heat, self.reference_temperature, self.liquidus_slope,
-                               self.freshwater_melting_temperature, self.bottom_salinity, self.ice_consolidation_thickness,
+                               self.freshwater_melting_temperature,
+                               float(self.bottom_salinity) if _is_number(self.bottom_salinity) else 0.0, self.ice_consolidation_thickness,
                                self.top_temperature, 1 if equilibrium else 0, 1 if frazil else 0,
                                float(top) if _is_number(top) else 0.0,
                                1.0 if frazil else (float(bottom) if _is_number(bottom) else 0.0),
@@ -328,6 +373,9 @@ class SeaIceModel:
         self._derived_fields = {}           # name -> CenterField of the derived fields asked for so far (derived_field)
         self._momentum_term_fields = {}     # name -> XFaceField / YFaceField of the momentum term fields asked for so far (momentum_term)
         self._series, self._pending_series = {}, []     # slot name -> what csi_time_series_set was given (kept alive)
+        self.linear_heat_flux = None        # the LinearHeatFlux term's per-cell (coefficient, reference_temperature) fields, if any
+        self.bottom_salinity = None         # the per-cell bottom salinity's field, if any
+        self._heat_fluxes_used = None
         self.ctx = _lib.Context(dev.index or 0, stream)
         self._configure()
         self._attach_pending_series()
@@ -481,9 +529,13 @@ class SeaIceModel:
         if isinstance(value, FieldTimeSeries):      # the series writes into a new field (bound by the caller, registered after it)
             fld = CenterField(g, self.device, name)
             self._pending_series.append(({"top_heat_flux": "TOP_HEAT_FLUX", "bottom_heat_flux": "BOTTOM_HEAT_FLUX",
-                                          "snowfall": "SNOWFALL"}[name], value, fld))
+                                          "snowfall": "SNOWFALL", "flux_coefficient": "FLUX_COEFFICIENT",
+                                          "flux_reference_temperature": "FLUX_REFERENCE_TEMPERATURE",
+                                          "bottom_salinity": "BOTTOM_SALINITY"}[name], value, fld))
             return fld
         arr = np.asarray(value, dtype=np.float64)
+        if arr.ndim == 0:                           # a number beside a per-cell partner (LinearHeatFlux): broadcast
+            arr = np.full((g.Ny, g.Nx), float(arr))
         if isinstance(g, TileGrid) and arr.shape == (g.global_grid.Ny, g.global_grid.Nx):
             arr = arr[g.j_off:g.j_off + g.Ny, g.i_off:g.i_off + g.Nx]
         if arr.shape != (g.Ny, g.Nx):
@@ -507,6 +559,17 @@ class SeaIceModel:
                 t.kind = _lib.FLUX_RADIATIVE_EMISSION
                 t.emissivity, t.stefan_boltzmann_constant, t.reference_temperature = (x.emissivity, x.stefan_boltzmann_constant,
                                                                                        x.reference_temperature)
+            elif isinstance(x, LinearHeatFlux):
+                t.kind, t.reserved = _lib.FLUX_LINEAR, _WEIGHTINGS[x.area_weighting]
+                if x.per_cell:          # both per cell: a number beside an array is broadcast into one
+                    t.reserved |= _lib.LINEAR_COEFFICIENT_ARRAY | _lib.LINEAR_REFERENCE_ARRAY
+                    k = self._cell_field(x.coefficient, "flux_coefficient")
+                    ta = self._cell_field(x.reference_temperature, "flux_reference_temperature")
+                    self._bind("FLUX_COEFFICIENT", k)
+                    self._bind("FLUX_REFERENCE_TEMPERATURE", ta)
+                    self.linear_heat_flux = SimpleNamespace(coefficient=k, reference_temperature=ta)
+                else:
+                    t.value, t.reference_temperature = x.coefficient, x.reference_temperature
             else:
                 field = self._cell_field(x, f"{side}_heat_flux")
                 t.kind = _lib.FLUX_ARRAY
@@ -542,7 +605,13 @@ class SeaIceModel:
         if snowfall_array:
             self.snowfall = self._cell_field(self.snowfall, "snowfall")
             self._bind("SNOWFALL", self.snowfall)
-        ss = _lib.SurfaceSolve(1e-3, 1000, int(prescribed is not None), int(snowfall_array), 0)
+        # IceWaterThermalEquilibrium.salinity per cell (bottom_heat_boundary_conditions.jl:36-39)
+        salinity_array = not _is_number(ice.bottom_salinity)
+        if salinity_array:
+            self.bottom_salinity = self._cell_field(ice.bottom_salinity, "bottom_salinity")
+            self._bind("BOTTOM_SALINITY", self.bottom_salinity)
+        ss = _lib.SurfaceSolve(1e-3, 1000, int(prescribed is not None), int(snowfall_array),
+                               _lib.SOLVE_BOTTOM_SALINITY_ARRAY if salinity_array else 0)
         self.ctx.call("csi_surface_solve_set", C.byref(ss))
         # top_surface_temperature (top_heat_boundary_conditions.jl:82-100): state that starts at 0 wherever the step reads or writes it
         if snow is not None:
@@ -637,6 +706,23 @@ class SeaIceModel:
                 self._stress_field(slot, "V", tv)
         self.ctx.call("csi_stress_set", side, C.byref(s))
 
+    @property
+    def heat_fluxes_used(self):
+        """(top, bottom): the CenterFields into which every thermodynamic step writes the external heat fluxes it used (W m^-2) --
+        the bare-ice step its Qu (the internal flux with the equilibrium default) and Qb, the layered step Qui per cell, before the
+        snow-melt partition, and Qbi.  Allocated and bound the first time they are asked for; from then on the flux kernels run also
+        for a numeric configuration, with the number path's bits.  Read them after the step (synchronize() first)."""
+        if self.ice_thermodynamics is None:
+            raise ValueError("heat_fluxes_used needs ice_thermodynamics")
+        if self._heat_fluxes_used is None:
+            top = CenterField(self.grid, self.device, "top_heat_flux_used")
+            bottom = CenterField(self.grid, self.device, "bottom_heat_flux_used")
+            torch.cuda.synchronize(self.device)      # (the zero fill ran on torch's stream)
+            self._bind("TOP_HEAT_FLUX_USED", top)
+            self._bind("BOTTOM_HEAT_FLUX_USED", bottom)
+            self._heat_fluxes_used = SimpleNamespace(top=top, bottom=bottom)
+        return self._heat_fluxes_used
+
     def external_stress_field(self, slot, comp):
         return self._stress_fields[f"{slot}_{comp}"]
 
@@ -665,7 +751,7 @@ class SeaIceModel:
 
     # ---- forcing time series (include/csi.h, csi_time_series_set) -----------------------------------------------------------------
     def _set_series(self, slot):
-        self.ctx.call("csi_time_series_set", _lib.F[slot], C.byref(self._series[slot].struct))
+        self.ctx.call("csi_time_series_set", _lib.slot_id(slot), C.byref(self._series[slot].struct))
 
     def _attach_pending_series(self):
         """Register the series met while the model was described (their fields are bound by now), interpolate them at the clock and

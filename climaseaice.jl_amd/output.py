@@ -196,6 +196,14 @@ def bound_fields(model):
             out[f"{side}_heat_flux"] = (f, slot)
     if isinstance(model.snowfall, Field):
         out["snowfall"] = (model.snowfall, "SNOWFALL")
+    if getattr(model, "linear_heat_flux", None) is not None:      # the LinearHeatFlux term's per-cell K and Ta
+        out["flux_coefficient"] = (model.linear_heat_flux.coefficient, "FLUX_COEFFICIENT")
+        out["flux_reference_temperature"] = (model.linear_heat_flux.reference_temperature, "FLUX_REFERENCE_TEMPERATURE")
+    if getattr(model, "bottom_salinity", None) is not None:
+        out["bottom_salinity"] = (model.bottom_salinity, "BOTTOM_SALINITY")
+    if getattr(model, "_heat_fluxes_used", None) is not None:     # the used-flux outputs, once allocated (model.heat_fluxes_used)
+        out["top_heat_flux_used"] = (model._heat_fluxes_used.top, "TOP_HEAT_FLUX_USED")
+        out["bottom_heat_flux_used"] = (model._heat_fluxes_used.bottom, "BOTTOM_HEAT_FLUX_USED")
     from .derived import slot_of
     for name, f in getattr(model, "_derived_fields", {}).items():      # derived fields, once allocated (model.derived_field)
         out[name] = (f, slot_of(name))

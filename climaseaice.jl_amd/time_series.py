@@ -6,8 +6,9 @@ FieldTimeSeries(grid, location, times, data, time_indexing, backend)   upstream 
 Clamp(), Cyclical(period=None), Linear()                               upstream time indexing (RECALLED: include/csi.h states the rules)
 InMemory() / InMemory(n)                                               all slices on the device / n of them, the rest in host memory
 
-A series drives one of eleven arrays of a SeaIceModel: the stress components or external velocities of the top and bottom stresses,
-model.forcing u / v, the free-drift fields, the array term of the top / bottom heat flux, snowfall.  The model allocates the array as
+A series drives one of fourteen arrays of a SeaIceModel: the stress components or external velocities of the top and bottom stresses,
+model.forcing u / v, the free-drift fields, the array term of the top / bottom heat flux, snowfall, the coefficient and reference
+temperature of a LinearHeatFlux, the bottom salinity.  The model allocates the array as
 for a plain array and registers the series; csi_time_series_update interpolates it in place at the start of every step.
 """
 import numpy as np

@@ -395,17 +395,48 @@ int32_t csi_slab_params_set(csi_context* ctx, const csi_slab_params* p);
  *     tol and maxiters are csi_surface_solve's (defaults 1e-3 and 1000, the recalled SolutionTolerance and maxiters).
  * With a PrescribedTemperature top (top_bc_kind 0) and prescribed_array = 1 the surface temperature is read per cell from
  * CSI_F_TU (bare ice) / CSI_F_TUS (snow) instead of top_temperature.  The arithmetic follows the reference's order without
- * contraction in STRICT and FAST alike. */
-typedef enum { CSI_FLUX_CONSTANT = 0, CSI_FLUX_ARRAY = 1, CSI_FLUX_RADIATIVE_EMISSION = 2 } csi_heat_flux_kind;
+ * contraction in STRICT and FAST alike.
+ *
+ * LINEAR (top only, at most one per model): the bulk form the reference's users write into a FluxFunction closure
+ * (examples/melting_in_spring.jl:64-73, test/test_energy_conservation.jl:8-13), as data:
+ *     Q(T) = (K * (T - Ta)) * w      in exactly this order, uncontracted, STRICT and FAST alike
+ *     CSI_WEIGHT_NONE           the product by w is not made
+ *     CSI_WEIGHT_CONCENTRATION  w = aice[i, j], the concentration the step starts from
+ *     CSI_WEIGHT_ICE_PRESENT    Q = (aice[i, j] == 0) ? 0 : K * (T - Ta)
+ * The existing members carry it: `value` = K, `reference_temperature` = Ta, `reserved` = weighting (bits 0-1) |
+ * CSI_LINEAR_COEFFICIENT_ARRAY | CSI_LINEAR_REFERENCE_ARRAY.  With the two array flags K and Ta are read per cell from the (c,c)
+ * arrays bound to CSI_F_FLUX_COEFFICIENT and CSI_F_FLUX_REFERENCE_TEMPERATURE; both flags or neither (a front end broadcasts the
+ * number into an array when only one of the two is per cell).  The term takes its place in the right-nested sum like any other.
+ * It makes Qx depend on T: under MeltingConstrainedFluxBalance every consolidated cell runs the secant solve above, exactly as with
+ * an emission term (same tol, same maxiters; no closed form is substituted, although f is linear: the solve then ends after at
+ * most two updates).  Under PrescribedTemperature the term is evaluated at the prescribed temperature.
+ *
+ * PER-CELL BOTTOM SALINITY.  With csi_surface_solve.reserved = CSI_SOLVE_BOTTOM_SALINITY_ARRAY both steps form
+ * Tb = liq_T0 - liq_slope * S[i, j] from the (c,c) array bound to CSI_F_BOTTOM_SALINITY (IceWaterThermalEquilibrium.salinity read per
+ * cell, bottom_heat_boundary_conditions.jl:36-39) instead of csi_slab_params.bottom_salinity.  The ice salinity (Tm) stays a number.
+ *
+ * THE FLUXES A STEP USED.  Two optional OUTPUT slots, CSI_F_TOP_HEAT_FLUX_USED and CSI_F_BOTTOM_HEAT_FLUX_USED: when bound, the
+ * thermodynamic step writes the values it used into their interior -- the bare-ice step its Qu (the internal flux under
+ * top_flux_kind 1) and Qb, the layered step Qui (per cell, before the snow-melt partition) and Qbi.  Binding either one selects the
+ * flux kernels also for a numeric configuration, which gives the number path's h, aice, hs bit for bit.  Read them after the step
+ * (csi_sync, or work queued on the context's stream).  In an RK3 step they hold the last stage's values.
+ *
+ * The five slots are numbered from CSI_F_COUNT_BINDABLE on, so that every older id and count keeps its value. */
+typedef enum { CSI_FLUX_CONSTANT = 0, CSI_FLUX_ARRAY = 1, CSI_FLUX_RADIATIVE_EMISSION = 2, CSI_FLUX_LINEAR = 3 } csi_heat_flux_kind;
 typedef enum { CSI_HEAT_TOP = 0, CSI_HEAT_BOTTOM = 1 } csi_heat_flux_side;
+typedef enum { CSI_WEIGHT_NONE = 0, CSI_WEIGHT_CONCENTRATION = 1, CSI_WEIGHT_ICE_PRESENT = 2 } csi_flux_weighting;
+#define CSI_LINEAR_WEIGHT_MASK 3
+#define CSI_LINEAR_COEFFICIENT_ARRAY 4      /* csi_heat_flux_term.reserved of a LINEAR term: K per cell */
+#define CSI_LINEAR_REFERENCE_ARRAY 8        /*                                               Ta per cell */
+#define CSI_SOLVE_BOTTOM_SALINITY_ARRAY 1   /* csi_surface_solve.reserved: Tb per cell from CSI_F_BOTTOM_SALINITY */
 #define CSI_MAX_HEAT_FLUX_TERMS 8
 typedef struct {
     int32_t kind;                      /* csi_heat_flux_kind */
-    int32_t reserved;
-    double value;                      /* CONSTANT */
+    int32_t reserved;                  /* LINEAR: weighting | array flags (above); 0 otherwise */
+    double value;                      /* CONSTANT; LINEAR: K, W m^-2 K^-1 */
     double emissivity;                 /* RADIATIVE_EMISSION: 1 */
     double stefan_boltzmann_constant;  /*                     5.67e-8 */
-    double reference_temperature;      /*                     273.15 */
+    double reference_temperature;      /*                     273.15; LINEAR: Ta, in the unit of the surface temperature */
 } csi_heat_flux_term;
 int32_t csi_heat_fluxes_set(csi_context* ctx, int32_t side, const csi_heat_flux_term* terms, int32_t n);
 typedef struct {
@@ -413,7 +444,7 @@ typedef struct {
     int32_t maxiters;                  /* >= 1 (1000) */
     int32_t prescribed_array;          /* 1: PrescribedTemperature per cell, read from CSI_F_TU / CSI_F_TUS */
     int32_t snowfall_array;            /* 1: the layered step reads snowfall per cell from CSI_F_SNOWFALL */
-    int32_t reserved;
+    int32_t reserved;                  /* flags: CSI_SOLVE_BOTTOM_SALINITY_ARRAY; other bits 0 */
 } csi_surface_solve;
 /* NULL restores the defaults. */
 int32_t csi_surface_solve_set(csi_context* ctx, const csi_surface_solve* p);
@@ -503,6 +534,8 @@ int32_t csi_dynamics_set(csi_context* ctx, int32_t kind);
  * clock) (sea_ice_model.jl:391-408) and its kernels read a FieldTimeSeries at Time(clock.time) (thermodynamic_time_step.jl:326-329).
  * Here a series drives one of ELEVEN slots of csi_field_bind: CSI_F_TOP_U / _V, CSI_F_BOT_U / _V (stress arrays or external
  * velocities), CSI_F_FORCING_U / _V, CSI_F_FREE_DRIFT_U / _V, CSI_F_TOP_HEAT_FLUX, CSI_F_BOTTOM_HEAT_FLUX, CSI_F_SNOWFALL.
+ * Three thermodynamic inputs joined the eleven, fourteen in all: CSI_F_FLUX_COEFFICIENT, CSI_F_FLUX_REFERENCE_TEMPERATURE and
+ * CSI_F_BOTTOM_SALINITY (csi_heat_fluxes_set); they ride in the same launch.
  * csi_time_series_update(ctx, t) interpolates every series in ONE launch, in place, into the INTERIOR of the arrays bound to those
  * slots -- the arrays the momentum and thermodynamic kernels already read; no kernel of theirs changes.  The halos of the
  * velocity-point slots stay the library's to fill where it fills them for plain arrays (csi_time_step_momentum; csi_free_drift_set).
@@ -549,7 +582,7 @@ typedef struct {
     int64_t ld;              /* doubles between rows */
     int64_t slice_stride;    /* doubles between slices */
 } csi_time_series;
-/* Set (or, ts == NULL, remove) the series of one slot.  Any slot but the eleven: CSI_ERR_INVALID_ARGUMENT.  The slot's field must be
+/* Set (or, ts == NULL, remove) the series of one slot.  Any slot but the eleven and the three: CSI_ERR_INVALID_ARGUMENT.  The slot's field must be
  * bound (CSI_ERR_NOT_BOUND): the series writes into that array.  Setting a slot again replaces its series (empty window, zero uploads). */
 int32_t csi_time_series_set(csi_context* ctx, int32_t field_id, const csi_time_series* ts);
 /* Interpolate every series at `time` into its bound array, one launch on the context's stream (no series: nothing is launched, CSI_OK).
@@ -857,8 +890,18 @@ typedef enum {
     CSI_F_M_INTERNAL_Y,
     CSI_F_M_FORCING_X,
     CSI_F_M_FORCING_Y,
-    CSI_F_COUNT_BINDABLE                    /* every slot csi_field_bind takes */
+    CSI_F_COUNT_BINDABLE                    /* every slot csi_field_bind took before the slots of csi_thermo_linear_field_id */
 } csi_momentum_term_field_id;
+/* Five further (c,c) slots of csi_field_bind (csi_heat_fluxes_set: the LINEAR term's per-cell K and Ta, the per-cell bottom salinity,
+ * the two used-flux outputs), numbered from CSI_F_COUNT_BINDABLE on so that every older id and count keeps its value. */
+typedef enum {
+    CSI_F_FLUX_COEFFICIENT = CSI_F_COUNT_BINDABLE,   /* K of the LINEAR top term, W m^-2 K^-1 */
+    CSI_F_FLUX_REFERENCE_TEMPERATURE,                /* Ta of the LINEAR top term */
+    CSI_F_BOTTOM_SALINITY,                           /* S of Tb = liq_T0 - liq_slope * S */
+    CSI_F_TOP_HEAT_FLUX_USED,                        /* output: the top flux the last thermodynamic step used, W m^-2 */
+    CSI_F_BOTTOM_HEAT_FLUX_USED,                     /* output: the bottom flux it used */
+    CSI_F_COUNT_THERMO                               /* every slot csi_field_bind takes */
+} csi_thermo_linear_field_id;
 #define CSI_MTERM_CORIOLIS 1
 #define CSI_MTERM_TOP 2
 #define CSI_MTERM_BOTTOM 4

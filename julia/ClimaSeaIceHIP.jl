@@ -96,6 +96,31 @@ const DERIVED = (divergence=41, shear=42, deformation=43, speed=44, sigma_I=45, 
 const MOMENTUM_TERMS = (coriolis_x=48, coriolis_y=49, top_x=50, top_y=51, bottom_x=52, bottom_y=53, internal_x=54, internal_y=55, forcing_x=56, forcing_y=57)
 const MOMENTUM_TERM_BITS = (coriolis=1, top=2, bottom=4, internal=8, forcing=16)
 
+# csi_thermo_linear_field_id (from CSI_F_COUNT_BINDABLE on): the LINEAR top-flux term's per-cell K and Ta, the per-cell bottom salinity
+# and the two used-flux outputs, all (Center, Center)
+const THERMO_LINEAR = (FLUX_COEFFICIENT=58, FLUX_REFERENCE_TEMPERATURE=59, BOTTOM_SALINITY=60, TOP_HEAT_FLUX_USED=61,
+                       BOTTOM_HEAT_FLUX_USED=62)
+# csi_heat_flux_kind's LINEAR term Q(T) = (K * (T - Ta)) * w: `value` = K, `reference_temperature` = Ta, `reserved` = weighting | flags
+const CSI_FLUX_LINEAR = 3
+const CSI_WEIGHT_NONE = 0
+const CSI_WEIGHT_CONCENTRATION = 1
+const CSI_WEIGHT_ICE_PRESENT = 2
+const CSI_LINEAR_COEFFICIENT_ARRAY = 4
+const CSI_LINEAR_REFERENCE_ARRAY = 8
+# csi_surface_solve.reserved: Tb per cell from THERMO_LINEAR.BOTTOM_SALINITY
+const CSI_SOLVE_BOTTOM_SALINITY_ARRAY = 1
+
+# A FluxFunction is a closure and cannot cross the C ABI: it raises by name.  Its usual content, the bulk form K (Tu - Ta) [* aice], is data:
+# csi_heat_fluxes_set takes it as a CSI_FLUX_LINEAR term.
+function refuse_flux_function(flux, side)
+    items = flux isa Tuple ? flux : (flux,)
+    for x in items
+        nameof(typeof(x)) === :FluxFunction &&
+            error("ClimaSeaIceHIP: $(side)_heat_flux: a FluxFunction cannot cross the C ABI; give the bulk form K (Tu - Ta) as a LinearHeatFlux term (CSI_FLUX_LINEAR)")
+    end
+    return nothing
+end
+
 mutable struct Context
     handle::Ptr{Cvoid}
     mask::Any            # UInt8 activity mask of an immersed grid (owned here so that it outlives the library's pointer)
