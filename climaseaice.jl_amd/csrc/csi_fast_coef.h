@@ -8,6 +8,7 @@
 // weights are computed once on the host in fp64 (build_fast_coef) and read by the kernels as
 // wave-uniform scalars; on a uniform grid they are kernel-argument constants.
 #pragma once
+#include <stddef.h>
 #include <vector>
 
 namespace csi {
@@ -87,6 +88,15 @@ struct FastCoef {
     double rdt;             // 1 / dt
     double Dmin2, rDmin, amin2, amax2, ramin, ramax;   // Delta_min^2, 1/Delta_min, alpha-^2, alpha+^2, 1/alpha-, 1/alpha+
 };
+
+// The EVP parameters FAST mode accepts (fast_supported, evp_fast.hip; CSI_ERR_UNSUPPORTED otherwise):
+//   minimum_mass > 0            evp_fast_math.h drops the reference's mi <= 0 guards, which the active / marginal selection makes
+//                               redundant in that case (the reference's default is 1 kg m^-2)
+//   minimum_plastic_stress > 0  fm::stress_update_* form 1 / Delta as rsqrt(max(Delta^2, Delta_min^2)): with Delta_min = 0 an ice-free
+//                               cell at rest gives rsqrt(0) = inf, P / Delta = 0 * inf = NaN and fma(NaN, 0, sigma) = NaN where the
+//                               reference's ifelse(m > 0, ...) leaves sigma alone (the reference's default is 2e-9 s^-1).  The
+//                               comparison is written so that NaN is refused too.
+inline bool fast_params_supported(double min_mass, double Dmin) { return (min_mass > 0) && (Dmin > 0); }
 
 // Host: fill `uni` (uniform) or `out` ([FC_COUNT][n], n = Ny + 2Hy + 1, entry for row j at [j + Hy - 1]).
 inline void build_fast_coef_uniform(double dx, double dy, double* uni) {

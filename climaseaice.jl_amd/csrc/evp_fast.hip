@@ -664,9 +664,9 @@ void launch_forcing_bars(const EvpDev& P, const FRef& ubar_v, const FRef& vbar_u
 }
 
 bool fast_supported(const EvpDev& P) {
-    // minimum_mass > 0: evp_fast_math.h drops the reference's mi <= 0 guards, which the active / marginal selection
-    // makes redundant in that case (the reference's default is 1 kg m^-2)
-    return P.min_mass > 0;
+    // minimum_mass > 0 and minimum_plastic_stress > 0: the rule and its reasons are csi_fast_coef.h's fast_params_supported (a host
+    // header, so that tests/test_host_logic.py can ask it without a device)
+    return fast_params_supported(P.min_mass, P.Dmin);
 }
 
 void launch_fast_init(const EvpDev& P, const Range& r, hipStream_t s) {

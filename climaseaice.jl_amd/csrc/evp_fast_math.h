@@ -29,24 +29,31 @@ __device__ __forceinline__ double fmin_(double a, double b) { return __builtin_f
 __device__ __forceinline__ double clampd(double x, double lo, double hi) { return x > hi ? hi : (x < lo ? lo : x); }
 __device__ __forceinline__ double avg2(double a, double b) { return 0.5 * (a + b); }
 // y-average of x-averages, 0.5 * (0.5 * (a + b) + 0.5 * (c + d)): the halvings are exact, so one scaling at the end
-// gives the same bits with two multiplications fewer (barring subnormal intermediates)
+// gives the same bits with two multiplications fewer (as long as no intermediate is subnormal: a halving of a subnormal number rounds)
 __device__ __forceinline__ double avg4(double a, double b, double c, double d) { return 0.25 * ((a + b) + (c + d)); }
 __device__ __forceinline__ double sum2(double a, double b) { return a + b; }
 // the same from two x-sums kept from row to row (the row pipelines of the fused kernels)
 __device__ __forceinline__ double quarter(double s_a, double s_b) { return 0.25 * (s_a + s_b); }
 
 // Reciprocal and square root without the IEEE special-case scaffolding of the library versions
-// (v_div_scale / v_div_fixup, denormal rescaling): hardware seed (v_rcp_f64 / v_rsq_f64, 2^-25 relative error, measured)
-// + ONE Newton / Goldschmidt step.  Measured on gfx950 over 120 binades (scripts/microbench/seed_acc.hip,
-// profiles/r01_microbenchmarks.md): rcp max 11 ulp / mean 0.7 ulp; 1 / sqrt max 19.5 / mean 1.0 ulp; sqrt max 35.7 / mean
-// 1.2 ulp -- i.e. <= 8e-15 relative, against a stated FAST tolerance of 1e-12 on u, v (measured whole-cycle differences to
-// STRICT at 2048^2: 2.8e-15 max|u| with these, 1.9e-15 with 0.5-ulp versions).  Round 2 dropped the second refinement
-// steps: 34 of 282 VALU instructions per stage-row, +11 % cell-updates/s.  The one place that keeps its residual correction
-// is the square root that becomes alpha (sqrt_rsqrt's `s`: 0.5 ulp max), so that the clamp plateaus alpha- / alpha+ are the
-// exact numbers the reference stores (sqrt(alpha+^2) == alpha+).
+// (v_div_scale / v_div_fixup, denormal rescaling): hardware seed (v_rcp_f64 / v_rsq_f64) + ONE Newton / Goldschmidt step.
+// With e the seed's relative error and u = 2^-53, one step with correctly rounded fused multiply-adds gives
+//     rcp: e^2 + 2 u        rsqrt, sqrt_fast: 1.5 e^2 + 2 u
+// (derived and emulated exactly in tests/test_fast_math_ref.py) and tests/test_gpu_fast_math.py holds every element of every binade
+// of [2^-1000, 2^1000] to exactly that, with e measured per element and capped at 2^-23.  On gfx950 (profiles/r20_fast_math_probe.md)
+// the seeds are good to 2^-24.4 (rcp) and 2^-24.2 (rsq), which puts the refined results within 2.2e-15 (rcp: max 11 ulp, mean 0.6) and
+// 4.2e-15 (1 / sqrt: max 19 ulp, mean 0.9; sqrt: max 36 ulp, mean 1.1) -- against a stated FAST tolerance of 1e-12 on u, v (measured
+// whole-cycle differences to STRICT at 2048^2: 2.8e-15 max|u| with these, 1.9e-15 with 0.5-ulp versions).  Round 2 dropped the second
+// refinement steps: 34 of 282 VALU instructions per stage-row, +11 % cell-updates/s.  The one place that keeps its residual correction
+// is the square root that becomes alpha (sqrt_rsqrt's `s`: the correctly rounded root on all 1 026 005 arguments of that test, and
+// asserted bit for bit on alpha^2 for every alpha = k / 4 up to 1000 and a sample of 20 000 alpha of at most 26 significant bits
+// in [0.5, 1024)), so that the clamp
+// plateaus alpha- / alpha+ are the exact numbers the reference stores (sqrt(alpha+^2) == alpha+).
 // Arguments are positive finite where the result is used; zero, infinite and NaN arguments may yield NaN, which every
 // caller absorbs with the same selects the reference uses (m <= 0 ? 0 : ..., isnan(gamma^2) ? alpha+^2 : ...) or an
-// explicit guard.
+// explicit guard.  One absorbed NaN is not the reference's value: rcp of a subnormal mass of 2^-1024 or less is NaN (the seed is inf), so
+// gamma^2 goes to alpha+^2 as for m = 0; the reference's zeta c dt / m is beyond alpha+^2 there as well -- alpha+ -- unless zeta is
+// exactly 0, where it is 0 and alpha-.  An ice strength of exactly 0 under a mass that is not 0 takes a thickness below 1e-319 m.
 __device__ __forceinline__ double rcp(double x) {
     const double r = __builtin_amdgcn_rcp(x);
     return fma_(fma_(-x, r, 1.0), r, r);
@@ -170,7 +177,12 @@ __device__ __forceinline__ StressOut stress_update_r(const StressConst& k, doubl
 //   y2         : 2 e12c         (1/16 of the sum of the four corners' E12)
 //   XP, M4     : 4 Pf, 4 mf     (sums of the four cells' ice strength / mass);  rM4 = rcp(M4) = rmf / 4
 //   hkf4       : 4 hkf;   k.em2_8 = e^-2 / 8, k.Dmin2_16 = 16 Delta_min^2
-// Delta_f^2 comes out times 16, 1 / Delta_f divided by 4, 2 zeta_f = XP / (4 Delta_f) exactly as before.
+// Delta_f^2 comes out times 16, 1 / Delta_f divided by 4, 2 zeta_f = XP / (4 Delta_f) exactly as before.  "The same bits" holds while
+// no intermediate is subnormal, where a scaling rounds: measured (tests/test_gpu_fast_math.py, all eight outputs, strain rates and
+// Delta_min scaled down together) bit for bit down to 2^-508, first difference at 2^-512, where the squares leave the normal range.
+// The corner's mass has a boundary of its own: rcp(M4) is finite where rcp(mf) is NaN for mf in (2^-1026, 2^-1024], so under an ice
+// strength of exactly 0 this form has gamma_f^2 = 0 -- alpha-, the reference's value -- where stress_update_r has alpha+ (see rcp
+// above), and sigma12 differs; measured on exactly those masses and nowhere else (any P > 0, any normal mass: the same bits).
 __device__ __forceinline__ StressOut stress_update_s(const StressConst& k, double e11c, double e22c, double E12f,
                                                      double S11f, double S22f, double y2, double Pc, double XP,
                                                      double mc, double M4, double rmc, double rM4, double hkc, double hkf4,
@@ -288,7 +300,7 @@ __device__ __forceinline__ double vel_update_fd(const VelConst& k, double w, dou
 
 // The same from SUMS over the two cells the face separates (m2 = 2 mi, a2 = 2 ai, al2 = 2 abar) and a VelConst whose dt,
 // min_mass, min_conc are DOUBLED (rdt is not): every intermediate is vel_update_avg's scaled by an exact power of two
-// (also through rcp: seed and Newton step scale exactly), so the result has the same bits -- the three halvings of the
+// (also through rcp: seed and Newton step scale exactly; tested bit for bit, subnormal masses included), so the result has the same bits -- the three halvings of the
 // averages become one doubling of 1 / m.  The row pipelines of the pair kernel (evp_pair_stage.h) use these.
 // div2: TWICE the stress divergence (the row pipelines form it with doubled coefficients: div2 / (2 mi) instead of div x (1 / (2 mi) +
 // 1 / (2 mi)), one addition less, the same bits)

@@ -204,6 +204,9 @@ typedef struct {
  *         by rounding only (tolerance stated in DESIGN.md and enforced in tests/).  Requires
  *         minimum_mass > 0 (the reference's default is 1 kg m^-2): the mi <= 0 guards of the velocity
  *         tendencies are then implied by the active / marginal ice selection and are not evaluated
+ *         (CSI_ERR_UNSUPPORTED otherwise).  Requires minimum_plastic_stress > 0 as well (the reference's default
+ *         is 2e-9 s^-1): 1 / Delta is formed from max(Delta^2, Delta_min^2) without a guard, and with Delta_min = 0
+ *         an ice-free cell at rest would turn its stresses into NaN where the reference leaves them alone
  *         (CSI_ERR_UNSUPPORTED otherwise).  Advection, the tracer update and the thermodynamic steps are
  *         computed in the reference's order in both modes. */
 typedef enum { CSI_MODE_STRICT = 0, CSI_MODE_FAST = 1 } csi_mode;

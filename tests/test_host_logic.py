@@ -169,3 +169,21 @@ def test_exchange_plans_of_all_ranks_match_in_posting_order():
                 assert gx[0] == gx[1] and gy[0] == gy[1], ((Rx, Ry), (tx, ty), a, b, (si, sj), (wi, wj))
                 matched += 1
     assert matched > 2000, matched
+
+
+def test_fast_mode_refuses_a_plastic_stress_floor_or_minimum_mass_that_is_not_positive():
+    """fast_supported (evp_fast.hip) decides by csi_fast_coef.h's fast_params_supported, asked here through the host wrapper
+    tests/fast_coef_host.cpp.  minimum_mass > 0 lets FAST drop the mi <= 0 guards; minimum_plastic_stress > 0 keeps rsqrt(max(Delta^2,
+    Delta_min^2)) finite: with Delta_min = 0 an ice-free cell at rest would give P / Delta = 0 * inf = NaN and fma(NaN, 0, sigma) = NaN
+    where the reference's ifelse(m > 0, ...) leaves sigma alone.  NaN parameters are refused as well."""
+    import ctypes
+    import fast_math_build
+    L = ctypes.CDLL(fast_math_build.build_coef())
+    L.fch_fast_params_supported.argtypes = [ctypes.c_double, ctypes.c_double]
+    ok = lambda min_mass, Dmin: bool(L.fch_fast_params_supported(min_mass, Dmin))
+    d = csi.SeaIceMomentumEquation(csi.RectilinearGrid((8, 8), x=(0, 1), y=(0, 1)), device="cpu")
+    assert ok(d.minimum_mass, d.rheology.minimum_plastic_stress)                 # the reference's defaults: 1 kg m^-2, 2e-9 s^-1
+    assert ok(5e-324, 5e-324)
+    nan = float("nan")
+    for min_mass, Dmin in ((1.0, 0.0), (1.0, -0.0), (1.0, -2e-9), (1.0, nan), (0.0, 2e-9), (-1.0, 2e-9), (nan, 2e-9), (0.0, 0.0)):
+        assert not ok(min_mass, Dmin), (min_mass, Dmin)
