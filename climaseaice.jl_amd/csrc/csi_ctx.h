@@ -280,20 +280,15 @@ struct csi_context {
     bool series_launched_valid = false;
     bool series_prefetch_pending = false;    // the newest update's look-ahead uploads have not been issued yet
     long series_updates = 0;
-    // csi_diagnostics_compute (csi_diagnostics.hip): the partial records followed by the DQ_COUNT result slots (sized at first use, for
-    // the grid), the page-locked copy of the result, and the device staging of an all-gather over an RCCL communicator (only grows)
-    DeviceBuf<double> diag_part;
-    PinnedBuf<double> diag_host;
+    // the ordered reductions (csi_diagnostics_compute, csi_budget_compute, csi_momentum_budget_compute; reduce_begin in
+    // csi_diagnostics.hip): ONE device buffer -- the partial records followed by the result slots, sized by the grid alone for the
+    // largest slot count, so alternating calls never reallocate -- and ONE page-locked copy of the result; every such call ends in a
+    // wait, so they never overlap.  gather_buf: the device staging of an all-gather over an RCCL communicator (only grows)
+    DeviceBuf<double> reduce_part;
+    PinnedBuf<double> reduce_host;
     DeviceBuf<uint8_t> gather_buf;
-    // csi_derived_compute / csi_budget_compute (csi_derived.hip): the budget's partial records followed by its BQ_COUNT result slots, their
-    // page-locked copy, and the calls made so far (csi_derived_stats)
-    DeviceBuf<double> budget_part;
-    PinnedBuf<double> budget_host;
+    // the calls made so far (csi_derived_stats, csi_momentum_terms_stats)
     int64_t derived_launches = 0, budget_calls = 0;
-    // csi_momentum_terms_compute / csi_momentum_budget_compute (csi_momentum_terms.hip): the power sums' partial records followed by
-    // their MQ_COUNT result slots, the page-locked copy, and the calls made so far (csi_momentum_terms_stats)
-    DeviceBuf<double> mterm_part;
-    PinnedBuf<double> mterm_host;
     int64_t mterm_launches = 0, mterm_budget_calls = 0;
     // csi_output_* (csi_output.hip): the sets and the copy stream their records leave on, made at the first csi_output_create
     OutputSet out_sets[kMaxOutputSets];
@@ -448,6 +443,19 @@ int img_of(int side, int loc);
 ImageSpec image_spec(const csi_context* c, int fid);
 FRef ref_of(const csi_context* c, int fid);
 int32_t need(csi_context* c, std::initializer_list<int> ids);
+// every id bound, or CSI_ERR_NOT_BOUND "<who>: <group>needs field <name> (not bound<hint>)" (group: empty, or with its trailing blank)
+int32_t need_named(csi_context* c, const char* who, const char* group, std::initializer_list<int> ids, const char* hint);
+// the host side of an ordered reduction (ordered_reduce.h), csi_diagnostics.hip.  reduce_begin: sizes the context's reduction buffers
+// and hands out the partial records, their count and the place of the result; the caller queues its partial and finishing kernel on
+// the context's stream; reduce_end: copies the n result slots to page-locked memory, waits ONCE and copies them to slots[n].
+// reduce_ranks: on a tiled context the all-gather of every rank's (status, slots) and the
+// combine of slots q0 .. q1 - 1 in rank order (combine == nullptr: every slot a sum); rc: this rank's status so far -- a rank that
+// has failed locally (a missing field, a HIP error) still enters the collective, with a status word that makes every other rank
+// return CSI_ERR_COMM "<who>: rank r ... failed locally": an early return would strand the others inside it (as in csi_peer.hip
+// peer_setup).  Returns rc, with its message, if set.
+int32_t reduce_begin(csi_context* c, double** part, long* nrec, double** result);
+int32_t reduce_end(csi_context* c, int n, const double* result, double* slots);
+int32_t reduce_ranks(csi_context* c, const char* who, int32_t rc, int n, int q0, int q1, double (*combine)(int q, double a, double b), double* slots);
 StressDev stress_dev(const csi_context* c, int side);
 int32_t check_stress_fields(csi_context* c, int side);
 int32_t sync_coriolis(csi_context* c);

@@ -4,20 +4,13 @@
 // test/test_rheology_energy_budget.jl sums the discrete budget cell by cell.  The kernels: derived.hip, budget.hip.
 //
 // Host side: argument and binding checks by name, ONE launch for the derived fields (nothing is waited for: the fields are read by
-// whatever is queued next on the context's stream, e.g. an output set's pack launch); for the budget the two launches, the copy of the
-// BQ_COUNT slots into page-locked memory and ONE wait, then on a tiled context the all-gather and the combine in rank order, with the
-// diagnostics' rule for a rank that fails locally (it still reaches the collective; then every rank returns an error).
+// whatever is queued next on the context's stream, e.g. an output set's pack launch); for the budget the host path of the ordered
+// reductions (csi_ctx.h reduce_begin / reduce_end, reduce_ranks).
 #include "csi_ctx.h"
 
 namespace csi_host {
 
 static const int kStressBits = CSI_DERIVED_SIGMA_I | CSI_DERIVED_SIGMA_II | CSI_DERIVED_STRESS_POWER;
-
-static int32_t need_named(csi_context* c, const char* who, const char* group, std::initializer_list<int> ids, const char* hint) {
-    for (int id : ids)
-        if (!c->f[id].p) return fail(c, CSI_ERR_NOT_BOUND, std::string(who) + ": " + group + " needs field " + kName[id] + " (not bound" + hint + ")");
-    return CSI_OK;
-}
 
 static int32_t budget_local(csi_context* c, int32_t what, double* slots) {
     if (what == 0 || (what & ~CSI_BUDGET_ALL)) return fail(c, CSI_ERR_INVALID_ARGUMENT, "budget: `what` must be a non-empty mask of CSI_BUDGET_STRESS (1) and CSI_BUDGET_KINETIC (2); unknown bit");
@@ -25,32 +18,22 @@ static int32_t budget_local(csi_context* c, int32_t what, double* slots) {
     if (c->Hx < 1 || c->Hy < 1) return fail(c, CSI_ERR_INVALID_ARGUMENT, "budget: the grid needs halo >= 1");
     const bool stress = what & CSI_BUDGET_STRESS, kin = what & CSI_BUDGET_KINETIC;
     int32_t rc;
-    if ((rc = need_named(c, "budget", "every group", {CSI_F_U, CSI_F_V}, ": a model without dynamics has no energy budget"))) return rc;
+    if ((rc = need_named(c, "budget", "every group ", {CSI_F_U, CSI_F_V}, ": a model without dynamics has no energy budget"))) return rc;
     if (stress) {
         if (c->rheology != CSI_RHEOLOGY_EVP) return fail(c, CSI_ERR_NOT_BOUND, "budget: the stress group needs field sigma11 (an ElastoViscoPlasticRheology's stress fields; this model's rheology has none)");
-        if ((rc = need_named(c, "budget", "the stress group", {CSI_F_S11, CSI_F_S22, CSI_F_S12}, ": an ElastoViscoPlasticRheology's stress fields"))) return rc;
+        if ((rc = need_named(c, "budget", "the stress group ", {CSI_F_S11, CSI_F_S22, CSI_F_S12}, ": an ElastoViscoPlasticRheology's stress fields"))) return rc;
     }
-    if (kin && (rc = need_named(c, "budget", "the kinetic group", {CSI_F_H, CSI_F_A}, ""))) return rc;
-    HIP_TRY(c, hipSetDevice(c->device));
+    if (kin && (rc = need_named(c, "budget", "the kinetic group ", {CSI_F_H, CSI_F_A}, ""))) return rc;
     BudgetDev D{};
     D.g = c->g;
     D.u = ref_of(c, CSI_F_U); D.v = ref_of(c, CSI_F_V);
     D.s11 = ref_of(c, CSI_F_S11); D.s22 = ref_of(c, CSI_F_S22); D.s12 = ref_of(c, CSI_F_S12);
     D.h = ref_of(c, CSI_F_H); D.a = ref_of(c, CSI_F_A);
     D.rho = c->evp_set ? c->evp.sea_ice_density : 900.0;
-    int nbx, nby;
-    diag_geometry(c->Nx, c->Ny, &nbx, &nby);
-    D.nrec = (long)nbx * nby;
-    HIP_TRY(c, c->budget_part.ensure((size_t)(D.nrec + 1) * BQ_COUNT, c->stream, false));
-    if (!c->budget_host) HIP_TRY(c, c->budget_host.alloc(BQ_COUNT, hipHostMallocDefault));
-    D.part = c->budget_part.get();
-    double* result = D.part + (size_t)D.nrec * BQ_COUNT;
+    double* result;
+    if ((rc = reduce_begin(c, &D.part, &D.nrec, &result))) return rc;
     launch_budget(D, stress, kin, result, c->stream);
-    HIP_TRY(c, hipGetLastError());
-    HIP_TRY(c, hipMemcpyAsync(c->budget_host.get(), result, sizeof(double) * BQ_COUNT, hipMemcpyDeviceToHost, c->stream));
-    HIP_TRY(c, hipStreamSynchronize(c->stream));
-    memcpy(slots, c->budget_host.get(), sizeof(double) * BQ_COUNT);
-    return CSI_OK;
+    return reduce_end(c, BQ_COUNT, result, slots);
 }
 
 }  // namespace csi_host
@@ -65,10 +48,10 @@ int32_t csi_derived_compute(csi_context* c, int32_t mask) {
     if (!c->grid_set) return fail(c, CSI_ERR_NOT_BOUND, "csi_grid_set has not been called");
     if (c->Hx < 1 || c->Hy < 1) return fail(c, CSI_ERR_INVALID_ARGUMENT, "derived: the grid needs halo >= 1");
     const bool stress = mask & kStressBits;
-    if ((rc = need_named(c, "derived", "every field", {CSI_F_U, CSI_F_V}, ": a model without velocities has no derived fields"))) return rc;
+    if ((rc = need_named(c, "derived", "every field ", {CSI_F_U, CSI_F_V}, ": a model without velocities has no derived fields"))) return rc;
     if (stress) {
         if (c->rheology != CSI_RHEOLOGY_EVP) return fail(c, CSI_ERR_NOT_BOUND, "derived: the stress group needs field sigma11 (an ElastoViscoPlasticRheology's stress fields; this model's rheology has none)");
-        if ((rc = need_named(c, "derived", "the stress group", {CSI_F_S11, CSI_F_S22, CSI_F_S12, CSI_F_P}, ": an ElastoViscoPlasticRheology's fields"))) return rc;
+        if ((rc = need_named(c, "derived", "the stress group ", {CSI_F_S11, CSI_F_S22, CSI_F_S12, CSI_F_P}, ": an ElastoViscoPlasticRheology's fields"))) return rc;
     }
     DerivedDev D{};
     for (int k = 0; k < DV_COUNT; ++k) {
@@ -90,27 +73,10 @@ int32_t csi_derived_compute(csi_context* c, int32_t mask) {
 int32_t csi_budget_compute(csi_context* c, int32_t what, csi_budget* out) {
     if (!c) return CSI_ERR_INVALID_ARGUMENT;
     if (!out) return fail(c, CSI_ERR_INVALID_ARGUMENT, "budget: out == NULL");
-    struct Payload { int64_t status; double slot[BQ_COUNT]; } mine{};
+    double slot[BQ_COUNT] = {};
     int32_t rc = peer_check_entry(c);
-    if (!rc) rc = budget_local(c, what, mine.slot);
-    mine.status = rc;
-    double slot[BQ_COUNT];
-    memcpy(slot, mine.slot, sizeof slot);
-    if (has_comm(c)) {
-        std::vector<uint8_t> all;
-        const std::string local_err = c->err;
-        const int32_t grc = comm_allgather(c, &mine, sizeof mine, all);
-        if (rc) { c->err = local_err; return rc; }
-        if (grc) return grc;
-        for (int r = 0; r < c->world; ++r) {
-            Payload p;
-            memcpy(&p, all.data() + (size_t)r * sizeof p, sizeof p);
-            if (p.status) return fail(c, CSI_ERR_COMM, "budget: rank " + std::to_string(r) + " of the decomposition failed locally (status " + std::to_string((long)p.status) + ")");
-            for (int q = 0; q < BQ_COUNT; ++q) slot[q] = r == 0 ? p.slot[q] : slot[q] + p.slot[q];
-        }
-    } else if (rc) {
-        return rc;
-    }
+    if (!rc) rc = budget_local(c, what, slot);
+    if ((rc = reduce_ranks(c, "budget", rc, BQ_COUNT, 0, BQ_COUNT, nullptr, slot))) return rc;
     const double nan = std::nan("");
     csi_budget b{};
     b.what = what;

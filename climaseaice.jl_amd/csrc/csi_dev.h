@@ -55,6 +55,10 @@ __device__ __forceinline__ double azm(const GridDev& g, int lx, int ly, int i, i
     return metric2(g, 2, lx, ly, i, j);
 }
 
+// the reference's four-point interpolation of values x0 .. x3 (x fastest): ((x0 + x1) / 2 + (x2 + x3) / 2) / 2, in this order everywhere
+__device__ __forceinline__ double avg4(double x0, double x1, double x2, double x3) { return ((x0 + x1) / 2 + (x2 + x3) / 2) / 2; }
+__device__ __forceinline__ double avg4(const double* x) { return avg4(x[0], x[1], x[2], x[3]); }
+
 struct StressDev {
     int kind, ue_kind, ve_kind, pad;
     double tau_u, tau_v, ue, ve, rho_e, Cd;

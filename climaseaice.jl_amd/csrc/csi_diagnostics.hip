@@ -2,13 +2,65 @@
 // Stands where the reference's root module has cell_advection_timescale(model::SeaIceModel) (src/ClimaSeaIce.jl:63-69) and where its
 // tests and validation scripts reduce whole fields on the host.  The kernels and the summation order: diagnostics.hip.
 //
-// Host side: argument and binding checks, the two launches and the copy of the DQ_COUNT result slots into page-locked memory on the
-// context's stream, ONE wait for that stream; on a tiled context the all-gather of every rank's slots and their combine in rank
-// order.  A rank that fails locally (a missing field, a HIP error) still reaches the all-gather, with a status word that makes every
-// rank return an error: an early return would strand the others inside the collective (as in csi_peer.hip peer_setup).
+// Host side: argument and binding checks, then the host path of every ordered reduction, stated here once (csi_ctx.h reduce_begin / reduce_end,
+// reduce_ranks; csi_budget_compute and csi_momentum_budget_compute use it too): the two launches and the copy of the result slots
+// into page-locked memory on the context's stream, ONE wait for that stream; on a tiled context the all-gather of every rank's slots
+// and their combine in rank order.
 #include "csi_ctx.h"
+#include "ordered_reduce.h"
 
 namespace csi_host {
+
+static_assert(DQ_COUNT >= BQ_COUNT && DQ_COUNT >= MQ_COUNT, "the reduction buffers are sized for the diagnostics' slot count");
+
+int32_t need_named(csi_context* c, const char* who, const char* group, std::initializer_list<int> ids, const char* hint) {
+    for (int id : ids)
+        if (!c->f[id].p) return fail(c, CSI_ERR_NOT_BOUND, std::string(who) + ": " + group + "needs field " + kName[id] + " (not bound" + hint + ")");
+    return CSI_OK;
+}
+
+int32_t reduce_begin(csi_context* c, double** part, long* nrec, double** result) {
+    HIP_TRY(c, hipSetDevice(c->device));
+    int nbx, nby;
+    red::diag_geometry(c->Nx, c->Ny, &nbx, &nby);
+    *nrec = (long)nbx * nby;
+    HIP_TRY(c, c->reduce_part.ensure((size_t)(*nrec + 1) * DQ_COUNT, c->stream, false));
+    if (!c->reduce_host) HIP_TRY(c, c->reduce_host.alloc(DQ_COUNT, hipHostMallocDefault));
+    *part = c->reduce_part.get();
+    *result = *part + (size_t)*nrec * DQ_COUNT;
+    return CSI_OK;
+}
+
+int32_t reduce_end(csi_context* c, int n, const double* result, double* slots) {
+    HIP_TRY(c, hipGetLastError());
+    HIP_TRY(c, hipMemcpyAsync(c->reduce_host.get(), result, sizeof(double) * n, hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(c, hipStreamSynchronize(c->stream));
+    memcpy(slots, c->reduce_host.get(), sizeof(double) * n);
+    return CSI_OK;
+}
+
+int32_t reduce_ranks(csi_context* c, const char* who, int32_t rc, int n, int q0, int q1, double (*combine)(int q, double a, double b), double* slots) {
+    if (!has_comm(c)) return rc;
+    // a rank's payload: the status word, then its n slots
+    const size_t nb = sizeof(int64_t) + sizeof(double) * n;
+    std::vector<uint8_t> mine(nb), all;
+    const int64_t status = rc;
+    memcpy(mine.data(), &status, sizeof status);
+    memcpy(mine.data() + sizeof status, slots, sizeof(double) * n);
+    const std::string local_err = c->err;
+    const int32_t grc = comm_allgather(c, mine.data(), nb, all);
+    if (rc) { c->err = local_err; return rc; }
+    if (grc) return grc;
+    std::vector<double> theirs(n);
+    for (int r = 0; r < c->world; ++r) {
+        int64_t st;
+        memcpy(&st, all.data() + (size_t)r * nb, sizeof st);
+        memcpy(theirs.data(), all.data() + (size_t)r * nb + sizeof st, sizeof(double) * n);
+        if (st) return fail(c, CSI_ERR_COMM, std::string(who) + ": rank " + std::to_string(r) + " of the decomposition failed locally (status " + std::to_string((long)st) + ")");
+        for (int q = q0; q < q1; ++q) slots[q] = r == 0 ? theirs[q] : (combine ? combine(q, slots[q], theirs[q]) : slots[q] + theirs[q]);
+    }
+    return CSI_OK;
+}
 
 static int32_t diag_local(csi_context* c, int32_t what, double thr, double* slots) {
     if (what == 0 || (what & ~CSI_DIAG_ALL)) return fail(c, CSI_ERR_INVALID_ARGUMENT, "diagnostics: `what` must be a non-empty mask of CSI_DIAG_VELOCITY (1) and CSI_DIAG_TRACERS (2); unknown bit");
@@ -21,7 +73,6 @@ static int32_t diag_local(csi_context* c, int32_t what, double thr, double* slot
     if (trc)
         for (int id : {CSI_F_H, CSI_F_A})
             if (!c->f[id].p) return fail(c, CSI_ERR_NOT_BOUND, std::string("diagnostics: the tracer group needs field ") + kName[id] + " (not bound)");
-    HIP_TRY(c, hipSetDevice(c->device));
     DiagDev D{};
     D.g = c->g;
     D.u = ref_of(c, CSI_F_U); D.v = ref_of(c, CSI_F_V); D.h = ref_of(c, CSI_F_H); D.a = ref_of(c, CSI_F_A); D.hs = ref_of(c, CSI_F_HS);
@@ -31,26 +82,23 @@ static int32_t diag_local(csi_context* c, int32_t what, double thr, double* slot
     if (vel && (c->f[CSI_F_U].ni < c->Nx + 2 * c->Hx + D.exu || c->f[CSI_F_V].nj < c->Ny + 2 * c->Hy + D.eyv))
         return fail(c, CSI_ERR_INVALID_ARGUMENT, "diagnostics: u / v parents are smaller than the grid's Face fields");
     D.threshold = thr;
-    int nbx, nby;
-    diag_geometry(c->Nx, c->Ny, &nbx, &nby);
-    D.nrec = (long)nbx * nby;
-    HIP_TRY(c, c->diag_part.ensure((size_t)(D.nrec + 1) * DQ_COUNT, c->stream, false));
-    if (!c->diag_host) HIP_TRY(c, c->diag_host.alloc(DQ_COUNT, hipHostMallocDefault));
-    D.part = c->diag_part.get();
-    double* result = D.part + (size_t)D.nrec * DQ_COUNT;
+    double* result;
+    int32_t rc = reduce_begin(c, &D.part, &D.nrec, &result);
+    if (rc) return rc;
     launch_diagnostics(D, vel, trc, result, c->stream);
-    HIP_TRY(c, hipGetLastError());
-    HIP_TRY(c, hipMemcpyAsync(c->diag_host.get(), result, sizeof(double) * DQ_COUNT, hipMemcpyDeviceToHost, c->stream));
-    HIP_TRY(c, hipStreamSynchronize(c->stream));
-    memcpy(slots, c->diag_host.get(), sizeof(double) * DQ_COUNT);
-    return CSI_OK;
+    return reduce_end(c, DQ_COUNT, result, slots);
 }
 
 static int64_t as_count(double slot) { int64_t n; memcpy(&n, &slot, sizeof n); return n; }
 static double from_count(int64_t n) { double d; memcpy(&d, &n, sizeof d); return d; }
-static bool is_sum(int q) { return q >= DQ_VOLUME && q <= DQ_ACTIVE_AREA; }
-static bool is_max(int q) { return q == DQ_INV_TIMESCALE || q == DQ_MAX_ABS_U || q == DQ_MAX_ABS_V || q == DQ_MAX_H || q == DQ_MAX_AICE || q == DQ_MAX_HS; }
-static bool is_min(int q) { return q == DQ_MIN_H || q == DQ_MIN_AICE; }
+static double diag_combine(int q, double a, double b) {
+    switch (DiagKinds::kind(q)) {
+        case K_SUM: return a + b;
+        case K_MAX: return std::fmax(a, b);
+        case K_MIN: return std::fmin(a, b);
+        default: return from_count(as_count(a) + as_count(b));
+    }
+}
 
 }  // namespace csi_host
 
@@ -59,34 +107,11 @@ extern "C" {
 int32_t csi_diagnostics_compute(csi_context* c, int32_t what, double extent_threshold, csi_diagnostics* out) {
     if (!c) return CSI_ERR_INVALID_ARGUMENT;
     if (!out) return fail(c, CSI_ERR_INVALID_ARGUMENT, "diagnostics: out == NULL");
-    struct Payload { int64_t status; double slot[DQ_COUNT]; } mine{};
+    double slot[DQ_COUNT] = {};
     int32_t rc = peer_check_entry(c);
-    if (!rc) rc = diag_local(c, what, extent_threshold, mine.slot);
-    mine.status = rc;
-    double slot[DQ_COUNT];
-    memcpy(slot, mine.slot, sizeof slot);
-    if (has_comm(c)) {
-        std::vector<uint8_t> all;
-        const std::string local_err = c->err;
-        const int32_t grc = comm_allgather(c, &mine, sizeof mine, all);
-        if (rc) { c->err = local_err; return rc; }
-        if (grc) return grc;
-        const bool vel = what & CSI_DIAG_VELOCITY;
-        for (int r = 0; r < c->world; ++r) {
-            Payload p;
-            memcpy(&p, all.data() + (size_t)r * sizeof p, sizeof p);
-            if (p.status) return fail(c, CSI_ERR_COMM, "diagnostics: rank " + std::to_string(r) + " of the decomposition failed locally (status " + std::to_string((long)p.status) + ")");
-            for (int q = vel ? 0 : DQ_VOLUME; q < ((what & CSI_DIAG_TRACERS) ? DQ_COUNT : DQ_VOLUME); ++q) {
-                if (r == 0) slot[q] = p.slot[q];
-                else if (is_sum(q)) slot[q] = slot[q] + p.slot[q];
-                else if (is_max(q)) slot[q] = std::fmax(slot[q], p.slot[q]);
-                else if (is_min(q)) slot[q] = std::fmin(slot[q], p.slot[q]);
-                else slot[q] = from_count(as_count(slot[q]) + as_count(p.slot[q]));
-            }
-        }
-    } else if (rc) {
-        return rc;
-    }
+    if (!rc) rc = diag_local(c, what, extent_threshold, slot);
+    const int q0 = (what & CSI_DIAG_VELOCITY) ? 0 : DQ_VOLUME, q1 = (what & CSI_DIAG_TRACERS) ? DQ_COUNT : DQ_VOLUME;
+    if ((rc = reduce_ranks(c, "diagnostics", rc, DQ_COUNT, q0, q1, diag_combine, slot))) return rc;
     const double nan = std::nan("");
     csi_diagnostics d{};
     d.what = what;

@@ -251,6 +251,17 @@ void launch_time_series(const SeriesTable& T, hipStream_t s);
 enum : int { DQ_INV_TIMESCALE = 0, DQ_MAX_ABS_U, DQ_MAX_ABS_V, DQ_NONFINITE_U, DQ_NONFINITE_V, DQ_NAN_U, DQ_NAN_V,
              DQ_VOLUME, DQ_AREA, DQ_EXTENT, DQ_SNOW_VOLUME, DQ_ACTIVE_AREA, DQ_MIN_H, DQ_MAX_H, DQ_MIN_AICE, DQ_MAX_AICE, DQ_MAX_HS,
              DQ_NONFINITE_H, DQ_NONFINITE_AICE, DQ_NONFINITE_HS, DQ_ACTIVE_CELLS, DQ_COUNT };
+// what a slot holds (ordered_reduce.h combine / identity), and the diagnostics' map from slot to kind: the ONE statement, used by the
+// kernels (diagnostics.hip) and by the host's combine over ranks (csi_diagnostics.hip)
+enum : int { K_SUM = 0, K_MAX = 1, K_MIN = 2, K_CNT = 3 };
+struct DiagKinds {
+    __host__ __device__ static constexpr int kind(int q) {
+        return (q == DQ_INV_TIMESCALE || q == DQ_MAX_ABS_U || q == DQ_MAX_ABS_V || q == DQ_MAX_H || q == DQ_MAX_AICE || q == DQ_MAX_HS) ? K_MAX
+             : (q == DQ_MIN_H || q == DQ_MIN_AICE) ? K_MIN
+             : (q >= DQ_VOLUME && q <= DQ_ACTIVE_AREA) ? K_SUM
+             : K_CNT;
+    }
+};
 struct DiagDev {
     GridDev g;
     FRef u, v, h, a, hs;       // (a group that is not requested: unused)
@@ -258,11 +269,9 @@ struct DiagDev {
     int has_hs;
     int pad_;
     double threshold;          // ice_extent counts cells with aice >= threshold
-    double* part;              // partial records, one slot after the other: slot q of record r at part[q * nrec + r]
-    long nrec;                 // records = blocks of the first launch (diag_geometry)
+    double* part;              // partial records (layout, block shape and order: ordered_reduce.h)
+    long nrec;                 // records = blocks of the first launch (red::diag_geometry)
 };
-// blocks of 64 x 64 cells over i = 1 .. Nx, j = 1 .. Ny: a function of (Nx, Ny) alone -- the summation order depends on nothing else
-void diag_geometry(int Nx, int Ny, int* nbx, int* nby);
 // the two launches: partial records into D.part, the folded result into out[DQ_COUNT] (device memory; only the requested groups' slots are written)
 void launch_diagnostics(const DiagDev& D, bool vel, bool trc, double* out, hipStream_t s);
 
@@ -276,8 +285,8 @@ struct DerivedDev {
 };
 void launch_derived(const DerivedDev& D, bool stress, hipStream_t s);
 
-// energy budget integrals (budget.hip; include/csi.h csi_budget_compute): the diagnostics' two launches and record layout (slot q of
-// record r at part[q * nrec + r], diag_geometry blocks) with three sums.  Slots below BQ_KINETIC: CSI_BUDGET_STRESS.
+// energy budget integrals (budget.hip; include/csi.h csi_budget_compute): the ordered reduction of ordered_reduce.h with three sums.
+// Slots below BQ_KINETIC: CSI_BUDGET_STRESS.
 enum : int { BQ_WORK = 0, BQ_POWER, BQ_KINETIC, BQ_COUNT };
 struct BudgetDev {
     GridDev g;
@@ -290,7 +299,7 @@ void launch_budget(const BudgetDev& D, bool stress, bool kin, double* out, hipSt
 
 // momentum balance terms and their power (momentum_terms.hip; include/csi.h csi_momentum_terms_compute / csi_momentum_budget_compute).
 // out[2 * t] / out[2 * t + 1]: the arrays bound to the _X / _Y slot of term t as (0, 0)-offset references, p == nullptr where the slot is
-// not requested.  The power sums: the diagnostics' two launches and record layout (slot q of record r at part[q * nrec + r]).
+// not requested.  The power sums: the ordered reduction of ordered_reduce.h, every slot a sum.
 enum : int { MQ_CORIOLIS = 0, MQ_TOP, MQ_BOTTOM, MQ_INTERNAL, MQ_FORCING, MQ_COUNT };
 struct MomTermsDev {
     EvpDev P;                  // grid, u, v, h, aice, sigma (unused by the viscous instantiation), stresses, Coriolis, forcing, rho

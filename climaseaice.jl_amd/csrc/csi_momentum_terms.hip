@@ -3,30 +3,22 @@
 // the reference call x_momentum_stress / y_momentum_stress (src/SeaIceDynamics/sea_ice_external_stress.jl:33-37, 162-174) from a coupler
 // and restate u_velocity_tendency term by term on the host.  The kernels: momentum_terms.hip.
 //
-// Host side: argument and binding checks by name, ONE launch for the fields (nothing is waited for); for the power sums the two
-// launches, the copy of the MQ_COUNT slots into page-locked memory and ONE wait, then on a tiled context the all-gather and the combine
-// in rank order, with csi_budget_compute's rule for a rank that fails locally (it still reaches the collective; then every rank returns
-// an error).  No halo is filled and nothing is exchanged: the elements read are the ones the step entry points leave valid.
+// Host side: argument and binding checks by name, ONE launch for the fields (nothing is waited for); for the power sums the host path
+// of the ordered reductions (csi_ctx.h reduce_begin / reduce_end, reduce_ranks).  No halo is filled and nothing is exchanged: the elements read are the ones the step entry points leave valid.
 #include "csi_ctx.h"
 
 namespace csi_host {
-
-static int32_t need_terms(csi_context* c, const char* who, std::initializer_list<int> ids, const char* hint) {
-    for (int id : ids)
-        if (!c->f[id].p) return fail(c, CSI_ERR_NOT_BOUND, std::string(who) + ": needs field " + kName[id] + " (not bound" + hint + ")");
-    return CSI_OK;
-}
 
 // The checks both entry points share and the kernels' description of the model.  internal: the internal term is wanted.
 static int32_t terms_dev(csi_context* c, const char* who, bool internal, MomTermsDev* out, bool* visc) {
     if (!c->grid_set) return fail(c, CSI_ERR_NOT_BOUND, "csi_grid_set has not been called");
     if (c->Hx < 1 || c->Hy < 1) return fail(c, CSI_ERR_INVALID_ARGUMENT, std::string(who) + ": the grid needs halo >= 1");
     int32_t rc;
-    if ((rc = need_terms(c, who, {CSI_F_U, CSI_F_V}, ": a model without dynamics has no momentum balance"))) return rc;
-    if ((rc = need_terms(c, who, {CSI_F_H, CSI_F_A}, ""))) return rc;
+    if ((rc = need_named(c, who, "", {CSI_F_U, CSI_F_V}, ": a model without dynamics has no momentum balance"))) return rc;
+    if ((rc = need_named(c, who, "", {CSI_F_H, CSI_F_A}, ""))) return rc;
     const bool free_drift = c->dynamics == CSI_DYNAMICS_FREE_DRIFT;
     const bool evp_sigma = internal && !free_drift && c->rheology == CSI_RHEOLOGY_EVP;
-    if (evp_sigma && (rc = need_terms(c, who, {CSI_F_S11, CSI_F_S22, CSI_F_S12}, ": the internal term of an ElastoViscoPlasticRheology reads its stress fields")))
+    if (evp_sigma && (rc = need_named(c, who, "", {CSI_F_S11, CSI_F_S22, CSI_F_S12}, ": the internal term of an ElastoViscoPlasticRheology reads its stress fields")))
         return rc;
     if ((rc = check_stress_fields(c, CSI_STRESS_TOP))) return rc;
     if ((rc = check_stress_fields(c, CSI_STRESS_BOTTOM))) return rc;
@@ -57,20 +49,10 @@ static int32_t power_local(csi_context* c, int32_t what, double* slots) {
     bool visc;
     int32_t rc = terms_dev(c, "momentum budget", what & CSI_MBUDGET_INTERNAL, &T, &visc);
     if (rc) return rc;
-    HIP_TRY(c, hipSetDevice(c->device));
-    int nbx, nby;
-    diag_geometry(c->Nx, c->Ny, &nbx, &nby);
-    T.nrec = (long)nbx * nby;
-    HIP_TRY(c, c->mterm_part.ensure((size_t)(T.nrec + 1) * MQ_COUNT, c->stream, false));
-    if (!c->mterm_host) HIP_TRY(c, c->mterm_host.alloc(MQ_COUNT, hipHostMallocDefault));
-    T.part = c->mterm_part.get();
-    double* result = T.part + (size_t)T.nrec * MQ_COUNT;
+    double* result;
+    if ((rc = reduce_begin(c, &T.part, &T.nrec, &result))) return rc;
     launch_momentum_power(T, visc, result, c->stream);
-    HIP_TRY(c, hipGetLastError());
-    HIP_TRY(c, hipMemcpyAsync(c->mterm_host.get(), result, sizeof(double) * MQ_COUNT, hipMemcpyDeviceToHost, c->stream));
-    HIP_TRY(c, hipStreamSynchronize(c->stream));
-    memcpy(slots, c->mterm_host.get(), sizeof(double) * MQ_COUNT);
-    return CSI_OK;
+    return reduce_end(c, MQ_COUNT, result, slots);
 }
 
 }  // namespace csi_host
@@ -105,27 +87,10 @@ int32_t csi_momentum_terms_compute(csi_context* c, int32_t mask) {
 int32_t csi_momentum_budget_compute(csi_context* c, int32_t what, csi_momentum_budget* out) {
     if (!c) return CSI_ERR_INVALID_ARGUMENT;
     if (!out) return fail(c, CSI_ERR_INVALID_ARGUMENT, "momentum budget: out == NULL");
-    struct Payload { int64_t status; double slot[MQ_COUNT]; } mine{};
+    double slot[MQ_COUNT] = {};
     int32_t rc = peer_check_entry(c);
-    if (!rc) rc = power_local(c, what, mine.slot);
-    mine.status = rc;
-    double slot[MQ_COUNT];
-    memcpy(slot, mine.slot, sizeof slot);
-    if (has_comm(c)) {
-        std::vector<uint8_t> all;
-        const std::string local_err = c->err;
-        const int32_t grc = comm_allgather(c, &mine, sizeof mine, all);
-        if (rc) { c->err = local_err; return rc; }
-        if (grc) return grc;
-        for (int r = 0; r < c->world; ++r) {
-            Payload p;
-            memcpy(&p, all.data() + (size_t)r * sizeof p, sizeof p);
-            if (p.status) return fail(c, CSI_ERR_COMM, "momentum budget: rank " + std::to_string(r) + " of the decomposition failed locally (status " + std::to_string((long)p.status) + ")");
-            for (int q = 0; q < MQ_COUNT; ++q) slot[q] = r == 0 ? p.slot[q] : slot[q] + p.slot[q];
-        }
-    } else if (rc) {
-        return rc;
-    }
+    if (!rc) rc = power_local(c, what, slot);
+    if ((rc = reduce_ranks(c, "momentum budget", rc, MQ_COUNT, 0, MQ_COUNT, nullptr, slot))) return rc;
     const double nan = std::nan("");
     csi_momentum_budget b{};
     b.what = what;

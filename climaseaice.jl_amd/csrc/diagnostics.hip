@@ -2,15 +2,9 @@
 //
 //   k_diag_partial   one pass over the interior i = 1 .. Nx, j = 1 .. Ny: every requested array is read once, each block of 64 x 64
 //                    cells writes one partial record (plain stores, one slot per quantity)
-//   k_diag_finish    ONE block folds the records into the result
-// Two launches on one stream: the launch boundary is the only hand-off between workgroups -- no atomics, no flags, no workgroup
-// waits for another.  Every combine has a fixed place in a fixed tree, so the sums are reproducible bit for bit; the order is part of
-// the interface and is stated in include/csi.h (tests/diagnostics_ref.py restates it in NumPy):
-//   thread (tx, ty) of a block adds the cells of column tx in rows ty, ty + 4, ..., ty + 60 of the block's tile, ascending, from +0.0;
-//   the wave (one 64-lane row of threads) combines over lane offsets 32, 16, 8, 4, 2, 1 (xor butterfly: a + b in both partners, so
-//   every lane ends with the same bits); the block adds its four waves' values in wave order; the finishing block's thread t adds
-//   records t, t + 256, ... ascending, from +0.0, then the same butterfly and the same wave order.
-// Lanes and rows outside the grid contribute +0.0 to sums, -Inf to maxima, +Inf to minima and 0 to counts.
+//   red::finish_records   ONE block folds the records into the result
+// The two-launch scheme, the tile walk, the fold and the SUMMATION ORDER: ordered_reduce.h (defined for users in include/csi.h).  Here:
+// what a cell contributes to each of the 21 slots (which slots are sums, maxima, minima and counts: csi_kernels.h DiagKinds).
 //
 // A bandwidth kernel: 16 B per cell for the velocity group (u, v), 16 or 24 B + the mask byte for the tracer group, plus the metric
 // planes on CSI_METRIC_FULL grids.  64-lane rows: consecutive lanes read consecutive elements; a thread walks sixteen rows, four of
@@ -22,67 +16,28 @@
 // block-uniform test.  Compiled without contraction; STRICT and FAST run the same code.
 #include "csi_dev.h"
 #include "csi_kernels.h"
-#include <math.h>
+#include "ordered_reduce.h"
 
 namespace csi {
 namespace diag {
 
-constexpr int kDiagRows = 64;      // rows of a block's tile (64 columns wide): sixteen per thread
-enum : int { K_SUM = 0, K_MAX = 1, K_MIN = 2, K_CNT = 3 };
+using namespace red;
 
-__host__ __device__ constexpr int kind_of(int q) {
-    return (q == DQ_INV_TIMESCALE || q == DQ_MAX_ABS_U || q == DQ_MAX_ABS_V || q == DQ_MAX_H || q == DQ_MAX_AICE || q == DQ_MAX_HS) ? K_MAX
-         : (q == DQ_MIN_H || q == DQ_MIN_AICE) ? K_MIN
-         : (q >= DQ_VOLUME && q <= DQ_ACTIVE_AREA) ? K_SUM
-         : K_CNT;
-}
-// counts travel through the double slots as bit patterns (moves only, never arithmetic)
-__device__ __forceinline__ double cnt(long long n) { return __longlong_as_double(n); }
-__device__ __forceinline__ double combine(int kind, double a, double b) {
-    if (kind == K_SUM) return a + b;
-    if (kind == K_MAX) return fmax(a, b);
-    if (kind == K_MIN) return fmin(a, b);
-    return cnt(__double_as_longlong(a) + __double_as_longlong(b));
-}
-__device__ __forceinline__ double identity(int kind) {
-    return kind == K_SUM ? 0.0 : kind == K_MAX ? -INFINITY : kind == K_MIN ? INFINITY : cnt(0);
-}
+using Kinds = DiagKinds;      // csi_kernels.h
 __device__ __forceinline__ bool nonfinite(double x) { return !(fabs(x) <= 1.7976931348623157e308); }
-
-// wave butterfly, then the block's waves in wave order; thread q - Q0 of the block ends with quantity q and stores it
-template <int Q0, int Q1>
-__device__ __forceinline__ void block_fold(double (&acc)[DQ_COUNT], int lane, int wave, int tid, double* dst, long stride) {
-    __shared__ double sm[4][DQ_COUNT];
-#pragma unroll
-    for (int q = Q0; q < Q1; ++q) {
-        double x = acc[q];
-#pragma unroll
-        for (int off = 32; off >= 1; off >>= 1) x = combine(kind_of(q), x, __shfl_xor(x, off));
-        if (lane == 0) sm[wave][q] = x;
-    }
-    __syncthreads();
-    const int q = Q0 + tid;
-    if (q < Q1) {
-        const int kind = kind_of(q);
-        double x = sm[0][q];
-        for (int w = 1; w < 4; ++w) x = combine(kind, x, sm[w][q]);
-        dst[(long)q * stride] = x;
-    }
-}
 
 template <bool VEL, bool TRC>
 __global__ void __launch_bounds__(256) k_diag_partial(DiagDev D) {
     constexpr int Q0 = VEL ? 0 : DQ_VOLUME, Q1 = TRC ? DQ_COUNT : DQ_VOLUME;
     const GridDev& g = D.g;
-    const int i = 1 + (int)blockIdx.x * 64 + (int)threadIdx.x;
+    const int i = tile_col();
     const int ic = min(i, g.Nx);
     double acc[DQ_COUNT];
-#pragma unroll
-    for (int q = 0; q < DQ_COUNT; ++q) acc[q] = identity(kind_of(q));
+    set_identity<DQ_COUNT, Kinds>(acc);
     const bool last_bx = blockIdx.x == gridDim.x - 1, last_by = blockIdx.y == gridDim.y - 1;
 #pragma unroll 4
-    for (int r = 0; r < kDiagRows / 4; ++r) {
-        const int j = 1 + (int)blockIdx.y * kDiagRows + 4 * r + (int)threadIdx.y;
+    for (int r = 0; r < kRowsPerThread; ++r) {
+        const int j = tile_row(r);
         const int jc = min(j, g.Ny);
         const bool in = (i <= g.Nx) & (j <= g.Ny);
         if (VEL) {
@@ -133,41 +88,25 @@ __global__ void __launch_bounds__(256) k_diag_partial(DiagDev D) {
             acc[DQ_ACTIVE_CELLS] = cnt(__double_as_longlong(acc[DQ_ACTIVE_CELLS]) + (long long)act);
         }
     }
-    const long rec = (long)blockIdx.y * gridDim.x + blockIdx.x;
-    block_fold<Q0, Q1>(acc, (int)threadIdx.x, (int)threadIdx.y, (int)(threadIdx.y * 64 + threadIdx.x), D.part + rec, D.nrec);
+    const long rec = tile_record();
+    block_fold<DQ_COUNT, Q0, Q1, Kinds>(acc, (int)threadIdx.x, (int)threadIdx.y, (int)(threadIdx.y * kTileCols + threadIdx.x), D.part + rec, D.nrec);
 }
 
-template <int Q0, int Q1>
-__global__ void __launch_bounds__(256) k_diag_finish(const double* __restrict__ part, long nrec, double* __restrict__ out) {
-    const int t = (int)threadIdx.x;
-    double acc[DQ_COUNT];
-#pragma unroll
-    for (int q = 0; q < DQ_COUNT; ++q) acc[q] = identity(kind_of(q));
-#pragma unroll 2
-    for (long r = t; r < nrec; r += 256) {
-#pragma unroll
-        for (int q = Q0; q < Q1; ++q) acc[q] = combine(kind_of(q), acc[q], part[(long)q * nrec + r]);
-    }
-    block_fold<Q0, Q1>(acc, t & 63, t >> 6, t, out, 1);
-}
+template <int Q0, int Q1> static void finish(const DiagDev& D, double* out, hipStream_t s) { launch_finish<DQ_COUNT, Q0, Q1, Kinds, 2>(D.part, D.nrec, out, s); }
 
 }  // namespace diag
 
-void diag_geometry(int Nx, int Ny, int* nbx, int* nby) { *nbx = (Nx + 63) / 64; *nby = (Ny + diag::kDiagRows - 1) / diag::kDiagRows; }
-
 void launch_diagnostics(const DiagDev& D, bool vel, bool trc, double* out, hipStream_t s) {
-    int nbx, nby;
-    diag_geometry(D.g.Nx, D.g.Ny, &nbx, &nby);
-    const dim3 b(64, 4), g((unsigned)nbx, (unsigned)nby, 1);
+    const dim3 b = red::tile_threads(), g = red::tile_blocks(D.g.Nx, D.g.Ny);
     if (vel && trc) {
         hipLaunchKernelGGL((diag::k_diag_partial<true, true>), g, b, 0, s, D);
-        hipLaunchKernelGGL((diag::k_diag_finish<0, DQ_COUNT>), dim3(1), dim3(256), 0, s, D.part, D.nrec, out);
+        diag::finish<0, DQ_COUNT>(D, out, s);
     } else if (vel) {
         hipLaunchKernelGGL((diag::k_diag_partial<true, false>), g, b, 0, s, D);
-        hipLaunchKernelGGL((diag::k_diag_finish<0, DQ_VOLUME>), dim3(1), dim3(256), 0, s, D.part, D.nrec, out);
+        diag::finish<0, DQ_VOLUME>(D, out, s);
     } else {
         hipLaunchKernelGGL((diag::k_diag_partial<false, true>), g, b, 0, s, D);
-        hipLaunchKernelGGL((diag::k_diag_finish<DQ_VOLUME, DQ_COUNT>), dim3(1), dim3(256), 0, s, D.part, D.nrec, out);
+        diag::finish<DQ_VOLUME, DQ_COUNT>(D, out, s);
     }
 }
 

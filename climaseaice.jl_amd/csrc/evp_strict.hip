@@ -11,16 +11,18 @@
 //   k_vstep     _v_velocity_step!          :231-264
 // with u/v_velocity_tendency (momentum_tendencies_kernel_functions.jl:11-74), the stress
 // divergence (Rheologies/ice_stress_divergence.jl:16-51) and the external stresses
-// (sea_ice_external_stress.jl:8-27,176-202) inlined.  The local halo fill that follows each
+// (sea_ice_external_stress.jl:8-27,176-202) inlined.  The strain rates, the four-point interpolations and the stress divergence
+// are derived_dev.h's, with the metric kind decided at run time (dv::MK_RUNTIME).  The local halo fill that follows each
 // velocity kernel in the reference (:180-187) is fused into the store (store_with_images).
 #include "csi_dev.h"
 #include "csi_kernels.h"
+#include "derived_dev.h"
 
 namespace csi {
 namespace strict {
 
-// metrics: dxm / dym / azm(g, lx, ly, i, j) in csi_dev.h, called with the location and indices the reference's
-// operators use (same calls as oracle/csi_oracle.c)
+using namespace dv;
+constexpr int MK = MK_RUNTIME;      // dxm / dym / azm (csi_dev.h) at every access: the same calls as oracle/csi_oracle.c
 #define F_ LOC_F
 #define C_ LOC_C
 
@@ -31,34 +33,10 @@ __device__ __forceinline__ double ice_mass(const EvpDev& P, int i, int j) {   //
     return P.h(i, j) * P.rho * P.a(i, j);
 }
 
-// ---- strain rates, evp:360-375 ----------------------------------------------------------------
-__device__ __forceinline__ double eps_D(const EvpDev& P, int i, int j) {
-    const GridDev& g = P.g;
-    double a = dym(g, F_, C_, i + 1, j) * P.u(i + 1, j) - dym(g, F_, C_, i, j) * P.u(i, j);
-    double b = dxm(g, C_, F_, i, j + 1) * P.v(i, j + 1) - dxm(g, C_, F_, i, j) * P.v(i, j);
-    return (a + b) / azm(g, C_, C_, i, j);
-}
-__device__ __forceinline__ double eps_T(const EvpDev& P, int i, int j) {
-    const GridDev& g = P.g;
-    double dycc = dym(g, C_, C_, i, j), dxcc = dxm(g, C_, C_, i, j);
-    double a = P.u(i + 1, j) / dym(g, F_, C_, i + 1, j) - P.u(i, j) / dym(g, F_, C_, i, j);
-    double b = P.v(i, j + 1) / dxm(g, C_, F_, i, j + 1) - P.v(i, j) / dxm(g, C_, F_, i, j);
-    return ((dycc * dycc) * a - (dxcc * dxcc) * b) / azm(g, C_, C_, i, j);
-}
-__device__ __forceinline__ double eps_S(const EvpDev& P, int i, int j) {
-    const GridDev& g = P.g;
-    double dxff = dxm(g, F_, F_, i, j), dyff = dym(g, F_, F_, i, j);
-    double a = P.u(i, j) / dxm(g, F_, C_, i, j) - P.u(i, j - 1) / dxm(g, F_, C_, i, j - 1);
-    double b = P.v(i, j) / dym(g, C_, F_, i, j) - P.v(i - 1, j) / dym(g, C_, F_, i - 1, j);
-    return ((dxff * dxff) * a + (dyff * dyff) * b) / azm(g, F_, F_, i, j);
-}
-__device__ __forceinline__ double e_xx(const EvpDev& P, int i, int j) { return (eps_D(P, i, j) + eps_T(P, i, j)) / 2; }
-__device__ __forceinline__ double e_yy(const EvpDev& P, int i, int j) { return (eps_D(P, i, j) - eps_T(P, i, j)) / 2; }
-__device__ __forceinline__ double e_xy(const EvpDev& P, int i, int j) { return eps_S(P, i, j) / 2; }
-
-#define AVG4_FF(fn, P, i, j) ((((fn)(P, (i) - 1, (j) - 1) + (fn)(P, (i), (j) - 1)) / 2 + ((fn)(P, (i) - 1, (j)) + (fn)(P, (i), (j))) / 2) / 2)
-#define AVG4_CC(fn, P, i, j) ((((fn)(P, (i), (j)) + (fn)(P, (i) + 1, (j))) / 2 + ((fn)(P, (i), (j) + 1) + (fn)(P, (i) + 1, (j) + 1)) / 2) / 2)
-__device__ __forceinline__ double P_at(const EvpDev& P, int i, int j) { return P.P(i, j); }
+// derived_dev.h's strain rates on this model's velocities
+__device__ __forceinline__ double exx(const EvpDev& P, int i, int j) { return e_xx<MK>(P.g, P.u, P.v, i, j); }
+__device__ __forceinline__ double eyy(const EvpDev& P, int i, int j) { return e_yy<MK>(P.g, P.u, P.v, i, j); }
+__device__ __forceinline__ double exy(const EvpDev& P, int i, int j) { return e_xy<MK>(P.g, P.u, P.v, i, j); }
 
 #define CELL_IJ(r)                                              \
     const int i = (r).i0 + (int)(blockIdx.x * blockDim.x + threadIdx.x); \
@@ -77,12 +55,12 @@ __global__ void k_visc(EvpDev P, Range r) {
     const double ie = 1.0 / P.ecc;
     const double em2 = ie * ie;
     const double Dm = P.Dmin;
-    double e11c = e_xx(P, i, j);
-    double e22c = e_yy(P, i, j);
-    double e12f = e_xy(P, i, j);
-    double e11f = AVG4_FF(e_xx, P, i, j);
-    double e22f = AVG4_FF(e_yy, P, i, j);
-    double e12c = AVG4_CC(e_xy, P, i, j);
+    double e11c = exx(P, i, j);
+    double e22c = eyy(P, i, j);
+    double e12f = exy(P, i, j);
+    double e11f = avg4(exx(P, i - 1, j - 1), exx(P, i, j - 1), exx(P, i - 1, j), exx(P, i, j));           // to (f, f)
+    double e22f = avg4(eyy(P, i - 1, j - 1), eyy(P, i, j - 1), eyy(P, i - 1, j), eyy(P, i, j));
+    double e12c = avg4(exy(P, i, j), exy(P, i + 1, j), exy(P, i, j + 1), exy(P, i + 1, j + 1));           // to (c, c)
     double dc = e11c + e22c;
     double df = e11f + e22f;
     double sc = sqrt((e11c - e22c) * (e11c - e22c) + 4 * (e12c * e12c));
@@ -90,7 +68,7 @@ __global__ void k_visc(EvpDev P, Range r) {
     double Dc = jmax(sqrt(dc * dc + (sc * sc) * em2), Dm);
     double Df = jmax(sqrt(df * df + (sf * sf) * em2), Dm);
     double Pc = P.P(i, j);
-    double Pf = AVG4_FF(P_at, P, i, j);
+    double Pf = avg4_ff(P.P, i, j);
     P.zf(i, j) = Pf / (2 * Df);
     P.zc(i, j) = Pc / (2 * Dc);
     P.Dl(i, j) = Dc;
@@ -104,9 +82,9 @@ __global__ void k_stress(EvpDev P, Range r) {
     const double ie = 1.0 / P.ecc;
     const double em2 = ie * ie;
     const double ap = P.amax, am = P.amin, ca = P.ca, dt = P.dt;
-    double e11 = e_xx(P, i, j);
-    double e22 = e_yy(P, i, j);
-    double e12 = e_xy(P, i, j);
+    double e11 = exx(P, i, j);
+    double e22 = eyy(P, i, j);
+    double e12 = exy(P, i, j);
     double zc = P.zc(i, j);
     double zf = P.zf(i, j);
     double Pr;
@@ -122,7 +100,7 @@ __global__ void k_stress(EvpDev P, Range r) {
     double s22n = 2 * etac * e22 + ((zc - etac) * (e11 + e22) - Pr / 2);
     double s12n = 2 * etaf * e12;
     double mc = ice_mass(P, i, j);
-    double mf = AVG4_FF(ice_mass, P, i, j);
+    double mf = avg4_ff([&](int ii, int jj) { return ice_mass(P, ii, jj); }, i, j);
     double g2c = zc * ca * dt / mc / azm(g, C_, C_, i, j);
     g2c = isnan(g2c) ? ap * ap : g2c;
     double gc = clampd(sqrt(g2c), am, ap);
@@ -138,34 +116,6 @@ __global__ void k_stress(EvpDev P, Range r) {
     P.al(i, j) = gc;
 }
 
-// ---- stress divergence, ice_stress_divergence.jl:16-51 ---------------------------------------
-__device__ __forceinline__ double sig11(const EvpDev& P, int i, int j) { return immersed_peripheral_cc(P.g, i, j) ? 0.0 : P.s11(i, j); }
-__device__ __forceinline__ double sig22(const EvpDev& P, int i, int j) { return immersed_peripheral_cc(P.g, i, j) ? 0.0 : P.s22(i, j); }
-__device__ __forceinline__ double sig12(const EvpDev& P, int i, int j) { return immersed_peripheral_ff(P.g, i, j) ? 0.0 : P.s12(i, j); }
-__device__ __forceinline__ double sigD(const EvpDev& P, int i, int j) { return sig11(P, i, j) + sig22(P, i, j); }
-__device__ __forceinline__ double sigT(const EvpDev& P, int i, int j) { return sig11(P, i, j) - sig22(P, i, j); }
-
-__device__ __forceinline__ double div_sigma_1(const EvpDev& P, int i, int j) {   // :39-44
-    const GridDev& g = P.g;
-    double dyfc = dym(g, F_, C_, i, j);
-    double d = dyfc * (sigD(P, i, j) - sigD(P, i - 1, j)) / 2;
-    double dyc = dym(g, C_, C_, i, j), dycm = dym(g, C_, C_, i - 1, j);
-    double T = ((dyc * dyc) * sigT(P, i, j) - (dycm * dycm) * sigT(P, i - 1, j)) / dyfc / 2;
-    double dxfn = dxm(g, F_, F_, i, j + 1), dxf = dxm(g, F_, F_, i, j);
-    double S = ((dxfn * dxfn) * sig12(P, i, j + 1) - (dxf * dxf) * sig12(P, i, j)) / dxm(g, F_, C_, i, j);
-    return (d + T + S) / azm(g, F_, C_, i, j);
-}
-__device__ __forceinline__ double div_sigma_2(const EvpDev& P, int i, int j) {   // :46-51
-    const GridDev& g = P.g;
-    double dxcf = dxm(g, C_, F_, i, j);
-    double d = dxcf * (sigD(P, i, j) - sigD(P, i, j - 1)) / 2;
-    double dxc = dxm(g, C_, C_, i, j), dxcm = dxm(g, C_, C_, i, j - 1);
-    double T = -((dxc * dxc) * sigT(P, i, j) - (dxcm * dxcm) * sigT(P, i, j - 1)) / dxcf / 2;
-    double dyfn = dym(g, F_, F_, i + 1, j), dyf = dym(g, F_, F_, i, j);
-    double S = ((dyfn * dyfn) * sig12(P, i + 1, j) - (dyf * dyf) * sig12(P, i, j)) / dym(g, C_, F_, i, j);
-    return (d + T + S) / azm(g, C_, F_, i, j);
-}
-
 // ---- external stresses, sea_ice_external_stress.jl:8-27,176-202 ------------------------------
 __device__ __forceinline__ double ext_ue(const StressDev& s, int i, int j) {
     return s.ue_kind == 2 ? s.fu(i, j) : (s.ue_kind == 1 ? s.ue : 0.0);
@@ -173,25 +123,15 @@ __device__ __forceinline__ double ext_ue(const StressDev& s, int i, int j) {
 __device__ __forceinline__ double ext_ve(const StressDev& s, int i, int j) {
     return s.ve_kind == 2 ? s.fv(i, j) : (s.ve_kind == 1 ? s.ve : 0.0);
 }
-#define AVG4_FC(X) (((X(i - 1, j) + X(i, j)) / 2 + (X(i - 1, j + 1) + X(i, j + 1)) / 2) / 2)
-#define AVG4_CF(X) (((X(i, j - 1) + X(i + 1, j - 1)) / 2 + (X(i, j) + X(i + 1, j)) / 2) / 2)
 
 __device__ __forceinline__ double drag_norm_u(const EvpDev& P, const StressDev& s, int i, int j) {
     double du = ext_ue(s, i, j) - P.u(i, j);
-#define VE_(ii, jj) ext_ve(s, ii, jj)
-#define V_(ii, jj) P.v(ii, jj)
-    double dv = AVG4_FC(VE_) - AVG4_FC(V_);
-#undef VE_
-#undef V_
+    double dv = avg4_fc([&](int ii, int jj) { return ext_ve(s, ii, jj); }, i, j) - avg4_fc(P.v, i, j);
     return sqrt(du * du + dv * dv);
 }
 __device__ __forceinline__ double drag_norm_v(const EvpDev& P, const StressDev& s, int i, int j) {
     double dv = ext_ve(s, i, j) - P.v(i, j);
-#define UE_(ii, jj) ext_ue(s, ii, jj)
-#define U_(ii, jj) P.u(ii, jj)
-    double du = AVG4_CF(UE_) - AVG4_CF(U_);
-#undef UE_
-#undef U_
+    double du = avg4_cf([&](int ii, int jj) { return ext_ue(s, ii, jj); }, i, j) - avg4_cf(P.u, i, j);
     return sqrt(du * du + dv * dv);
 }
 __device__ __forceinline__ double explicit_tau_x(const EvpDev& P, const StressDev& s, int i, int j) {
@@ -217,17 +157,13 @@ __device__ __forceinline__ double free_drift_u(const EvpDev& P, int i, int j) {
     const StressDev& semi = P.bot.kind == 3 ? P.bot : P.top;
     const StressDev& expl = P.bot.kind == 3 ? P.top : P.bot;
     const double tx = explicit_tau_x(P, expl, i, j);
-#define TY_(ii, jj) explicit_tau_y(P, expl, ii, jj)
-    const double ty = AVG4_FC(TY_);
-#undef TY_
+    const double ty = avg4_fc([&](int ii, int jj) { return explicit_tau_y(P, expl, ii, jj); }, i, j);
     return stress_balance_velocity(ext_ue(semi, i, j), tx, tx, ty, semi.rho_e * semi.Cd);
 }
 __device__ __forceinline__ double free_drift_v(const EvpDev& P, int i, int j) {
     const StressDev& semi = P.bot.kind == 3 ? P.bot : P.top;
     const StressDev& expl = P.bot.kind == 3 ? P.top : P.bot;
-#define TX_(ii, jj) explicit_tau_x(P, expl, ii, jj)
-    const double tx = AVG4_CF(TX_);
-#undef TX_
+    const double tx = avg4_cf([&](int ii, int jj) { return explicit_tau_x(P, expl, ii, jj); }, i, j);
     const double ty = explicit_tau_y(P, expl, i, j);
     return stress_balance_velocity(ext_ve(semi, i, j), ty, tx, ty, semi.rho_e * semi.Cd);
 }
@@ -251,9 +187,7 @@ __global__ void k_ustep(EvpDev P, Range r, ImageSpec im) {
     // u_velocity_tendency, momentum_tendencies_kernel_functions.jl:11-41
     double cor = 0.0;
     if (P.has_cor) {
-#define V_(ii, jj) P.v(ii, jj)
-        cor = -fcor_at_u(P, i, j) * AVG4_FC(V_);     // FPlane / BetaPlane (f at this row's u points) / per-point f
-#undef V_
+        cor = -fcor_at_u(P, i, j) * avg4_fc(P.v, i, j);     // FPlane / BetaPlane (f at this row's u points) / per-point f
     }
     const double user = P.has_forcing ? P.forcing_u(i, j) : 0.0;    // model.forcing.u as an array
     double forcing = user + (P.un(i, j) - P.u(i, j)) / dtau / abar;  // sum_of_forcing_u, evp:391-395
@@ -261,7 +195,7 @@ __global__ void k_ustep(EvpDev P, Range r, ImageSpec im) {
     double G = (-cor
                 - explicit_tau_x(P, P.top, i, j) / mi * ai
                 + explicit_tau_x(P, P.bot, i, j) / mi * ai
-                + div_sigma_1(P, i, j) / mi
+                + div_sigma_1<MK>(P.g, Sigma{P.s11, P.s22, P.s12}, i, j) / mi
                 + imm
                 + forcing);
     G = (mi <= 0) ? 0.0 : G;
@@ -286,9 +220,7 @@ __global__ void k_vstep(EvpDev P, Range r, ImageSpec im) {
     double dtau = dt / abar;
     double cor = 0.0;
     if (P.has_cor) {
-#define U_(ii, jj) P.u(ii, jj)
-        cor = fcor_at_v(P, i, j) * AVG4_CF(U_);
-#undef U_
+        cor = fcor_at_v(P, i, j) * avg4_cf(P.u, i, j);
     }
     const double user = P.has_forcing ? P.forcing_v(i, j) : 0.0;
     double forcing = user + (P.vn(i, j) - P.v(i, j)) / dtau / abar;
@@ -296,7 +228,7 @@ __global__ void k_vstep(EvpDev P, Range r, ImageSpec im) {
     double G = (-cor
                 - explicit_tau_y(P, P.top, i, j) / mi * ai
                 + explicit_tau_y(P, P.bot, i, j) / mi * ai
-                + div_sigma_2(P, i, j) / mi
+                + div_sigma_2<MK>(P.g, Sigma{P.s11, P.s22, P.s12}, i, j) / mi
                 + imm
                 + forcing);
     G = (mi <= 0) ? 0.0 : G;

@@ -16,6 +16,7 @@
 // arithmetic follows on registers.  tests/test_momentum_variants.py gates the generated code.
 #pragma once
 #include "csi_dev.h"
+#include "derived_dev.h"
 
 namespace csi {
 
@@ -111,37 +112,25 @@ template <bool FAST> __device__ __forceinline__ double msub(double a, double x, 
 }
 
 // the divergence of (sigma_11, sigma_12) at a u point (ice_stress_divergence.jl:36-44) from the invariants at the cells i, i - 1
-// and the shear stress at the corners j + 1 (N), j (S)
-// m: dy(f,c)(i,j), dy(c,c)(i,j), dy(c,c)(i-1,j), dx(f,f)(i,j+1), dx(f,f)(i,j), dx(f,c)(i,j), Az(f,c)(i,j)
+// and the shear stress at the corners j + 1 (N), j (S); STRICT: derived_dev.h div1_strict, which also names the seven metrics of m
 template <bool FAST>
 __device__ __forceinline__ double div1(const double* m, double sD0, double sDm, double sT0, double sTm, double sN, double sS) {
+    if (!FAST) return dv::div1_strict(m, sD0, sDm, sT0, sTm, sN, sS);
     const double dyfc = m[0], dyc = m[1], dycm = m[2], dxfn = m[3], dxf = m[4], dxfc = m[5], az = m[6];
-    if (FAST) {
-        const double rdy = 1.0 / dyfc;
-        const double T = msub<true>(dyc * dyc, sT0, dycm * dycm, sTm) * (0.5 * rdy);
-        const double S = msub<true>(dxfn * dxfn, sN, dxf * dxf, sS) * (1.0 / dxfc);
-        return fma(0.5 * dyfc, sD0 - sDm, T + S) * (1.0 / az);
-    }
-    const double d = dyfc * (sD0 - sDm) / 2;
-    const double T = ((dyc * dyc) * sT0 - (dycm * dycm) * sTm) / dyfc / 2;
-    const double S = ((dxfn * dxfn) * sN - (dxf * dxf) * sS) / dxfc;
-    return (d + T + S) / az;
+    const double rdy = 1.0 / dyfc;
+    const double T = msub<true>(dyc * dyc, sT0, dycm * dycm, sTm) * (0.5 * rdy);
+    const double S = msub<true>(dxfn * dxfn, sN, dxf * dxf, sS) * (1.0 / dxfc);
+    return fma(0.5 * dyfc, sD0 - sDm, T + S) * (1.0 / az);
 }
 // ... of (sigma_21, sigma_22) at a v point (:46-51): invariants at the cells j, j - 1, shear stress at the corners i + 1 (E), i (W)
-// m: dx(c,f)(i,j), dx(c,c)(i,j), dx(c,c)(i,j-1), dy(f,f)(i+1,j), dy(f,f)(i,j), dy(c,f)(i,j), Az(c,f)(i,j)
 template <bool FAST>
 __device__ __forceinline__ double div2(const double* m, double sD0, double sDm, double sT0, double sTm, double sE, double sW) {
+    if (!FAST) return dv::div2_strict(m, sD0, sDm, sT0, sTm, sE, sW);
     const double dxcf = m[0], dxc = m[1], dxcm = m[2], dyfn = m[3], dyf = m[4], dycf = m[5], az = m[6];
-    if (FAST) {
-        const double rdx = 1.0 / dxcf;
-        const double T = msub<true>(dxc * dxc, sT0, dxcm * dxcm, sTm) * (-0.5 * rdx);
-        const double S = msub<true>(dyfn * dyfn, sE, dyf * dyf, sW) * (1.0 / dycf);
-        return fma(0.5 * dxcf, sD0 - sDm, T + S) * (1.0 / az);
-    }
-    const double d = dxcf * (sD0 - sDm) / 2;
-    const double T = -((dxc * dxc) * sT0 - (dxcm * dxcm) * sTm) / dxcf / 2;
-    const double S = ((dyfn * dyfn) * sE - (dyf * dyf) * sW) / dycf;
-    return (d + T + S) / az;
+    const double rdx = 1.0 / dxcf;
+    const double T = msub<true>(dxc * dxc, sT0, dxcm * dxcm, sTm) * (-0.5 * rdx);
+    const double S = msub<true>(dyfn * dyfn, sE, dyf * dyf, sW) * (1.0 / dycf);
+    return fma(0.5 * dxcf, sD0 - sDm, T + S) * (1.0 / az);
 }
 
 // ---- external stresses (sea_ice_external_stress.jl:8-27,176-202) on gathered values -----------------------------------------
@@ -174,8 +163,6 @@ __device__ __forceinline__ void gather_stress_v(const StressDev& s, const FRef& 
     const double* sx[4] = {addr(U, i, j - 1), addr(U, i + 1, j - 1), addr(U, i, j), addr(U, i + 1, j)};
     gather_stress(s, s.fv, s.ve_kind, s.ve, s.fu, s.ue_kind, s.ue, i, j, xp, addr(V, i, j), sx, p);
 }
-// the four-point averages of the reference's operators: ((x0 + x1) / 2 + (x2 + x3) / 2) / 2
-__device__ __forceinline__ double avg4(const double* x) { return ((x[0] + x[1]) / 2 + (x[2] + x[3]) / 2) / 2; }
 // |U_e - U| at the point: own component difference and the cross average
 __device__ __forceinline__ double drag_norm(const StressPt& p, double own_vel, const double* x_vel4) {
     const double d1 = p.own - own_vel;
@@ -267,14 +254,22 @@ __device__ __forceinline__ void gather_v(const EvpDev& P, const FRef& U, const F
     gather_cells<3, 2>(g, i - 1, j - 1, safe, q.c);
 }
 
-// ---- the tendency at a u point (u_velocity_tendency, :11-41) ----------------------------------------------------------------
-// dt_forcing: the Delta t of sum_of_forcing_u (EVP only).  Returns G; mi, ai: the interpolated mass and concentration
+// ---- the front half of a tendency: everything up to the stress divergence, shared by the stepping kernels (u_tendency / v_tendency)
+// and by the kernels that keep the terms apart (momentum_terms.hip, with FAST = false) ------------------------------------------------
+// mi, ai: the interpolated ice mass (ClimaSeaIce.jl:42) and concentration; c0, c1 / f0, f1: the immersed-peripheral predicates of the
+// point's two cells / two corners (lower index first); div: the stress divergence with the conditional fluxes; imm: the immersed
+// flux term -- both per unit area, not yet divided by mi
+struct Front {
+    double mi, ai, div, imm;
+    bool c0, c1, f0, f1;
+};
 template <bool FAST, bool VISC>
-__device__ __forceinline__ double u_tendency(const EvpDev& P, double nu, UPoint& q, int i, int j, double dt_forcing, double& mi, double& ai) {
+__device__ __forceinline__ Front u_front(const EvpDev& P, double nu, UPoint& q, int i, int j) {
     const GridDev& g = P.g;
+    Front r;
     resolve_cells<2, 3>(g, i - 1, j - 1, q.c);
-    mi = (q.hw * P.rho * q.aw + q.he * P.rho * q.ae) / 2;          // ice_mass (ClimaSeaIce.jl:42) interpolated, Ixᶠᵃᵃ
-    ai = (q.aw + q.ae) / 2;
+    r.mi = (q.hw * P.rho * q.aw + q.he * P.rho * q.ae) / 2;        // Ixᶠᵃᵃ
+    r.ai = (q.aw + q.ae) / 2;
     // corners: (i, j) = cells 0, 1, 2, 3; (i, j + 1) = cells 2, 3, 4, 5.  Cells (i-1, j) = 2, (i, j) = 3
     const bool cw = ipcc(g, q.c, 2), ce = ipcc(g, q.c, 3), fs = ipff<2>(g, q.c, 0), fn = ipff<2>(g, q.c, 2);
     double s11w, s11e, s22w, s22e, s12s, s12n;
@@ -289,16 +284,59 @@ __device__ __forceinline__ double u_tendency(const EvpDev& P, double nu, UPoint&
     s11w = cw ? 0.0 : s11w; s22w = cw ? 0.0 : s22w;
     s11e = ce ? 0.0 : s11e; s22e = ce ? 0.0 : s22e;
     s12s = fs ? 0.0 : s12s; s12n = fn ? 0.0 : s12n;
-    const double div = div1<FAST>(q.m, s11e + s22e, s11w + s22w, s11e - s22e, s11w - s22w, s12n, s12s);
+    r.div = div1<FAST>(q.m, s11e + s22e, s11w + s22w, s11e - s22e, s11w - s22w, s12n, s12s);
     // immersed_dj_sigma_1j (:65-92): west / east faces are the cells i - 1, i; south / north the corners j, j + 1
-    double imm = 0.0;
+    r.imm = 0.0;
     if (g.has_mask) {
         const double qW = (cw ? -P.ibc_u[0] : 0.0) * q.m[2];          // dy(c,c)(i-1, j)
         const double qE = (ce ? P.ibc_u[1] : 0.0) * q.m[1];           // dy(c,c)(i, j)
         const double qS = (fs ? -P.ibc_u[2] : 0.0) * q.m[4];          // dx(f,f)(i, j)
         const double qN = (fn ? P.ibc_u[3] : 0.0) * q.m[3];           // dx(f,f)(i, j + 1)
-        imm = (qE - qW + qN - qS) / q.m[6];
+        r.imm = (qE - qW + qN - qS) / q.m[6];
     }
+    r.c0 = cw; r.c1 = ce; r.f0 = fs; r.f1 = fn;
+    return r;
+}
+template <bool FAST, bool VISC>
+__device__ __forceinline__ Front v_front(const EvpDev& P, double nu, VPoint& q, int i, int j) {
+    const GridDev& g = P.g;
+    Front r;
+    resolve_cells<3, 2>(g, i - 1, j - 1, q.c);
+    r.mi = (q.hs * P.rho * q.as_ + q.hn * P.rho * q.an) / 2;
+    r.ai = (q.as_ + q.an) / 2;
+    // cells (i-1..i+1) x (j-1..j): (i, j-1) = 1, (i, j) = 4; corners (i, j) = cells 0, 1, 3, 4; (i + 1, j) = cells 1, 2, 4, 5
+    const bool cs = ipcc(g, q.c, 1), cn = ipcc(g, q.c, 4), fw = ipff<3>(g, q.c, 0), fe = ipff<3>(g, q.c, 1);
+    double s11s, s11n, s22s, s22n, s12w, s12e;
+    if (VISC) {
+        s11s = nu * (q.u4[1] - q.u4[0]); s11n = nu * (q.u4[3] - q.u4[2]);   // ux at cells j - 1, j
+        s22s = nu * (q.vc - q.vs); s22n = nu * (q.vn - q.vc);                // vy
+        s12w = nu * (q.vc - q.vw); s12e = nu * (q.ve - q.vc);                // vx at corners (i, j), (i + 1, j)
+    } else {
+        s11s = q.s11s; s11n = q.s11n; s22s = q.s22s; s22n = q.s22n; s12w = q.s12w; s12e = q.s12e;
+    }
+    s11s = cs ? 0.0 : s11s; s22s = cs ? 0.0 : s22s;
+    s11n = cn ? 0.0 : s11n; s22n = cn ? 0.0 : s22n;
+    s12w = fw ? 0.0 : s12w; s12e = fe ? 0.0 : s12e;
+    r.div = div2<FAST>(q.m, s11n + s22n, s11s + s22s, s11n - s22n, s11s - s22s, s12e, s12w);
+    r.imm = 0.0;
+    if (g.has_mask) {                                                // immersed_dj_sigma_2j (:94-123)
+        const double qW = (fw ? -P.ibc_v[0] : 0.0) * q.m[4];          // dy(f,f)(i, j)
+        const double qE = (fe ? P.ibc_v[1] : 0.0) * q.m[3];           // dy(f,f)(i + 1, j)
+        const double qS = (cs ? -P.ibc_v[2] : 0.0) * q.m[2];          // dx(c,c)(i, j - 1)
+        const double qN = (cn ? P.ibc_v[3] : 0.0) * q.m[1];           // dx(c,c)(i, j)
+        r.imm = (qE - qW + qN - qS) / q.m[6];
+    }
+    r.c0 = cs; r.c1 = cn; r.f0 = fw; r.f1 = fe;
+    return r;
+}
+
+// ---- the tendency at a u point (u_velocity_tendency, :11-41) ----------------------------------------------------------------
+// dt_forcing: the Delta t of sum_of_forcing_u (EVP only).  Returns G; mi, ai: the interpolated mass and concentration
+template <bool FAST, bool VISC>
+__device__ __forceinline__ double u_tendency(const EvpDev& P, double nu, UPoint& q, int i, int j, double dt_forcing, double& mi, double& ai) {
+    const Front fr = u_front<FAST, VISC>(P, nu, q, i, j);
+    mi = fr.mi; ai = fr.ai;
+    const double div = fr.div, imm = fr.imm;
     const double cor = P.has_cor ? -q.f * avg4(q.v4) : 0.0;          // x_f_cross_U
     double forcing = q.user;                                          // sum_of_forcing_u: viscous = the user forcing alone
     if (!VISC) forcing = q.user + (q.unn - q.uc) / dt_forcing / ((q.alw + q.ale) / 2);
@@ -315,32 +353,9 @@ __device__ __forceinline__ double u_tendency(const EvpDev& P, double nu, UPoint&
 }
 template <bool FAST, bool VISC>
 __device__ __forceinline__ double v_tendency(const EvpDev& P, double nu, VPoint& q, int i, int j, double dt_forcing, double& mi, double& ai) {
-    const GridDev& g = P.g;
-    resolve_cells<3, 2>(g, i - 1, j - 1, q.c);
-    mi = (q.hs * P.rho * q.as_ + q.hn * P.rho * q.an) / 2;
-    ai = (q.as_ + q.an) / 2;
-    // cells (i-1..i+1) x (j-1..j): (i, j-1) = 1, (i, j) = 4; corners (i, j) = cells 0, 1, 3, 4; (i + 1, j) = cells 1, 2, 4, 5
-    const bool cs = ipcc(g, q.c, 1), cn = ipcc(g, q.c, 4), fw = ipff<3>(g, q.c, 0), fe = ipff<3>(g, q.c, 1);
-    double s11s, s11n, s22s, s22n, s12w, s12e;
-    if (VISC) {
-        s11s = nu * (q.u4[1] - q.u4[0]); s11n = nu * (q.u4[3] - q.u4[2]);   // ux at cells j - 1, j
-        s22s = nu * (q.vc - q.vs); s22n = nu * (q.vn - q.vc);                // vy
-        s12w = nu * (q.vc - q.vw); s12e = nu * (q.ve - q.vc);                // vx at corners (i, j), (i + 1, j)
-    } else {
-        s11s = q.s11s; s11n = q.s11n; s22s = q.s22s; s22n = q.s22n; s12w = q.s12w; s12e = q.s12e;
-    }
-    s11s = cs ? 0.0 : s11s; s22s = cs ? 0.0 : s22s;
-    s11n = cn ? 0.0 : s11n; s22n = cn ? 0.0 : s22n;
-    s12w = fw ? 0.0 : s12w; s12e = fe ? 0.0 : s12e;
-    const double div = div2<FAST>(q.m, s11n + s22n, s11s + s22s, s11n - s22n, s11s - s22s, s12e, s12w);
-    double imm = 0.0;
-    if (g.has_mask) {                                                // immersed_dj_sigma_2j (:94-123)
-        const double qW = (fw ? -P.ibc_v[0] : 0.0) * q.m[4];          // dy(f,f)(i, j)
-        const double qE = (fe ? P.ibc_v[1] : 0.0) * q.m[3];           // dy(f,f)(i + 1, j)
-        const double qS = (cs ? -P.ibc_v[2] : 0.0) * q.m[2];          // dx(c,c)(i, j - 1)
-        const double qN = (cn ? P.ibc_v[3] : 0.0) * q.m[1];           // dx(c,c)(i, j)
-        imm = (qE - qW + qN - qS) / q.m[6];
-    }
+    const Front fr = v_front<FAST, VISC>(P, nu, q, i, j);
+    mi = fr.mi; ai = fr.ai;
+    const double div = fr.div, imm = fr.imm;
     const double cor = P.has_cor ? q.f * avg4(q.u4) : 0.0;            // y_f_cross_U
     double forcing = q.user;
     if (!VISC) forcing = q.user + (q.vnn - q.vc) / dt_forcing / ((q.als + q.aln) / 2);

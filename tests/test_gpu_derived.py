@@ -110,6 +110,24 @@ def test_fields_and_budget_equal_the_restatement_bitwise(shape, topo, metrics):
     assert m.ctx.derived_stats() == (2 * (2 + 7), 2 * 4)
 
 
+def test_budget_with_more_records_than_the_finishing_block_has_threads():
+    """1030 x 961 cells are 17 x 16 = 272 records (the last block column six cells wide, the last block row one cell high): threads
+    0 .. 15 of the finishing block add two records each, the strided part of the order that no smaller grid reaches.  Uniform metrics,
+    doubly periodic, both groups, one call per mode, bit for bit against the restatement."""
+    c = case_of((1030, 961), "periodic", "uniform")
+    g = c["g"]
+    assert -(-g.Nx // 64) * -(-g.Ny // 64) == 272
+    m = cases.csi_model(c, mode="strict")
+    par, _ = ref.white_noise(g, seed=17, land=False, poison="budget")
+    set_land(m, None)
+    load(m, par)
+    sums = ref.Ref(g, par, None, rho=m.sea_ice_density).budget()
+    assert all(math.isfinite(v) for v in sums.values())
+    for mode in ("strict", "fast"):
+        m.set_mode(mode)
+        assert budget_bits(m.energy_budget(), sums) == [], mode
+
+
 # ---- errors by name ----------------------------------------------------------------------------------------------------------------------------
 def test_errors_by_name():
     c = case_of((37, 29), "periodic", "uniform")

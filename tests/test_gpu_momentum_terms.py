@@ -417,7 +417,9 @@ def test_explicit_solver_tendency_is_the_sum_of_the_fields(topo, rheo):
 
 
 # ---- 13. the budget ------------------------------------------------------------------------------------------------------------------------
-@pytest.mark.parametrize("shape", [(64, 64), (65, 65), (130, 65)], ids=lambda s: f"{s[0]}x{s[1]}")
+# (16385 x 4: 257 x 1 records, more than the finishing block has 256 threads -- thread 0 adds records 0 and 256; a thin grid because the
+#  restatement walks the points in Python: 65 540 points are a few seconds, the 17 x 16 blocks of a square grid would be most of a minute)
+@pytest.mark.parametrize("shape", [(64, 64), (65, 65), (130, 65), (16385, 4)], ids=lambda s: f"{s[0]}x{s[1]}")
 def test_budget_at_the_record_layout_edges(shape, oracle_lib):
     """Uniform doubly periodic f-plane, uniform h and aice, random u and v, a wind stress and an ocean at rest: the five powers equal
     the restatement bit for bit in both modes and on repeated calls; the Coriolis power vanishes within (2 n + 8) 2^-53 sum |summand|;
