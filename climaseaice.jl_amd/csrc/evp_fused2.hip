@@ -29,45 +29,6 @@
 #include <cstdio>
 #include <cstdlib>
 
-#ifndef CSI_PAIR_WAVES
-#define CSI_PAIR_WAVES 3        // waves per SIMD the register allocation aims at (512 / 3 -> 168 VGPRs)
-#endif
-#ifndef CSI_PAIR_UNI_WAVES
-#define CSI_PAIR_UNI_WAVES 2    // ... of the uniform-coefficient instantiations: pair_geom (csi_core.hip) gives them 1024 tiles = two waves per SIMD
-#endif                          //     (round 5), so the velocity coefficients they hold in vector registers (Stage::hoist_uniform) cost no occupancy
-#ifndef CSI_PAIR_FULL_WAVES
-#define CSI_PAIR_FULL_WAVES 2   // ... of the per-point-coefficient (CSI_METRIC_FULL) instantiations
-#endif
-#ifndef CSI_PAIR_PRIO
-#define CSI_PAIR_PRIO 2         // 2: the consumer wave of every pair above the producers (see k_pair); 1: rotate the priority of the
-                                // resident workgroups of a CU every row; 0: none
-#endif
-#ifndef CSI_PAIR_HOIST
-#define CSI_PAIR_HOIST 1        // 1: let the compiler keep the table constants in SGPRs across rows (no per-row reload fence); not in the
-                                // array-forcing and per-point-metric instantiations (scalar spills: curvilinear 30.3 -> 27.1 G with it)
-#endif
-#ifndef CSI_FULL_FENCE
-#define CSI_FULL_FENCE 1        // per-point-metric instantiations: reload the table constants every row (1) or let the compiler keep them (0: scalar spills)
-#endif
-#ifndef CSI_PAIR_STORES
-#define CSI_PAIR_STORES 7       // which of stage B's results the CONSUMER stores itself (bit 0: the stresses, bit 1: the first velocity, bit 2: the
-                                // second); the producer stores the rest, handed over through the out ring, two iterations later
-#endif
-#ifndef CSI_PEER_EXP
-#define CSI_PEER_EXP 3          // how an edge tile publishes its halo images (PEER instantiations).  3 (default): the images are write-through
-                                // stores at system scope (sc0 sc1) and the flags follow a drained store queue (vmcnt(0)); 0: plain stores and a
-                                // system-scope release fence before the flags -- the fence writes the XCD's whole L2 back (buffer_wbl2), once per
-                                // edge tile: +6 us per launch on a 1024 x 512 tile, +20 us at 2048^2 (profiles/r03_peer_protocol.md); bit 0 alone:
-                                // no fence, bit 2: no wait at the start of an edge tile (timing experiments, not valid protocols); bit 3: wait for the fifteen tiles
-                                // around this one only (experiment on a tile connected to itself, CSI_EXP_OVERLAP=3: profiles/r06_tile_overlap.txt)
-#endif
-#ifndef CSI_PAIR_SKIPB
-#define CSI_PAIR_SKIPB 0       // 1: the consumer wave skips its first iterations of a tile (pure pipeline lag; see bodyB).  Measured round 5, same-box A/B: 2048 x 256 43.0 G with, 43.4 without; 1024 x 512 43.1 / 43.5 -- the test in every iteration costs more than two idle iterations save: off
-#endif
-#ifndef CSI_PAIR_PD
-#define CSI_PAIR_PD 1           // rows the producer prefetches ahead (1 or 2; 2 costs 20 more VGPRs)
-#endif
-
 namespace csi {
 namespace fused {
 
@@ -98,13 +59,7 @@ enum : int { RF_S11 = 0, RF_S22, RF_S12, RF_U, RF_V, RF_P, RF_M, RF_A, RF_UN, RF
 // The last three -- ice strength at the corner, 1 / m at the cell and the corner, of the producer's row -- spare the consumer
 // two reciprocals, a lane shift and four more operations per row (it is the longer wave of the pair); 26 KB of LDS per
 // workgroup instead of 20: six workgroups per CU still fit, except with the mask rows of the immersed-boundary
-// instantiations, which therefore keep the ten-field ring (CSI_PAIR_PRE).
-#ifndef CSI_PAIR_LDSC_NOPRE
-#define CSI_PAIR_LDSC_NOPRE 1   // per-row coefficients through the LDS window (Stage::pc): the ten-field ring, so that six workgroups per CU still fit
-#endif
-#ifndef CSI_PAIR_PRE
-#define CSI_PAIR_PRE 1
-#endif
+// instantiations, which therefore keep the ten-field ring (PairLayout::PRE).
 // FULL (per-point metric planes): nine of the twelve plane values of a stage-row travel through the ring as well (fields 10 .. 18:
 // what the producer's step consumed for row r is what the consumer's step needs for the same row two iterations later), the
 // consumer loads the other three itself (1 / Az at the cell and at the velocity points).  Loaded by both waves -- rounds 3 / 4 --
@@ -123,9 +78,6 @@ enum : int { RF_S11 = 0, RF_S22, RF_S12, RF_U, RF_V, RF_P, RF_M, RF_A, RF_UN, RF
 // style 40.5 -> 48-49 G.  The wind-drag / bottom-stress-array instantiations (EXTRA 2, no free drift there) map their own eight
 // values onto the same slots, and so do model.forcing arrays on unmasked grids (EXTRA 1 without MASK: in the free-drift slots).  Not
 // with immersed-flux-BC divergences (EXTRA 1 with MASK: ten values and the mask rows -- more than four workgroups per CU hold).
-#ifndef CSI_PAIR_FRING
-#define CSI_PAIR_FRING 1
-#endif
 constexpr int RF_FORCING = 8;
 enum : int { RF_FU_TAU = 10, RF_FU_WE, RF_FU_WB, RF_FU_FD, RF_FV_TAU, RF_FV_WE, RF_FV_WB, RF_FV_FD };
 // Round 5: ALL TWELVE plane values of a stage-row travel from the producer to the consumer, through a ring of their own that is
@@ -138,6 +90,20 @@ enum : int { RF_FU_TAU = 10, RF_FU_WE, RF_FU_WB, RF_FU_FD, RF_FV_TAU, RF_FV_WE, 
 constexpr int RP_ROWS = 3, RP_FIELDS = 12;
 enum : int { RP_DXV = 0, RP_RDYV, RP_RDXU, RP_DXF2, RP_DYF2, RP_RAZF, RP_DYU, RP_DYC2, RP_DXC2, RP_RAZC, RP_RAZU, RP_RAZV };
 
+// What decides an instantiation's LDS layout and occupancy, stated once: pair_body, k_pair and its __launch_bounds__ read it.
+template <bool UNI, bool MASK, bool FORCE, bool FULL, int EXTRA>
+struct PairLayout {
+    // Stage's HOLDK: every family but mask + model.forcing / immersed-flux terms (EXTRA 1 with MASK: ten forcing values and the mask rows)
+    static constexpr bool HOLDK = !(EXTRA == 1 && MASK);
+    static constexpr bool FRING = FORCE && !FULL && HOLDK;      // the forcing values of a stage-row travel through the ring too (above)
+    static constexpr bool PRE = !MASK && !FULL && !FRING;       // ... or the corner ice strength and the reciprocal masses do (RF_PF ..)
+    static constexpr int RING_FIELDS = FRING ? 10 + RF_FORCING : (PRE ? 13 : 10);      // (FULL: ten fields; its plane values have a ring of their own, ringp)
+    // Waves per SIMD the register allocation aims at.  2 (256 VGPRs): per-point metrics and ring-forced; uniform coefficients too -- pair_geom
+    // (csi_core.hip) gives them 1024 tiles = two waves per SIMD (round 5), so the velocity coefficients they hold in vector registers
+    // (Stage::hoist_uniform) cost no occupancy.  3 (512 / 3 -> 168 VGPRs): the rest.
+    static constexpr int WAVES = (FULL || FRING) ? 2 : (UNI && HOLDK) ? 2 : 3;
+};
+
 // FULL (orthogonal curvilinear grids, per-point metric planes, csi_fast_coef.h): 14 more loads per stage-row
 // in flight -- compiled for 2 waves per SIMD (256 VGPRs); the kernel is bound by the planes' traffic and load count there.
 // The kernel's body is a function of its own (not inlined: its registers are allocated for it alone), so that the PEER kernels can
@@ -146,22 +112,16 @@ enum : int { RP_DXV = 0, RP_RDYV, RP_RDXU, RP_DXF2, RP_DYF2, RP_RAZF, RP_DYU, RP
 // were 6 % slower (1.7 us per launch on a 1024 x 512 tile with no neighbour at all; round 4, profiles/r04_tile_1024x512.md).
 template <bool UNI, bool AUF, bool WALLS, bool MASK, bool FORCE, bool FD, int CF, bool FULL = false, bool PEER = false, int EXTRA = 0, bool DLD = false>
 __device__ __forceinline__ void pair_body(const FusedTable* __restrict__ table, const int w, int nstrips, int nchunks, int rows,
-                                       int blocks_per_xcd, int write_diag, unsigned long long seq,
-                                       double* __restrict__ ring, unsigned* __restrict__ ringm, double* __restrict__ outr, unsigned* __restrict__ peer_abort_p, double* __restrict__ ringp,
-                                       double* __restrict__ ringc) {
-    constexpr bool LDSC = !UNI && !FULL && !(EXTRA == 1 && MASK) && (CSI_PAIR_LDSC != 0);
-    constexpr bool FRING = FORCE && !FULL && (EXTRA != 1 || !MASK) && CSI_PAIR_FRING;      // the forcing values of a stage-row travel through the ring too (below)
-    constexpr bool PRE = CSI_PAIR_PRE && !MASK && !FULL && !FRING && !(CSI_PAIR_LDSC_NOPRE && !UNI && !(EXTRA == 1 && MASK) && (CSI_PAIR_LDSC != 0));
-    constexpr int RING_FIELDS = FRING ? 10 + RF_FORCING : (PRE ? 13 : 10);      // (FULL: ten fields; its plane values have a ring of their own, ringp)
+                                       int blocks_per_xcd, int write_diag, unsigned long long seq,      // (w: this workgroup's tile, from k_pair -- dealt over the XCDs there)
+                                       double* __restrict__ ring, unsigned* __restrict__ ringm, unsigned* __restrict__ peer_abort_p, double* __restrict__ ringp) {
+    using Layout = PairLayout<UNI, MASK, FORCE, FULL, EXTRA>;
+    constexpr bool FRING = Layout::FRING, PRE = Layout::PRE;
+    constexpr int RING_FIELDS = Layout::RING_FIELDS;
 #define peer_abort (*peer_abort_p)
-    const int b = (int)blockIdx.x;      // (w: this workgroup's tile, from k_pair -- dealt over the XCDs there)
     // Roles: wave 0 produces, wave 1 consumes.  (Measured placement of the 12 waves of a CU's six workgroups, in dispatch
     // order, on its SIMDs a..d: a b | b c | c d | d a | a b | c d -- every SIMD gets producers and consumers, the two waves
     // of a workgroup never share a SIMD; swapping the roles in some workgroups changed nothing measurable.)
-#ifndef CSI_EXP_ROLESWAP
-#define CSI_EXP_ROLESWAP 0     // experiment: workgroups of odd arrival rank on their CU swap the roles of their waves (SIMDs then hold two producers or two consumers)
-#endif
-    const bool consumer = (__builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6)) != 0) != (CSI_EXP_ROLESWAP && ((((b >> 3) / CSI_EXP_ROLESWAP) & 1) != 0));
+    const bool consumer = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6)) != 0;
     const int chunk = w / nstrips, strip = w - chunk * nstrips;
     const int lane = (int)(threadIdx.x & 63);
     tptr_t T = (tptr_t)table;
@@ -235,11 +195,7 @@ __device__ __forceinline__ void pair_body(const FusedTable* __restrict__ table, 
         lanes_same = __builtin_amdgcn_ballot_w64(!same) == 0;
         lanes_uniform = !wave_has_dx_b && lanes_same;
         rstart = max(ja - 3, T->I[FI_AJ0]);
-#ifndef CSI_EXP_RINGCUT
-#define CSI_EXP_RINGCUT 0       // TIMING EXPERIMENT ONLY (wrong results): so many of a tile's top ring rows are not run -- what a launch would
-                                // cost if vertically adjacent tiles shared their seam rows instead of recomputing them (profiles/r05_tile.md)
-#endif
-        rend = min(jb + 3 - CSI_EXP_RINGCUT, T->I[FI_AJ1]);
+        rend = min(jb + 3, T->I[FI_AJ1]);      // (timing experiment: a ring row less is an iteration less -- profiles/r05_tile.md)
         if (i <= Hx) flags |= L_LOW;                         // this column's x image lies beyond the HIGH side of the low-side neighbour
         sc = (unsigned)T->I[FI_LD_C] * 8u;
         sf = (unsigned)T->I[FI_LD_F] * 8u;
@@ -262,7 +218,7 @@ __device__ __forceinline__ void pair_body(const FusedTable* __restrict__ table, 
                  ((pn & pw) ? 64u : 0u) | ((pn & pe) ? 128u : 0u)) & (unsigned)T->I[FI_PMASK];
         pdirs = (unsigned)__builtin_amdgcn_readfirstlane((int)pdirs);
         if (pdirs) {
-            if (!consumer && !(CSI_PEER_EXP & 4)) {
+            if (!consumer) {
                 // One poll = the slots of ALL this tile's directions in flight at once (lane l reads slot l of each direction; the
                 // sets are a few dozen tiles).  No cache invalidate afterwards: every tile whose footprint shares a 128-byte line
                 // with halo cells of a direction is in that direction's set and loads nothing before it has seen the flags, and the
@@ -277,16 +233,6 @@ __device__ __forceinline__ void pair_body(const FusedTable* __restrict__ table, 
                 bool dead = false;
                 for (;;) {
                     bool behind = false, poison = false;
-                    if constexpr ((CSI_PEER_EXP & 8) != 0) {
-                        // TIMING EXPERIMENT (a tile connected to ITSELF in y with every tile in its S and N sets, CSI_EXP_OVERLAP=3:
-                        // profiles/r06_tile_overlap.txt): wait for the tiles of the previous launch around this one only (3 strips x 5 chunks) -- the
-                        // tiles whose stores this one reads and whose loads its stores would overtake -- instead of for all of them
-                        const unsigned long long* slots = (const unsigned long long*)T->P[FP_SLOT_IN + 2];      // (direction S)
-                        if (lane < 15) {      // (two chunks up and down: the chunks next to a connected side may be shorter than a footprint's reach)
-                            const int cq = (chunk + lane / 3 - 2 + 2 * nchunks) % nchunks, cs = (strip + lane % 3 - 1 + nstrips) % nstrips;
-                            behind |= __hip_atomic_load(slots + (cq * nstrips + cs), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM) + 1ull < seq;
-                        }
-                    } else
 #pragma unroll
                     for (int d = 0; d < 8; ++d) {
                         if (!((pdirs >> d) & 1u)) continue;
@@ -416,27 +362,15 @@ __device__ __forceinline__ void pair_body(const FusedTable* __restrict__ table, 
         kv.min_conc = T->K[FK_MIN_CONC2]; kv.has_cor = T->I[FI_HAS_COR];
     };
     // Issue arbitration favours the OLDEST wave of a SIMD: without help the workgroups dispatched first finish after ~2/3 of
-    // the launch and the youngest run on alone (measured: tile lifetimes 100 .. 180 us in one launch; by age rank on the CU
-    // 115 .. 136 us even with a rotation keyed on the dispatch order, because the allocator does not place ranks r, r + 3 on
-    // different SIMDs).  The waves therefore rotate the user priority every row, keyed on their own slot in the SIMD
-    // (HW_ID.wave_id: the three resident waves of a SIMD hold slots 0, 1, 2): slot + row (mod 3) gives each of them the
-    // top priority one row in three.
-    // (Measured with static priorities: the two youngest workgroups of a CU at a higher priority finish after 77 us, the others
-    // after 108 .. 138 us, the launch still takes 150 us -- the SIMDs are work-conserving, the launch time is set by the
-    // work per SIMD and by how often its three waves stall at the same time, not by the order they finish in.)
-    const int prio_rank = (int)(__builtin_amdgcn_s_getreg((3 << 11) | (0 << 6) | 4) % 3u);      // HW_REG_HW_ID bits [3:0]
-    auto set_prio = [&](int k) __attribute__((always_inline)) {
-        if (CSI_PAIR_PRIO == 2) {                    // the longer wave of the pair (since the stores moved: the consumer) first
-            if (consumer) __builtin_amdgcn_s_setprio(2); else __builtin_amdgcn_s_setprio(0);
-        } else if (CSI_PAIR_PRIO == 3) {             // (the other way round: measured worse)
-            if (consumer) __builtin_amdgcn_s_setprio(0); else __builtin_amdgcn_s_setprio(2);
-        } else if (CSI_PAIR_PRIO == 4) {
-            if (consumer) __builtin_amdgcn_s_setprio(3); else __builtin_amdgcn_s_setprio(0);
-        } else if (CSI_PAIR_PRIO) {
-            int p = prio_rank + k;
-            p = p >= 3 ? p - 3 : p;
-            if (p == 0) __builtin_amdgcn_s_setprio(0); else if (p == 1) __builtin_amdgcn_s_setprio(1); else __builtin_amdgcn_s_setprio(2);
-        }
+    // the launch and the youngest run on alone (measured: tile lifetimes 100 .. 180 us in one launch).  The longer wave of the pair
+    // (since the stores moved: the consumer) therefore runs above the producers.  (Measured and not taken: the other way round --
+    // worse; a per-row rotation of the priority keyed on the wave's slot in its SIMD -- by age rank on the CU still 115 .. 136 us,
+    // because the allocator does not place ranks r, r + 3 on different SIMDs; static priorities for the youngest workgroups -- they
+    // finish after 77 us, the others after 108 .. 138 us, the launch still takes 150 us: the SIMDs are work-conserving, the launch
+    // time is set by the work per SIMD and by how often its waves stall at the same time, not by the order they finish in:
+    // profiles/r02c_progress_feedback_priority_probe.txt, profiles/r05_prio_ab.txt.)
+    auto set_prio = [&]() __attribute__((always_inline)) {
+        if (consumer) __builtin_amdgcn_s_setprio(2); else __builtin_amdgcn_s_setprio(0);
     };
     // rows of this tile each kind of store covers (wave-uniform, fixed for the whole march)
     const int rs_lo = max(ja, T->I[FI_RS + 2]), rs_hi = min(jb, T->I[FI_RS + 3]);
@@ -479,7 +413,7 @@ __device__ __forceinline__ void pair_body(const FusedTable* __restrict__ table, 
     auto put4 = [&](int k, unsigned off, unsigned dy, bool ylow, int dxl, double val, double valy, double valx, double valxy, int j, int yr) __attribute__((always_inline)) {
         const unsigned long base = own(k);
         auto sti = [&](unsigned long b_, unsigned o_, double v_) __attribute__((always_inline)) {
-            if constexpr (PEER && (CSI_PEER_EXP & 2) != 0)
+            if constexpr (PEER)      // (write-through at system scope, sc0 sc1: the protocol in `publish`)
                 __scoped_atomic_store_n((__attribute__((address_space(1))) long*)((gptr_t)b_ + o_), __builtin_bit_cast(long, v_), __ATOMIC_RELAXED, __MEMORY_SCOPE_SYSTEM);
             else sto(b_, o_, v_);
         };
@@ -539,27 +473,23 @@ __device__ __forceinline__ void pair_body(const FusedTable* __restrict__ table, 
         if (wrap_hi | yhi_wall) fast_hi = min(fast_hi, NyW - HyW);              // ... and of the high ones N-H+1 .. N
     }
     const bool fast_plain = lanes_uniform;                // no lane of the wave has an x image either
-    // Stage B's results of row q (sigma(q); first velocity v(q) / u(q-1); second velocity u(q-1) / v(q-1)) go to memory from
-    // whichever wave CSI_PAIR_STORES names: the consumer itself, straight from its registers (the default), or the producer,
-    // which gets them through a two-row LDS ring and stores them two iterations later.  The stores and their bookkeeping
-    // are ~20 % of a wave's row time, so they decide which wave of the pair waits for the other at the barrier: while the
-    // arithmetic was 282 instructions per stage-row the consumer was the longer wave and the producer stored (+3 %); at 234
-    // the producer -- loads, address arithmetic, eleven LDS writes -- became the longer one (probe: 36 + 4 waiting against
-    // 30 + 12 waiting) and the stores went back to the consumer: +5 % at 2048^2, +7 % on a 1024 x 512 tile (28 + 13 against
-    // 39 + 5 now; splitting the five stores between the waves balances them better and measures the same within noise).
-    auto flush = [&](int q, double v11, double v22, double v12, double vfirst, double vsecond, auto WH, auto VFT) __attribute__((always_inline)) {
-        constexpr int which = decltype(WH)::value;
-        constexpr bool VF = decltype(VFT)::value != 0;         // the stored stage is v-first (pairs: stage B, i.e. A is u-first; single sub-step: stage A itself)           // bit 0: stresses, bit 1: first velocity, bit 2: second velocity
-        if (which == 0) return;
+    // Stage B's results of row q (sigma(q); first velocity v(q) / u(q-1); second velocity u(q-1) / v(q-1)) go to memory from the
+    // consumer itself, straight from its registers.  The stores and their bookkeeping are ~20 % of a wave's row time, so they
+    // decide which wave of the pair waits for the other at the barrier: with the producer -- loads, address arithmetic, eleven LDS
+    // writes -- storing them (handed over through an LDS ring, two iterations later) it was the longer wave (probe: 36 + 4 waiting
+    // against 30 + 12 waiting); with the consumer +5 % at 2048^2, +7 % on a 1024 x 512 tile (28 + 13 against 39 + 5; splitting
+    // the five stores between the waves measures the same within noise: profiles/r02e_consumer_stores.md).
+    auto flush = [&](int q, double v11, double v22, double v12, double vfirst, double vsecond, auto VFT) __attribute__((always_inline)) {
+        constexpr bool VF = decltype(VFT)::value != 0;         // the stored stage is v-first (pairs: stage B, i.e. A is u-first; single sub-step: stage A itself)
         if ((q >= fast_lo) & (q <= fast_hi)) {
             // interior rows (nearly every call): every kind of store is due, no row has a y image
             const unsigned ocq = offc(q), ofq = offf(q);
             if (fast_plain) {
                 // interior tile: the owned lanes store five values, no images
                 if (flags & L_RS) {
-                    if (which & 1) { sto(T->P[FP_S11_OUT], ocq, v11); sto(T->P[FP_S22_OUT], ocq, v22); sto(T->P[FP_S12_OUT], ofq, v12); }
-                    if (which & 2) sto(T->P[VF ? FP_V_OUTP : FP_U_OUTP], VF ? ocq : ofq - sf, vfirst);
-                    if (which & 4) sto(T->P[VF ? FP_U_OUTP : FP_V_OUTP], VF ? ofq - sf : ocq - sc, vsecond);
+                    sto(T->P[FP_S11_OUT], ocq, v11); sto(T->P[FP_S22_OUT], ocq, v22); sto(T->P[FP_S12_OUT], ofq, v12);
+                    sto(T->P[VF ? FP_V_OUTP : FP_U_OUTP], VF ? ocq : ofq - sf, vfirst);
+                    sto(T->P[VF ? FP_U_OUTP : FP_V_OUTP], VF ? ofq - sf : ocq - sc, vsecond);
                 }
             } else {
                 // tile on an x edge of the domain: some lanes also store the x image of their column (periodic wrap / the
@@ -568,15 +498,14 @@ __device__ __forceinline__ void pair_body(const FusedTable* __restrict__ table, 
                 // wall is no u to store), and such a strip took the general path for every row -- the east strip of a Bounded grid
                 // 25 % longer than the others, which set the launch's end (bounded 2048^2: 147 us against 125 for the interior strips)
                 const bool ls = (flags & L_RS) != 0, l1 = (flags & L_R1) != 0, l2 = (flags & L_R2) != 0;
-                if ((which & 1) && ls) { put(0, ocq, 0u, false, dx, v11, q, 0); put(1, ocq, 0u, false, dx, v22, q, 0); put(2, ofq, 0u, false, dx, v12, q, 0); }
-                if (VF) { if ((which & 2) && l1) put_v(ocq, 0u, false, vfirst, q, 0); if ((which & 4) && l2) put(3, ofq - sf, 0u, false, dx, vsecond, q - 1, 0); }
-                else { if ((which & 2) && l1) put(3, ofq - sf, 0u, false, dx, vfirst, q - 1, 0); if ((which & 4) && l2) put_v(ocq - sc, 0u, false, vsecond, q - 1, 0); }
+                if (ls) { put(0, ocq, 0u, false, dx, v11, q, 0); put(1, ocq, 0u, false, dx, v22, q, 0); put(2, ofq, 0u, false, dx, v12, q, 0); }
+                if (VF) { if (l1) put_v(ocq, 0u, false, vfirst, q, 0); if (l2) put(3, ofq - sf, 0u, false, dx, vsecond, q - 1, 0); }
+                else { if (l1) put(3, ofq - sf, 0u, false, dx, vfirst, q - 1, 0); if (l2) put_v(ocq - sc, 0u, false, vsecond, q - 1, 0); }
             }
             return;
         }
         const int j1 = VF ? q : q - 1, j2 = q - 1;            // rows of the first / second velocity
-        const bool do_s = ((which & 1) != 0) & (q >= rs_lo) & (q <= rs_hi), do_1 = ((which & 2) != 0) & (j1 >= r1_lo) & (j1 <= r1_hi),
-                   do_2 = ((which & 4) != 0) & (j2 >= r2_lo) & (j2 <= r2_hi);
+        const bool do_s = (q >= rs_lo) & (q <= rs_hi), do_1 = (j1 >= r1_lo) & (j1 <= r1_hi), do_2 = (j2 >= r2_lo) & (j2 <= r2_hi);
         if (!(do_s | do_1 | do_2)) return;
         const unsigned ocq = offc(q), ofq = offf(q);
         const unsigned o1 = VF ? ocq : ofq - sf;                 // first velocity: v(q) / u(q-1)
@@ -609,27 +538,12 @@ __device__ __forceinline__ void pair_body(const FusedTable* __restrict__ table, 
     };
     auto rslot = [&](int j) __attribute__((always_inline)) { return (unsigned)((j - rstart) & (RING_ROWS - 1)) * (RING_FIELDS * 64) + lane_it; };
 
-#ifndef CSI_PAIR_UNROLL
-#define CSI_PAIR_UNROLL 3
-#endif
-
     if (!consumer) {
         // ===== PRODUCER: stage A = sub-step s, rows rstart .. rend ===================================================
         PROBE_DECL;
-        Stage<UNI, AUF, MASK, FORCE, CF, FULL, !(EXTRA == 1 && MASK)> A;    // (TIGHT scalar live ranges in the array-forcing variants)
-        A.lc = ringc;
-        // LDSC: the address of lane k's entry (k < FC_COUNT; the other lanes re-read the last one) of coefficient row j of the table
-        const int cjmin = LDSC ? T->I[FI_COEF_JMIN] : 0, cjmax = LDSC ? T->I[FI_COEF_JMAX] : 0;
-        const unsigned ck_lane = (unsigned)min(lane, FC_COUNT - 1) * 8u;
-        auto coef_row_base = [&](int j) __attribute__((always_inline)) {
-            return T->P[FP_PCOEF_VEC] + (unsigned long)((long)min(max(j, cjmin), cjmax) * (long)(FC_COUNT * 8));
-        };
-#ifndef CSI_EXP_RINGALIAS
-#define CSI_EXP_RINGALIAS 0     // TIMING EXPERIMENT ONLY (wrong results): a tile's ring rows are read from the nearest rows it owns -- same instructions,
-                                // same arithmetic, but no ring row ever comes from HBM: what it would be worth if every ring-row re-read hit the L2
-#endif
-        auto alias_row = [&](int j) __attribute__((always_inline)) { return CSI_EXP_RINGALIAS ? min(max(j, ja + 1), max(jb - 1, ja + 1)) : j; };
-        unsigned oc = offc(alias_row(rstart)), of = offf(alias_row(rstart)), om = MASK ? offm(rstart) : 0u;
+        Stage<UNI, AUF, MASK, FORCE, CF, FULL, Layout::HOLDK> A;    // (TIGHT scalar live ranges in the array-forcing variants)
+        // (timing experiment: a tile's ring rows re-read from rows it owns, so that none comes from HBM, +0.7 % -- profiles/r05_tile.md)
+        unsigned oc = offc(rstart), of = offf(rstart), om = MASK ? offm(rstart) : 0u;
         {
             const double rho0 = T->K[FK_RHO];
             A.u_m = ldg(T->P[FP_U_IN], of - sf); A.v_m = ldg(T->P[FP_V_IN], oc - sc);
@@ -681,43 +595,23 @@ __device__ __forceinline__ void pair_body(const FusedTable* __restrict__ table, 
             mhist = (mhist << 2) | (wi ? 3u : (act ? 0u : 1u));
             ringm[(unsigned)((-1) & (RING_ROWS - 1)) * 64 + (unsigned)lane] = mhist & 3u;      // row rstart - 1, for the consumer
         }
-        // Prefetch CSI_PAIR_PD rows ahead (three rotating register sets; the loop is unrolled by three, so the set of every
+        // Prefetch one row ahead (three rotating register sets; the loop is unrolled by three, so the set of every
         // iteration is fixed at compile time).  The producer issues no stores and loads return in order, so the wait at the
-        // top of an iteration leaves exactly the younger rows in flight.  (Measured: one row ahead already hides the
-        // memory latency -- 9 cycles of 2500 per iteration are spent in that wait.)
+        // top of an iteration leaves exactly the younger row in flight.  (Measured: one row ahead already hides the
+        // memory latency -- 9 cycles of 2500 per iteration are spent in that wait; two rows ahead cost 20 more VGPRs.)
         RowIn R[3];
-#ifndef CSI_FULL_HOISTP
-#define CSI_FULL_HOISTP 1
-#endif
-        // FULL (no hoisting of the table by the compiler, see body): the ten input addresses read ONCE (CSI_FULL_HOISTP >= 2)
-#ifndef CSI_FORCE_HOIST
-#define CSI_FORCE_HOIST 0
-#endif
-        constexpr bool HIN = (FULL && CSI_FULL_HOISTP >= 2) || (FORCE && !FULL && (CSI_FORCE_HOIST & 1));
-        const unsigned long hU = HIN ? T->P[FP_U_IN] : 0ul, hV = HIN ? T->P[FP_V_IN] : 0ul, hP = HIN ? T->P[FP_P] : 0ul, hH = HIN ? T->P[FP_H] : 0ul,
-                            hA = HIN ? T->P[FP_A] : 0ul, h11 = HIN ? T->P[FP_S11_IN] : 0ul, h22 = HIN ? T->P[FP_S22_IN] : 0ul, h12 = HIN ? T->P[FP_S12_IN] : 0ul,
-                            hUN = HIN ? T->P[FP_UN] : 0ul, hVN = HIN ? T->P[FP_VN] : 0ul;
         int rnext = rstart;                               // the row the NEXT load_row fetches (advance())
         auto load_row = [&](RowIn& Q) __attribute__((always_inline)) {
-            if constexpr (HIN) {
-                Q.u_p = ldg(hU, of + sf); Q.v_p = ldg(hV, oc + sc);
-                Q.P_0 = ldg(hP, oc); Q.h_0 = ldg(hH, oc); Q.a_0 = ldg(hA, oc);
-                Q.s11 = ldg(h11, oc); Q.s22 = ldg(h22, oc); Q.s12 = ldg(h12, of);
-                Q.un_m = ldg(hUN, of - sf); Q.vn_x = ldg(hVN, AUF ? oc - sc : oc);
-            } else {
             Q.u_p = ldg(T->P[FP_U_IN], of + sf); Q.v_p = ldg(T->P[FP_V_IN], oc + sc);
             Q.P_0 = ldg(T->P[FP_P], oc); Q.h_0 = ldg(T->P[FP_H], oc); Q.a_0 = ldg(T->P[FP_A], oc);
             Q.s11 = ldg(T->P[FP_S11_IN], oc); Q.s22 = ldg(T->P[FP_S22_IN], oc); Q.s12 = ldg(T->P[FP_S12_IN], of);
             Q.un_m = ldg(T->P[FP_UN], of - sf); Q.vn_x = ldg(T->P[FP_VN], AUF ? oc - sc : oc);
-            }
             Q.mk = MASK ? ldub(T->P[FP_MASK], om) : 1u;
-            if constexpr (LDSC) Q.ck = ldg(coef_row_base(rnext + 2), ck_lane);      // coefficient row (state row) + 2: in LDS one iteration before its first use
         };
         // oc / of / om: offsets of the row the NEXT load_row fetches; advance by one row, stopping at rend (the last
         // iterations re-read row rend: an unconditional prefetch keeps the number of loads in flight static)
         auto advance = [&]() __attribute__((always_inline)) {
             const bool more = rnext < rend;
-            if (CSI_EXP_RINGALIAS) { rnext += more ? 1 : 0; oc = offc(alias_row(rnext)); of = offf(alias_row(rnext)); return; }
             oc += more ? sc : 0u; of += more ? sf : 0u;
             if (MASK) om += more ? sm : 0u;
             rnext += more ? 1 : 0;
@@ -725,27 +619,17 @@ __device__ __forceinline__ void pair_body(const FusedTable* __restrict__ table, 
         int r = rstart;
         auto body = [&](auto KK) __attribute__((always_inline)) {
             constexpr int k = decltype(KK)::value;
-            if (!CSI_PAIR_HOIST || FORCE || (FULL && CSI_FULL_FENCE)) asm volatile("" : "+s"(T));
-            set_prio(k);
+            // the array-forcing and per-point-metric instantiations reload the table constants every row; the others let the compiler keep
+            // them in SGPRs across rows (kept there too they spill scalars: curvilinear 30.3 -> 27.1 G)
+            if (FORCE || FULL) asm volatile("" : "+s"(T));
+            set_prio();
             fresh_lane();
             PROBE_START;
             // rows r and r + 1 are in flight (loads return in order; FORCE: the array loads of the previous iteration were
             // consumed there): wait until only row r + 1's remain
-            if (CSI_PAIR_PD == 1) __builtin_amdgcn_s_waitcnt(0x0F70);
-            else if (MASK) __builtin_amdgcn_s_waitcnt(0x0F70 | 11);
-            else __builtin_amdgcn_s_waitcnt(0x0F70 | 10);
+            __builtin_amdgcn_s_waitcnt(0x0F70);
             PROBE(pacc0);
             const RowIn& C = R[k];
-            // LDSC: this row's loads brought lane k's entry of coefficient row r + 2: into the window, behind this iteration's barrier
-            // it is visible to both waves (first use: the corner coefficients of the producer's iteration r + 1)
-            if constexpr (LDSC) { if (lane < FC_COUNT) ringc[(unsigned)((r + 2) & 7) * FC_COUNT + (unsigned)lane] = C.ck; }
-            // stage B's results of two iterations ago (rows r - 4 / r - 5): read them now, store them after the prefetch
-            const unsigned so = (unsigned)((r - rstart) & 1) * (5 * 64) + (unsigned)lane;
-            constexpr int PW = 7 & ~CSI_PAIR_STORES;          // what the producer stores
-            double o11 = 0, o22 = 0, o12 = 0, ofirst = 0, osecond = 0;
-            if (PW & 1) { o11 = outr[so]; o22 = outr[so + 64]; o12 = outr[so + 128]; }
-            if (PW & 2) ofirst = outr[so + 192];
-            if (PW & 4) osecond = outr[so + 256];
             // FORCE: this row's forcing values are issued BEFORE the next row's prefetch -- the vector-memory counter is in order, so
             // the velocity phase, which consumes them, waits for them alone and not for the prefetched row behind them.  (Measured
             // at 2048^2, round 4: no change, 39.8 / 44.1 / 52.7 G on the OMIP-style / coupled / model.forcing configurations either
@@ -756,9 +640,8 @@ __device__ __forceinline__ void pair_body(const FusedTable* __restrict__ table, 
             // (FULL: the next row's loads are issued between the phases of the step below, with the plane prefetch)
             if constexpr (!FULL) {
                 advance();
-                load_row(R[(k + CSI_PAIR_PD) % 3]);           // row r + CSI_PAIR_PD (clamped to rend)
+                load_row(R[(k + 1) % 3]);                     // row r + 1 (clamped to rend)
             }
-            flush(r - 4, o11, o22, o12, ofirst, osecond, Idx<PW>{}, Idx<AUF ? 1 : 0>{});
             fm::StressConst ks; stress_consts(ks);
             fm::VelConst kv; vel_consts(kv);
             const double m_0 = C.h_0 * T->K[FK_RHO] * C.a_0;
@@ -770,7 +653,6 @@ __device__ __forceinline__ void pair_body(const FusedTable* __restrict__ table, 
                 mhist = (mhist << 2) | (wi ? 3u : (C.mk ? 0u : 1u));
             }
             if constexpr (FULL) {
-                static_assert(CSI_PAIR_PD == 1, "the per-point-metric producer prefetches one row ahead");
                 auto mid = [&]() __attribute__((always_inline)) { advance(); load_row(R[(k + 1) % 3]); };
                 A.template step<false>(T, ks, kv, r, C.u_p, C.v_p, C.P_0, m_0, C.a_0, C.s11, C.s22, C.s12, C.un_m, C.vn_x, true, r > rstart, pa1, pa2, mhist, FA,
                                        off2(r), c2s, off2(min(r + 1, rend)), off2(max(r - 1, row0)), mid);
@@ -822,27 +704,10 @@ __device__ __forceinline__ void pair_body(const FusedTable* __restrict__ table, 
             }
             A.shift(C.u_p, C.v_p, m_0, C.a_0);
             PROBE(pacc1);
-#ifndef CSI_EXP_HALFBARRIER
-#define CSI_EXP_HALFBARRIER 0      // timing experiment (RACY, wrong results): the two waves meet at every second row only
-#endif
-            if (!(CSI_EXP_HALFBARRIER && ((r - rstart) & 1)))
             __syncthreads();                              // row r is complete: the consumer may run its iteration r
             PROBE(pacc2);
         };
-        if constexpr (LDSC) {
-            // the window's first rows: rstart - 3 .. rstart + 1 (the consumer's first iteration reads down to rstart - 3, the producer's
-            // first up to rstart + 1); the same wave reads them back in order, the consumer behind the first row barrier
-#pragma unroll
-            for (int d = -3; d <= 1; ++d) {
-                const double v = ldg(coef_row_base(rstart + d), ck_lane);
-                if (lane < FC_COUNT) ringc[(unsigned)((rstart + d) & 7) * FC_COUNT + (unsigned)lane] = v;
-            }
-        }
         load_row(R[0]);                                   // row rstart
-        if (CSI_PAIR_PD == 2) {
-            advance();
-            load_row(R[1]);                               // row rstart + 1 (clamped)
-        }
         for (;;) {
             body(Idx<0>{});
             if (++r > rend) break;
@@ -851,13 +716,7 @@ __device__ __forceinline__ void pair_body(const FusedTable* __restrict__ table, 
             body(Idx<2>{});
             if (++r > rend) break;
         }
-        // drain: the consumer's last two rows (r = rend + 1: its iteration rend - 1 is complete; one more barrier for rend)
-        for (int d = 0; d < 2; ++d) {
-            const unsigned so = (unsigned)((r - rstart) & 1) * (5 * 64) + (unsigned)lane;
-            flush(r - 4, outr[so], outr[so + 64], outr[so + 128], outr[so + 192], outr[so + 256], Idx<(7 & ~CSI_PAIR_STORES)>{}, Idx<AUF ? 1 : 0>{});
-            if (d == 0) __syncthreads();
-            ++r;
-        }
+        __syncthreads();      // (the barrier count matches the consumer's: its last one, after row rend)
 #define PSTAGE A
         PROBE_END(w * 2);
 #undef PSTAGE
@@ -869,9 +728,11 @@ __device__ __forceinline__ void pair_body(const FusedTable* __restrict__ table, 
             // this tile is done with launch seq: its images are stored (release at system scope) and its halo reads are complete
             // (the producer's loads were consumed before its last barrier).  One lane per direction publishes seq in this tile's
             // slot of that neighbour's flag array.
-            // tier >= 2: a system-scope release fence (writes this XCD's L2 back: + 6 us per launch on a 1024 x 512 tile) on top of
-            // the write-through image stores and the drained store queue
-            if ((CSI_PEER_EXP & 1) && T->I[FI_PTIER] < 2) __builtin_amdgcn_s_waitcnt(0x0F70);
+            // The protocol: the images are write-through stores at system scope (sc0 sc1, put4) and the flags follow a drained store
+            // queue (vmcnt(0)).  Plain stores and a system-scope release fence before the flags instead: the fence writes the XCD's
+            // whole L2 back (buffer_wbl2), once per edge tile -- +6 us per launch on a 1024 x 512 tile, +20 us at 2048^2
+            // (profiles/r03_peer_protocol.md).  Tier >= 2: that fence on top of the write-through image stores and the drained queue.
+            if (T->I[FI_PTIER] < 2) __builtin_amdgcn_s_waitcnt(0x0F70);
             else { __builtin_amdgcn_fence(__ATOMIC_RELEASE, ""); asm volatile("s_waitcnt vmcnt(0)" ::: "memory"); }   // system scope: this wave's stores are in their -- possibly remote -- memory
             if ((lane < 8) && ((pdirs >> lane) & 1u)) {
                 const int nW = T->I[FI_PSET], nE = T->I[FI_PSET + 1], nN = T->I[FI_PSET + 3];
@@ -904,7 +765,7 @@ __device__ __forceinline__ void pair_body(const FusedTable* __restrict__ table, 
             const double vfirst = AUF ? ring[s1 + RF_U * 64] : ring[s0 + RF_V * 64];
             const double vsecond = AUF ? ring[s1 + RF_V * 64] : ring[s1 + RF_U * 64];
             const double dal = ring[s0 + RF_P * 64], dzf = ring[s0 + RF_M * 64], dzc = ring[s0 + RF_A * 64], ddl = ring[s0 + RF_VN * 64];
-            flush(r, v11, v22, v12, vfirst, vsecond, Idx<7>{}, Idx<AUF ? 0 : 1>{});
+            flush(r, v11, v22, v12, vfirst, vsecond, Idx<AUF ? 0 : 1>{});
             if (write_diag) {
                 if (((flags & L_RS) != 0) & (r >= rs_lo) & (r <= rs_hi)) {
                     const unsigned ocq = offc(r), ofq = offf(r);
@@ -923,8 +784,7 @@ __device__ __forceinline__ void pair_body(const FusedTable* __restrict__ table, 
 
     // ===== CONSUMER: stage B = sub-step s + 1, rows q = r - 2, one iteration behind the producer ====================
     PROBE_DECL;
-    Stage<UNI, !AUF, MASK, FORCE, CF, FULL, !(EXTRA == 1 && MASK)> B;
-    B.lc = ringc;
+    Stage<UNI, !AUF, MASK, FORCE, CF, FULL, Layout::HOLDK> B;
     B.u_m = 0; B.u_0 = 0; B.v_m = 0; B.v_0 = 0; B.Xv_m = 0; B.Xv_0 = 0;
     B.a_mm = 0; B.a_m = 0; B.m_mm = 0; B.m_m = 0;
     B.XP_m = 0; B.Xm_m = 0; B.Xa_m = 0; B.Xe11_m = 0; B.Xe22_m = 0; B.Ye12_0 = 0; B.e12_0 = 0;
@@ -954,19 +814,15 @@ __device__ __forceinline__ void pair_body(const FusedTable* __restrict__ table, 
     double fvd_tau = 0.0, fvd_we = 0.0, fvd_wb = 0.0, fvd_fd = 0.0;      // FRING, B u-first: the v-point forcing values of row q - 1 likewise
     int r = rstart;
     auto bodyB = [&](auto KK) __attribute__((always_inline)) {
-        if (!CSI_PAIR_HOIST || FORCE || (FULL && CSI_FULL_FENCE)) asm volatile("" : "+s"(T));
-        set_prio(decltype(KK)::value);
+        if (FORCE || FULL) asm volatile("" : "+s"(T));
+        set_prio();
         const int q = r - 2;
         PROBE_START;
-        if (!(CSI_EXP_HALFBARRIER && ((r - rstart) & 1)))
         __syncthreads();                                  // the producer has finished row r
         PROBE(pacc0);
-        // The consumer's first iterations of a tile (q < ja - 3: q = rstart - 2, rstart - 1 unless the tile starts at the low end of
-        // the first sub-step's range) read ring rows the producer has not written yet: pure pipeline lag, whose results the next two
-        // iterations -- which fill the window from rows ja - 2, ja - 1 -- overwrite completely (the first stress row is ja - 1, the
-        // first velocity row ja).  They are skipped (round 5): the wave only keeps the barrier count, and the SIMD's other wave has
-        // the vector ALU to itself meanwhile.  (Not with per-point metrics: their steps carry the plane prefetch of the next one.)
-        if constexpr (!FULL && CSI_PAIR_SKIPB) { if (q < ja - 3) return; }
+        // (The consumer's first iterations of a tile, q < ja - 3, read ring rows the producer has not written yet: pure pipeline lag, whose
+        // results the next two iterations overwrite completely.  Skipping them measured worse, 2048 x 256 43.0 G against 43.4, 1024 x 512
+        // 43.1 / 43.5: the test in every iteration costs more than two idle iterations save -- round 5, same-box A/B.)
         fresh_lane();
         // ---- stage A's results from the ring: u, v of row q + 1, sigma of row q; P, m, aice of row q, u^n of row q - 1, v^n
         const unsigned s1 = rslot(r - 1), s2 = rslot(r - 2), s3 = rslot(r - 3);
@@ -979,7 +835,7 @@ __device__ __forceinline__ void pair_body(const FusedTable* __restrict__ table, 
         vn_delay = vn_new;
         const unsigned bmk = MASK ? ringm[(unsigned)((r - 2 - rstart) & (RING_ROWS - 1)) * 64 + lane_it] : 0u;
         if constexpr (FULL) {
-            if (fhave) flush(fq, f11, f22, f12, ffirst, fsecond, Idx<(CSI_PAIR_STORES & 7)>{}, Idx<AUF ? 1 : 0>{});
+            if (fhave) flush(fq, f11, f22, f12, ffirst, fsecond, Idx<AUF ? 1 : 0>{});
         }
         PROBE(pacc1);
         fm::StressConst ks; stress_consts(ks);
@@ -1032,10 +888,8 @@ __device__ __forceinline__ void pair_body(const FusedTable* __restrict__ table, 
             // u points of row q-1, v points of row q (B v-first) / q-1 (B u-first); B's first rows of a tile only fill its
             // window: clamp their row to the array instead of running off it
             const int qm = max(q - 1, row0), qa = max(q, row0);
-#ifndef CSI_EXP_NOCONSLOADS      // (TIMING EXPERIMENT ONLY, wrong results: the consumer's forcing loads left out -- the upper bound of what forcing
-                                 //  values handed over through the ring could buy the per-point-metric instantiations)
+            // (without these loads -- what a forcing ring could buy the per-point-metric instantiations: profiles/r06_full_force_ring_experiment.txt)
             arrays(FB, offf(qm), AUF ? offc(qa) : offc(qm));
-#endif
         }
         const bool pb1 = WALLS && (!AUF ? (lane_wu | wall_row(q - 1)) : (lane_wv | wall_vrow(q)));
         const bool pb2 = WALLS && (!AUF ? (lane_wv | wall_vrow(q - 1)) : (lane_wu | wall_row(q - 1)));
@@ -1061,13 +915,7 @@ __device__ __forceinline__ void pair_body(const FusedTable* __restrict__ table, 
             fq = q; f11 = B.S11_0; f22 = B.S22_0; f12 = B.S12_0; ffirst = B.first; fsecond = B.second; fhave = true;
         } else {
         B.template step<PRE>(T, ks, kv, q, bu_p, bv_p, bP_0, bm_0, ba_0, s11, s22, s12, bun, bvn, q >= ja - 1, q >= ja, pb1, pb2, mhistB, FB);
-        flush(q, B.S11_0, B.S22_0, B.S12_0, B.first, B.second, Idx<(CSI_PAIR_STORES & 7)>{}, Idx<AUF ? 1 : 0>{});
-        }
-        if ((CSI_PAIR_STORES & 7) != 7) {
-            const unsigned so = (unsigned)((r - rstart) & 1) * (5 * 64) + (unsigned)lane;
-            if (!(CSI_PAIR_STORES & 1)) { outr[so] = B.S11_0; outr[so + 64] = B.S22_0; outr[so + 128] = B.S12_0; }
-            if (!(CSI_PAIR_STORES & 2)) outr[so + 192] = B.first;
-            if (!(CSI_PAIR_STORES & 4)) outr[so + 256] = B.second;
+        flush(q, B.S11_0, B.S22_0, B.S12_0, B.first, B.second, Idx<AUF ? 1 : 0>{});
         }
         // diagnostics: last launch of the sub-cycle only, stored at once (with their halo images on periodic sides,
         // where the reference computes them from halo data: same values)
@@ -1093,9 +941,9 @@ __device__ __forceinline__ void pair_body(const FusedTable* __restrict__ table, 
         if (++r > rend) break;
     }
     if constexpr (FULL) {
-        if (fhave) flush(fq, f11, f22, f12, ffirst, fsecond, Idx<(CSI_PAIR_STORES & 7)>{}, Idx<AUF ? 1 : 0>{});
+        if (fhave) flush(fq, f11, f22, f12, ffirst, fsecond, Idx<AUF ? 1 : 0>{});
     }
-    __syncthreads();                                      // the last row's results are in the out ring: the producer drains them
+    __syncthreads();                                      // (the producer's last barrier)
     publish();
 #define PSTAGE B
     PROBE_END(w * 2 + 1);
@@ -1104,24 +952,13 @@ __device__ __forceinline__ void pair_body(const FusedTable* __restrict__ table, 
 }
 
 template <bool UNI, bool AUF, bool WALLS, bool MASK, bool FORCE, bool FD, int CF, bool FULL = false, bool PEER = false, int EXTRA = 0, bool DLD = false>
-__global__ void __launch_bounds__(128, (FULL || (FORCE && (EXTRA != 1 || !MASK) && CSI_PAIR_FRING)) ? CSI_PAIR_FULL_WAVES
-                                       : (UNI && !(EXTRA == 1 && MASK)) ? CSI_PAIR_UNI_WAVES : CSI_PAIR_WAVES) k_pair(const FusedTable* __restrict__ table, int nstrips, int nchunks, int rows,
-                                                              int blocks_per_xcd, int write_diag, unsigned long long seq) {
-    constexpr bool FRING = FORCE && !FULL && (EXTRA != 1 || !MASK) && CSI_PAIR_FRING;
-    constexpr bool PRE = CSI_PAIR_PRE && !MASK && !FULL && !FRING && !(CSI_PAIR_LDSC_NOPRE && !UNI && !(EXTRA == 1 && MASK) && (CSI_PAIR_LDSC != 0));
-    constexpr int RING_FIELDS = FRING ? 10 + RF_FORCING : (PRE ? 13 : 10);      // (FULL: ten fields; its plane values have a ring of their own, ringp)
-    __shared__ double ring[RING_ROWS * RING_FIELDS * 64];
+__global__ void __launch_bounds__(128, (PairLayout<UNI, MASK, FORCE, FULL, EXTRA>::WAVES))
+k_pair(const FusedTable* __restrict__ table, int nstrips, int nchunks, int rows, int blocks_per_xcd, int write_diag, unsigned long long seq) {
+    using Layout = PairLayout<UNI, MASK, FORCE, FULL, EXTRA>;
+    __shared__ double ring[RING_ROWS * Layout::RING_FIELDS * 64];
     __shared__ double ringp[FULL ? RP_ROWS * RP_FIELDS * 64 : 1];      // FULL: the plane values of three rows
     __shared__ unsigned ringm[MASK ? RING_ROWS * 64 : 1];
-    __shared__ double outr[(CSI_PAIR_STORES & 7) != 7 ? 2 * 5 * 64 : 1];      // stage B's results on their way to the producer's stores
     __shared__ unsigned peer_abort_w;                      // PEER: the producer's wait has given up
-#ifdef CSI_EXP_LDSPAD      // TIMING EXPERIMENT ONLY: so many more bytes of LDS per workgroup of the per-point-metric + array-forcing instantiations -- what a
-                           // forcing ring there would cost in occupancy (12 KB more: three workgroups per CU instead of four; profiles/r06_full_force_ring_experiment.txt)
-    __shared__ double lds_pad[(FULL && FORCE) ? CSI_EXP_LDSPAD / 8 : 1];
-    if (FULL && FORCE) { lds_pad[threadIdx.x] = 0.0; asm volatile("" :: "v"(lds_pad[threadIdx.x])); }
-#endif
-    constexpr bool LDSC = !UNI && !FULL && !(EXTRA == 1 && MASK) && (CSI_PAIR_LDSC != 0);
-    __shared__ double ringc[LDSC ? 8 * FC_COUNT : 1];      // per-row coefficients: an eight-row window (Stage::pc)
     // This workgroup's tile.  XCD-aware: blocks are dealt round-robin over the XCDs, each XCD walks one band of consecutive tiles.
     const int b = (int)blockIdx.x;
     int w = (b & 7) * blocks_per_xcd + (b >> 3);
@@ -1146,11 +983,11 @@ __global__ void __launch_bounds__(128, (FULL || (FORCE && (EXTRA != 1 || !MASK) 
         const unsigned pd = ((pw ? 1u : 0u) | (pe ? 2u : 0u) | (ps ? 4u : 0u) | (pn ? 8u : 0u) | ((ps & pw) ? 16u : 0u) | ((ps & pe) ? 32u : 0u) |
                              ((pn & pw) ? 64u : 0u) | ((pn & pe) ? 128u : 0u)) & (unsigned)T->I[FI_PMASK];
         if (__builtin_amdgcn_readfirstlane((int)pd) == 0) {
-            pair_body<UNI, AUF, WALLS, MASK, FORCE, FD, CF, FULL, false, EXTRA, false>(table, w, nstrips, nchunks, rows, blocks_per_xcd, write_diag, seq, ring, ringm, outr, &peer_abort_w, ringp, ringc);
+            pair_body<UNI, AUF, WALLS, MASK, FORCE, FD, CF, FULL, false, EXTRA, false>(table, w, nstrips, nchunks, rows, blocks_per_xcd, write_diag, seq, ring, ringm, &peer_abort_w, ringp);
             return;
         }
     }
-    pair_body<UNI, AUF, WALLS, MASK, FORCE, FD, CF, FULL, PEER, EXTRA, DLD>(table, w, nstrips, nchunks, rows, blocks_per_xcd, write_diag, seq, ring, ringm, outr, &peer_abort_w, ringp, ringc);
+    pair_body<UNI, AUF, WALLS, MASK, FORCE, FD, CF, FULL, PEER, EXTRA, DLD>(table, w, nstrips, nchunks, rows, blocks_per_xcd, write_diag, seq, ring, ringm, &peer_abort_w, ringp);
 }
 
 }  // namespace fused

@@ -54,31 +54,15 @@ __device__ __forceinline__ double pcoef(tptr_t T, int which, int j) {
 // dimension and all Face-in-x fields another (dense Oceananigans parents; checked on the host), so two running
 // offsets (oc, of) address every field.
 typedef __attribute__((address_space(1))) char* gptr_t;     // global address space: global_load / global_store, not flat
-// Cache policy of the streaming loads -- an experiment knob, plain loads are the default.  Non-temporal loads
-// (`global_load ... nt`) gain 3-5 % at exactly 2048^2 (62.4 -> 65.4 G on one box) and LOSE everywhere else measured:
-// 1024 x 512 -4.7 %, 1024^2 -6 %, 1536^2 -5 %, 3072^2 -7 %, 4096^2 -13 % (the ring lanes a strip shares with its neighbour
-// are evicted before the neighbour reads them); non-temporal stores lose 5.5 %, agent- / system-scope loads change
-// nothing (profiles/r02d_experiments.md).  ldg_keep: loads that are re-read soon whatever the policy (the per-point
-// coefficient planes: stage B reads what stage A read three rows earlier).
-#ifndef CSI_NT_LOAD
-#define CSI_NT_LOAD 0           // 0 plain, 1 non-temporal, 2 / 3: agent- / system-scope relaxed atomic loads (sc1 / sc0 sc1; experiments)
-#endif
-#ifndef CSI_NT_STORE
-#define CSI_NT_STORE 0
-#endif
+// Cache policy of the streaming loads: plain.  Non-temporal loads (`global_load ... nt`) gain 3-5 % at exactly 2048^2 and lose
+// 5-13 % at every other size measured (the ring lanes a strip shares with its neighbour are evicted before the neighbour reads
+// them); non-temporal stores lose 5.5 %, agent- / system-scope loads change nothing (profiles/r02d_experiments.md).
+// ldg_keep: the loads that are re-read soon (the per-point coefficient planes: stage B reads what stage A read three rows earlier).
 __device__ __forceinline__ double ldg_keep(unsigned long base, unsigned off) {
     return *(const __attribute__((address_space(1))) double*)((gptr_t)base + off);
 }
 __device__ __forceinline__ double ldg(unsigned long base, unsigned off) {
-#if CSI_NT_LOAD == 1
-    return __builtin_nontemporal_load((const __attribute__((address_space(1))) double*)((gptr_t)base + off));
-#elif CSI_NT_LOAD == 2
-    return __builtin_bit_cast(double, __scoped_atomic_load_n((const __attribute__((address_space(1))) long*)((gptr_t)base + off), __ATOMIC_RELAXED, __MEMORY_SCOPE_DEVICE));
-#elif CSI_NT_LOAD == 3
-    return __builtin_bit_cast(double, __scoped_atomic_load_n((const __attribute__((address_space(1))) long*)((gptr_t)base + off), __ATOMIC_RELAXED, __MEMORY_SCOPE_SYSTEM));
-#else
-    return ldg_keep(base, off);
-#endif
+    return *(const __attribute__((address_space(1))) double*)((gptr_t)base + off);
 }
 // write-through at agent scope (sc1): the line leaves the XCD's L2 when the store completes, not at the end of the launch
 __device__ __forceinline__ void stg_agent(unsigned long base, unsigned off, double v) {
@@ -88,15 +72,7 @@ __device__ __forceinline__ unsigned ldub(unsigned long base, unsigned off) {
     return *(const __attribute__((address_space(1))) unsigned char*)((gptr_t)base + off);
 }
 __device__ __forceinline__ void stg(unsigned long base, unsigned off, double v) {
-#if CSI_NT_STORE == 1
-    __builtin_nontemporal_store(v, (__attribute__((address_space(1))) double*)((gptr_t)base + off));
-#elif CSI_NT_STORE == 2      // write-through at agent scope (sc1): the line leaves the XCD's L2 during the launch, not at its end
-    __scoped_atomic_store_n((__attribute__((address_space(1))) long*)((gptr_t)base + off), __builtin_bit_cast(long, v), __ATOMIC_RELAXED, __MEMORY_SCOPE_DEVICE);
-#elif CSI_NT_STORE == 3      // ... at system scope (sc0 sc1)
-    __scoped_atomic_store_n((__attribute__((address_space(1))) long*)((gptr_t)base + off), __builtin_bit_cast(long, v), __ATOMIC_RELAXED, __MEMORY_SCOPE_SYSTEM);
-#else
     *(__attribute__((address_space(1))) double*)((gptr_t)base + off) = v;
-#endif
 }
 
 // CSI_METRIC_FULL: stencil coefficient `which` (C2_*, csi_fast_coef.h) of this lane's column at the row whose byte offset in

@@ -22,7 +22,7 @@ struct Forcing {
     int extra;           // bit 0: xc present, bit 1: xd present (0 in every other instantiation: the terms vanish at compile time)
 };
 
-struct RowIn { double u_p, v_p, P_0, h_0, a_0, s11, s22, s12, un_m, vn_x; unsigned mk; double ck; };      // ck: lane k's entry of a per-row coefficient row (Stage::LDSC)
+struct RowIn { double u_p, v_p, P_0, h_0, a_0, s11, s22, s12, un_m, vn_x; unsigned mk; };
 
 // One sub-step as a row pipeline.  step(r) consumes row r of P, m, a, sigma, rows r+1 of u, v and produces
 // sigma(r) and  UFIRST: u(r-1) ["first"], v(r-1) ["second"]   /   v first: v(r) ["first"], u(r-1) ["second"].
@@ -76,10 +76,6 @@ struct Stage {
     double DXV_0, RDXV_0, RDYV_0, RDXU_0, DXF2_0, DYF2_0, RAZF_0;
     double DXV_m, RDXV_m, RDYV_m, RDXU_m, DXF2_m, DYF2_m, DYU_m, RDYU_m, DYC2_m, DXC2_m, DXC2_mm;
     double DXV_p, RDXV_p, RDYV_p, RDXU_p, DXF2_p, DYF2_p, RAZF_p, DYU_0, RDYU_0, DYC2_0, DXC2_0;      // pending (shift)
-#ifndef CSI_FULL_HOISTP
-#define CSI_FULL_HOISTP 1
-#endif
-#if CSI_FULL_HOISTP >= 1
     // FULL: the twelve plane base addresses, read from the table ONCE (the row loop's reload fence on the table pointer does not reach
     // them): two wide scalar loads and their waits per stage-row less
     unsigned long c2p[12];
@@ -92,11 +88,6 @@ struct Stage {
         for (int k = 0; k < 12; ++k) c2p[k] = T->P[FP_C2_0 + k + rcd];
     }
     __device__ __forceinline__ double c2m(tptr_t, int which, unsigned off) const { return ldg_keep(c2p[which], off); }
-#else
-    int rcd_ = 0;
-    __device__ __forceinline__ void hoist_planes(tptr_t, int rcd = 0) { rcd_ = rcd; }
-    __device__ __forceinline__ double c2m(tptr_t T, int which, unsigned off) const { return c2at(T, which + rcd_, off); }
-#endif
     __device__ __forceinline__ unsigned long f2u(tptr_t T) const { return T->P[FP_F2U + rcd_]; }
     __device__ __forceinline__ unsigned long f2v(tptr_t T) const { return T->P[FP_F2V + rcd_]; }
     double RAZC_0, RAZU_m, RAZV_x, FU_m, FV_x;       // this step's 1 / Az at the cell (row r), the u point (row r - 1), the v point (row r - 1 / r); f likewise
@@ -106,10 +97,7 @@ struct Stage {
     // re-read them from the table in every row -- three scalar loads per stage-row, each waited for on the spot (24-42 ns,
     // profiles/r01_microbenchmarks.md) by a wave that shares its SIMD with ONE other since the tile-count rule.  The opaque
     // asm pins the VGPR copy (a value the compiler cannot rematerialise from the table).
-#ifndef CSI_PAIR_VK
-#define CSI_PAIR_VK 1
-#endif
-    static constexpr bool VKC = UNI && !FULL && HOLDK && (CSI_PAIR_VK != 0);       // (k_pair's register budget of these instantiations: CSI_PAIR_UNI_WAVES)
+    static constexpr bool VKC = UNI && !FULL && HOLDK;       // (k_pair's register budget of these instantiations: PairLayout::WAVES)
     double VK_E, VK_FN, VK_FS, VK_FU, VK_Q2N, VK_K, VK_FV, VK_BRHO;
     __device__ __forceinline__ void hoist_uniform(tptr_t T) {
         if constexpr (VKC) {
@@ -118,20 +106,11 @@ struct Stage {
             asm volatile("" : "+v"(VK_E), "+v"(VK_FN), "+v"(VK_FS), "+v"(VK_FU), "+v"(VK_Q2N), "+v"(VK_K), "+v"(VK_FV), "+v"(VK_BRHO));
         }
     }
-    // Per-row coefficients from an eight-row window in LDS (`lc`, filled by the producer wave one row ahead of its first use:
-    // evp_fused2.hip) instead of the table's scalar loads -- built in round 5 and LEFT OFF (CSI_PAIR_LDSC=1 enables it).  The scalar
-    // loads come in five or six bursts per stage-row, each waited for on the spot (no scalar register is left to hold a row's twenty
-    // values), and lat-lon tiles run 10-14 % behind uniform ones of the same shape where the arithmetic explains 4 %; but the
-    // broadcast `ds_read`s that replace them wait too (and share lgkmcnt with the ring traffic), and the window's 1.3 KB end the
-    // six-workgroups-per-CU fit of the 13-field ring: tiles +0-3 %, 2048^2 -3 %, 4096^2 -7 % (profiles/r05_row_coef_lds.txt).
-#ifndef CSI_PAIR_LDSC
-#define CSI_PAIR_LDSC 0
-#endif
-    static constexpr bool LDSC = !UNI && !FULL && HOLDK && (CSI_PAIR_LDSC != 0);
-    const double* lc = nullptr;
-    __device__ __forceinline__ double pc(tptr_t T, int which, int j) const {
-        if constexpr (LDSC) return lc[(unsigned)(j & 7) * FC_COUNT + which]; else return pcoef<UNI>(T, which, j);
-    }
+    // Per-row coefficients: the table's scalar loads (five or six bursts per stage-row, each waited for on the spot: lat-lon tiles run
+    // 10-14 % behind uniform ones of the same shape).  An eight-row window in LDS filled by the producer measured no better -- its
+    // broadcast reads wait too, and its 1.3 KB end the six-workgroups-per-CU fit: tiles +0-3 %, 2048^2 -3 %, 4096^2 -7 %
+    // (profiles/r05_row_coef_lds.txt).
+    __device__ __forceinline__ double pc(tptr_t T, int which, int j) const { return pcoef<UNI>(T, which, j); }
     __device__ __forceinline__ double vk(tptr_t T, int which, int j, double held) const { if constexpr (VKC) return held; else return pc(T, which, j); }
     __device__ __forceinline__ double brho(tptr_t T) const { if constexpr (VKC) return VK_BRHO; else return T->K[FK_BOT_RHOCD]; }
 

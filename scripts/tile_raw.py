@@ -1,5 +1,5 @@
 """Raw launch time of the sub-cycle on one tile shape, no result checks (for TIMING EXPERIMENTS with builds that compute wrong
-results, e.g. -DCSI_EXP_RINGCUT): python scripts/tile_raw.py NX NY [peer_y [tier]]   (CSI_HIP_LIBRARY selects the build)"""
+results, such as the seam-row experiment of profiles/r05_tile.md): python scripts/tile_raw.py NX NY [peer_y [tier]]   (CSI_HIP_LIBRARY selects the build)"""
 import os, sys, time
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT); sys.path.insert(0, os.path.join(ROOT, "tests"))
