@@ -36,11 +36,18 @@ THERMO_LINEAR_FIELD_IDS = ["FLUX_COEFFICIENT", "FLUX_REFERENCE_TEMPERATURE", "BO
                            "BOTTOM_HEAT_FLUX_USED"]
 F_THERMO_LINEAR = {n: F_COUNT_BINDABLE + k for k, n in enumerate(THERMO_LINEAR_FIELD_IDS)}
 F_COUNT_THERMO = F_COUNT_BINDABLE + len(F_THERMO_LINEAR)
+# csi_mixed_layer_field_id: the slab-ocean mixed layer's temperature, its Psi^- copy, its four inputs and the open-water flux it used,
+# numbered from CSI_F_COUNT_THERMO on
+MIXED_LAYER_FIELD_IDS = ["ML_TEMPERATURE", "ML_TEMPERATURE_M", "ML_SURFACE_HEAT_FLUX", "ML_COEFFICIENT", "ML_REFERENCE_TEMPERATURE",
+                         "ML_DEEP_HEAT_FLUX", "ML_SURFACE_FLUX_USED"]
+F_MIXED_LAYER = {n: F_COUNT_THERMO + k for k, n in enumerate(MIXED_LAYER_FIELD_IDS)}
+F_COUNT_MIXED_LAYER = F_COUNT_THERMO + len(F_MIXED_LAYER)
 
 
 def slot_id(name):
-    """The number of a csi_field_bind slot by name: F, or one of the derived fields', momentum term fields' or thermodynamic slots."""
-    for table in (F, F_DERIVED, F_MOMENTUM_TERMS):
+    """The number of a csi_field_bind slot by name: F, or one of the derived fields', momentum term fields', thermodynamic or
+    mixed-layer slots."""
+    for table in (F, F_DERIVED, F_MOMENTUM_TERMS, F_MIXED_LAYER):
         if name in table:
             return table[name]
     return F_THERMO_LINEAR[name]
@@ -68,6 +75,9 @@ SERIES_SLOTS = ["TOP_U", "TOP_V", "BOT_U", "BOT_V", "FORCING_U", "FORCING_V", "F
                 "TOP_HEAT_FLUX", "BOTTOM_HEAT_FLUX", "SNOWFALL"]
 # ... and the three thermodynamic inputs that joined them (slot_id names them): fourteen in all
 THERMO_SERIES_SLOTS = ["FLUX_COEFFICIENT", "FLUX_REFERENCE_TEMPERATURE", "BOTTOM_SALINITY"]
+# ... and the mixed layer's four inputs: eighteen
+MIXED_LAYER_SERIES_SLOTS = ["ML_SURFACE_HEAT_FLUX", "ML_COEFFICIENT", "ML_REFERENCE_TEMPERATURE", "ML_DEEP_HEAT_FLUX"]
+ML_SURFACE_ARRAY, ML_BULK_ARRAYS, ML_DEEP_ARRAY, ML_HAS_SURFACE, ML_HAS_BULK = 1, 2, 4, 8, 16      # csi_mixed_layer_params.flags
 
 # every symbol include/csi.h declares (checked by tests/test_abi.py against the header text)
 SYMBOLS = ["csi_version", "csi_context_create", "csi_context_destroy", "csi_last_error", "csi_sync", "csi_set_mode",
@@ -86,7 +96,8 @@ SYMBOLS = ["csi_version", "csi_context_create", "csi_context_destroy", "csi_last
            "csi_output_plan_layout", "csi_output_create", "csi_output_layout", "csi_output_record_bytes", "csi_output_accumulate",
            "csi_output_snapshot", "csi_output_test", "csi_output_wait", "csi_output_release", "csi_output_destroy",
            "csi_derived_compute", "csi_budget_compute", "csi_derived_stats",
-           "csi_momentum_terms_compute", "csi_momentum_budget_compute", "csi_momentum_terms_stats"]
+           "csi_momentum_terms_compute", "csi_momentum_budget_compute", "csi_momentum_terms_stats",
+           "csi_mixed_layer_set", "csi_mixed_layer_step", "csi_mixed_layer_stats"]
 DIAG_VELOCITY, DIAG_TRACERS, DIAG_ALL = 1, 2, 3
 OUT_F64, OUT_F32 = 0, 1
 DERIVED_ALL = 127
@@ -142,6 +153,13 @@ class HeatFluxTerm(C.Structure):
 class SurfaceSolve(C.Structure):
     _fields_ = [("tol", C.c_double), ("maxiters", C.c_int32), ("prescribed_array", C.c_int32), ("snowfall_array", C.c_int32),
                 ("reserved", C.c_int32)]
+
+
+class MixedLayerParams(C.Structure):
+    """csi_mixed_layer_params (include/csi.h): the slab-ocean mixed layer."""
+    _fields_ = [("density", C.c_double), ("heat_capacity", C.c_double), ("depth", C.c_double), ("exchange_velocity", C.c_double),
+                ("surface_heat_flux", C.c_double), ("coefficient", C.c_double), ("reference_temperature", C.c_double),
+                ("deep_heat_flux", C.c_double), ("flags", C.c_int32), ("reserved", C.c_int32)]
 
 
 class TimeSeries(C.Structure):
@@ -263,6 +281,8 @@ def load():
         "csi_derived_stats": [vp, C.POINTER(i64), C.POINTER(i64)],
         "csi_momentum_terms_compute": [vp, i32], "csi_momentum_budget_compute": [vp, i32, C.POINTER(MomentumBudget)],
         "csi_momentum_terms_stats": [vp, C.POINTER(i64), C.POINTER(i64)],
+        "csi_mixed_layer_set": [vp, C.POINTER(MixedLayerParams)], "csi_mixed_layer_step": [vp, dbl, i32],
+        "csi_mixed_layer_stats": [vp, C.POINTER(i64)],
     }
     for name, args in sig.items():
         fn = getattr(L, name, None)
@@ -512,6 +532,17 @@ class Context:
         a, b = C.c_int64(), C.c_int64()
         self.call("csi_momentum_terms_stats", C.byref(a), C.byref(b))
         return a.value, b.value
+
+    # ---- the slab-ocean mixed layer (include/csi.h, csi_mixed_layer_set) -----------------------------------------------------------
+    def mixed_layer_step(self, dt, from_cache=False):
+        """csi_mixed_layer_step: one launch that writes To' and the bottom heat-flux array (nothing is waited for)."""
+        self.call("csi_mixed_layer_step", float(dt), int(bool(from_cache)))
+
+    def mixed_layer_stats(self):
+        """Launches of the mixed-layer kernel made on this context so far."""
+        n = C.c_int64()
+        self.call("csi_mixed_layer_stats", C.byref(n))
+        return n.value
 
     # ---- device-side output (include/csi.h, csi_output_*) -------------------------------------------------------------------------
     def output_create(self, fields, slots):

@@ -84,7 +84,6 @@ static int32_t do_layered(csi_context* c, const SlabDev& S, const SnowDev& W, do
     return CSI_OK;
 }
 // thermodynamic_time_step!(model, ice_thermodynamics, snow_thermodynamics, dt): dispatch on the snow layer
-static int32_t do_thermo(csi_context* c, double dt);
 static int32_t do_slab(csi_context* c, const SlabDev& S, double dt) {
     const bool has_mf = c->f[CSI_F_MASS_FLUX].p != nullptr;
     if (S.top_bc_kind == 1 && S.top_flux_kind != 0)
@@ -101,8 +100,65 @@ static int32_t do_slab(csi_context* c, const SlabDev& S, double dt) {
     HIP_TRY(c, hipGetLastError());
     return CSI_OK;
 }
-static int32_t do_thermo(csi_context* c, double dt) {
+// The slab-ocean mixed layer (include/csi.h csi_mixed_layer_set): one launch of k_mixed_layer, which writes To' and the bottom
+// heat-flux array the ice step reads next.
+static int32_t do_mixed_layer(csi_context* c, double dt, int from_cache) {
+    if (!c->ml_set) return fail(c, CSI_ERR_NOT_BOUND, "csi_mixed_layer_set has not been called");
+    if (!c->slab_set)
+        return fail(c, CSI_ERR_NOT_BOUND, "the mixed layer needs csi_slab_params_set (the liquidus and the bottom salinity of the ice thermodynamics)");
+    const FluxTermsDev& bot = c->heat.bot;
+    if (bot.n != 1 || bot.kind[0] != FLUX_ARRAY)
+        return fail(c, CSI_ERR_INVALID_ARGUMENT, "the mixed layer needs exactly one ARRAY bottom heat-flux term (csi_heat_fluxes_set): it writes Qb "
+                                                 "into the array bound to bottom_heat_flux");
+    for (const TimeSeries& S : c->series)
+        if (S.fid == CSI_F_BOTTOM_HEAT_FLUX)
+            return fail(c, CSI_ERR_INVALID_ARGUMENT, "time series on bottom_heat_flux: the mixed layer (csi_mixed_layer_set) writes that array at every step");
+    if (!(dt > 0) || !std::isfinite(dt)) return fail(c, CSI_ERR_INVALID_ARGUMENT, "the mixed layer needs a finite dt > 0");
+    const csi_mixed_layer_params& p = c->ml;
+    int32_t rc = need(c, {CSI_F_ML_TEMPERATURE, CSI_F_A, CSI_F_BOTTOM_HEAT_FLUX});
+    if (rc) return rc;
+    if (from_cache && (rc = need(c, {CSI_F_ML_TEMPERATURE_M}))) return rc;
+    MixedLayerFields F{};
+    F.to_out = ref_of(c, CSI_F_ML_TEMPERATURE);
+    F.to_in = from_cache ? ref_of(c, CSI_F_ML_TEMPERATURE_M) : F.to_out;
+    F.a = ref_of(c, CSI_F_A);
+    F.qb = ref_of(c, CSI_F_BOTTOM_HEAT_FLUX);
+    if (p.flags & CSI_ML_SURFACE_ARRAY) {
+        if ((rc = need(c, {CSI_F_ML_SURFACE_HEAT_FLUX}))) return rc;
+        F.fo = ref_of(c, CSI_F_ML_SURFACE_HEAT_FLUX);
+    }
+    if (p.flags & CSI_ML_BULK_ARRAYS) {
+        if ((rc = need(c, {CSI_F_ML_COEFFICIENT, CSI_F_ML_REFERENCE_TEMPERATURE}))) return rc;
+        F.k = ref_of(c, CSI_F_ML_COEFFICIENT); F.ta = ref_of(c, CSI_F_ML_REFERENCE_TEMPERATURE);
+    }
+    if (p.flags & CSI_ML_DEEP_ARRAY) {
+        if ((rc = need(c, {CSI_F_ML_DEEP_HEAT_FLUX}))) return rc;
+        F.qd = ref_of(c, CSI_F_ML_DEEP_HEAT_FLUX);
+    }
+    if (c->heat.bottom_salinity_array) {
+        if ((rc = need(c, {CSI_F_BOTTOM_SALINITY}))) return rc;
+        F.sb = ref_of(c, CSI_F_BOTTOM_SALINITY);
+    }
+    F.qow = ref_of(c, CSI_F_ML_SURFACE_FLUX_USED);      // (unbound: p == nullptr)
+    MixedLayerDev M{};
+    M.rc = p.density * p.heat_capacity;
+    M.C = M.rc * p.depth;
+    M.grc = p.exchange_velocity * M.rc;
+    M.Fo = p.surface_heat_flux; M.K = p.coefficient; M.Ta = p.reference_temperature; M.Qd = p.deep_heat_flux;
+    M.liq_T0 = c->slab.liq_T0; M.liq_slope = c->slab.liq_slope; M.S = c->slab.S;
+    M.dt = dt;
+    M.has_surface = (p.flags & (CSI_ML_HAS_SURFACE | CSI_ML_SURFACE_ARRAY)) != 0;
+    M.has_bulk = (p.flags & (CSI_ML_HAS_BULK | CSI_ML_BULK_ARRAYS)) != 0;
+    M.nx = c->Nx; M.ny = c->Ny;
+    launch_mixed_layer(M, F, c->stream);
+    ++c->ml_launches;
+    HIP_TRY(c, hipGetLastError());
+    return CSI_OK;
+}
+static int32_t do_thermo(csi_context* c, double dt, int from_cache = 0) {
     if (!c->slab_set) return CSI_OK;                       // thermodynamic_time_step!(model, ::Nothing, ...) = nothing
+    int32_t rc;
+    if (c->ml_set && (rc = do_mixed_layer(c, dt, from_cache))) return rc;      // the ocean under the ice first: it writes the bottom flux
     return c->snow_set ? do_layered(c, c->slab, c->snow, dt) : do_slab(c, c->slab, dt);
 }
 
@@ -389,7 +445,7 @@ int32_t csi_mask_set(csi_context* c, const uint8_t* dev_mask, int64_t ld) {
 int32_t csi_field_bind(csi_context* c, int32_t fid, void* dev_ptr, int64_t ld, int32_t ni, int32_t nj) {
     if (!c) return CSI_ERR_INVALID_ARGUMENT;
     if (!c->grid_set) return fail(c, CSI_ERR_NOT_BOUND, "csi_grid_set has not been called");
-    if (fid < 0 || fid >= CSI_F_COUNT_THERMO) return fail(c, CSI_ERR_INVALID_ARGUMENT, "unknown field id");
+    if (fid < 0 || fid >= CSI_F_COUNT_MIXED_LAYER) return fail(c, CSI_ERR_INVALID_ARGUMENT, "unknown field id");
     if (!dev_ptr) { c->f[fid] = Bound{}; return CSI_OK; }
     const int eni = c->Nx + 2 * c->Hx + extra_x(c, fid), enj = c->Ny + 2 * c->Hy + extra_y(c, fid);
     if (ni != eni || nj != enj || ld < ni) {
@@ -557,6 +613,8 @@ int32_t csi_cache_current_fields(csi_context* c) {
         if ((rc = add(CSI_F_UM, CSI_F_U))) return rc;
         if ((rc = add(CSI_F_VM, CSI_F_V))) return rc;
     }
+    // (the mixed-layer temperature is a prognostic field of the step like h and aice: the sixth and last entry of the batch)
+    if (c->f[CSI_F_ML_TEMPERATURE].p && c->f[CSI_F_ML_TEMPERATURE_M].p && (rc = add(CSI_F_ML_TEMPERATURE_M, CSI_F_ML_TEMPERATURE))) return rc;
     launch_copy_batch(B, c->stream);
     HIP_TRY(c, hipGetLastError());
     return CSI_OK;
@@ -649,6 +707,7 @@ int32_t csi_time_step_rk3(csi_context* c, double dt, int32_t substeps, int32_t s
     int32_t rc = dynamics ? need_momentum(c) : need(c, {CSI_F_H, CSI_F_A});
     if (rc) return rc;
     if ((rc = dynamics ? need(c, {CSI_F_HM, CSI_F_AM, CSI_F_UM, CSI_F_VM}) : need(c, {CSI_F_HM, CSI_F_AM}))) return rc;
+    if (c->ml_set && c->slab_set && (rc = need(c, {CSI_F_ML_TEMPERATURE, CSI_F_ML_TEMPERATURE_M}))) return rc;
     if (advect_stage_supported(c, scheme)) {
         const bool third = scheme == CSI_ADVECT_WENO3 || scheme == CSI_ADVECT_UPWIND3;
         const int need_h = scheme == CSI_ADVECT_WENO7 ? 4 : (scheme == CSI_ADVECT_UPWIND1 ? 1 : (third ? 2 : 3));
@@ -664,7 +723,7 @@ int32_t csi_time_step_rk3(csi_context* c, double dt, int32_t substeps, int32_t s
         if (dynamics && (rc = do_momentum(c, dtau, substeps, 1))) return rc;             // :87
         const bool fused_fill = !c->g.has_mask && !c->slab_set;
         if ((rc = do_tracer_step(c, dtau, 1, fused_fill))) return rc;     // :89
-        if ((rc = do_thermo(c, dtau))) return rc;                         // :91 thermodynamic_time_step!
+        if ((rc = do_thermo(c, dtau, 1))) return rc;                      // :91 thermodynamic_time_step! (the mixed layer: from Psi^-)
         if ((rc = do_update_state(c, true, fused_fill))) return rc;
     }
     return finish_step(c, CSI_OK);
@@ -693,6 +752,39 @@ int32_t csi_slab_params_set(csi_context* c, const csi_slab_params* p) {
     if (!c) return CSI_ERR_INVALID_ARGUMENT;
     c->slab_set = p != nullptr;
     if (p) c->slab = slab_dev(p);
+    return CSI_OK;
+}
+
+int32_t csi_mixed_layer_set(csi_context* c, const csi_mixed_layer_params* p) {
+    if (!c) return CSI_ERR_INVALID_ARGUMENT;
+    if (!p) { c->ml_set = false; return CSI_OK; }
+    const double values[8] = {p->density, p->heat_capacity, p->depth, p->exchange_velocity, p->surface_heat_flux, p->coefficient,
+                              p->reference_temperature, p->deep_heat_flux};
+    const char* const names[8] = {"density", "heat_capacity", "depth", "exchange_velocity", "surface_heat_flux", "coefficient",
+                                  "reference_temperature", "deep_heat_flux"};
+    for (int k = 0; k < 8; ++k)
+        if (!std::isfinite(values[k])) return fail(c, CSI_ERR_INVALID_ARGUMENT, std::string("csi_mixed_layer_params.") + names[k] + " is not finite");
+    for (int k = 0; k < 3; ++k)
+        if (!(values[k] > 0)) return fail(c, CSI_ERR_INVALID_ARGUMENT, std::string("csi_mixed_layer_params.") + names[k] + " must be > 0");
+    if (p->exchange_velocity < 0) return fail(c, CSI_ERR_INVALID_ARGUMENT, "csi_mixed_layer_params.exchange_velocity must be >= 0");
+    if ((p->flags & ~(CSI_ML_SURFACE_ARRAY | CSI_ML_BULK_ARRAYS | CSI_ML_DEEP_ARRAY | CSI_ML_HAS_SURFACE | CSI_ML_HAS_BULK)) || p->reserved)
+        return fail(c, CSI_ERR_INVALID_ARGUMENT, "csi_mixed_layer_params.flags: unknown flag bits (reserved must be 0)");
+    for (const TimeSeries& S : c->series)
+        if (S.fid == CSI_F_BOTTOM_HEAT_FLUX)
+            return fail(c, CSI_ERR_INVALID_ARGUMENT, "time series on bottom_heat_flux: the mixed layer (csi_mixed_layer_set) writes that array at every step");
+    c->ml = *p;
+    c->ml_set = true;
+    return CSI_OK;
+}
+
+int32_t csi_mixed_layer_step(csi_context* c, double dt, int32_t from_cache) {
+    if (!c) return CSI_ERR_INVALID_ARGUMENT;
+    return do_mixed_layer(c, dt, from_cache != 0);
+}
+
+int32_t csi_mixed_layer_stats(csi_context* c, int64_t* launches) {
+    if (!c) return CSI_ERR_INVALID_ARGUMENT;
+    if (launches) *launches = c->ml_launches;
     return CSI_OK;
 }
 

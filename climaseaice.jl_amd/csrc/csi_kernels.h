@@ -229,10 +229,22 @@ void launch_slab_flux_step(const SlabDev& S, const HeatFluxDev& F, const FluxFie
 void launch_layered_flux_step(const SlabDev& S, const SnowDev& W, const HeatFluxDev& F, const FluxFields& ff, const GridDev& g,
                               const FRef& h, const FRef& a, const FRef& hs, const LayeredOut& o, double dt, hipStream_t s);
 
+// the slab-ocean mixed layer (mixed_layer.hip; include/csi.h csi_mixed_layer_set).  rc = rho * c, C = rc * depth, grc = gamma * rc,
+// formed on the host in this order; Fo, K, Ta, Qd, S: the numbers a configuration without the array reads; nx, ny: the interior.
+struct MixedLayerDev {
+    double rc, C, grc, Fo, K, Ta, Qd, liq_T0, liq_slope, S, dt;
+    int has_surface, has_bulk;       // which terms of Qs exist (an array implies its term)
+    int nx, ny;
+};
+// to_in: To or its Psi^- copy; to_out: To; a: the concentration; qb: the bottom heat-flux array (output); fo, k, ta, qd, sb: the arrays
+// a configuration has (p == nullptr: the number); qow: optional output (p == nullptr: absent)
+struct MixedLayerFields { FRef to_in, to_out, a, qb, fo, k, ta, qd, sb, qow; };
+void launch_mixed_layer(const MixedLayerDev& M, const MixedLayerFields& F, hipStream_t s);
+
 // forcing time series interpolated at the model clock (time_series.hip; include/csi.h csi_time_series_update): every series-driven
 // slot in ONE launch.  A descriptor: the two slices around the clock (a: psi_1, b: psi_2; b == a where n1 == n2), the interior of the
 // bound array, row strides in doubles, the interior extents and the weights w2 = n~, w1 = 1 - n~ (formed on the host, in double).
-constexpr int kMaxSeries = 14;
+constexpr int kMaxSeries = 18;      // (fourteen and the mixed layer's four inputs)
 struct SeriesDesc {
     const double *a, *b;
     double* dst;

@@ -18,12 +18,20 @@ from . import _lib
 from .dynamics import (ElastoViscoPlasticRheology, ExplicitSolver, FPlane, FreeDriftVelocities, IceStrength, SeaIceMomentumEquation,
                        SemiImplicitStress, StressBalanceFreeDrift, ViscousRheology)
 from .fields import CenterField, Field, XFaceField, YFaceField
+from .ocean import SlabOceanMixedLayer, check_ocean
 from .time_series import FieldTimeSeries, refuse_series
 from .grids import (METRIC_NAMES, Bounded, Center, FullyConnected, LeftConnected, LeftConnectedRightFolded, Periodic, RightConnected,
                     RightFolded, TileGrid)
 
 
 _OWN = object()      # SlabThermodynamics.params: use the object's own fluxes
+
+# the name _cell_field gives a per-cell input's field -> the slot of csi_time_series_set a FieldTimeSeries in its place drives
+_SERIES_SLOT_OF = {"top_heat_flux": "TOP_HEAT_FLUX", "bottom_heat_flux": "BOTTOM_HEAT_FLUX", "snowfall": "SNOWFALL",
+                   "flux_coefficient": "FLUX_COEFFICIENT", "flux_reference_temperature": "FLUX_REFERENCE_TEMPERATURE",
+                   "bottom_salinity": "BOTTOM_SALINITY", "ocean_surface_heat_flux": "ML_SURFACE_HEAT_FLUX",
+                   "ocean_coefficient": "ML_COEFFICIENT", "ocean_reference_temperature": "ML_REFERENCE_TEMPERATURE",
+                   "ocean_deep_heat_flux": "ML_DEEP_HEAT_FLUX"}
 
 
 def _cell_shape_ok(value, grid):
@@ -308,7 +316,7 @@ class SeaIceModel:
     def __init__(self, grid, dynamics=None, advection=None, timestepper="SplitRungeKutta3", sea_ice_density=900.0,
                  ice_thermodynamics=None, snow_thermodynamics=None, snow_density=330.0, snowfall=0.0,
                  boundary_conditions=None, forcing=None, device="cuda:0", mode="fast", stream=None, top_heat_flux=None,
-                 bottom_heat_flux=None):
+                 bottom_heat_flux=None, ocean=None):
         self.grid = grid
         # dynamics: None (prescribed velocities), a SeaIceMomentumEquation, or StressBalanceFreeDrift(top_momentum_stress = ...,
         # bottom_momentum_stress = ...) as the whole dynamics (stress_balance_free_drift.jl:131-151)
@@ -328,6 +336,9 @@ class SeaIceModel:
         self._heat_flux_args = (top_heat_flux, bottom_heat_flux)
         if ice_thermodynamics is not None:
             check_heat_fluxes(grid, ice_thermodynamics, top_heat_flux, bottom_heat_flux, snowfall if snow_thermodynamics else None)
+        # ocean: None (the bottom heat flux is given) or a SlabOceanMixedLayer, which computes it (ocean.py; include/csi.h)
+        check_ocean(grid, ocean, ice_thermodynamics, bottom_heat_flux, _cell_shape_ok)
+        self.ocean = ocean
         self.external_heat_fluxes = SimpleNamespace(top=None, bottom=None)
         if snow_thermodynamics is not None and ice_thermodynamics is None:
             raise ValueError("a snow layer needs ice_thermodynamics")
@@ -528,10 +539,7 @@ class SeaIceModel:
             return value
         if isinstance(value, FieldTimeSeries):      # the series writes into a new field (bound by the caller, registered after it)
             fld = CenterField(g, self.device, name)
-            self._pending_series.append(({"top_heat_flux": "TOP_HEAT_FLUX", "bottom_heat_flux": "BOTTOM_HEAT_FLUX",
-                                          "snowfall": "SNOWFALL", "flux_coefficient": "FLUX_COEFFICIENT",
-                                          "flux_reference_temperature": "FLUX_REFERENCE_TEMPERATURE",
-                                          "bottom_salinity": "BOTTOM_SALINITY"}[name], value, fld))
+            self._pending_series.append((_SERIES_SLOT_OF[name], value, fld))
             return fld
         arr = np.asarray(value, dtype=np.float64)
         if arr.ndim == 0:                           # a number beside a per-cell partner (LinearHeatFlux): broadcast
@@ -582,6 +590,8 @@ class SeaIceModel:
         top_arg, bottom_arg = self._heat_flux_args
         top = top_arg if top_arg is not None else ice.top_heat_flux
         bottom = bottom_arg if bottom_arg is not None else ice.bottom_heat_flux
+        if self.ocean is not None:       # the mixed layer writes the one ARRAY bottom term's array before every thermodynamic step
+            bottom = np.zeros((self.grid.Ny, self.grid.Nx))
         sp = ice.params(self.sea_ice_density, snow=snow is not None, top_heat_flux=top, bottom_heat_flux=bottom)
         self.ctx.call("csi_slab_params_set", C.byref(sp))
         self._slab_params = sp
@@ -626,6 +636,8 @@ class SeaIceModel:
             tu = self._cell_field(prescribed, "Tu") if prescribed is not None else CenterField(self.grid, self.device, "Tu")
             self.ice_top_temperature = ice.top_surface_temperature = tu
             self._bind("TU", tu)
+        if self.ocean is not None:
+            self.ocean.attach(self)
 
     def _init_tiles(self, g):
         """csi_tile_set + RCCL communicator: rank 0 makes the unique id, the host broadcasts it
@@ -1015,6 +1027,8 @@ def _state_fields(model):
         f = getattr(model, name, None)
         if f is not None:
             out[key] = f
+    if getattr(model, "ocean", None) is not None:      # the mixed-layer temperature and its Psi^- copy
+        out.update(model.ocean.state_fields())
     return {k: f for k, f in out.items() if isinstance(f, Field)}
 
 
@@ -1072,6 +1086,8 @@ def time_step(model, dt):
         # (sea_ice_fe_step.jl:13-34 with time_step_momentum!, compute_tendencies! and dynamic_time_step! no-ops)
         if model.ice_thermodynamics is None:
             raise NotImplementedError("a model without dynamics, advection and thermodynamics has nothing to step")
+        if model.ocean is not None:      # the ocean under the ice first: it writes the bottom heat flux the ice step reads
+            model.ctx.mixed_layer_step(dt, False)
         if model.snow_thermodynamics is None:
             model.ctx.call("csi_slab_thermo_step", C.byref(model._slab_params), float(dt))
         else:

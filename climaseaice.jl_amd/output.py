@@ -174,7 +174,8 @@ _SHORT = {"sigma11": "dynamics.s11", "sigma22": "dynamics.s22", "sigma12": "dyna
 def bound_fields(model):
     """name -> (Field, slot of csi_field_bind) of every field the model has bound to its context: the names of _state_fields(model),
     the stress / external-velocity arrays ("top_u", ...), model.forcing ("forcing_u", "forcing_v"), the prescribed free-drift fields,
-    the array terms of the heat fluxes and a per-cell snowfall; "sigma11" / "sigma22" / "sigma12" are short for "dynamics.s11" ..."""
+    the array terms of the heat fluxes and a per-cell snowfall, the mixed layer's "ocean.temperature", its per-cell inputs and, once
+    allocated, "ocean.surface_flux_used"; "sigma11" / "sigma22" / "sigma12" are short for "dynamics.s11" ..."""
     from .fields import Field
     from .model import _state_fields
     out = {}
@@ -204,6 +205,8 @@ def bound_fields(model):
     if getattr(model, "_heat_fluxes_used", None) is not None:     # the used-flux outputs, once allocated (model.heat_fluxes_used)
         out["top_heat_flux_used"] = (model._heat_fluxes_used.top, "TOP_HEAT_FLUX_USED")
         out["bottom_heat_flux_used"] = (model._heat_fluxes_used.bottom, "BOTTOM_HEAT_FLUX_USED")
+    if getattr(model, "ocean", None) is not None:                 # the mixed layer: its temperature, per-cell inputs, Qow once allocated
+        out.update(model.ocean.bound_fields())
     from .derived import slot_of
     for name, f in getattr(model, "_derived_fields", {}).items():      # derived fields, once allocated (model.derived_field)
         out[name] = (f, slot_of(name))
@@ -285,6 +288,7 @@ class OutputWriter:
               else is refused by name.  The names of the derived fields ("shear", "divergence", ...: derived.py) may appear in a list:
               they are allocated here and computed on the device immediately before every accumulate and snapshot; so are
               the momentum term fields ("top_x", "internal_y", ...: momentum_terms.py)
+              "ocean.temperature" and "ocean.surface_flux_used" name the mixed layer's fields (ocean.py); the second is allocated here
     schedule  IterationInterval, TimeInterval (snapshots) or AveragedTimeInterval (every output is a time average)
     dtype     "f32" (round to nearest even on the device) or "f64"
     mask      True: (Center, Center) outputs take fill_value in the inactive cells of the model's mask
@@ -312,6 +316,8 @@ class OutputWriter:
             for name in outputs:                     # ... and so is a momentum term field
                 if name in TERM_FIELD_NAMES:
                     model.momentum_term(name)
+        if not isinstance(outputs, dict) and "ocean.surface_flux_used" in outputs and getattr(model, "ocean", None) is not None:
+            model.ocean.surface_flux_used        # (allocated and bound the first time it is asked for)
         bound = recorder.bound_fields(model)
         if isinstance(outputs, dict):
             items = []

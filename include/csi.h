@@ -538,7 +538,8 @@ int32_t csi_dynamics_set(csi_context* ctx, int32_t kind);
  * Here a series drives one of ELEVEN slots of csi_field_bind: CSI_F_TOP_U / _V, CSI_F_BOT_U / _V (stress arrays or external
  * velocities), CSI_F_FORCING_U / _V, CSI_F_FREE_DRIFT_U / _V, CSI_F_TOP_HEAT_FLUX, CSI_F_BOTTOM_HEAT_FLUX, CSI_F_SNOWFALL.
  * Three thermodynamic inputs joined the eleven, fourteen in all: CSI_F_FLUX_COEFFICIENT, CSI_F_FLUX_REFERENCE_TEMPERATURE and
- * CSI_F_BOTTOM_SALINITY (csi_heat_fluxes_set); they ride in the same launch.
+ * CSI_F_BOTTOM_SALINITY (csi_heat_fluxes_set); they ride in the same launch.  So do the mixed layer's four inputs (csi_mixed_layer_set:
+ * CSI_F_ML_SURFACE_HEAT_FLUX, CSI_F_ML_COEFFICIENT, CSI_F_ML_REFERENCE_TEMPERATURE, CSI_F_ML_DEEP_HEAT_FLUX), eighteen in all.
  * csi_time_series_update(ctx, t) interpolates every series in ONE launch, in place, into the INTERIOR of the arrays bound to those
  * slots -- the arrays the momentum and thermodynamic kernels already read; no kernel of theirs changes.  The halos of the
  * velocity-point slots stay the library's to fill where it fills them for plain arrays (csi_time_step_momentum; csi_free_drift_set).
@@ -924,6 +925,90 @@ typedef struct {
 } csi_momentum_budget;
 int32_t csi_momentum_budget_compute(csi_context* ctx, int32_t what, csi_momentum_budget* out);
 int32_t csi_momentum_terms_stats(csi_context* ctx, int64_t* launches, int64_t* budget_calls);
+
+/* ---- the slab-ocean mixed layer under the ice: frazil growth, basal melt ---------------------------------------------------------------
+ * The reference leaves the ocean under the ice to a FluxFunction closure; its example examples/freezing_of_a_lake.jl:91-120 shows what
+ * that closure does: a bucket of water with a temperature of its own, cooled by the atmosphere over the open-water fraction 1 - aice,
+ * whose heat deficit below freezing becomes a negative bottom flux that grows ice.  What users write into that closure is a fixed form,
+ * and a fixed form is data: a mixed-layer heat budget with frazil formation and a bulk ice-ocean heat flux, as every stand-alone
+ * sea-ice code carries it (recalled from CICE's ocean_mixed_layer).  THIS TEXT IS THE DEFINITION.
+ *
+ * All heat fluxes are positive upward, like top_heat_flux.  Per interior cell:
+ *   To   the mixed-layer temperature the step starts from (CSI_F_ML_TEMPERATURE, or its Psi^- copy CSI_F_ML_TEMPERATURE_M)
+ *   a    the concentration the thermodynamic step starts from (CSI_F_A)
+ *   Tf = liq_T0 - liq_slope * Sb, with the same Sb (csi_slab_params.bottom_salinity, or per cell CSI_F_BOTTOM_SALINITY under
+ *        CSI_SOLVE_BOTTOM_SALINITY_ARRAY) that the ice step uses for Tb
+ * The arithmetic is uncontracted, in exactly this order, and STRICT and FAST are alike:
+ *   C   = (rho * c) * depth
+ *   Qs  = Fo + (K * (To - Ta))          absent terms are not added: Fo alone, the bulk term alone, or 0
+ *   Qow = Qs * (1 - a)                  open-water surface flux, per cell area
+ *   dT  = To - Tf
+ *   Qio = dT > 0 ? min(((gamma * (rho * c)) * dT) * a, (C * dT) / dt) : 0      basal melt flux, >= 0
+ *   T1  = To + (dt * ((Qd - Qow) - Qio)) / C
+ *   Qfr = T1 < Tf ? (C * (T1 - Tf)) / dt : 0                                   frazil, <= 0
+ *   To' = T1 < Tf ? Tf : T1
+ *   Qb  = Qio + Qfr                     the ice step's bottom external flux, per cell area
+ * Fo (surface_heat_flux), K (coefficient), Ta (reference_temperature) and Qd (deep_heat_flux, heat from below the mixed layer) are
+ * each a number or a (c,c) array: CSI_ML_SURFACE_ARRAY reads Fo from CSI_F_ML_SURFACE_HEAT_FLUX, CSI_ML_BULK_ARRAYS reads K and Ta
+ * from CSI_F_ML_COEFFICIENT and CSI_F_ML_REFERENCE_TEMPERATURE (both or neither; a front end broadcasts the number), CSI_ML_DEEP_ARRAY
+ * reads Qd from CSI_F_ML_DEEP_HEAT_FLUX.  CSI_ML_HAS_SURFACE / CSI_ML_HAS_BULK say which terms of Qs exist (an array flag implies its
+ * term).  The same K, Ta and flux arrays may serve the ice top (CSI_FLUX_LINEAR) and the open water.  gamma (exchange_velocity,
+ * m s^-1), rho (density), c (heat_capacity) and depth are numbers.  The budget C (To' - To) / dt = Qd - Qow - Qb holds to rounding.
+ * Every interior cell is computed, land included, as the thermodynamic kernels do.  No halo element is read or written.
+ *
+ * ONE point-wise launch (mixed_layer.hip, k_mixed_layer) writes To' into CSI_F_ML_TEMPERATURE, Qb into the interior of the array
+ * bound to CSI_F_BOTTOM_HEAT_FLUX -- which the ice step reads as the ARRAY bottom term it already knows; its kernels do not change --
+ * and, where CSI_F_ML_SURFACE_FLUX_USED is bound, Qow there.
+ * LIMIT: heat offered as Qio beyond what melts the cell's ice is lost where ice_volume_update clips, as any bottom flux is today.
+ *
+ * csi_mixed_layer_set(ctx, p): p == NULL removes the mixed layer.  CSI_ERR_INVALID_ARGUMENT, by name, for non-finite values, for
+ *   density, heat_capacity or depth <= 0, for exchange_velocity < 0 and for unknown flag bits.
+ * csi_mixed_layer_step(ctx, dt, from_cache): the launch above; from_cache != 0 reads To from CSI_F_ML_TEMPERATURE_M.  Refused by
+ *   name: no csi_slab_params_set (it needs the liquidus and Sb; CSI_ERR_NOT_BOUND); bottom heat-flux terms other than exactly one
+ *   ARRAY term (CSI_ERR_INVALID_ARGUMENT); an unbound slot that a flag names, CSI_F_ML_TEMPERATURE, CSI_F_A or CSI_F_BOTTOM_HEAT_FLUX
+ *   (CSI_ERR_NOT_BOUND); from_cache without CSI_F_ML_TEMPERATURE_M (CSI_ERR_NOT_BOUND).
+ * csi_mixed_layer_stats(ctx, &launches): launches of k_mixed_layer on the context so far.
+ *
+ * Where it runs: csi_time_step_fe and csi_time_step_rk3 run the step immediately before the thermodynamic step of every stage.  FE
+ * uses from_cache = 0.  RK3 uses from_cache = 1 (CSI_F_ML_TEMPERATURE_M must be bound): every stage computes To from Psi^- with its
+ * own stage step and the last stage (the whole step) is the step's result, exactly as h and aice behave -- without this To would
+ * advance 11/6 of the step per step.  csi_cache_current_fields copies To into its Psi^- slot when both are bound, in the same single
+ * launch.  csi_slab_thermo_step and csi_layered_thermo_step called on their own run what they ran before: a caller runs
+ * csi_mixed_layer_step first.  The four input slots may be driven by time series (csi_time_series_set: eighteen slots, one launch); a
+ * series on CSI_F_BOTTOM_HEAT_FLUX together with a mixed layer is refused by name (the step writes that array).  A context that never
+ * calls csi_mixed_layer_set launches what it launched before.
+ *
+ * The seven slots are numbered from CSI_F_COUNT_THERMO on, so that every older id and count keeps its value. */
+typedef enum {
+    CSI_F_ML_TEMPERATURE = CSI_F_COUNT_THERMO,       /* (c,c) To, state */
+    CSI_F_ML_TEMPERATURE_M,                          /* (c,c) its Psi^- copy */
+    CSI_F_ML_SURFACE_HEAT_FLUX,                      /* (c,c) Fo per cell, W m^-2 */
+    CSI_F_ML_COEFFICIENT,                            /* (c,c) K per cell, W m^-2 K^-1 */
+    CSI_F_ML_REFERENCE_TEMPERATURE,                  /* (c,c) Ta per cell */
+    CSI_F_ML_DEEP_HEAT_FLUX,                         /* (c,c) Qd per cell, W m^-2 */
+    CSI_F_ML_SURFACE_FLUX_USED,                      /* (c,c) optional output: Qow */
+    CSI_F_COUNT_MIXED_LAYER                          /* every slot csi_field_bind takes */
+} csi_mixed_layer_field_id;
+#define CSI_ML_SURFACE_ARRAY 1
+#define CSI_ML_BULK_ARRAYS 2
+#define CSI_ML_DEEP_ARRAY 4
+#define CSI_ML_HAS_SURFACE 8
+#define CSI_ML_HAS_BULK 16
+typedef struct {
+    double density;                    /* rho, 1026 kg m^-3 */
+    double heat_capacity;              /* c, 3991 J kg^-1 K^-1 */
+    double depth;                      /* m */
+    double exchange_velocity;          /* gamma, 6e-5 m s^-1 */
+    double surface_heat_flux;          /* Fo, W m^-2 */
+    double coefficient;                /* K, W m^-2 K^-1 */
+    double reference_temperature;      /* Ta, in the unit of To */
+    double deep_heat_flux;             /* Qd, W m^-2 */
+    int32_t flags;                     /* CSI_ML_* */
+    int32_t reserved;                  /* 0 */
+} csi_mixed_layer_params;
+int32_t csi_mixed_layer_set(csi_context* ctx, const csi_mixed_layer_params* p);
+int32_t csi_mixed_layer_step(csi_context* ctx, double dt, int32_t from_cache);
+int32_t csi_mixed_layer_stats(csi_context* ctx, int64_t* launches);
 
 /* ---- rheology and momentum solver (SeaIceMomentumEquation(grid; rheology, solver), sea_ice_momentum_equations.jl:67-94) ------------
  * Defaults: CSI_RHEOLOGY_EVP with CSI_SOLVER_SPLIT_EXPLICIT -- the library's EVP path, unchanged by these calls.  The scalars both

@@ -110,6 +110,25 @@ const CSI_LINEAR_REFERENCE_ARRAY = 8
 # csi_surface_solve.reserved: Tb per cell from THERMO_LINEAR.BOTTOM_SALINITY
 const CSI_SOLVE_BOTTOM_SALINITY_ARRAY = 1
 
+# csi_mixed_layer_field_id (from CSI_F_COUNT_THERMO on): the slab-ocean mixed layer's temperature To, its Psi^- copy, its four per-cell
+# inputs and the open-water flux the last step used, all (Center, Center)
+const MIXED_LAYER = (ML_TEMPERATURE=63, ML_TEMPERATURE_M=64, ML_SURFACE_HEAT_FLUX=65, ML_COEFFICIENT=66,
+                     ML_REFERENCE_TEMPERATURE=67, ML_DEEP_HEAT_FLUX=68, ML_SURFACE_FLUX_USED=69)
+# csi_mixed_layer_params.flags
+const CSI_ML_SURFACE_ARRAY = 1
+const CSI_ML_BULK_ARRAYS = 2
+const CSI_ML_DEEP_ARRAY = 4
+const CSI_ML_HAS_SURFACE = 8
+const CSI_ML_HAS_BULK = 16
+# csi_mixed_layer_params (include/csi.h, where the model is defined): density rho, heat_capacity c, depth, exchange_velocity gamma, the four
+# numbers Fo, K, Ta, Qd, the flags above
+struct CsiMixedLayerParams
+    density::Cdouble; heat_capacity::Cdouble; depth::Cdouble; exchange_velocity::Cdouble
+    surface_heat_flux::Cdouble; coefficient::Cdouble; reference_temperature::Cdouble; deep_heat_flux::Cdouble
+    flags::Int32; reserved::Int32
+end
+@assert sizeof(CsiMixedLayerParams) == 72 && fieldoffset(CsiMixedLayerParams, 9) == 64      # the layout gcc gives csi_mixed_layer_params
+
 # A FluxFunction is a closure and cannot cross the C ABI: it raises by name.  Its usual content, the bulk form K (Tu - Ta) [* aice], is data:
 # csi_heat_fluxes_set takes it as a CSI_FLUX_LINEAR term.
 function refuse_flux_function(flux, side)
@@ -586,6 +605,66 @@ function attach_free_drift!(model, dynamics::StressBalanceFreeDrift)
     arch isa Distributed && attach_tiles!(ctx, arch, grid)
     check(ctx, ccall((:csi_dynamics_set, libcsi), Int32, (Ptr{Cvoid}, Int32), ctx.handle, 1))      # CSI_DYNAMICS_FREE_DRIFT
     return ctx
+end
+
+# ---- the slab-ocean mixed layer (include/csi.h, csi_mixed_layer_set) ----------------------------------------------------------------
+# What the closure of examples/freezing_of_a_lake.jl:91-120 does, as data: a bucket of water with a temperature of its own that the
+# atmosphere cools over the open-water fraction, whose heat deficit below freezing is the negative bottom flux that grows ice.
+# attach_mixed_layer!(ctx, temperature, bottom_heat_flux; ...) binds To (a Center field that is state from now on), its Psi^- copy for
+# SplitRungeKutta3 (temperature_minus), the array the layer writes Qb into -- set here as the ONE ARRAY bottom heat-flux term --, and
+# each of Fo, K, Ta, Qd given as a Field or a FieldTimeSeries (bind_forcing!); Numbers travel in the struct.  csi_time_step_fe / csi_time_step_rk3 then run the layer
+# immediately before the thermodynamic step of every stage; a caller that keeps the Julia stage loop calls mixed_layer_step! itself.
+function attach_mixed_layer!(ctx, temperature, bottom_heat_flux; depth, temperature_minus = nothing, density = 1026.0, heat_capacity = 3991.0,
+                             ice_ocean_exchange_velocity = 6e-5, surface_heat_flux = nothing, coefficient = nothing,
+                             atmosphere_temperature = nothing, deep_heat_flux = 0.0)
+    for x in (surface_heat_flux, coefficient, atmosphere_temperature, deep_heat_flux)
+        (x isa Function || nameof(typeof(x)) === :FluxFunction) &&
+            error("ClimaSeaIceHIP: attach_mixed_layer!: a FluxFunction cannot cross the C ABI; give Numbers or fields")
+    end
+    (coefficient === nothing) == (atmosphere_temperature === nothing) ||
+        error("ClimaSeaIceHIP: attach_mixed_layer!: coefficient and atmosphere_temperature are given together or not at all")
+    bind!(ctx, MIXED_LAYER.ML_TEMPERATURE, temperature)
+    temperature_minus === nothing || bind!(ctx, MIXED_LAYER.ML_TEMPERATURE_M, temperature_minus)
+    bind!(ctx, F.BOTTOM_HEAT_FLUX, bottom_heat_flux)
+    term = Ref((Int32(1), Int32(0), 0.0, 0.0, 0.0, 0.0))      # csi_heat_flux_term: kind CSI_FLUX_ARRAY
+    check(ctx, ccall((:csi_heat_fluxes_set, libcsi), Int32, (Ptr{Cvoid}, Int32, Ptr{Cvoid}, Int32), ctx.handle, 1, term, 1))
+    flags = Int32(0)
+    number(x) = x isa Number ? Float64(x) : 0.0
+    if surface_heat_flux !== nothing
+        flags |= CSI_ML_HAS_SURFACE
+        if surface_heat_flux isa ArrayLike
+            flags |= CSI_ML_SURFACE_ARRAY
+            bind_forcing!(ctx, MIXED_LAYER.ML_SURFACE_HEAT_FLUX, surface_heat_flux)
+        end
+    end
+    if coefficient !== nothing
+        flags |= CSI_ML_HAS_BULK
+        if coefficient isa ArrayLike || atmosphere_temperature isa ArrayLike
+            (coefficient isa ArrayLike && atmosphere_temperature isa ArrayLike) ||
+                error("ClimaSeaIceHIP: attach_mixed_layer!: coefficient and atmosphere_temperature are both Numbers or both fields (broadcast the Number)")
+            flags |= CSI_ML_BULK_ARRAYS
+            bind_forcing!(ctx, MIXED_LAYER.ML_COEFFICIENT, coefficient)
+            bind_forcing!(ctx, MIXED_LAYER.ML_REFERENCE_TEMPERATURE, atmosphere_temperature)
+        end
+    end
+    if deep_heat_flux isa ArrayLike
+        flags |= CSI_ML_DEEP_ARRAY
+        bind_forcing!(ctx, MIXED_LAYER.ML_DEEP_HEAT_FLUX, deep_heat_flux)
+    end
+    p = Ref(CsiMixedLayerParams(density, heat_capacity, depth, ice_ocean_exchange_velocity, number(surface_heat_flux), number(coefficient),
+                                number(atmosphere_temperature), number(deep_heat_flux), flags, 0))
+    check(ctx, ccall((:csi_mixed_layer_set, libcsi), Int32, (Ptr{Cvoid}, Ref{CsiMixedLayerParams}), ctx.handle, p))
+    return nothing
+end
+
+# One launch: To', Qb into the bottom heat-flux array (and Qow where MIXED_LAYER.ML_SURFACE_FLUX_USED is bound).  from_cache: read To from Psi^-.
+mixed_layer_step!(ctx, Δt; from_cache = false) =
+    check(ctx, ccall((:csi_mixed_layer_step, libcsi), Int32, (Ptr{Cvoid}, Cdouble, Int32), ctx.handle, Δt, from_cache ? 1 : 0))
+
+function mixed_layer_launches(ctx)
+    n = Ref{Int64}(0)
+    check(ctx, ccall((:csi_mixed_layer_stats, libcsi), Int32, (Ptr{Cvoid}, Ptr{Int64}), ctx.handle, n))
+    return n[]
 end
 
 function ClimaSeaIce.SeaIceDynamics.time_step_momentum!(model, dynamics::StressBalanceFreeDrift, Δt)
