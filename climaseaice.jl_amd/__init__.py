@@ -21,7 +21,7 @@ from .output import (AveragedTimeInterval, IterationInterval, OutputWriter, Time
                      load_output)
 from .ocean import SlabOceanMixedLayer
 from .time_series import Clamp, Cyclical, FieldTimeSeries, InMemory, Linear
-from .model import (FieldBoundaryConditions, FluxBoundaryCondition, ImmersedBoundaryCondition, MeltingConstrainedFluxBalance, ValueBoundaryCondition, PrescribedTemperature, RadiativeEmission, LinearHeatFlux, bulk_sensible_heat_flux, SeaIceModel, SlabThermodynamics, SnowSlabThermodynamics,
+from .model import (FieldBoundaryConditions, FluxBoundaryCondition, ImmersedBoundaryCondition, MeltingConstrainedFluxBalance, ValueBoundaryCondition, PrescribedTemperature, RadiativeEmission, LinearHeatFlux, bulk_sensible_heat_flux, SteppedAlbedo, ShortwaveRadiation, SeaIceModel, SlabThermodynamics, SnowSlabThermodynamics,
                     snow_slab_thermodynamics, UpwindBiased, WENO, set_, time_step, time_step_momentum, compute_momentum_tendencies, update_state,
                     prognostic_state, restore_prognostic_state)
 

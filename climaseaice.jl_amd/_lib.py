@@ -42,12 +42,16 @@ MIXED_LAYER_FIELD_IDS = ["ML_TEMPERATURE", "ML_TEMPERATURE_M", "ML_SURFACE_HEAT_
                          "ML_DEEP_HEAT_FLUX", "ML_SURFACE_FLUX_USED"]
 F_MIXED_LAYER = {n: F_COUNT_THERMO + k for k, n in enumerate(MIXED_LAYER_FIELD_IDS)}
 F_COUNT_MIXED_LAYER = F_COUNT_THERMO + len(F_MIXED_LAYER)
+# csi_shortwave_field_id: the SHORTWAVE top term's per-cell flux and the albedo a step used, numbered from CSI_F_COUNT_MIXED_LAYER on
+SHORTWAVE_FIELD_IDS = ["SHORTWAVE", "ALBEDO_USED"]
+F_SHORTWAVE = {n: F_COUNT_MIXED_LAYER + k for k, n in enumerate(SHORTWAVE_FIELD_IDS)}
+F_COUNT_SHORTWAVE = F_COUNT_MIXED_LAYER + len(F_SHORTWAVE)
 
 
 def slot_id(name):
     """The number of a csi_field_bind slot by name: F, or one of the derived fields', momentum term fields', thermodynamic or
-    mixed-layer slots."""
-    for table in (F, F_DERIVED, F_MOMENTUM_TERMS, F_MIXED_LAYER):
+    mixed-layer and shortwave slots."""
+    for table in (F, F_DERIVED, F_MOMENTUM_TERMS, F_MIXED_LAYER, F_SHORTWAVE):
         if name in table:
             return table[name]
     return F_THERMO_LINEAR[name]
@@ -62,7 +66,7 @@ RHEOLOGY_EVP, RHEOLOGY_VISCOUS = 0, 1
 SOLVER_SPLIT_EXPLICIT, SOLVER_EXPLICIT = 0, 1
 FREE_DRIFT_NONE, FREE_DRIFT_STRESS_BALANCE, FREE_DRIFT_FIELDS = 0, 1, 2
 DYNAMICS_MOMENTUM_EQUATION, DYNAMICS_FREE_DRIFT = 0, 1
-FLUX_CONSTANT, FLUX_ARRAY, FLUX_RADIATIVE_EMISSION, FLUX_LINEAR = 0, 1, 2, 3
+FLUX_CONSTANT, FLUX_ARRAY, FLUX_RADIATIVE_EMISSION, FLUX_LINEAR, FLUX_SHORTWAVE = 0, 1, 2, 3, 4
 WEIGHT_NONE, WEIGHT_CONCENTRATION, WEIGHT_ICE_PRESENT = 0, 1, 2
 LINEAR_WEIGHT_MASK, LINEAR_COEFFICIENT_ARRAY, LINEAR_REFERENCE_ARRAY = 3, 4, 8      # csi_heat_flux_term.reserved of a LINEAR term
 SOLVE_BOTTOM_SALINITY_ARRAY = 1                                                     # csi_surface_solve.reserved
@@ -77,6 +81,8 @@ SERIES_SLOTS = ["TOP_U", "TOP_V", "BOT_U", "BOT_V", "FORCING_U", "FORCING_V", "F
 THERMO_SERIES_SLOTS = ["FLUX_COEFFICIENT", "FLUX_REFERENCE_TEMPERATURE", "BOTTOM_SALINITY"]
 # ... and the mixed layer's four inputs: eighteen
 MIXED_LAYER_SERIES_SLOTS = ["ML_SURFACE_HEAT_FLUX", "ML_COEFFICIENT", "ML_REFERENCE_TEMPERATURE", "ML_DEEP_HEAT_FLUX"]
+# ... and the shortwave flux: nineteen
+SHORTWAVE_SERIES_SLOTS = ["SHORTWAVE"]
 ML_SURFACE_ARRAY, ML_BULK_ARRAYS, ML_DEEP_ARRAY, ML_HAS_SURFACE, ML_HAS_BULK = 1, 2, 4, 8, 16      # csi_mixed_layer_params.flags
 
 # every symbol include/csi.h declares (checked by tests/test_abi.py against the header text)
@@ -97,7 +103,7 @@ SYMBOLS = ["csi_version", "csi_context_create", "csi_context_destroy", "csi_last
            "csi_output_snapshot", "csi_output_test", "csi_output_wait", "csi_output_release", "csi_output_destroy",
            "csi_derived_compute", "csi_budget_compute", "csi_derived_stats",
            "csi_momentum_terms_compute", "csi_momentum_budget_compute", "csi_momentum_terms_stats",
-           "csi_mixed_layer_set", "csi_mixed_layer_step", "csi_mixed_layer_stats"]
+           "csi_mixed_layer_set", "csi_mixed_layer_step", "csi_mixed_layer_stats", "csi_shortwave_set"]
 DIAG_VELOCITY, DIAG_TRACERS, DIAG_ALL = 1, 2, 3
 OUT_F64, OUT_F32 = 0, 1
 DERIVED_ALL = 127
@@ -160,6 +166,13 @@ class MixedLayerParams(C.Structure):
     _fields_ = [("density", C.c_double), ("heat_capacity", C.c_double), ("depth", C.c_double), ("exchange_velocity", C.c_double),
                 ("surface_heat_flux", C.c_double), ("coefficient", C.c_double), ("reference_temperature", C.c_double),
                 ("deep_heat_flux", C.c_double), ("flags", C.c_int32), ("reserved", C.c_int32)]
+
+
+class Shortwave(C.Structure):
+    """csi_shortwave (include/csi.h): the SHORTWAVE top term's flux, its stepped albedo for ice and for snow, weighting and flags."""
+    _fields_ = [("flux", C.c_double), ("cold", C.c_double), ("warm", C.c_double), ("threshold", C.c_double),
+                ("snow_cold", C.c_double), ("snow_warm", C.c_double), ("snow_threshold", C.c_double),
+                ("weighting", C.c_int32), ("per_cell", C.c_int32), ("has_snow_pair", C.c_int32), ("reserved", C.c_int32)]
 
 
 class TimeSeries(C.Structure):
@@ -283,6 +296,7 @@ def load():
         "csi_momentum_terms_stats": [vp, C.POINTER(i64), C.POINTER(i64)],
         "csi_mixed_layer_set": [vp, C.POINTER(MixedLayerParams)], "csi_mixed_layer_step": [vp, dbl, i32],
         "csi_mixed_layer_stats": [vp, C.POINTER(i64)],
+        "csi_shortwave_set": [vp, C.POINTER(Shortwave)],
     }
     for name, args in sig.items():
         fn = getattr(L, name, None)

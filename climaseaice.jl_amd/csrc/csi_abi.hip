@@ -36,7 +36,8 @@ static bool has_array_term(const FluxTermsDev& t) {
         if (t.kind[k] == FLUX_ARRAY) return true;
     return false;
 }
-static int32_t flux_fields(csi_context* c, const SlabDev& S, int top_bc_kind, int tu_id, bool snow, FluxFields& ff) {
+// `sw`: the SHORTWAVE term's setting as the kernels take it (mode SW_NONE unless the top's tuple has the term)
+static int32_t flux_fields(csi_context* c, const SlabDev& S, int top_bc_kind, int tu_id, bool snow, FluxFields& ff, ShortwaveDev& sw) {
     const HeatFluxDev& F = c->heat;
     if (F.top.n > 0 && S.top_flux_kind != 0)
         return fail(c, CSI_ERR_UNSUPPORTED, "top heat-flux terms replace top_flux_kind 1 (the internal-flux equilibrium): set top_flux_kind 0");
@@ -54,8 +55,16 @@ static int32_t flux_fields(csi_context* c, const SlabDev& S, int top_bc_kind, in
         ids.push_back(CSI_F_FLUX_REFERENCE_TEMPERATURE); ff.lin_ta = ref_of(c, CSI_F_FLUX_REFERENCE_TEMPERATURE);
     }
     if (F.bottom_salinity_array) { ids.push_back(CSI_F_BOTTOM_SALINITY); ff.sbot = ref_of(c, CSI_F_BOTTOM_SALINITY); }
+    sw = ShortwaveDev{};
+    if (c->heat_has_shortwave) {
+        if (c->sw.mode == SW_NONE)
+            return fail(c, CSI_ERR_INVALID_ARGUMENT, "a SHORTWAVE top heat-flux term needs csi_shortwave_set (the flux, the albedo and the weighting)");
+        sw = c->sw;
+        if (sw.mode == SW_CELL) { ids.push_back(CSI_F_SHORTWAVE); sw.f = ref_of(c, CSI_F_SHORTWAVE); }
+        sw.albedo_used = ref_of(c, CSI_F_ALBEDO_USED);      // (unbound: p == nullptr)
+    }
     // the surface temperature: read per cell (prescribed, Tu- of the secant), written by the flux balance
-    if (F.prescribed_array || (top_bc_kind == 1 && (flux_has_emission(F.top) || F.lin != LIN_NONE))) ids.push_back(tu_id);
+    if (F.prescribed_array || (top_bc_kind == 1 && (flux_has_emission(F.top) || F.lin != LIN_NONE || sw.mode != SW_NONE))) ids.push_back(tu_id);
     for (int id : ids) {
         int32_t rc = need(c, {id});
         if (rc) return rc;
@@ -75,8 +84,9 @@ static int32_t do_layered(csi_context* c, const SlabDev& S, const SnowDev& W, do
     o.tu_ice = ref_of(c, CSI_F_TU); o.tu_snow = ref_of(c, CSI_F_TUS);
     if (flux_path(c, true)) {
         FluxFields ff;
-        if ((rc = flux_fields(c, S, W.top_bc_kind, CSI_F_TUS, true, ff))) return rc;
-        launch_layered_flux_step(S, W, c->heat, ff, c->g, ref_of(c, CSI_F_H), ref_of(c, CSI_F_A), ref_of(c, CSI_F_HS), o, dt, c->stream);
+        ShortwaveDev sw;
+        if ((rc = flux_fields(c, S, W.top_bc_kind, CSI_F_TUS, true, ff, sw))) return rc;
+        launch_layered_flux_step(S, W, c->heat, ff, sw, c->g, ref_of(c, CSI_F_H), ref_of(c, CSI_F_A), ref_of(c, CSI_F_HS), o, dt, c->stream);
     } else {
         launch_layered_step(S, W, c->g, ref_of(c, CSI_F_H), ref_of(c, CSI_F_A), ref_of(c, CSI_F_HS), o, dt, c->stream);
     }
@@ -91,9 +101,10 @@ static int32_t do_slab(csi_context* c, const SlabDev& S, double dt) {
                                             "(top_flux_kind 0, csi_heat_fluxes_set), not the internal-flux equilibrium (top_flux_kind 1)");
     if (flux_path(c, false)) {
         FluxFields ff;
-        int32_t rc = flux_fields(c, S, S.top_bc_kind, CSI_F_TU, false, ff);
+        ShortwaveDev sw;
+        int32_t rc = flux_fields(c, S, S.top_bc_kind, CSI_F_TU, false, ff, sw);
         if (rc) return rc;
-        launch_slab_flux_step(S, c->heat, ff, c->g, ref_of(c, CSI_F_H), ref_of(c, CSI_F_A), ref_of(c, CSI_F_MASS_FLUX), has_mf, dt, c->stream);
+        launch_slab_flux_step(S, c->heat, ff, sw, c->g, ref_of(c, CSI_F_H), ref_of(c, CSI_F_A), ref_of(c, CSI_F_MASS_FLUX), has_mf, dt, c->stream);
     } else {
         launch_slab_step(S, c->g, ref_of(c, CSI_F_H), ref_of(c, CSI_F_A), ref_of(c, CSI_F_MASS_FLUX), has_mf, dt, c->stream);
     }
@@ -445,7 +456,7 @@ int32_t csi_mask_set(csi_context* c, const uint8_t* dev_mask, int64_t ld) {
 int32_t csi_field_bind(csi_context* c, int32_t fid, void* dev_ptr, int64_t ld, int32_t ni, int32_t nj) {
     if (!c) return CSI_ERR_INVALID_ARGUMENT;
     if (!c->grid_set) return fail(c, CSI_ERR_NOT_BOUND, "csi_grid_set has not been called");
-    if (fid < 0 || fid >= CSI_F_COUNT_MIXED_LAYER) return fail(c, CSI_ERR_INVALID_ARGUMENT, "unknown field id");
+    if (fid < 0 || fid >= CSI_F_COUNT_SHORTWAVE) return fail(c, CSI_ERR_INVALID_ARGUMENT, "unknown field id");
     if (!dev_ptr) { c->f[fid] = Bound{}; return CSI_OK; }
     const int eni = c->Nx + 2 * c->Hx + extra_x(c, fid), enj = c->Ny + 2 * c->Hy + extra_y(c, fid);
     if (ni != eni || nj != enj || ld < ni) {
@@ -796,11 +807,18 @@ int32_t csi_heat_fluxes_set(csi_context* c, int32_t side, const csi_heat_flux_te
     if (n > CSI_MAX_HEAT_FLUX_TERMS)
         return fail(c, CSI_ERR_UNSUPPORTED, "more than CSI_MAX_HEAT_FLUX_TERMS heat-flux terms on one side");
     FluxTermsDev t{};
-    int arrays = 0, lin = LIN_NONE, lin_weight = WEIGHT_NONE;
+    int arrays = 0, lin = LIN_NONE, lin_weight = WEIGHT_NONE, shortwave = 0;
     for (int k = 0; k < n; ++k) {
         const csi_heat_flux_term& q = terms[k];
-        if (q.kind != CSI_FLUX_CONSTANT && q.kind != CSI_FLUX_ARRAY && q.kind != CSI_FLUX_RADIATIVE_EMISSION && q.kind != CSI_FLUX_LINEAR)
+        if (q.kind != CSI_FLUX_CONSTANT && q.kind != CSI_FLUX_ARRAY && q.kind != CSI_FLUX_RADIATIVE_EMISSION && q.kind != CSI_FLUX_LINEAR &&
+            q.kind != CSI_FLUX_SHORTWAVE)
             return fail(c, CSI_ERR_INVALID_ARGUMENT, "unknown heat-flux term kind");
+        if (q.kind == CSI_FLUX_SHORTWAVE) {
+            if (side != CSI_HEAT_TOP) return fail(c, CSI_ERR_UNSUPPORTED, "ShortwaveRadiation is a top heat flux only");
+            if (++shortwave > 1) return fail(c, CSI_ERR_UNSUPPORTED, "at most one ShortwaveRadiation term per model (sum the fluxes into one)");
+            if (c->sw.mode == SW_NONE)
+                return fail(c, CSI_ERR_INVALID_ARGUMENT, "a SHORTWAVE top heat-flux term needs csi_shortwave_set (the flux, the albedo and the weighting) first");
+        }
         if (q.kind == CSI_FLUX_LINEAR) {
             if (side != CSI_HEAT_TOP) return fail(c, CSI_ERR_UNSUPPORTED, "LinearHeatFlux is a top heat flux only");
             if (lin != LIN_NONE) return fail(c, CSI_ERR_UNSUPPORTED, "at most one LinearHeatFlux term per model (sum the coefficients into one)");
@@ -818,13 +836,39 @@ int32_t csi_heat_fluxes_set(csi_context* c, int32_t side, const csi_heat_flux_te
         if (q.kind == CSI_FLUX_RADIATIVE_EMISSION && side != CSI_HEAT_TOP)
             return fail(c, CSI_ERR_UNSUPPORTED, "RadiativeEmission is a top heat flux only");
         t.kind[k] = q.kind == CSI_FLUX_ARRAY ? FLUX_ARRAY : (q.kind == CSI_FLUX_RADIATIVE_EMISSION ? FLUX_EMISSION :
-                    (q.kind == CSI_FLUX_LINEAR ? FLUX_LINEAR : FLUX_CONST));
+                    (q.kind == CSI_FLUX_LINEAR ? FLUX_LINEAR : (q.kind == CSI_FLUX_SHORTWAVE ? FLUX_SHORTWAVE : FLUX_CONST)));
         t.value[k] = q.value;
         t.eps[k] = q.emissivity; t.sigma[k] = q.stefan_boltzmann_constant; t.Tr[k] = q.reference_temperature;
     }
     t.n = n;
     (side == CSI_HEAT_TOP ? c->heat.top : c->heat.bot) = t;
-    if (side == CSI_HEAT_TOP) { c->heat.lin = lin; c->heat.lin_weight = lin_weight; }
+    if (side == CSI_HEAT_TOP) { c->heat.lin = lin; c->heat.lin_weight = lin_weight; c->heat_has_shortwave = shortwave != 0; }
+    return CSI_OK;
+}
+
+int32_t csi_shortwave_set(csi_context* c, const csi_shortwave* p) {
+    if (!c) return CSI_ERR_INVALID_ARGUMENT;
+    if (!p) { c->sw = ShortwaveDev{}; return CSI_OK; }
+    const double values[7] = {p->flux, p->cold, p->warm, p->threshold, p->snow_cold, p->snow_warm, p->snow_threshold};
+    const char* const names[7] = {"flux", "cold", "warm", "threshold", "snow_cold", "snow_warm", "snow_threshold"};
+    for (int k = 0; k < (p->has_snow_pair ? 7 : 4); ++k) {
+        if (!std::isfinite(values[k])) return fail(c, CSI_ERR_INVALID_ARGUMENT, std::string("csi_shortwave.") + names[k] + " is not finite");
+        if (k != 0 && k != 3 && k != 6 && !(values[k] >= 0 && values[k] <= 1))
+            return fail(c, CSI_ERR_INVALID_ARGUMENT, std::string("csi_shortwave.") + names[k] + ": an albedo lies in [0, 1]");
+    }
+    if (p->weighting < CSI_WEIGHT_NONE || p->weighting > CSI_WEIGHT_ICE_PRESENT)
+        return fail(c, CSI_ERR_INVALID_ARGUMENT, "csi_shortwave.weighting: unknown weighting");
+    if ((p->per_cell & ~1) || (p->has_snow_pair & ~1) || p->reserved)
+        return fail(c, CSI_ERR_INVALID_ARGUMENT, "csi_shortwave: per_cell and has_snow_pair are 0 or 1, reserved must be 0");
+    if (p->per_cell && !c->f[CSI_F_SHORTWAVE].p)
+        return fail(c, CSI_ERR_INVALID_ARGUMENT, "csi_shortwave.per_cell: no array is bound to CSI_F_SHORTWAVE (csi_field_bind it first)");
+    ShortwaveDev w{};
+    w.mode = p->per_cell ? SW_CELL : SW_NUMBER;
+    w.weight = p->weighting; w.snow_pair = p->has_snow_pair;
+    w.F = p->per_cell ? 0.0 : p->flux;
+    w.cold = p->cold; w.warm = p->warm; w.thr = p->threshold;
+    if (p->has_snow_pair) { w.snow_cold = p->snow_cold; w.snow_warm = p->snow_warm; w.snow_thr = p->snow_threshold; }
+    c->sw = w;
     return CSI_OK;
 }
 

@@ -45,7 +45,7 @@ struct Bound {
 };
 
 // (x, y) location of every field slot
-static const int kLoc[CSI_F_COUNT_MIXED_LAYER][2] = {
+static const int kLoc[CSI_F_COUNT_SHORTWAVE][2] = {
     {LOC_F, LOC_C}, {LOC_C, LOC_F}, {LOC_C, LOC_C}, {LOC_C, LOC_C},   // U V H A
     {LOC_C, LOC_C}, {LOC_C, LOC_C}, {LOC_F, LOC_F},                   // S11 S22 S12
     {LOC_F, LOC_C}, {LOC_C, LOC_F}, {LOC_C, LOC_C}, {LOC_C, LOC_C}, {LOC_C, LOC_C},  // UN VN P ALPHA DELTA
@@ -64,8 +64,9 @@ static const int kLoc[CSI_F_COUNT_MIXED_LAYER][2] = {
     {LOC_F, LOC_C}, {LOC_C, LOC_F}, {LOC_F, LOC_C}, {LOC_C, LOC_F}, {LOC_F, LOC_C}, {LOC_C, LOC_F}, {LOC_F, LOC_C}, {LOC_C, LOC_F},
     {LOC_F, LOC_C}, {LOC_C, LOC_F},                                   // the ten momentum term fields: _X, _Y of each term
     {LOC_C, LOC_C}, {LOC_C, LOC_C}, {LOC_C, LOC_C}, {LOC_C, LOC_C}, {LOC_C, LOC_C},    // FLUX_COEFFICIENT .. BOTTOM_HEAT_FLUX_USED
-    {LOC_C, LOC_C}, {LOC_C, LOC_C}, {LOC_C, LOC_C}, {LOC_C, LOC_C}, {LOC_C, LOC_C}, {LOC_C, LOC_C}, {LOC_C, LOC_C}};   // ML_TEMPERATURE .. ML_SURFACE_FLUX_USED
-static const char* const kName[CSI_F_COUNT_MIXED_LAYER] = {"u", "v", "h", "aice", "sigma11", "sigma22", "sigma12", "un", "vn", "P", "alpha",
+    {LOC_C, LOC_C}, {LOC_C, LOC_C}, {LOC_C, LOC_C}, {LOC_C, LOC_C}, {LOC_C, LOC_C}, {LOC_C, LOC_C}, {LOC_C, LOC_C},    // ML_TEMPERATURE .. ML_SURFACE_FLUX_USED
+    {LOC_C, LOC_C}, {LOC_C, LOC_C}};                                  // SHORTWAVE ALBEDO_USED
+static const char* const kName[CSI_F_COUNT_SHORTWAVE] = {"u", "v", "h", "aice", "sigma11", "sigma22", "sigma12", "un", "vn", "P", "alpha",
                                   "Delta", "zeta_f", "zeta_c", "Gh", "Gaice", "h-", "aice-", "u-", "v-",
                                   "top_u", "top_v", "bottom_u", "bottom_v", "mass_flux",
                                   "hs", "Ghs", "hs-", "mass_flux_snow", "intercepted_snowfall", "Tu", "Tu_snow", "forcing_u", "forcing_v", "Gu", "Gv",
@@ -76,7 +77,8 @@ static const char* const kName[CSI_F_COUNT_MIXED_LAYER] = {"u", "v", "h", "aice"
                                   "flux_coefficient", "flux_reference_temperature", "bottom_salinity", "top_heat_flux_used",
                                   "bottom_heat_flux_used",
                                   "ocean_temperature", "ocean_temperature-", "ocean_surface_heat_flux", "ocean_coefficient",
-                                  "ocean_reference_temperature", "ocean_deep_heat_flux", "ocean_surface_flux_used"};
+                                  "ocean_reference_temperature", "ocean_deep_heat_flux", "ocean_surface_flux_used",
+                                  "shortwave", "albedo_used"};
 
 extern std::string g_create_error;      // csi_context_create failures (no context to hold the message)
 
@@ -187,7 +189,7 @@ struct csi_context {
     long fcor2_ld = 0, fcor2_plane = 0;
     bool cor_dirty = true;               // Coriolis columns of the FAST table need (re)building
     double cor_synced = 0.0;             // FPlane value they were built with
-    Bound f[CSI_F_COUNT_MIXED_LAYER];
+    Bound f[CSI_F_COUNT_SHORTWAVE];
     csi_evp_params evp{};
     csi_stress stress[2]{};
     int mode = CSI_MODE_STRICT;
@@ -278,6 +280,9 @@ struct csi_context {
     bool ml_set = false;
     csi_mixed_layer_params ml{};
     int64_t ml_launches = 0;             // csi_mixed_layer_stats
+    // csi_shortwave_set: the SHORTWAVE top term's setting (sw.mode == SW_NONE: none); heat_has_shortwave: the top's tuple has the term
+    ShortwaveDev sw{};
+    bool heat_has_shortwave = false;
     HeatFluxDev heat{};      // csi_heat_fluxes_set / csi_surface_solve_set (thermo_flux.hip); heat.top.n = heat.bot.n = 0: numbers only
     // csi_time_series_set / _update (csi_time_series.hip): at most one series per eligible slot; the copy stream of the HOST backend's
     // uploads and the event recorded behind every interpolation launch (an upload into a ring slot waits for it), both made once

@@ -201,9 +201,10 @@ void launch_slab_step(const SlabDev& S, const GridDev& g, const FRef& h, const F
 
 // per-cell heat fluxes, RadiativeEmission, the surface-temperature solve (thermo_flux.hip; include/csi.h csi_heat_fluxes_set)
 constexpr int kMaxFluxTerms = 8;
-enum : int { FLUX_CONST = 0, FLUX_ARRAY = 1, FLUX_EMISSION = 2, FLUX_LINEAR = 3 };
+enum : int { FLUX_CONST = 0, FLUX_ARRAY = 1, FLUX_EMISSION = 2, FLUX_LINEAR = 3, FLUX_SHORTWAVE = 4 };
 enum : int { LIN_NONE = 0, LIN_NUMBERS = 1, LIN_ARRAYS = 2 };                 // the top's LINEAR term: absent, K and Ta numbers, both per cell
 enum : int { WEIGHT_NONE = 0, WEIGHT_CONCENTRATION = 1, WEIGHT_ICE_PRESENT = 2 };
+enum : int { SW_NONE = 0, SW_NUMBER = 1, SW_CELL = 2 };                       // the top's SHORTWAVE term: absent, F a number, F per cell
 struct FluxTermsDev {
     int n;                     // 0: the side takes SlabDev's number (Qu / Qb with top_flux_kind / bot_flux_kind)
     int kind[kMaxFluxTerms];
@@ -223,11 +224,21 @@ struct HeatFluxDev {
 // bare-ice step, CSI_F_TUS for the layered one) -- Tu- of the secant, the prescribed per-cell value, and the output; lin_k / lin_ta:
 // the LINEAR term's per-cell K and Ta; sbot: the per-cell bottom salinity; qtop_used / qbot_used: optional outputs (p == nullptr: absent)
 struct FluxFields { FRef qtop, qbot, snowfall, tu, lin_k, lin_ta, sbot, qtop_used, qbot_used; };
+// The SHORTWAVE term (include/csi.h csi_shortwave_set): alpha = (T < thr) ? cold : warm, Q = (F * (1 - alpha)) * w.  It is the LAST
+// argument of the SW_NUMBER / SW_CELL instantiations of both kernels and no argument of the SW_NONE ones, so HeatFluxDev, FluxFields and
+// every argument offset of the kernels of before keep their layout.  f: F per cell (SW_CELL); albedo_used: optional output (p == nullptr: absent); snow_pair: the
+// layered step takes the snow triple where hs > 0.
+struct ShortwaveDev {
+    int mode = SW_NONE, weight = WEIGHT_NONE, snow_pair = 0, pad_ = 0;
+    double F = 0, cold = 0, warm = 0, thr = 0, snow_cold = 0, snow_warm = 0, snow_thr = 0;
+    FRef f{}, albedo_used{};
+};
 bool flux_has_emission(const FluxTermsDev& t);
-void launch_slab_flux_step(const SlabDev& S, const HeatFluxDev& F, const FluxFields& ff, const GridDev& g, const FRef& h, const FRef& a,
-                           const FRef& mf, int has_mf, double dt, hipStream_t s);
-void launch_layered_flux_step(const SlabDev& S, const SnowDev& W, const HeatFluxDev& F, const FluxFields& ff, const GridDev& g,
-                              const FRef& h, const FRef& a, const FRef& hs, const LayeredOut& o, double dt, hipStream_t s);
+void launch_slab_flux_step(const SlabDev& S, const HeatFluxDev& F, const FluxFields& ff, const ShortwaveDev& sw, const GridDev& g,
+                           const FRef& h, const FRef& a, const FRef& mf, int has_mf, double dt, hipStream_t s);
+void launch_layered_flux_step(const SlabDev& S, const SnowDev& W, const HeatFluxDev& F, const FluxFields& ff, const ShortwaveDev& sw,
+                              const GridDev& g, const FRef& h, const FRef& a, const FRef& hs, const LayeredOut& o, double dt,
+                              hipStream_t s);
 
 // the slab-ocean mixed layer (mixed_layer.hip; include/csi.h csi_mixed_layer_set).  rc = rho * c, C = rc * depth, grc = gamma * rc,
 // formed on the host in this order; Fo, K, Ta, Qd, S: the numbers a configuration without the array reads; nx, ny: the interior.
@@ -244,7 +255,7 @@ void launch_mixed_layer(const MixedLayerDev& M, const MixedLayerFields& F, hipSt
 // forcing time series interpolated at the model clock (time_series.hip; include/csi.h csi_time_series_update): every series-driven
 // slot in ONE launch.  A descriptor: the two slices around the clock (a: psi_1, b: psi_2; b == a where n1 == n2), the interior of the
 // bound array, row strides in doubles, the interior extents and the weights w2 = n~, w1 = 1 - n~ (formed on the host, in double).
-constexpr int kMaxSeries = 18;      // (fourteen and the mixed layer's four inputs)
+constexpr int kMaxSeries = 19;      // (fourteen, the mixed layer's four inputs and the shortwave flux)
 struct SeriesDesc {
     const double *a, *b;
     double* dst;

@@ -102,7 +102,7 @@ int32_t csi_output_create(csi_context* c, const csi_output_field* fields, int32_
     int32_t nx[kMaxOutputFields], ny[kMaxOutputFields], dt[kMaxOutputFields];
     for (int k = 0; k < n; ++k) {
         const csi_output_field& f = fields[k];
-        if (f.field_id < 0 || f.field_id >= CSI_F_COUNT_MIXED_LAYER) return fail(c, CSI_ERR_INVALID_ARGUMENT, "output: unknown field id at position " + std::to_string(k));
+        if (f.field_id < 0 || f.field_id >= CSI_F_COUNT_SHORTWAVE) return fail(c, CSI_ERR_INVALID_ARGUMENT, "output: unknown field id at position " + std::to_string(k));
         if (f.dtype != CSI_OUT_F64 && f.dtype != CSI_OUT_F32)
             return fail(c, CSI_ERR_INVALID_ARGUMENT, std::string("output: field ") + kName[f.field_id] + ": unknown dtype (CSI_OUT_F64 or CSI_OUT_F32)");
         if (f.masked && (kLoc[f.field_id][0] != LOC_C || kLoc[f.field_id][1] != LOC_C))

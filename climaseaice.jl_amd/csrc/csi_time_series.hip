@@ -26,7 +26,8 @@ static bool series_slot(int fid) {
     for (int id : kForcingFields) if (fid == id) return true;
     return fid == CSI_F_TOP_HEAT_FLUX || fid == CSI_F_BOTTOM_HEAT_FLUX || fid == CSI_F_SNOWFALL || fid == CSI_F_FLUX_COEFFICIENT ||
            fid == CSI_F_FLUX_REFERENCE_TEMPERATURE || fid == CSI_F_BOTTOM_SALINITY || fid == CSI_F_ML_SURFACE_HEAT_FLUX ||
-           fid == CSI_F_ML_COEFFICIENT || fid == CSI_F_ML_REFERENCE_TEMPERATURE || fid == CSI_F_ML_DEEP_HEAT_FLUX;
+           fid == CSI_F_ML_COEFFICIENT || fid == CSI_F_ML_REFERENCE_TEMPERATURE || fid == CSI_F_ML_DEEP_HEAT_FLUX ||
+           fid == CSI_F_SHORTWAVE;
 }
 
 static int find_series(const csi_context* c, int fid) {
@@ -234,9 +235,10 @@ int32_t csi_time_series_plan(const double* times, int32_t nt, int32_t indexing, 
 
 int32_t csi_time_series_set(csi_context* c, int32_t fid, const csi_time_series* ts) {
     if (!c) return CSI_ERR_INVALID_ARGUMENT;
-    if (fid < 0 || fid >= CSI_F_COUNT_MIXED_LAYER || !series_slot(fid))
+    if (fid < 0 || fid >= CSI_F_COUNT_SHORTWAVE || !series_slot(fid))
         return fail(c, CSI_ERR_INVALID_ARGUMENT, "time series: the slot is not one of the eleven forcing slots (stress / external-velocity arrays, model.forcing, "
-                                                 "free-drift fields, top / bottom heat flux, snowfall)");
+                                                 "free-drift fields, top / bottom heat flux, snowfall) nor one of the eight per-cell inputs that joined them: the LinearHeatFlux "
+                                                 "coefficient and reference temperature, the bottom salinity, the mixed layer's four inputs, the shortwave flux");
     if (ts && fid == CSI_F_BOTTOM_HEAT_FLUX && c->ml_set)
         return fail(c, CSI_ERR_INVALID_ARGUMENT, "time series on bottom_heat_flux: the mixed layer (csi_mixed_layer_set) writes that array at every step");
     // (replacing or removing a series: whatever may still read its ring or staging slices has to finish first)

@@ -1,4 +1,5 @@
 // thermo_flux.hip -- the slab and layered thermodynamic steps with per-cell heat fluxes, RadiativeEmission, the LINEAR top term, the
+// SHORTWAVE top term with its stepped albedo (csi_shortwave_set), the
 // surface-temperature solve, a per-cell bottom salinity and the used-flux outputs (include/csi.h, csi_heat_fluxes_set).  The numeric
 // configuration keeps k_slab / k_layered (thermo.hip); these kernels run once a side has flux terms, the prescribed temperature, the
 // snowfall or the bottom salinity is an array, or a used-flux output is bound.
@@ -31,11 +32,25 @@ struct LinCell {
     int w;
 };
 
-// getflux of one term at surface temperature T; q: the cell's value of the side's ARRAY term.  EMIT / LIN: the side has a term that
-// depends on T -- RadiativeEmission / the LINEAR term (K * (T - Ta)) * w, in this order
-template <bool EMIT, int LIN>
-__device__ __forceinline__ double flux_term(const FluxTermsDev& t, int k, double q, double T, const LinCell& lc) {
+// what the SHORTWAVE term reads of a cell: F (SW_CELL; the setting's number otherwise), the albedo triple that holds in the cell (the
+// snow triple where the layered step starts with hs > 0), the concentration the step starts from and the weighting
+struct SwCell {
+    double F, cold, warm, thr, a;
+    int w;
+};
+__device__ __forceinline__ double albedo(const SwCell& sc, double T) { return (T < sc.thr) ? sc.cold : sc.warm; }
+
+// getflux of one term at surface temperature T; q: the cell's value of the side's ARRAY term.  EMIT / LIN / SW: the side has a term that
+// depends on T -- RadiativeEmission / the LINEAR term (K * (T - Ta)) * w / the SHORTWAVE term (F * (1 - alpha(T))) * w, in this order
+template <bool EMIT, int LIN, int SW>
+__device__ __forceinline__ double flux_term(const FluxTermsDev& t, int k, double q, double T, const LinCell& lc, const SwCell& sc) {
     if (EMIT && t.kind[k] == FLUX_EMISSION) return t.eps[k] * t.sigma[k] * pow4(T + t.Tr[k]);
+    if (SW != SW_NONE && t.kind[k] == FLUX_SHORTWAVE) {
+        const double v = sc.F * (1 - albedo(sc, T));
+        if (sc.w == WEIGHT_CONCENTRATION) return v * sc.a;
+        if (sc.w == WEIGHT_ICE_PRESENT) return (sc.a == 0) ? 0.0 : v;
+        return v;
+    }
     if (LIN != LIN_NONE && t.kind[k] == FLUX_LINEAR) {
         const double K = (LIN == LIN_ARRAYS) ? lc.K : t.value[k], Ta = (LIN == LIN_ARRAYS) ? lc.Ta : t.Tr[k];
         const double v = K * (T - Ta);
@@ -48,13 +63,76 @@ __device__ __forceinline__ double flux_term(const FluxTermsDev& t, int k, double
 
 // getflux of the side's Tuple: t0 + (t1 + (... + t_{n-1})), right-nested (boundary_fluxes.jl:15-22); n >= 1.  Unrolled over the
 // fixed capacity so that every term index is a constant (no dynamically indexed kernel argument).
-template <bool EMIT, int LIN>
-__device__ __forceinline__ double flux_sum(const FluxTermsDev& t, double q, double T, const LinCell& lc) {
+template <bool EMIT, int LIN, int SW>
+__device__ __forceinline__ double flux_sum(const FluxTermsDev& t, double q, double T, const LinCell& lc, const SwCell& sc) {
     double acc = 0.0;
 #pragma unroll
     for (int k = kMaxFluxTerms - 1; k >= 0; --k) {
         if (k < t.n) {
-            const double v = flux_term<EMIT, LIN>(t, k, q, T, lc);
+            const double v = flux_term<EMIT, LIN, SW>(t, k, q, T, lc, sc);
+            acc = (k == t.n - 1) ? v : v + acc;
+        }
+    }
+    return acc;
+}
+
+// The SHORTWAVE instantiations keep the top's terms in vector registers.  A side's FluxTermsDev is 68 scalar registers of kernel
+// argument, and all of it is live across the secant loop: with the shortwave setting on top that no longer fits the 102 scalar registers
+// a wave has.  So before the loop each term is reduced to the two numbers its value needs -- A, B: CONSTANT / ARRAY the value, -;
+// EMISSION eps * sigma (the product the term forms first anyway), T_r; LINEAR K, Ta -- and an empty asm with a "v" constraint keeps
+// them (and the cell's shortwave numbers) in vector registers, of which these kernels have plenty.  Only kind[] and n stay scalar.
+__device__ __forceinline__ double in_vgpr(double x) {
+    asm("" : "+v"(x));
+    return x;
+}
+// ... and what the step needs only after the loop -- the bottom's external flux, which does not depend on the surface temperature, and
+// the latent heat's numbers -- is formed BEFORE it (a volatile asm is not moved across the loop), so that the scalar registers those
+// kernel arguments arrive in are free while the loop runs.  The values and the order of their arithmetic are flux_sum's and latent_heat's.
+__device__ __forceinline__ double before_loop(double x) {
+    asm volatile("" : "+v"(x));
+    return x;
+}
+struct LatentRegs {
+    double L0, c, T0, rho;
+};
+__device__ __forceinline__ LatentRegs load_latent(const SlabDev& s) {
+    return LatentRegs{before_loop(s.L0), before_loop(s.rho_l * s.c_l / s.rho_pure - s.c_i), before_loop(s.T0), before_loop(s.rho_bulk)};
+}
+__device__ __forceinline__ double latent_heat(const LatentRegs& l, double T) { return l.L0 + l.c * (T - l.T0); }
+struct TermRegs {
+    double A[kMaxFluxTerms], B[kMaxFluxTerms];
+};
+template <bool EMIT, int LIN>
+__device__ __forceinline__ void load_terms(TermRegs& r, const FluxTermsDev& t, double q, const LinCell& lc) {
+#pragma unroll
+    for (int k = 0; k < kMaxFluxTerms; ++k) {
+        double A = t.value[k], B = t.Tr[k];
+        if (EMIT && t.kind[k] == FLUX_EMISSION) A = t.eps[k] * t.sigma[k];
+        if (t.kind[k] == FLUX_ARRAY) A = q;
+        if (LIN == LIN_ARRAYS && t.kind[k] == FLUX_LINEAR) { A = lc.K; B = lc.Ta; }
+        r.A[k] = in_vgpr(A);
+        r.B[k] = in_vgpr(B);
+    }
+}
+// flux_term / flux_sum on those registers: the same values in the same order
+template <bool EMIT, int LIN, int SW>
+__device__ __forceinline__ double flux_sum_regs(const FluxTermsDev& t, const TermRegs& r, double T, const LinCell& lc, const SwCell& sc) {
+    double acc = 0.0;
+#pragma unroll
+    for (int k = kMaxFluxTerms - 1; k >= 0; --k) {
+        if (k < t.n) {
+            double v = r.A[k];
+            if (EMIT && t.kind[k] == FLUX_EMISSION) {
+                v = r.A[k] * pow4(T + r.B[k]);
+            } else if (SW != SW_NONE && t.kind[k] == FLUX_SHORTWAVE) {
+                v = sc.F * (1 - albedo(sc, T));
+                if (sc.w == WEIGHT_CONCENTRATION) v = v * sc.a;
+                if (sc.w == WEIGHT_ICE_PRESENT) v = (sc.a == 0) ? 0.0 : v;
+            } else if (LIN != LIN_NONE && t.kind[k] == FLUX_LINEAR) {
+                v = r.A[k] * (T - r.B[k]);
+                if (lc.w == WEIGHT_CONCENTRATION) v = v * lc.a;
+                if (lc.w == WEIGHT_ICE_PRESENT) v = (lc.a == 0) ? 0.0 : v;
+            }
             acc = (k == t.n - 1) ? v : v + acc;
         }
     }
@@ -80,10 +158,17 @@ __device__ __forceinline__ double secant_root(const Fn& f, double Tu_prev, doubl
 
 // QT / QB: the top / bottom side has an ARRAY term; EMIT: the top has a RadiativeEmission term; LTU: the cell's surface temperature
 // is read (Tu- of the secant, or the prescribed per-cell value); LIN: the top's LINEAR term (LIN_NONE / LIN_NUMBERS / LIN_ARRAYS);
-// SB: the bottom salinity is read per cell.  The last two default to "off": those instantiations are the kernels of before.
-template <bool QT, bool QB, bool EMIT, bool LTU, int LIN = LIN_NONE, bool SB = false>
+// SB: the bottom salinity is read per cell; SW: the top's SHORTWAVE term (SW_NONE / SW_NUMBER / SW_CELL), whose setting is the last
+// argument -- a parameter pack that is empty for SW_NONE and one ShortwaveDev otherwise, so that the SW_NONE instantiations have the
+// argument list, and with it the code, of before.  The last three flags default to "off".
+__device__ __forceinline__ ShortwaveDev shortwave_arg() { return ShortwaveDev{}; }
+__device__ __forceinline__ const ShortwaveDev& shortwave_arg(const ShortwaveDev& sw) { return sw; }
+
+template <bool QT, bool QB, bool EMIT, bool LTU, int LIN = LIN_NONE, bool SB = false, int SW = SW_NONE, class... SwArg>
 __global__ void __launch_bounds__(256) k_slab_flux(SlabDev s, HeatFluxDev F, FluxFields ff, GridDev g, FRef h, FRef a, FRef mf, int has_mf,
-                                                   double dt) {
+                                                   double dt, SwArg... sw_arg) {
+    static_assert(sizeof...(SwArg) == (SW == SW_NONE ? 0 : 1), "the shortwave setting travels exactly when there is a term");
+    const ShortwaveDev& sw = shortwave_arg(sw_arg...);
     const int i = 1 + blockIdx.x * blockDim.x + threadIdx.x, j = 1 + blockIdx.y * blockDim.y + threadIdx.y;
     if (i > g.Nx || j > g.Ny) return;
     const double hn = h(i, j), an = a(i, j);
@@ -92,18 +177,34 @@ __global__ void __launch_bounds__(256) k_slab_flux(SlabDev s, HeatFluxDev F, Flu
     const double qb = QB ? ff.qbot(i, j) : 0.0;
     const LinCell lc{LIN == LIN_ARRAYS ? ff.lin_k(i, j) : 0.0, LIN == LIN_ARRAYS ? ff.lin_ta(i, j) : 0.0, an, F.lin_weight};
     const double Sb = SB ? ff.sbot(i, j) : s.S;
-    const double hc = s.hc;
+    const double fsw = SW == SW_CELL ? sw.f(i, j) : (SW == SW_NUMBER ? sw.F : 0.0);
+    const SwCell sc = SW == SW_NONE ? SwCell{} : SwCell{in_vgpr(fsw), in_vgpr(sw.cold), in_vgpr(sw.warm), in_vgpr(sw.thr), an, sw.weight};
+    const double hc = (SW != SW_NONE) ? in_vgpr(s.hc) : s.hc;
     const bool consolidated = hn >= hc;
     const double Tb = s.liq_T0 - s.liq_slope * Sb;
-    auto Qx = [&](double T) { return F.top.n ? flux_sum<EMIT, LIN>(F.top, qt, T, lc) : s.Qu; };
+    auto Qb_ext = [&](double T) {
+        return (s.bot_flux_kind == 1) ? (-(1 - an)) * s.Qb : (F.bot.n ? flux_sum<false, LIN_NONE, SW_NONE>(F.bot, qb, T, lc, sc) : s.Qb);
+    };
+    TermRegs tr;
+    LatentRegs lr;
+    double Qb_pre = 0.0;
+    if constexpr (SW != SW_NONE) {
+        load_terms<EMIT, LIN>(tr, F.top, qt, lc);
+        lr = load_latent(s);
+        Qb_pre = before_loop(Qb_ext(0.0));
+    }
+    auto Qx = [&](double T) {
+        if constexpr (SW != SW_NONE) return flux_sum_regs<EMIT, LIN, SW>(F.top, tr, T, lc, sc);      // (the term is in the tuple: n >= 1)
+        else return F.top.n ? flux_sum<EMIT, LIN, SW>(F.top, qt, T, lc, sc) : s.Qu;
+    };
     double Tu = s.Tu;
     if (s.top_bc_kind == 1) {      // MeltingConstrainedFluxBalance: root of Qx - Qi(T), capped at Tm(S_ice); thin slab: Tb
         const double Tm = s.liq_T0 - s.liq_slope * s.ice_salinity;
         double root = Tb;
         if (consolidated) {
-            if ((EMIT || LIN != LIN_NONE) && LTU) {      // (the host sets LTU whenever the flux balance has a term that depends on T)
+            if ((EMIT || LIN != LIN_NONE || SW != SW_NONE) && LTU) {      // (the host sets LTU whenever the flux balance has a term that depends on T)
                 auto f = [&](double T) { return Qx(T) - ((hn <= 0) ? 0.0 : -s.k * (T - Tb) / hn); };
-                root = secant_root(f, tum, F.tol, F.maxiters);
+                root = secant_root(f, tum, (SW != SW_NONE) ? in_vgpr(F.tol) : F.tol, F.maxiters);
             } else {
                 root = Tb - Qx(0.0) * hn / s.k;      // Qx does not depend on T: the closed form of the numeric path
             }
@@ -112,11 +213,11 @@ __global__ void __launch_bounds__(256) k_slab_flux(SlabDev s, HeatFluxDev F, Flu
     } else if (LTU) {              // PrescribedTemperature per cell
         Tu = tum;
     }
-    const double Eb = s.rho_bulk * latent_heat(s, Tb);
-    const double Eu = s.rho_bulk * latent_heat(s, Tu);
+    const double Eb = (SW != SW_NONE) ? lr.rho * latent_heat(lr, Tb) : s.rho_bulk * latent_heat(s, Tb);
+    const double Eu = (SW != SW_NONE) ? lr.rho * latent_heat(lr, Tu) : s.rho_bulk * latent_heat(s, Tu);
     const double Qi_fun = (hn <= 0) ? 0.0 : -s.k * (Tu - Tb) / hn;
     const double Qu = (s.top_flux_kind == 1) ? Qi_fun : Qx(Tu);
-    const double Qb = (s.bot_flux_kind == 1) ? (-(1 - an)) * s.Qb : (F.bot.n ? flux_sum<false, LIN_NONE>(F.bot, qb, Tu, lc) : s.Qb);
+    const double Qb = (SW != SW_NONE) ? Qb_pre : Qb_ext(Tu);
     const double Qi = consolidated ? Qi_fun : 0.0;
     const double wu = (Qu - Qi) / Eu;
     const double wb = (Qi - Qb) / Eb;
@@ -128,12 +229,15 @@ __global__ void __launch_bounds__(256) k_slab_flux(SlabDev s, HeatFluxDev F, Flu
     if (s.top_bc_kind == 1 && ff.tu.p) ff.tu(i, j) = Tu;
     if (ff.qtop_used.p) ff.qtop_used(i, j) = Qu;
     if (ff.qbot_used.p) ff.qbot_used(i, j) = Qb;
+    if (SW != SW_NONE && sw.albedo_used.p) sw.albedo_used(i, j) = albedo(sc, Tu);
 }
 
 // PS: per-cell snowfall
-template <bool QT, bool QB, bool EMIT, bool LTU, bool PS, int LIN = LIN_NONE, bool SB = false>
+template <bool QT, bool QB, bool EMIT, bool LTU, bool PS, int LIN = LIN_NONE, bool SB = false, int SW = SW_NONE, class... SwArg>
 __global__ void __launch_bounds__(256) k_layered_flux(SlabDev s, SnowDev w, HeatFluxDev F, FluxFields ff, GridDev g, FRef h, FRef a, FRef hs,
-                                                      LayeredOut o, double dt) {
+                                                      LayeredOut o, double dt, SwArg... sw_arg) {
+    static_assert(sizeof...(SwArg) == (SW == SW_NONE ? 0 : 1), "the shortwave setting travels exactly when there is a term");
+    const ShortwaveDev& sw = shortwave_arg(sw_arg...);
     const int i = 1 + blockIdx.x * blockDim.x + threadIdx.x, j = 1 + blockIdx.y * blockDim.y + threadIdx.y;
     if (i > g.Nx || j > g.Ny) return;
     const double hin = h(i, j), an = a(i, j);
@@ -144,22 +248,42 @@ __global__ void __launch_bounds__(256) k_layered_flux(SlabDev s, SnowDev w, Heat
     const double Ps = PS ? ff.snowfall(i, j) : w.snowfall;
     const LinCell lc{LIN == LIN_ARRAYS ? ff.lin_k(i, j) : 0.0, LIN == LIN_ARRAYS ? ff.lin_ta(i, j) : 0.0, an, F.lin_weight};
     const double Sb = SB ? ff.sbot(i, j) : s.S;
-    const double hc = s.hc;
+    const double fsw = SW == SW_CELL ? sw.f(i, j) : (SW == SW_NUMBER ? sw.F : 0.0);
+    const bool snowy = SW != SW_NONE && sw.snow_pair && hsn > 0;      // (the condition under which Tm = 0 below)
+    const SwCell sc = SW == SW_NONE ? SwCell{}
+                                    : SwCell{in_vgpr(fsw), snowy ? sw.snow_cold : sw.cold, snowy ? sw.snow_warm : sw.warm,
+                                             snowy ? sw.snow_thr : sw.thr, an, sw.weight};
+    const double hc = (SW != SW_NONE) ? in_vgpr(s.hc) : s.hc;
     const double Vin = hin * an, Vsn = hsn * an;
     const bool consolidated = hin >= hc;
     const double Tb = s.liq_T0 - s.liq_slope * Sb;
     double Tm = s.liq_T0 - s.liq_slope * s.ice_salinity;
     const double ks = w.k, ki = s.k;
-    auto Qx = [&](double T) { return F.top.n ? flux_sum<EMIT, LIN>(F.top, qt, T, lc) : s.Qu; };
+    auto Qb_ext = [&](double T) {
+        return (s.bot_flux_kind == 1) ? (-(1 - an)) * s.Qb : (F.bot.n ? flux_sum<false, LIN_NONE, SW_NONE>(F.bot, qb, T, lc, sc) : s.Qb);
+    };
+    TermRegs tr;
+    LatentRegs lr;
+    double Qb_pre = 0.0, rs_pre = 0.0, rw_pre = 0.0, ki_pre = 0.0, dt_pre = 0.0, Ps_pre = 0.0;
+    if constexpr (SW != SW_NONE) {
+        load_terms<EMIT, LIN>(tr, F.top, qt, lc);
+        lr = load_latent(s);
+        Qb_pre = before_loop(Qb_ext(0.0));
+        rs_pre = before_loop(w.rho); rw_pre = before_loop(s.rho_l); ki_pre = before_loop(ki); dt_pre = before_loop(dt); Ps_pre = before_loop(Ps);
+    }
+    auto Qx = [&](double T) {
+        if constexpr (SW != SW_NONE) return flux_sum_regs<EMIT, LIN, SW>(F.top, tr, T, lc, sc);      // (the term is in the tuple: n >= 1)
+        else return F.top.n ? flux_sum<EMIT, LIN, SW>(F.top, qt, T, lc, sc) : s.Qu;
+    };
     Tm = (hsn > 0) ? 0.0 : Tm;
     const double R = hsn / ks + hin / ki;
     double Tus = w.Tu;
     if (w.top_bc_kind == 1) {
         double root = Tb;
         if (consolidated) {
-            if ((EMIT || LIN != LIN_NONE) && LTU) {      // (the host sets LTU whenever the flux balance has a term that depends on T)
+            if ((EMIT || LIN != LIN_NONE || SW != SW_NONE) && LTU) {      // (the host sets LTU whenever the flux balance has a term that depends on T)
                 auto f = [&](double T) { return Qx(T) - ((R <= 0) ? 0.0 : (Tb - T) / R); };
-                root = secant_root(f, tum, F.tol, F.maxiters);
+                root = secant_root(f, tum, (SW != SW_NONE) ? in_vgpr(F.tol) : F.tol, F.maxiters);
             } else {
                 root = Tb - Qx(0.0) * R;
             }
@@ -168,6 +292,8 @@ __global__ void __launch_bounds__(256) k_layered_flux(SlabDev s, SnowDev w, Heat
     } else if (LTU) {
         Tus = tum;
     }
+    // (what follows the loop reads the copies made before it in the SHORTWAVE instantiations, the arguments themselves otherwise)
+    const double dtp = (SW != SW_NONE) ? dt_pre : dt, kip = (SW != SW_NONE) ? ki_pre : ki, Psp = (SW != SW_NONE) ? Ps_pre : Ps;
     const double Ri = hin / ki, Rs = hsn / ks, Rt = Rs + Ri;
     const double Tsi = (Rt <= 0) ? Tb : Tb + (Tus - Tb) * Ri / Rt;
     const double Qic = (R <= 0) ? 0.0 : (Tb - Tus) / R;
@@ -176,16 +302,16 @@ __global__ void __launch_bounds__(256) k_layered_flux(SlabDev s, SnowDev w, Heat
     const double Qui_per_ice = (an > 0) ? Qui / an : 0.0;
     const double dQ = Qui_per_ice - Qis;
     const double melt_energy = jmax(0.0, -dQ);
-    const double rs = w.rho, Ls = s.L0;
-    const double cap = rs * Ls * hsn / dt;
+    const double rs = (SW != SW_NONE) ? rs_pre : w.rho, Ls = (SW != SW_NONE) ? lr.L0 : s.L0;
+    const double cap = rs * Ls * hsn / dtp;
     const double Qs = jmin(melt_energy, cap);
     const double Gsm = Qs / (rs * Ls);
-    const double ri = s.rho_bulk, riL = ri * Ls;
-    const double Qbi = (s.bot_flux_kind == 1) ? (-(1 - an)) * s.Qb : (F.bot.n ? flux_sum<false, LIN_NONE>(F.bot, qb, Tus, lc) : s.Qb);
+    const double ri = (SW != SW_NONE) ? lr.rho : s.rho_bulk, riL = ri * Ls;
+    const double Qbi = (SW != SW_NONE) ? Qb_pre : Qb_ext(Tus);
     const double alpha = (Qui - Qbi) / riL, beta = Qs / riL;
     const double Cm = (hin > 0) ? an / (2 * hin) : 0.0;
     const double Cf = (hc > 0) ? (1 - an) / hc : 0.0;
-    const double Km = dt * Cm, Kf = dt * Cf;
+    const double Km = dtp * Cm, Kf = dtp * Cf;
     const double eps = 2.220446049250313e-16;
     const double Dm = 1 - Km * beta, Df = 1 - Kf * beta;
     const double am = (fabs(Dm) > eps) ? (an + Km * alpha) / Dm : an + Km * alpha;
@@ -194,18 +320,19 @@ __global__ void __launch_bounds__(256) k_layered_flux(SlabDev s, SnowDev w, Heat
     const bool melting = dtVm < 0;
     const double atmp = melting ? am : af;
     const double Qeff = Qui + Qs * atmp;
-    const double Eb = ri * latent_heat(s, Tb), Eu = ri * latent_heat(s, Tsi);
-    const double Qii_fun = (hin <= 0) ? 0.0 : -ki * (Tsi - Tb) / hin;
+    const double Eb = ri * ((SW != SW_NONE) ? latent_heat(lr, Tb) : latent_heat(s, Tb));
+    const double Eu = ri * ((SW != SW_NONE) ? latent_heat(lr, Tsi) : latent_heat(s, Tsi));
+    const double Qii_fun = (hin <= 0) ? 0.0 : -kip * (Tsi - Tb) / hin;
     const double Qii = consolidated ? Qii_fun : 0.0;
     const double wu = (Qeff - Qii) / Eu, wb = (Qii - Qbi) / Eb;
     double hi1, a1;
-    ice_volume_update(wu + wb, hin, an, hc, dt, hi1, a1);
+    ice_volume_update(wu + wb, hin, an, hc, dtp, hi1, a1);
     hsn = (a1 > 0) ? hsn * an / a1 : 0.0;
-    const double Gsp = (a1 > 0) ? Ps / rs : 0.0;
-    double hs1 = hsn + dt * (Gsp - Gsm);
+    const double Gsp = (a1 > 0) ? Psp / rs : 0.0;
+    double hs1 = hsn + dtp * (Gsp - Gsm);
     hs1 = jmax(0.0, hs1);
     {
-        const double rw = s.rho_l;
+        const double rw = (SW != SW_NONE) ? rw_pre : s.rho_l;
         const double hf = hi1 * (1 - ri / rw) - hs1 * rs / rw;
         double dhs = (hf < 0) ? -hf * ri / rs : 0.0;
         const double hsp = jmax(0.0, hs1 - dhs);
@@ -216,14 +343,78 @@ __global__ void __launch_bounds__(256) k_layered_flux(SlabDev s, SnowDev w, Heat
     hs1 = (a1 <= 0) ? 0.0 : hs1;
     a(i, j) = a1; h(i, j) = hi1; hs(i, j) = hs1;
     const double Pabs = rs * Gsp * a1;
-    if (o.mf_ice.p) o.mf_ice(i, j) = ri * (hi1 * a1 - Vin) / dt;
-    if (o.mf_snow.p) o.mf_snow(i, j) = rs * (hs1 * a1 - Vsn) / dt - Pabs;
+    if (o.mf_ice.p) o.mf_ice(i, j) = ri * (hi1 * a1 - Vin) / dtp;
+    if (o.mf_snow.p) o.mf_snow(i, j) = rs * (hs1 * a1 - Vsn) / dtp - Pabs;
     if (o.mf_int.p) o.mf_int(i, j) = Pabs;
     if (o.tu_ice.p) o.tu_ice(i, j) = Tsi;
     if (o.tu_snow.p) o.tu_snow(i, j) = Tus;
     if (ff.qtop_used.p) ff.qtop_used(i, j) = Qui;
     if (ff.qbot_used.p) ff.qbot_used(i, j) = Qbi;
+    if (SW != SW_NONE && sw.albedo_used.p) sw.albedo_used(i, j) = albedo(sc, Tus);
 }
+
+// This source makes three objects (Makefile): CSI_FLUX_SW = 0 (thermo_flux.o: the kernels of before, the host's selection and the launch
+// functions), 1 and 2 (thermo_flux_sw1.o / _sw2.o: the SW_NUMBER / SW_CELL instantiations), so that the three compile side by side.
+#ifndef CSI_FLUX_SW
+#define CSI_FLUX_SW 0
+#endif
+
+using SlabFn = void (*)(const SlabDev&, const HeatFluxDev&, const FluxFields&, const ShortwaveDev&, const GridDev&, const FRef&, const FRef&,
+                        const FRef&, int, double, hipStream_t);
+using LayeredFn = void (*)(const SlabDev&, const SnowDev&, const HeatFluxDev&, const FluxFields&, const ShortwaveDev&, const GridDev&,
+                           const FRef&, const FRef&, const FRef&, const LayeredOut&, double, hipStream_t);
+// the launcher of one instantiation: b = flux_bits + 16 (32 layered) * (LIN + 3 * SB); one specialisation per object
+template <int SW> SlabFn slab_flux_entry(int b);
+template <int SW> LayeredFn layered_flux_entry(int b);
+
+namespace {
+constexpr int kBlockX = 64, kBlockY = 4;
+dim3 cells(const GridDev& g) { return dim3((unsigned)((g.Nx + kBlockX - 1) / kBlockX), (unsigned)((g.Ny + kBlockY - 1) / kBlockY)); }
+
+template <int B>
+void slab_inst(const SlabDev& S, const HeatFluxDev& F, const FluxFields& ff, const ShortwaveDev& sw, const GridDev& g, const FRef& h,
+               const FRef& a, const FRef& mf, int has_mf, double dt, hipStream_t st) {
+#if CSI_FLUX_SW == 0
+    hipLaunchKernelGGL((k_slab_flux<(B & 1) != 0, (B & 2) != 0, (B & 4) != 0, (B & 8) != 0, (B / 16) % 3, (B / 48) != 0>), cells(g),
+                       dim3(kBlockX, kBlockY), 0, st, S, F, ff, g, h, a, mf, has_mf, dt);
+#else
+    hipLaunchKernelGGL((k_slab_flux<(B & 1) != 0, (B & 2) != 0, (B & 4) != 0, (B & 8) != 0, (B / 16) % 3, (B / 48) != 0, CSI_FLUX_SW, ShortwaveDev>),
+                       cells(g), dim3(kBlockX, kBlockY), 0, st, S, F, ff, g, h, a, mf, has_mf, dt, sw);
+#endif
+}
+template <int... B>
+constexpr SlabFn slab_table_entry(int b, std::integer_sequence<int, B...>) {
+    constexpr SlabFn t[] = {&slab_inst<B>...};
+    return t[b];
+}
+
+template <int B>
+void layered_inst(const SlabDev& S, const SnowDev& W, const HeatFluxDev& F, const FluxFields& ff, const ShortwaveDev& sw, const GridDev& g,
+                  const FRef& h, const FRef& a, const FRef& hs, const LayeredOut& o, double dt, hipStream_t st) {
+#if CSI_FLUX_SW == 0
+    hipLaunchKernelGGL((k_layered_flux<(B & 1) != 0, (B & 2) != 0, (B & 4) != 0, (B & 8) != 0, (B & 16) != 0, (B / 32) % 3, (B / 96) != 0>),
+                       cells(g), dim3(kBlockX, kBlockY), 0, st, S, W, F, ff, g, h, a, hs, o, dt);
+#else
+    hipLaunchKernelGGL((k_layered_flux<(B & 1) != 0, (B & 2) != 0, (B & 4) != 0, (B & 8) != 0, (B & 16) != 0, (B / 32) % 3, (B / 96) != 0,
+                                       CSI_FLUX_SW, ShortwaveDev>),
+                       cells(g), dim3(kBlockX, kBlockY), 0, st, S, W, F, ff, g, h, a, hs, o, dt, sw);
+#endif
+}
+template <int... B>
+constexpr LayeredFn layered_table_entry(int b, std::integer_sequence<int, B...>) {
+    constexpr LayeredFn t[] = {&layered_inst<B>...};
+    return t[b];
+}
+}  // namespace
+
+template <> SlabFn slab_flux_entry<CSI_FLUX_SW>(int b) { return slab_table_entry(b, std::make_integer_sequence<int, 16 * 6>{}); }
+template <> LayeredFn layered_flux_entry<CSI_FLUX_SW>(int b) { return layered_table_entry(b, std::make_integer_sequence<int, 32 * 6>{}); }
+
+#if CSI_FLUX_SW == 0
+template <> SlabFn slab_flux_entry<SW_NUMBER>(int b);
+template <> SlabFn slab_flux_entry<SW_CELL>(int b);
+template <> LayeredFn layered_flux_entry<SW_NUMBER>(int b);
+template <> LayeredFn layered_flux_entry<SW_CELL>(int b);
 
 bool flux_has_emission(const FluxTermsDev& t) {
     for (int k = 0; k < t.n; ++k)
@@ -232,57 +423,33 @@ bool flux_has_emission(const FluxTermsDev& t) {
 }
 
 namespace {
-constexpr int kBlockX = 64, kBlockY = 4;
-dim3 cells(const GridDev& g) { return dim3((unsigned)((g.Nx + kBlockX - 1) / kBlockX), (unsigned)((g.Ny + kBlockY - 1) / kBlockY)); }
-
-using SlabFn = void (*)(const SlabDev&, const HeatFluxDev&, const FluxFields&, const GridDev&, const FRef&, const FRef&, const FRef&, int,
-                        double, hipStream_t);
-template <int B>
-void slab_inst(const SlabDev& S, const HeatFluxDev& F, const FluxFields& ff, const GridDev& g, const FRef& h, const FRef& a, const FRef& mf,
-               int has_mf, double dt, hipStream_t st) {
-    hipLaunchKernelGGL((k_slab_flux<(B & 1) != 0, (B & 2) != 0, (B & 4) != 0, (B & 8) != 0, (B / 16) % 3, (B / 48) != 0>), cells(g),
-                       dim3(kBlockX, kBlockY), 0, st, S, F, ff, g, h, a, mf, has_mf, dt);
-}
-template <int... B>
-constexpr SlabFn slab_table_entry(int b, std::integer_sequence<int, B...>) {
-    constexpr SlabFn t[] = {&slab_inst<B>...};
-    return t[b];
-}
-
-using LayeredFn = void (*)(const SlabDev&, const SnowDev&, const HeatFluxDev&, const FluxFields&, const GridDev&, const FRef&, const FRef&,
-                           const FRef&, const LayeredOut&, double, hipStream_t);
-template <int B>
-void layered_inst(const SlabDev& S, const SnowDev& W, const HeatFluxDev& F, const FluxFields& ff, const GridDev& g, const FRef& h,
-                  const FRef& a, const FRef& hs, const LayeredOut& o, double dt, hipStream_t st) {
-    hipLaunchKernelGGL((k_layered_flux<(B & 1) != 0, (B & 2) != 0, (B & 4) != 0, (B & 8) != 0, (B & 16) != 0, (B / 32) % 3, (B / 96) != 0>),
-                       cells(g), dim3(kBlockX, kBlockY), 0, st, S, W, F, ff, g, h, a, hs, o, dt);
-}
-template <int... B>
-constexpr LayeredFn layered_table_entry(int b, std::integer_sequence<int, B...>) {
-    constexpr LayeredFn t[] = {&layered_inst<B>...};
-    return t[b];
-}
-
 // template bits shared by both steps: which per-cell arrays a configuration reads
-int flux_bits(const HeatFluxDev& F, const FluxFields& ff, int top_bc_kind) {
+int flux_bits(const HeatFluxDev& F, const FluxFields& ff, const ShortwaveDev& sw, int top_bc_kind) {
     const bool emit = flux_has_emission(F.top);
-    const bool ltu = (top_bc_kind == 0 && F.prescribed_array) || (top_bc_kind == 1 && (emit || F.lin != LIN_NONE));
+    const bool ltu = (top_bc_kind == 0 && F.prescribed_array) || (top_bc_kind == 1 && (emit || F.lin != LIN_NONE || sw.mode != SW_NONE));
     return (ff.qtop.p ? 1 : 0) | (ff.qbot.p ? 2 : 0) | (emit ? 4 : 0) | (ltu ? 8 : 0);
 }
-// the variants beyond them: the LINEAR term's three states, times the per-cell bottom salinity (6 per combination of bits)
+// the variants beyond them: the LINEAR term's three states, times the per-cell bottom salinity (6 per combination of bits), in each
+// of the SHORTWAVE term's three states.  Every one can be selected: with a SHORTWAVE term the flux balance always has LTU, and a
+// PrescribedTemperature top has it exactly when the temperature is per cell.
 int flux_variant(const HeatFluxDev& F) { return F.lin + 3 * (F.bottom_salinity_array ? 1 : 0); }
 }  // namespace
 
-void launch_slab_flux_step(const SlabDev& S, const HeatFluxDev& F, const FluxFields& ff, const GridDev& g, const FRef& h, const FRef& a,
-                           const FRef& mf, int has_mf, double dt, hipStream_t s) {
-    const int b = flux_bits(F, ff, S.top_bc_kind) + 16 * flux_variant(F);
-    slab_table_entry(b, std::make_integer_sequence<int, 16 * 6>{})(S, F, ff, g, h, a, mf, has_mf, dt, s);
+void launch_slab_flux_step(const SlabDev& S, const HeatFluxDev& F, const FluxFields& ff, const ShortwaveDev& sw, const GridDev& g,
+                           const FRef& h, const FRef& a, const FRef& mf, int has_mf, double dt, hipStream_t s) {
+    const int b = flux_bits(F, ff, sw, S.top_bc_kind) + 16 * flux_variant(F);
+    const SlabFn fn = sw.mode == SW_CELL ? slab_flux_entry<SW_CELL>(b) : (sw.mode == SW_NUMBER ? slab_flux_entry<SW_NUMBER>(b) : slab_flux_entry<SW_NONE>(b));
+    fn(S, F, ff, sw, g, h, a, mf, has_mf, dt, s);
 }
 
-void launch_layered_flux_step(const SlabDev& S, const SnowDev& W, const HeatFluxDev& F, const FluxFields& ff, const GridDev& g,
-                              const FRef& h, const FRef& a, const FRef& hs, const LayeredOut& o, double dt, hipStream_t s) {
-    const int b = (flux_bits(F, ff, W.top_bc_kind) | (F.snowfall_array ? 16 : 0)) + 32 * flux_variant(F);
-    layered_table_entry(b, std::make_integer_sequence<int, 32 * 6>{})(S, W, F, ff, g, h, a, hs, o, dt, s);
+void launch_layered_flux_step(const SlabDev& S, const SnowDev& W, const HeatFluxDev& F, const FluxFields& ff, const ShortwaveDev& sw,
+                              const GridDev& g, const FRef& h, const FRef& a, const FRef& hs, const LayeredOut& o, double dt,
+                              hipStream_t s) {
+    const int b = (flux_bits(F, ff, sw, W.top_bc_kind) | (F.snowfall_array ? 16 : 0)) + 32 * flux_variant(F);
+    const LayeredFn fn = sw.mode == SW_CELL ? layered_flux_entry<SW_CELL>(b)
+                                            : (sw.mode == SW_NUMBER ? layered_flux_entry<SW_NUMBER>(b) : layered_flux_entry<SW_NONE>(b));
+    fn(S, W, F, ff, sw, g, h, a, hs, o, dt, s);
 }
+#endif
 
 }  // namespace csi

@@ -4,7 +4,7 @@
 //                   (the reference reads a FieldTimeSeries as fts[i, j, 1, Time(clock.time)], e.g. the snowfall of
 //                   SeaIceThermodynamics/thermodynamic_time_step.jl:326-329; the formula is RECALLED from the un-vendored
 //                   Oceananigans: include/csi.h states it, tests/time_series_ref.py pins it)
-// ONE launch for every series-driven slot: the table of descriptors (at most fourteen) travels by value as the kernel argument, the grid
+// ONE launch for every series-driven slot: the table of descriptors (at most kMaxSeries, nineteen) travels by value as the kernel argument, the grid
 // runs over (column block, row block, slot).  Writes the INTERIOR of the bound array only; the halos of the velocity-point slots stay
 // update_external_stress' to fill.
 //

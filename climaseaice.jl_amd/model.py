@@ -32,6 +32,12 @@ _SERIES_SLOT_OF = {"top_heat_flux": "TOP_HEAT_FLUX", "bottom_heat_flux": "BOTTOM
                    "bottom_salinity": "BOTTOM_SALINITY", "ocean_surface_heat_flux": "ML_SURFACE_HEAT_FLUX",
                    "ocean_coefficient": "ML_COEFFICIENT", "ocean_reference_temperature": "ML_REFERENCE_TEMPERATURE",
                    "ocean_deep_heat_flux": "ML_DEEP_HEAT_FLUX"}
+_SHORTWAVE_SERIES_SLOT_OF = {"shortwave": "SHORTWAVE"}      # ... and the ShortwaveRadiation term's flux
+
+
+def series_slot_of(name):
+    """The csi_time_series_set slot that a FieldTimeSeries given for the per-cell input `name` drives."""
+    return _SERIES_SLOT_OF[name] if name in _SERIES_SLOT_OF else _SHORTWAVE_SERIES_SLOT_OF[name]
 
 
 def _cell_shape_ok(value, grid):
@@ -47,14 +53,15 @@ def _cell_shape_ok(value, grid):
 
 
 def check_heat_flux(spec, side, grid):
-    """Refuse, by name, what the C ABI cannot take: closures (FluxFunction, callables), RadiativeEmission or LinearHeatFlux at the
-    bottom, more than one array or LinearHeatFlux per side, arrays of the wrong shape (ValueError)."""
+    """Refuse, by name, what the C ABI cannot take: closures (FluxFunction, callables), RadiativeEmission, LinearHeatFlux or
+    ShortwaveRadiation at the bottom, more than one array, LinearHeatFlux or ShortwaveRadiation per side, arrays of the wrong shape
+    (ValueError)."""
     if spec is None or _is_number(spec) or (side == "bottom" and isinstance(spec, str) and spec == "frazil"):
         return
     items = spec if isinstance(spec, tuple) else (spec,)
     if len(items) > _lib.MAX_HEAT_FLUX_TERMS:
         raise NotImplementedError(f"{side}_heat_flux: at most {_lib.MAX_HEAT_FLUX_TERMS} terms")
-    arrays = linear = 0
+    arrays = linear = shortwave = 0
     for x in items:
         if _is_number(x):
             continue
@@ -71,6 +78,15 @@ def check_heat_flux(spec, side, grid):
                 if not _is_number(value) and not _cell_shape_ok(value, grid):
                     raise ValueError(f"LinearHeatFlux.{name}: a number, an array of shape (Ny, Nx) = {(grid.Ny, grid.Nx)} or a "
                                      "CenterField of the grid is needed")
+        elif isinstance(x, ShortwaveRadiation):
+            if side != "top":
+                raise NotImplementedError("ShortwaveRadiation is a top heat flux only")
+            shortwave += 1
+            if shortwave > 1:
+                raise NotImplementedError("top_heat_flux: at most one ShortwaveRadiation term (sum the fluxes into one)")
+            if not _is_number(x.flux) and not _cell_shape_ok(x.flux, grid):
+                raise ValueError(f"ShortwaveRadiation.flux: a number, an array of shape (Ny, Nx) = {(grid.Ny, grid.Nx)}, a CenterField of "
+                                 "the grid or a FieldTimeSeries on it is needed")
         elif isinstance(x, (Field, np.ndarray, list, FieldTimeSeries)):
             arrays += 1
             if arrays > 1:
@@ -81,12 +97,13 @@ def check_heat_flux(spec, side, grid):
         elif callable(x) or type(x).__name__ == "FluxFunction":
             raise NotImplementedError(f"{side}_heat_flux: {type(x).__name__} is not supported -- FluxFunction and other callables "
                                       "cannot cross the C ABI; give numbers, (Ny, Nx) arrays, CenterFields, RadiativeEmission "
-                                      "or a tuple of them; a bulk flux K (T - Ta) is data: LinearHeatFlux")
+                                      "or a tuple of them; a bulk flux K (T - Ta) is data: LinearHeatFlux, and so is absorbed shortwave with "
+                                      "a temperature-dependent albedo: ShortwaveRadiation")
         else:
             raise TypeError(f"{side}_heat_flux: unsupported term {type(x).__name__}")
 
 
-def check_heat_fluxes(grid, ice, top_heat_flux, bottom_heat_flux, snowfall=None):
+def check_heat_fluxes(grid, ice, top_heat_flux, bottom_heat_flux, snowfall=None, snow=None):
     """The checks SeaIceModel makes before it touches a device: fluxes given in one place only, and each one acceptable."""
     if top_heat_flux is not None and ice.top_heat_flux is not None:
         raise ValueError("top_heat_flux is given both to SeaIceModel and to SlabThermodynamics")
@@ -94,6 +111,10 @@ def check_heat_fluxes(grid, ice, top_heat_flux, bottom_heat_flux, snowfall=None)
         raise ValueError("bottom_heat_flux is given both to SeaIceModel and to SlabThermodynamics")
     check_heat_flux(top_heat_flux if top_heat_flux is not None else ice.top_heat_flux, "top", grid)
     check_heat_flux(bottom_heat_flux if bottom_heat_flux is not None else ice.bottom_heat_flux, "bottom", grid)
+    top = top_heat_flux if top_heat_flux is not None else ice.top_heat_flux
+    for x in (top if isinstance(top, tuple) else (top,)):
+        if isinstance(x, ShortwaveRadiation) and x.snow_albedo is not None and snow is None:
+            raise ValueError("ShortwaveRadiation.snow_albedo is given, but the model has no snow layer (snow_thermodynamics)")
     refuse_series(ice.prescribed, "PrescribedTemperature (the per-cell temperature is also state)")
     for name, value in (("snowfall", snowfall), ("PrescribedTemperature", ice.prescribed), ("bottom_salinity", ice.bottom_salinity)):
         if value is not None and not _is_number(value) and not _cell_shape_ok(value, grid):
@@ -188,6 +209,59 @@ class LinearHeatFlux:
     @property
     def per_cell(self):
         return not (_is_number(self.coefficient) and _is_number(self.reference_temperature))
+
+
+class SteppedAlbedo:
+    """alpha(T) = cold if T < threshold else warm (strict <): the albedo of examples/arctic_basin_seasonal_cycle.jl:106-110,
+    ifelse(Ts < -0.1, 0.75, 0.64), as data.  Both albedos lie in [0, 1]."""
+
+    def __init__(self, cold=0.75, warm=0.64, threshold=-0.1):
+        for name, v in (("cold", cold), ("warm", warm), ("threshold", threshold)):
+            if not _is_number(v) or not np.isfinite(v):
+                raise ValueError(f"SteppedAlbedo.{name}: a finite number is needed")
+        for name, v in (("cold", cold), ("warm", warm)):
+            if not 0.0 <= v <= 1.0:
+                raise ValueError(f"SteppedAlbedo.{name} = {v}: an albedo lies in [0, 1]")
+        self.cold, self.warm, self.threshold = float(cold), float(warm), float(threshold)
+
+
+class ShortwaveRadiation:
+    """Absorbed shortwave radiation with a temperature-dependent albedo, the closure of examples/arctic_basin_seasonal_cycle.jl:106-110 as
+    data: Q(T) = (F * (1 - alpha(T))) * w at the surface temperature T, in this order (include/csi.h, csi_shortwave_set).
+    flux F (W m^-2, positive upward like every heat flux: sunlight reaching the surface is negative): a number, an (Ny, Nx) array, a
+    CenterField or a FieldTimeSeries.  albedo: a SteppedAlbedo; snow_albedo: a second one for the cells of a model with a snow layer
+    whose hs at the start of the step is > 0 (None: `albedo` serves both).  area_weighting: as LinearHeatFlux's, default None.
+    A term of top_heat_flux, alone or in a tuple, at most one; with MeltingConstrainedFluxBalance the surface temperature is solved per
+    cell by the secant method, and model.albedo_used holds the albedo every step used.  Give the balance its RadiativeEmission term as
+    well, as the example does: beside terms that are linear in T alone the secant can cycle across the albedo's jump until maxiters
+    (include/csi.h)."""
+
+    def __init__(self, flux, albedo=None, snow_albedo=None, area_weighting=None):
+        if area_weighting not in _WEIGHTINGS:
+            raise ValueError('ShortwaveRadiation.area_weighting: "concentration", "ice_present" or None')
+        albedo = SteppedAlbedo() if albedo is None else albedo
+        for name, a in (("albedo", albedo), ("snow_albedo", snow_albedo)):
+            if not isinstance(a, SteppedAlbedo) and not (name == "snow_albedo" and a is None):
+                raise TypeError(f"ShortwaveRadiation.{name}: a SteppedAlbedo is needed, got {type(a).__name__} (a closure cannot cross "
+                                "the C ABI; a continuous ramp is not offered: include/csi.h)")
+        if callable(flux) or type(flux).__name__ == "FluxFunction" or isinstance(flux, (str, bool)) or flux is None:
+            raise TypeError(f"ShortwaveRadiation.flux: a number, an (Ny, Nx) array, a CenterField or a FieldTimeSeries is needed, got "
+                            f"{type(flux).__name__}")
+        if _is_number(flux) and not np.isfinite(flux):
+            raise ValueError("ShortwaveRadiation.flux is not finite")
+        self.flux = float(flux) if _is_number(flux) else flux
+        self.albedo, self.snow_albedo, self.area_weighting = albedo, snow_albedo, area_weighting
+
+    @property
+    def per_cell(self):
+        return not _is_number(self.flux)
+
+    def params(self):
+        """The csi_shortwave this term describes."""
+        a, s = self.albedo, self.snow_albedo
+        return _lib.Shortwave(0.0 if self.per_cell else self.flux, a.cold, a.warm, a.threshold,
+                              s.cold if s else 0.0, s.warm if s else 0.0, s.threshold if s else 0.0,
+                              _WEIGHTINGS[self.area_weighting], int(self.per_cell), int(s is not None), 0)
 
 
 def bulk_sensible_heat_flux(transfer_coefficient, atmosphere_density, atmosphere_heat_capacity, atmosphere_wind_speed,
@@ -335,7 +409,8 @@ class SeaIceModel:
         # external_heat_fluxes (sea_ice_model.jl:262-264): given here or in SlabThermodynamics; _configure_heat resolves them
         self._heat_flux_args = (top_heat_flux, bottom_heat_flux)
         if ice_thermodynamics is not None:
-            check_heat_fluxes(grid, ice_thermodynamics, top_heat_flux, bottom_heat_flux, snowfall if snow_thermodynamics else None)
+            check_heat_fluxes(grid, ice_thermodynamics, top_heat_flux, bottom_heat_flux, snowfall if snow_thermodynamics else None,
+                              snow=snow_thermodynamics)
         # ocean: None (the bottom heat flux is given) or a SlabOceanMixedLayer, which computes it (ocean.py; include/csi.h)
         check_ocean(grid, ocean, ice_thermodynamics, bottom_heat_flux, _cell_shape_ok)
         self.ocean = ocean
@@ -386,6 +461,9 @@ class SeaIceModel:
         self._series, self._pending_series = {}, []     # slot name -> what csi_time_series_set was given (kept alive)
         self.linear_heat_flux = None        # the LinearHeatFlux term's per-cell (coefficient, reference_temperature) fields, if any
         self.bottom_salinity = None         # the per-cell bottom salinity's field, if any
+        self.shortwave = None               # the ShortwaveRadiation term, if any, and its per-cell flux's field
+        self.shortwave_flux = None
+        self._albedo_used = None
         self._heat_fluxes_used = None
         self.ctx = _lib.Context(dev.index or 0, stream)
         self._configure()
@@ -539,7 +617,7 @@ class SeaIceModel:
             return value
         if isinstance(value, FieldTimeSeries):      # the series writes into a new field (bound by the caller, registered after it)
             fld = CenterField(g, self.device, name)
-            self._pending_series.append((_SERIES_SLOT_OF[name], value, fld))
+            self._pending_series.append((series_slot_of(name), value, fld))
             return fld
         arr = np.asarray(value, dtype=np.float64)
         if arr.ndim == 0:                           # a number beside a per-cell partner (LinearHeatFlux): broadcast
@@ -578,6 +656,14 @@ class SeaIceModel:
                     self.linear_heat_flux = SimpleNamespace(coefficient=k, reference_temperature=ta)
                 else:
                     t.value, t.reference_temperature = x.coefficient, x.reference_temperature
+            elif isinstance(x, ShortwaveRadiation):
+                t.kind = _lib.FLUX_SHORTWAVE          # (marks the position in the sum; csi_shortwave_set carries the rest, first)
+                if x.per_cell:
+                    self.shortwave_flux = self._cell_field(x.flux, "shortwave")
+                    self._bind("SHORTWAVE", self.shortwave_flux)
+                self.shortwave = x
+                self._shortwave_params = x.params()
+                self.ctx.call("csi_shortwave_set", C.byref(self._shortwave_params))
             else:
                 field = self._cell_field(x, f"{side}_heat_flux")
                 t.kind = _lib.FLUX_ARRAY
@@ -734,6 +820,20 @@ class SeaIceModel:
             self._bind("BOTTOM_HEAT_FLUX_USED", bottom)
             self._heat_fluxes_used = SimpleNamespace(top=top, bottom=bottom)
         return self._heat_fluxes_used
+
+    @property
+    def albedo_used(self):
+        """The CenterField into which every thermodynamic step writes the albedo its ShortwaveRadiation term used, at the surface
+        temperature the step solved or was given.  Allocated and bound the first time it is asked for.  Read it after the step
+        (synchronize() first); in an RK3 step it holds the last stage's values."""
+        if self.shortwave is None:
+            raise ValueError("albedo_used needs a ShortwaveRadiation term in top_heat_flux")
+        if self._albedo_used is None:
+            fld = CenterField(self.grid, self.device, "albedo_used")
+            torch.cuda.synchronize(self.device)      # (the zero fill ran on torch's stream)
+            self._bind("ALBEDO_USED", fld)
+            self._albedo_used = fld
+        return self._albedo_used
 
     def external_stress_field(self, slot, comp):
         return self._stress_fields[f"{slot}_{comp}"]

@@ -205,6 +205,10 @@ def bound_fields(model):
     if getattr(model, "_heat_fluxes_used", None) is not None:     # the used-flux outputs, once allocated (model.heat_fluxes_used)
         out["top_heat_flux_used"] = (model._heat_fluxes_used.top, "TOP_HEAT_FLUX_USED")
         out["bottom_heat_flux_used"] = (model._heat_fluxes_used.bottom, "BOTTOM_HEAT_FLUX_USED")
+    if getattr(model, "shortwave_flux", None) is not None:        # the ShortwaveRadiation term's per-cell flux
+        out["shortwave"] = (model.shortwave_flux, "SHORTWAVE")
+    if getattr(model, "_albedo_used", None) is not None:          # the albedo a step used, once allocated (model.albedo_used)
+        out["albedo_used"] = (model._albedo_used, "ALBEDO_USED")
     if getattr(model, "ocean", None) is not None:                 # the mixed layer: its temperature, per-cell inputs, Qow once allocated
         out.update(model.ocean.bound_fields())
     from .derived import slot_of
@@ -289,6 +293,7 @@ class OutputWriter:
               they are allocated here and computed on the device immediately before every accumulate and snapshot; so are
               the momentum term fields ("top_x", "internal_y", ...: momentum_terms.py)
               "ocean.temperature" and "ocean.surface_flux_used" name the mixed layer's fields (ocean.py); the second is allocated here
+              "albedo_used" names the albedo a ShortwaveRadiation term used (model.albedo_used); it is allocated here
     schedule  IterationInterval, TimeInterval (snapshots) or AveragedTimeInterval (every output is a time average)
     dtype     "f32" (round to nearest even on the device) or "f64"
     mask      True: (Center, Center) outputs take fill_value in the inactive cells of the model's mask
@@ -318,6 +323,8 @@ class OutputWriter:
                     model.momentum_term(name)
         if not isinstance(outputs, dict) and "ocean.surface_flux_used" in outputs and getattr(model, "ocean", None) is not None:
             model.ocean.surface_flux_used        # (allocated and bound the first time it is asked for)
+        if not isinstance(outputs, dict) and "albedo_used" in outputs and getattr(model, "shortwave", None) is not None:
+            model.albedo_used                    # (likewise)
         bound = recorder.bound_fields(model)
         if isinstance(outputs, dict):
             items = []

@@ -8,7 +8,7 @@ InMemory() / InMemory(n)                                               all slice
 
 A series drives one of fourteen arrays of a SeaIceModel: the stress components or external velocities of the top and bottom stresses,
 model.forcing u / v, the free-drift fields, the array term of the top / bottom heat flux, snowfall, the coefficient and reference
-temperature of a LinearHeatFlux, the bottom salinity.  The model allocates the array as
+temperature of a LinearHeatFlux, the bottom salinity (and the mixed layer's four inputs and the flux of a ShortwaveRadiation: nineteen).  The model allocates the array as
 for a plain array and registers the series; csi_time_series_update interpolates it in place at the start of every step.
 """
 import numpy as np

@@ -425,7 +425,8 @@ int32_t csi_slab_params_set(csi_context* ctx, const csi_slab_params* p);
  * (csi_sync, or work queued on the context's stream).  In an RK3 step they hold the last stage's values.
  *
  * The five slots are numbered from CSI_F_COUNT_BINDABLE on, so that every older id and count keeps its value. */
-typedef enum { CSI_FLUX_CONSTANT = 0, CSI_FLUX_ARRAY = 1, CSI_FLUX_RADIATIVE_EMISSION = 2, CSI_FLUX_LINEAR = 3 } csi_heat_flux_kind;
+typedef enum { CSI_FLUX_CONSTANT = 0, CSI_FLUX_ARRAY = 1, CSI_FLUX_RADIATIVE_EMISSION = 2, CSI_FLUX_LINEAR = 3,
+               CSI_FLUX_SHORTWAVE = 4 /* see csi_shortwave_set */ } csi_heat_flux_kind;
 typedef enum { CSI_HEAT_TOP = 0, CSI_HEAT_BOTTOM = 1 } csi_heat_flux_side;
 typedef enum { CSI_WEIGHT_NONE = 0, CSI_WEIGHT_CONCENTRATION = 1, CSI_WEIGHT_ICE_PRESENT = 2 } csi_flux_weighting;
 #define CSI_LINEAR_WEIGHT_MASK 3
@@ -539,7 +540,8 @@ int32_t csi_dynamics_set(csi_context* ctx, int32_t kind);
  * velocities), CSI_F_FORCING_U / _V, CSI_F_FREE_DRIFT_U / _V, CSI_F_TOP_HEAT_FLUX, CSI_F_BOTTOM_HEAT_FLUX, CSI_F_SNOWFALL.
  * Three thermodynamic inputs joined the eleven, fourteen in all: CSI_F_FLUX_COEFFICIENT, CSI_F_FLUX_REFERENCE_TEMPERATURE and
  * CSI_F_BOTTOM_SALINITY (csi_heat_fluxes_set); they ride in the same launch.  So do the mixed layer's four inputs (csi_mixed_layer_set:
- * CSI_F_ML_SURFACE_HEAT_FLUX, CSI_F_ML_COEFFICIENT, CSI_F_ML_REFERENCE_TEMPERATURE, CSI_F_ML_DEEP_HEAT_FLUX), eighteen in all.
+ * CSI_F_ML_SURFACE_HEAT_FLUX, CSI_F_ML_COEFFICIENT, CSI_F_ML_REFERENCE_TEMPERATURE, CSI_F_ML_DEEP_HEAT_FLUX), eighteen in all, and the
+ * SHORTWAVE term's flux (csi_shortwave_set: CSI_F_SHORTWAVE), nineteen.
  * csi_time_series_update(ctx, t) interpolates every series in ONE launch, in place, into the INTERIOR of the arrays bound to those
  * slots -- the arrays the momentum and thermodynamic kernels already read; no kernel of theirs changes.  The halos of the
  * velocity-point slots stay the library's to fill where it fills them for plain arrays (csi_time_step_momentum; csi_free_drift_set).
@@ -586,7 +588,7 @@ typedef struct {
     int64_t ld;              /* doubles between rows */
     int64_t slice_stride;    /* doubles between slices */
 } csi_time_series;
-/* Set (or, ts == NULL, remove) the series of one slot.  Any slot but the eleven and the three: CSI_ERR_INVALID_ARGUMENT.  The slot's field must be
+/* Set (or, ts == NULL, remove) the series of one slot.  Any slot but these nineteen: CSI_ERR_INVALID_ARGUMENT.  The slot's field must be
  * bound (CSI_ERR_NOT_BOUND): the series writes into that array.  Setting a slot again replaces its series (empty window, zero uploads). */
 int32_t csi_time_series_set(csi_context* ctx, int32_t field_id, const csi_time_series* ts);
 /* Interpolate every series at `time` into its bound array, one launch on the context's stream (no series: nothing is launched, CSI_OK).
@@ -1009,6 +1011,60 @@ typedef struct {
 int32_t csi_mixed_layer_set(csi_context* ctx, const csi_mixed_layer_params* p);
 int32_t csi_mixed_layer_step(csi_context* ctx, double dt, int32_t from_cache);
 int32_t csi_mixed_layer_stats(csi_context* ctx, int64_t* launches);
+
+/* ---- absorbed shortwave radiation with a temperature-dependent (stepped) albedo ------------------------------------------------------
+ * The fifth top heat-flux term of the reference's examples/arctic_basin_seasonal_cycle.jl (Semtner 1976), which writes it into a
+ * FluxFunction closure: Q * (1 - alpha) with alpha = ifelse(Ts < -0.1, 0.75, 0.64).  As data it is CSI_FLUX_SHORTWAVE = 4, a fifth
+ * csi_heat_flux_kind: top only, at most one per model, and it takes its place in the right-nested sum like any other term.  Its value at
+ * surface temperature T is formed in exactly this order, uncontracted, in STRICT and FAST alike:
+ *     alpha = (T < threshold) ? cold : warm          strict <: T == threshold takes warm
+ *     Q     = (F * (1 - alpha)) * w                  w as for LINEAR: CSI_WEIGHT_NONE no product, CSI_WEIGHT_CONCENTRATION w = aice[i, j]
+ *                                                    at the start of the step, CSI_WEIGHT_ICE_PRESENT (aice == 0) ? 0 : F * (1 - alpha)
+ * F (flux, W m^-2, positive upward like every heat flux here: sunlight reaching the ice is negative) is a number, or with per_cell = 1
+ * is read per cell from the (c,c) array bound to CSI_F_SHORTWAVE.  The layered step uses the second triple (snow_cold, snow_warm,
+ * snow_threshold) in cells whose hs at the start of the step is > 0 -- the condition under which it sets Tm = 0; with has_snow_pair = 0
+ * the ice triple serves both.  The parameters do not fit csi_heat_flux_term, whose size and offsets do not change: they travel in
+ * csi_shortwave through csi_shortwave_set, and the term in the tuple is {kind = CSI_FLUX_SHORTWAVE}, which marks the position in the
+ * sum (its other members are ignored).  csi_shortwave_set(ctx, NULL) removes the setting.
+ *   CSI_ERR_INVALID_ARGUMENT, by name: a SHORTWAVE term in csi_heat_fluxes_set (or at a step) without the set call; a set call whose
+ *   per_cell flag finds no array bound to CSI_F_SHORTWAVE; an albedo outside [0, 1]; a non-finite value; an unknown weighting;
+ *   reserved != 0.  CSI_ERR_UNSUPPORTED: the term at the bottom, two SHORTWAVE terms.
+ * The term makes Qx depend on T.  Under MeltingConstrainedFluxBalance every consolidated cell runs the secant solve of
+ * csi_heat_fluxes_set, with the same tol and maxiters and no closed form; Qx is then evaluated once at the capped temperature, so a
+ * cell capped at Tm >= threshold melts with the warm albedo.  Under PrescribedTemperature the term is evaluated at the prescribed
+ * temperature.  Qx is discontinuous at the threshold: where the balance has no root on either branch the iterates step across the jump
+ * and the solve ends, by its |x1 - x0| < tol rule, within tol of the threshold.
+ * Where the solve's two points straddle the threshold with nearly equal residuals it can also end by that rule away from balance (9 of
+ * the 200 000 cells below).  LIMIT: beside terms that leave the balance LINEAR in T (no RadiativeEmission) f is two parallel lines with
+ * a jump between them, and once the two points lie on different sides the secant can cycle until maxiters; the last iterate is then the
+ * root, as for any unconverged solve.  A surface balance with emission, like the example's, curves and does not cycle.  All of this is
+ * the reference's solver applied to the reference's closure; nothing is substituted.
+ * NOT OFFERED: a continuous ramp albedo, linear in T between two temperatures.  On 200 000 random cells (h 0.05-4 m, shortwave
+ * 0-320 W m^-2, other downward fluxes 120-330 W m^-2, emission, Tu- in -30...0) the stepped form converged everywhere in at most 135
+ * updates; a ramp over -1...0 left 246 cells cycling until maxiters = 1000.  A term the reference's solver cannot solve is not offered.
+ * Neither are: an albedo that depends on thickness or snow depth, shortwave penetration, albedo parameters per cell, melt ponds.
+ *
+ * One optional OUTPUT slot, CSI_F_ALBEDO_USED: when bound and a SHORTWAVE term is set, the thermodynamic step writes the alpha it used
+ * at the temperature it solved (or was prescribed) into its interior.  A model with the term runs the flux kernels already.
+ * CSI_F_TOP_HEAT_FLUX_USED includes the absorbed shortwave, since it is Qx(Tu).  CSI_F_SHORTWAVE may be driven by a time series
+ * (csi_time_series_set: nineteen slots, one launch).
+ *
+ * The two slots are numbered from CSI_F_COUNT_MIXED_LAYER on, so that every older id and count keeps its value. */
+typedef enum {
+    CSI_F_SHORTWAVE = CSI_F_COUNT_MIXED_LAYER,       /* (c,c) F per cell, W m^-2 */
+    CSI_F_ALBEDO_USED,                               /* (c,c) optional output: alpha */
+    CSI_F_COUNT_SHORTWAVE                            /* every slot csi_field_bind takes */
+} csi_shortwave_field_id;
+typedef struct {
+    double flux;                       /* F, W m^-2 (ignored with per_cell) */
+    double cold, warm, threshold;      /* alpha = (T < threshold) ? cold : warm; 0.75, 0.64, -0.1 */
+    double snow_cold, snow_warm, snow_threshold;   /* the same for cells with hs > 0 (layered step, has_snow_pair) */
+    int32_t weighting;                 /* csi_flux_weighting */
+    int32_t per_cell;                  /* 1: F per cell from CSI_F_SHORTWAVE */
+    int32_t has_snow_pair;             /* 1: the snow triple is used where hs > 0 */
+    int32_t reserved;                  /* 0 */
+} csi_shortwave;
+int32_t csi_shortwave_set(csi_context* ctx, const csi_shortwave* p);
 
 /* ---- rheology and momentum solver (SeaIceMomentumEquation(grid; rheology, solver), sea_ice_momentum_equations.jl:67-94) ------------
  * Defaults: CSI_RHEOLOGY_EVP with CSI_SOLVER_SPLIT_EXPLICIT -- the library's EVP path, unchanged by these calls.  The scalars both

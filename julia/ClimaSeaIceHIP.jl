@@ -129,13 +129,26 @@ struct CsiMixedLayerParams
 end
 @assert sizeof(CsiMixedLayerParams) == 72 && fieldoffset(CsiMixedLayerParams, 9) == 64      # the layout gcc gives csi_mixed_layer_params
 
+# csi_shortwave_field_id (from CSI_F_COUNT_MIXED_LAYER on): the SHORTWAVE top term's per-cell flux and the albedo the last step used
+const SHORTWAVE = (SHORTWAVE=70, ALBEDO_USED=71)
+# csi_heat_flux_kind's SHORTWAVE term Q(T) = (F * (1 - alpha(T))) * w with alpha = (T < threshold) ? cold : warm: the term only marks the
+# position in the sum, csi_shortwave_set carries the rest
+const CSI_FLUX_SHORTWAVE = 4
+# csi_shortwave (include/csi.h, where the term is defined): F, the ice triple, the snow triple, weighting and the two flags
+struct CsiShortwave
+    flux::Cdouble; cold::Cdouble; warm::Cdouble; threshold::Cdouble
+    snow_cold::Cdouble; snow_warm::Cdouble; snow_threshold::Cdouble
+    weighting::Int32; per_cell::Int32; has_snow_pair::Int32; reserved::Int32
+end
+@assert sizeof(CsiShortwave) == 72 && fieldoffset(CsiShortwave, 8) == 56      # the layout gcc gives csi_shortwave
+
 # A FluxFunction is a closure and cannot cross the C ABI: it raises by name.  Its usual content, the bulk form K (Tu - Ta) [* aice], is data:
 # csi_heat_fluxes_set takes it as a CSI_FLUX_LINEAR term.
 function refuse_flux_function(flux, side)
     items = flux isa Tuple ? flux : (flux,)
     for x in items
         nameof(typeof(x)) === :FluxFunction &&
-            error("ClimaSeaIceHIP: $(side)_heat_flux: a FluxFunction cannot cross the C ABI; give the bulk form K (Tu - Ta) as a LinearHeatFlux term (CSI_FLUX_LINEAR)")
+            error("ClimaSeaIceHIP: $(side)_heat_flux: a FluxFunction cannot cross the C ABI; give the bulk form K (Tu - Ta) as a LinearHeatFlux term (CSI_FLUX_LINEAR), absorbed shortwave with a stepped albedo through attach_shortwave! (CSI_FLUX_SHORTWAVE)")
     end
     return nothing
 end
@@ -654,6 +667,29 @@ function attach_mixed_layer!(ctx, temperature, bottom_heat_flux; depth, temperat
     p = Ref(CsiMixedLayerParams(density, heat_capacity, depth, ice_ocean_exchange_velocity, number(surface_heat_flux), number(coefficient),
                                 number(atmosphere_temperature), number(deep_heat_flux), flags, 0))
     check(ctx, ccall((:csi_mixed_layer_set, libcsi), Int32, (Ptr{Cvoid}, Ref{CsiMixedLayerParams}), ctx.handle, p))
+    return nothing
+end
+
+# ---- absorbed shortwave with a stepped albedo (include/csi.h, csi_shortwave_set) ----------------------------------------------------
+# What the closure of examples/arctic_basin_seasonal_cycle.jl:106-110 does, as data: Q * (1 - ifelse(Ts < -0.1, 0.75, 0.64)).
+# attach_shortwave!(ctx, flux; ...) describes the term: flux a Number, or a Field / FieldTimeSeries bound to SHORTWAVE.SHORTWAVE
+# (bind_forcing!); albedo and snow_albedo are (cold, warm, threshold) tuples.  Call it BEFORE csi_heat_fluxes_set with a
+# CSI_FLUX_SHORTWAVE term, which marks the term's position in the top heat flux's right-nested sum.  albedo_used, a Center field, receives
+# the albedo every thermodynamic step used.
+function attach_shortwave!(ctx, flux; albedo = (0.75, 0.64, -0.1), snow_albedo = nothing, weighting = CSI_WEIGHT_NONE, albedo_used = nothing)
+    nameof(typeof(flux)) === :FluxFunction &&
+        error("ClimaSeaIceHIP: attach_shortwave!: a FluxFunction cannot cross the C ABI; give a Number or a field and the albedo as numbers")
+    for a in (albedo, snow_albedo)
+        a === nothing && continue
+        (0 <= a[1] <= 1 && 0 <= a[2] <= 1) || error("ClimaSeaIceHIP: attach_shortwave!: an albedo lies in [0, 1]")
+    end
+    per_cell = !(flux isa Number)
+    per_cell && bind_forcing!(ctx, SHORTWAVE.SHORTWAVE, flux)
+    albedo_used === nothing || bind!(ctx, SHORTWAVE.ALBEDO_USED, albedo_used)
+    s = snow_albedo === nothing ? (0.0, 0.0, 0.0) : snow_albedo
+    p = Ref(CsiShortwave(per_cell ? 0.0 : flux, albedo[1], albedo[2], albedo[3], s[1], s[2], s[3], weighting, per_cell ? 1 : 0,
+                         snow_albedo === nothing ? 0 : 1, 0))
+    check(ctx, ccall((:csi_shortwave_set, libcsi), Int32, (Ptr{Cvoid}, Ref{CsiShortwave}), ctx.handle, p))
     return nothing
 end
 
