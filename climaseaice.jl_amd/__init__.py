@@ -20,7 +20,8 @@ from .momentum_terms import MOMENTUM_TERMS, TERM_FIELD_NAMES, MomentumBudget
 from .output import (AveragedTimeInterval, IterationInterval, OutputWriter, TimeInterval, aligned_time_step, bound_fields,
                      load_output)
 from .ocean import SlabOceanMixedLayer
-from .time_series import Clamp, Cyclical, FieldTimeSeries, InMemory, Linear
+from .time_series import (Clamp, Cyclical, FieldTimeSeries, InMemory, Linear, RegriddedTimeSeries, RegriddedVectorTimeSeries, SourceGrid,
+                          fill_missing)
 from .model import (FieldBoundaryConditions, FluxBoundaryCondition, ImmersedBoundaryCondition, MeltingConstrainedFluxBalance, ValueBoundaryCondition, PrescribedTemperature, RadiativeEmission, LinearHeatFlux, bulk_sensible_heat_flux, SteppedAlbedo, ShortwaveRadiation, SeaIceModel, SlabThermodynamics, SnowSlabThermodynamics,
                     snow_slab_thermodynamics, UpwindBiased, WENO, set_, time_step, time_step_momentum, compute_momentum_tendencies, update_state,
                     prognostic_state, restore_prognostic_state)

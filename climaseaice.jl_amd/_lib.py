@@ -74,6 +74,8 @@ HEAT_TOP, HEAT_BOTTOM = 0, 1
 MAX_HEAT_FLUX_TERMS = 8
 TIME_CLAMP, TIME_CYCLICAL, TIME_LINEAR = 0, 1, 2
 SERIES_DEVICE, SERIES_HOST = 0, 1
+REGRID_FACE_CENTER, REGRID_CENTER_FACE, REGRID_CENTER_CENTER = 0, 1, 2      # csi_regrid_location
+REGRID_MAX_MAPS, REGRID_MAX_SOURCE_EXTENT = 16, 65536
 # the eleven slots a time series may drive (csi_time_series_set)
 SERIES_SLOTS = ["TOP_U", "TOP_V", "BOT_U", "BOT_V", "FORCING_U", "FORCING_V", "FREE_DRIFT_U", "FREE_DRIFT_V",
                 "TOP_HEAT_FLUX", "BOTTOM_HEAT_FLUX", "SNOWFALL"]
@@ -98,6 +100,7 @@ SYMBOLS = ["csi_version", "csi_context_create", "csi_context_destroy", "csi_last
            "csi_rheology_set", "csi_momentum_solver_set", "csi_compute_momentum_tendencies",
            "csi_heat_fluxes_set", "csi_surface_solve_set", "csi_dynamics_set",
            "csi_time_series_plan", "csi_time_series_set", "csi_time_series_update", "csi_time_series_status",
+           "csi_regrid_plan_axis", "csi_regrid_map_create", "csi_regrid_map_destroy", "csi_time_series_set_regridded", "csi_regrid_stats",
            "csi_diagnostics_compute",
            "csi_output_plan_layout", "csi_output_create", "csi_output_layout", "csi_output_record_bytes", "csi_output_accumulate",
            "csi_output_snapshot", "csi_output_test", "csi_output_wait", "csi_output_release", "csi_output_destroy",
@@ -178,6 +181,14 @@ class Shortwave(C.Structure):
 class TimeSeries(C.Structure):
     _fields_ = [("nt", C.c_int32), ("indexing", C.c_int32), ("backend", C.c_int32), ("window", C.c_int32), ("period", C.c_double),
                 ("times", C.POINTER(C.c_double)), ("data", C.c_void_p), ("ld", C.c_int64), ("slice_stride", C.c_int64)]
+
+
+class RegridMap(C.Structure):
+    """csi_regrid_map (include/csi.h): one location's target points on a source grid -- indices, weights and optionally the rotation."""
+    _fields_ = [("location", C.c_int32), ("nx", C.c_int32), ("ny", C.c_int32), ("src_nx", C.c_int32), ("src_ny", C.c_int32),
+                ("reserved", C.c_int32), ("i0", C.POINTER(C.c_int32)), ("i1", C.POINTER(C.c_int32)), ("j0", C.POINTER(C.c_int32)),
+                ("j1", C.POINTER(C.c_int32)), ("wx", C.POINTER(C.c_double)), ("wy", C.POINTER(C.c_double)),
+                ("cos", C.POINTER(C.c_double)), ("sin", C.POINTER(C.c_double))]
 
 
 class Diagnostics(C.Structure):
@@ -282,6 +293,10 @@ def load():
         "csi_time_series_plan": [C.POINTER(dbl), i32, i32, dbl, dbl, C.POINTER(i32), C.POINTER(i32), C.POINTER(dbl)],
         "csi_time_series_set": [vp, i32, C.POINTER(TimeSeries)], "csi_time_series_update": [vp, dbl],
         "csi_time_series_status": [vp, i32, C.POINTER(i32), C.POINTER(i64)],
+        "csi_regrid_plan_axis": [C.POINTER(dbl), i32, i32, dbl, dbl, C.POINTER(i32), C.POINTER(i32), C.POINTER(dbl)],
+        "csi_regrid_map_create": [vp, C.POINTER(RegridMap), C.POINTER(i32)], "csi_regrid_map_destroy": [vp, i32],
+        "csi_time_series_set_regridded": [vp, i32, C.POINTER(TimeSeries), i32, C.POINTER(TimeSeries), i32],
+        "csi_regrid_stats": [vp, C.POINTER(i64), C.POINTER(i32)],
         "csi_diagnostics_compute": [vp, i32, dbl, C.POINTER(Diagnostics)],
         "csi_output_plan_layout": [C.POINTER(i32), C.POINTER(i32), C.POINTER(i32), i32, C.POINTER(i64), C.POINTER(i64)],
         "csi_output_create": [vp, C.POINTER(OutputField), i32, i32, C.POINTER(i32)],
@@ -345,6 +360,17 @@ def time_series_plan(times, indexing, period, t):
     if rc != OK:
         raise CsiError(rc, "csi_time_series_plan: invalid input")
     return n1.value, n2.value, frac.value
+
+
+def regrid_plan_axis(nodes, periodic, period, x):
+    """csi_regrid_plan_axis: (i0, i1, weight of i1) of coordinate x on a source axis (pure host function; CsiError on invalid input)."""
+    a = np.ascontiguousarray(nodes, dtype=np.float64)
+    i0, i1, w = C.c_int32(), C.c_int32(), C.c_double()
+    rc = load().csi_regrid_plan_axis(a.ctypes.data_as(C.POINTER(C.c_double)), a.size, int(bool(periodic)), float(period or 0.0), float(x),
+                                     C.byref(i0), C.byref(i1), C.byref(w))
+    if rc != OK:
+        raise CsiError(rc, "csi_regrid_plan_axis: invalid input")
+    return i0.value, i1.value, w.value
 
 
 def output_plan_layout(shapes, dtypes):
@@ -510,6 +536,29 @@ class Context:
         res, up = (C.c_int32 * max(int(window), 1))(*([-1] * max(int(window), 1))), C.c_int64()
         self.call("csi_time_series_status", slot_id(slot), res, C.byref(up))
         return list(res)[:int(window)], up.value
+
+    # ---- series on a source grid of their own (include/csi.h, csi_regrid_map_create) -----------------------------------------------
+    def regrid_map_create(self, location, i0, i1, j0, j1, wx, wy, source_shape, cos=None, sin=None):
+        """csi_regrid_map_create: the map's id.  location: REGRID_*; i0 .. wy (and cos, sin): (ny, nx) arrays; source_shape: (src_ny, src_nx).
+        The library copies everything."""
+        ny, nx = np.shape(wx)
+        idx = [np.ascontiguousarray(a, dtype=np.int32) for a in (i0, i1, j0, j1)]
+        w = [np.ascontiguousarray(a, dtype=np.float64) for a in (wx, wy)]
+        rot = [None if a is None else np.ascontiguousarray(a, dtype=np.float64) for a in (cos, sin)]
+        if any(a.shape != (ny, nx) for a in idx + w + [a for a in rot if a is not None]):
+            raise ValueError("regrid map: every array has the (ny, nx) shape of the target interior")
+        ip, dp = C.POINTER(C.c_int32), C.POINTER(C.c_double)
+        d = RegridMap(int(location), nx, ny, int(source_shape[1]), int(source_shape[0]), 0, *[a.ctypes.data_as(ip) for a in idx],
+                      *[a.ctypes.data_as(dp) for a in w], *[None if a is None else a.ctypes.data_as(dp) for a in rot])
+        out = C.c_int32(-1)
+        self.call("csi_regrid_map_create", C.byref(d), C.byref(out))
+        return out.value
+
+    def regrid_stats(self):
+        """(launches of the regridding kernel so far, maps alive) of this context."""
+        n, m = C.c_int64(), C.c_int32()
+        self.call("csi_regrid_stats", C.byref(n), C.byref(m))
+        return n.value, m.value
 
     # ---- derived fields and energy budget integrals (include/csi.h) ---------------------------------------------------------------
     def derived_compute(self, mask):

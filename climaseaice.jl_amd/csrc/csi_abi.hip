@@ -121,9 +121,8 @@ static int32_t do_mixed_layer(csi_context* c, double dt, int from_cache) {
     if (bot.n != 1 || bot.kind[0] != FLUX_ARRAY)
         return fail(c, CSI_ERR_INVALID_ARGUMENT, "the mixed layer needs exactly one ARRAY bottom heat-flux term (csi_heat_fluxes_set): it writes Qb "
                                                  "into the array bound to bottom_heat_flux");
-    for (const TimeSeries& S : c->series)
-        if (S.fid == CSI_F_BOTTOM_HEAT_FLUX)
-            return fail(c, CSI_ERR_INVALID_ARGUMENT, "time series on bottom_heat_flux: the mixed layer (csi_mixed_layer_set) writes that array at every step");
+    if (series_drives(c, CSI_F_BOTTOM_HEAT_FLUX))
+        return fail(c, CSI_ERR_INVALID_ARGUMENT, "time series on bottom_heat_flux: the mixed layer (csi_mixed_layer_set) writes that array at every step");
     if (!(dt > 0) || !std::isfinite(dt)) return fail(c, CSI_ERR_INVALID_ARGUMENT, "the mixed layer needs a finite dt > 0");
     const csi_mixed_layer_params& p = c->ml;
     int32_t rc = need(c, {CSI_F_ML_TEMPERATURE, CSI_F_A, CSI_F_BOTTOM_HEAT_FLUX});
@@ -780,9 +779,8 @@ int32_t csi_mixed_layer_set(csi_context* c, const csi_mixed_layer_params* p) {
     if (p->exchange_velocity < 0) return fail(c, CSI_ERR_INVALID_ARGUMENT, "csi_mixed_layer_params.exchange_velocity must be >= 0");
     if ((p->flags & ~(CSI_ML_SURFACE_ARRAY | CSI_ML_BULK_ARRAYS | CSI_ML_DEEP_ARRAY | CSI_ML_HAS_SURFACE | CSI_ML_HAS_BULK)) || p->reserved)
         return fail(c, CSI_ERR_INVALID_ARGUMENT, "csi_mixed_layer_params.flags: unknown flag bits (reserved must be 0)");
-    for (const TimeSeries& S : c->series)
-        if (S.fid == CSI_F_BOTTOM_HEAT_FLUX)
-            return fail(c, CSI_ERR_INVALID_ARGUMENT, "time series on bottom_heat_flux: the mixed layer (csi_mixed_layer_set) writes that array at every step");
+    if (series_drives(c, CSI_F_BOTTOM_HEAT_FLUX))
+        return fail(c, CSI_ERR_INVALID_ARGUMENT, "time series on bottom_heat_flux: the mixed layer (csi_mixed_layer_set) writes that array at every step");
     c->ml = *p;
     c->ml_set = true;
     return CSI_OK;

@@ -147,6 +147,28 @@ struct TimeSeries {
     int cur[2] = {-1, -1}, next = -1;    // the newest update's pair and the slice wanted after it (series_prefetch)
 };
 
+// One regridding map (csi_regrid_map_create): the caller's arrays, validated and kept on the host, and their device layout
+// (csi_kernels.h RegridDesc), packed when the first slot that needs it is set: a layout per alignment pattern of the destination rows
+// (the first interior row starts on a 16-byte boundary or 8 bytes behind one; the row stride is even or odd).
+struct RegridMap {
+    bool live = false;
+    int location = 0, nx = 0, ny = 0, src_nx = 0, src_ny = 0;
+    bool rotation = false;
+    std::vector<unsigned long long> idx;         // {i0, i1, j0, j1} as uint16, ny * nx
+    std::vector<double> wx, wy, cs, sn;
+    int64_t mld = 0, plane = 0;                  // entries between rows / planes of a device layout
+    DeviceBuf<unsigned long long> dev[4];        // [head of row 0 * 2 + (ld odd)]
+};
+
+// One regridded slot (csi_time_series_set_regridded): a scalar's source series, or the east and the north series of a vector pair
+// -- each a TimeSeries whose slices have the source shape, with a ring of its own on the HOST backend.
+struct RegridSeries {
+    int fid = -1, map = -1, parts = 1, component = 0;
+    int variant = 0;                     // which device layout of the map the bound array's rows select
+    int64_t dst_ld = 0;                  // ... and the row stride it was chosen for
+    TimeSeries part[2];
+};
+
 // One output set (csi_output_create): the caller's field list, what the fields were bound to then, the record layout, the averaged
 // fields' accumulators and the staging slots on both sides of the bus.
 struct OutputSet {
@@ -292,6 +314,11 @@ struct csi_context {
     bool series_launched_valid = false;
     bool series_prefetch_pending = false;    // the newest update's look-ahead uploads have not been issued yet
     long series_updates = 0;
+    // csi_regrid_map_create / csi_time_series_set_regridded: the maps (a map's id is its index) and the regridded slots, at most one
+    // series of either kind per slot; they share the copy stream, the event and the look-ahead with the series above
+    std::vector<RegridMap> maps;
+    std::vector<RegridSeries> regrid;
+    int64_t regrid_launches = 0;         // csi_regrid_stats
     // the ordered reductions (csi_diagnostics_compute, csi_budget_compute, csi_momentum_budget_compute; reduce_begin in
     // csi_diagnostics.hip): ONE device buffer -- the partial records followed by the result slots, sized by the grid alone for the
     // largest slot count, so alternating calls never reallocate -- and ONE page-locked copy of the result; every such call ends in a
@@ -554,6 +581,7 @@ Range v_second_range(const csi_context* c, const SideV& v);
 static inline const Bound& band_bound(const csi_context* c, int q) { return c->f[c->band[q].fid]; }
 int32_t series_prefetch(csi_context* c);                 // ... the look-ahead uploads of the newest csi_time_series_update, once (no-op otherwise)
 void series_release(csi_context* c);                     // csi_time_series.hip: events, copy stream, rings (the streams have been drained)
+bool series_drives(const csi_context* c, int fid);       // ... a series of either kind (model grid, regridded) is set on the slot
 void output_release(csi_context* c);                     // csi_output.hip: every set, the copy stream (the context's stream has been drained)
 int32_t peer_check_entry(csi_context* c);      // (csi_abi.hip: the error word of the peer transport, checked at every entry point)
 

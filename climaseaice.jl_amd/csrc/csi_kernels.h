@@ -268,6 +268,29 @@ struct SeriesDesc {
 struct SeriesTable { int n; int pad_; SeriesDesc d[kMaxSeries]; };
 void launch_time_series(const SeriesTable& T, hipStream_t s);
 
+// ... given on a source grid of their own (time_series_regrid.hip; include/csi.h csi_time_series_set_regridded): every regridded slot
+// in ONE launch.  A descriptor: per source series (part 0: the scalar or the east series, part 1: the north series of a pair) the two
+// slices around the clock, their row stride and time weights as in SeriesDesc; the map's planes (entries of 8 bytes, `plane` entries
+// apart, rows mld entries apart: IDX, WX, WY and, with rotation, COS, SIN; target point x of row j at entry j * mld + x + head(j),
+// head(j) = 1 where the destination row's interior starts 8 bytes behind a 16-byte boundary -- the padding entries are zero); the
+// interior of the bound array.
+struct RegridDesc {
+    const double *a[2], *b[2];
+    double w1[2], w2[2];
+    long lds[2];
+    const unsigned long long* map;
+    long mld, plane;
+    double* dst;
+    long ldd;
+    int nx, ny;
+    int same[2];
+    int pair;                  // 0: scalar; 1: one component of a vector pair (the map has COS and SIN)
+    int component;             // 0: x = E cos + N sin; 1: y = N cos - E sin
+};
+struct RegridTable { int n; int pad_; RegridDesc d[kMaxSeries]; };
+static_assert(sizeof(RegridTable) <= 4096, "the table travels by value as the kernel argument");
+void launch_time_series_regrid(const RegridTable& T, hipStream_t s);
+
 // device diagnostics (diagnostics.hip; include/csi.h csi_diagnostics_compute).  One 8-byte slot per quantity, in this order, in every
 // partial record and in the result; the counts are int64 bit patterns in their slots.  Slots below DQ_VOLUME: CSI_DIAG_VELOCITY,
 // from DQ_VOLUME on: CSI_DIAG_TRACERS.

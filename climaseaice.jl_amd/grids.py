@@ -106,6 +106,18 @@ class _Grid2D:
         """KernelParameters(-Hx+2:Nx+Hx-1, -Hy+2:Ny+Hy-1), elasto_visco_plastic_rheology.jl:145."""
         return (-self.Hx + 2, self.Nx + self.Hx - 1, -self.Hy + 2, self.Ny + self.Hy - 1)
 
+    def rotation(self, LX, LY):
+        """(cos, sin) of the bearing of the grid's x direction against east at the interior points of (LX, LY), as (ny, nx) arrays: a
+        vector (E, N) in geographic axes has the grid components x = E cos + N sin, y = N cos - E sin.  Exactly (1, 0) on a grid
+        whose x direction is east (RectilinearGrid, LatitudeLongitudeGrid)."""
+        nx, ny = self.interior_size(LX, LY)
+        return np.ones((ny, nx)), np.zeros((ny, nx))
+
+    def target_nodes(self, LX, LY):
+        """The coordinates of the interior points of (LX, LY) in which a SourceGrid is given: (x, y) as 1-D arrays (nx,), (ny,) on a grid
+        with per-axis nodes, as (ny, nx) arrays on one with 2-D nodes."""
+        return np.asarray(self.xnodes(LX), dtype=np.float64), np.asarray(self.ynodes(LY), dtype=np.float64)
+
 
 class RectilinearGrid(_Grid2D):
     """RectilinearGrid(size=(Nx, Ny), x=(x0, x1), y=(y0, y1), topology=(TX, TY), halo=(Hx, Hy)), regular spacing."""
@@ -265,6 +277,20 @@ class OrthogonalCurvilinearGrid(_Grid2D):
                 out[name] = fold_north(out[name], g.Nx, g.Ny, g.Hx, g.Hy, name[2] == "f", name[3] == "f", 1)
         return cls((g.Nx, g.Ny), out, topology=g.topology, halo=(g.Hx, g.Hy), nodes=(g.xnodes, g.ynodes, g._ynode))
 
+    def _need_nodes(self, what):
+        if self._nodes is None:
+            raise NotImplementedError(f"OrthogonalCurvilinearGrid.{what}: the grid was given by its metrics alone -- without nodes there is no "
+                                      "bearing of its x direction and no coordinate to regrid to (use from_grid, or a TripolarGrid)")
+
+    def rotation(self, LX, LY):
+        """(1, 0): a grid made by from_grid keeps the x direction of the RectilinearGrid / LatitudeLongitudeGrid it came from."""
+        self._need_nodes("rotation")
+        return super().rotation(LX, LY)
+
+    def target_nodes(self, LX, LY):
+        self._need_nodes("target_nodes")
+        return super().target_nodes(LX, LY)
+
     def xnodes(self, LX):
         return self._nodes[0](LX)
 
@@ -401,6 +427,31 @@ class TripolarGrid(OrthogonalCurvilinearGrid):
         lam, phi = self._node_fn(xi, eta)
         return (lam + 180.0) % 360.0 - 180.0, phi
 
+    def _interior_coordinates(self, LX, LY):
+        ia, ja = np.arange(1, self.Nx + 1), np.arange(1, self.Ny + 1)
+        return (ia - 1.0 if LX is Face else ia - 0.5)[None, :], (ja - 1.0 if LY is Face else ja - 0.5)[:, None]
+
+    def rotation(self, LX, LY):
+        """(cos, sin) of the bearing of the net's x direction against east at the interior points of (LX, LY), (Ny, Nx) arrays.
+        THE DEFINITION: with (lam+, phi+) and (lam-, phi-) the nodes at column coordinate + 1/2 and - 1/2 of the point on its own row
+        (_node_fn) and phi the point's own latitude,
+            bearing = atan2(phi+ - phi-, cos(phi) * dlam),   dlam = lam+ - lam- wrapped to (-180, 180],
+        cos = cos(bearing), sin = sin(bearing).  In the latitude-longitude rows (row coordinate at or below the cap's first face) it is
+        exactly (1, 0).  A vector (E, N) has the grid components x = E cos + N sin, y = N cos - E sin."""
+        xi, eta = self._interior_coordinates(LX, LY)
+        lam_p, phi_p = self._node_fn(xi + 0.5, eta)
+        lam_m, phi_m = self._node_fn(xi - 0.5, eta)
+        _, phi = self._node_fn(xi, eta)
+        dlam = -((-(lam_p - lam_m) + 180.0) % 360.0 - 180.0)              # (-180, 180]
+        bearing = np.arctan2(np.deg2rad(phi_p - phi_m), np.cos(np.deg2rad(phi)) * np.deg2rad(dlam))
+        c, s = np.cos(bearing), np.sin(bearing)
+        psi = self.southernmost_latitude + np.asarray(eta, dtype=np.float64) * self.dpsi
+        flat = np.broadcast_to(~(psi > self.north_poles_latitude), c.shape)
+        return np.where(flat, 1.0, c), np.where(flat, 0.0, s)
+
+    def target_nodes(self, LX, LY):
+        return self.nodes_2d(LX, LY)
+
     def coriolis_planes(self, rotation_rate=7.292115e-5):
         """f = 2 Omega sin(latitude) at the u and the v points, in the metric planes' layout (PointwiseCoriolis): per row in the
         latitude-longitude part (one value per row, bit for bit), per point in the cap, fold images beyond the fold."""
@@ -492,6 +543,17 @@ class TileGrid(_Grid2D):
             for k in METRIC_NAMES:
                 m[k] = np.ascontiguousarray(m[k][self.j_off:self.j_off + n, self.i_off:self.i_off + ni])
         return m
+
+    def rotation(self, LX, LY):
+        """The tile's slice of the global grid's rotation."""
+        c, s = self.global_grid.rotation(LX, LY)
+        return self.local_interior(c, LX, LY), self.local_interior(s, LX, LY)
+
+    def target_nodes(self, LX, LY):
+        x, y = self.global_grid.target_nodes(LX, LY)
+        if np.ndim(x) == 2:
+            return self.local_interior(x, LX, LY), self.local_interior(y, LX, LY)
+        return self.xnodes(LX), self.ynodes(LY)
 
     def local_interior(self, global_interior, LX, LY):
         """The part of a global (ny, nx) interior array this tile owns (plus the wall face, if any)."""

@@ -19,8 +19,8 @@ from .dynamics import (ElastoViscoPlasticRheology, ExplicitSolver, FPlane, FreeD
                        SemiImplicitStress, StressBalanceFreeDrift, ViscousRheology)
 from .fields import CenterField, Field, XFaceField, YFaceField
 from .ocean import SlabOceanMixedLayer, check_ocean
-from .time_series import FieldTimeSeries, refuse_series
-from .grids import (METRIC_NAMES, Bounded, Center, FullyConnected, LeftConnected, LeftConnectedRightFolded, Periodic, RightConnected,
+from .time_series import FieldTimeSeries, RegriddedTimeSeries, refuse_series
+from .grids import (METRIC_NAMES, Bounded, Center, Face, FullyConnected, LeftConnected, LeftConnectedRightFolded, Periodic, RightConnected,
                     RightFolded, TileGrid)
 
 
@@ -459,6 +459,7 @@ class SeaIceModel:
         self._derived_fields = {}           # name -> CenterField of the derived fields asked for so far (derived_field)
         self._momentum_term_fields = {}     # name -> XFaceField / YFaceField of the momentum term fields asked for so far (momentum_term)
         self._series, self._pending_series = {}, []     # slot name -> what csi_time_series_set was given (kept alive)
+        self._regrid_maps, self._series_arrays = {}, {}   # (id(source), location) -> (map id, source); id(source data) -> its device copy
         self.linear_heat_flux = None        # the LinearHeatFlux term's per-cell (coefficient, reference_temperature) fields, if any
         self.bottom_salinity = None         # the per-cell bottom salinity's field, if any
         self.shortwave = None               # the ShortwaveRadiation term, if any, and its per-cell flux's field
@@ -863,25 +864,55 @@ class SeaIceModel:
 
     # ---- forcing time series (include/csi.h, csi_time_series_set) -----------------------------------------------------------------
     def _set_series(self, slot):
-        self.ctx.call("csi_time_series_set", _lib.slot_id(slot), C.byref(self._series[slot].struct))
+        s = self._series[slot]
+        if s.map is None:
+            self.ctx.call("csi_time_series_set", _lib.slot_id(slot), C.byref(s.struct))
+        else:
+            self.ctx.call("csi_time_series_set_regridded", _lib.slot_id(slot), C.byref(s.struct), s.map,
+                          C.byref(s.other) if s.other is not None else None, s.series.component or 0)
+
+    def _regrid_map(self, source, location):
+        """The library's map from `source` to the points of `location` on this model's grid or tile: one per (source, location),
+        shared by the slots; computed with csi_regrid_plan_axis (SourceGrid.plan) from grid.target_nodes, with grid.rotation."""
+        key = (id(source), location)
+        if key not in self._regrid_maps:
+            i0, i1, j0, j1, wx, wy = source.plan(*self.grid.target_nodes(*location))
+            cos, sin = self.grid.rotation(*location)
+            kind = {(Face, Center): _lib.REGRID_FACE_CENTER, (Center, Face): _lib.REGRID_CENTER_FACE,
+                    (Center, Center): _lib.REGRID_CENTER_CENTER}[location]
+            self._regrid_maps[key] = (self.ctx.regrid_map_create(kind, i0, i1, j0, j1, wx, wy, source.shape, cos, sin), source)
+        return self._regrid_maps[key][0]
 
     def _attach_pending_series(self):
         """Register the series met while the model was described (their fields are bound by now), interpolate them at the clock and
         fill the halos the library fills for plain arrays at construction."""
         for slot, fts, fld in self._pending_series:
+            if isinstance(fts, RegriddedTimeSeries) and fts.component is not None and fts.location != fld.location:
+                raise ValueError(f"{slot.lower()}: the {'xy'[fts.component]} component of a RegriddedVectorTimeSeries (.{'xy'[fts.component]}) "
+                                 f"drives an array at ({fts.location[0].__name__}, {fts.location[1].__name__}); this one lies at "
+                                 f"({fld.LX.__name__}, {fld.LY.__name__}) and takes .{'yx'[fts.component]}")
             if fts.location != fld.location or fts.interior_shape != tuple(reversed(self.grid.interior_size(*fld.location))):
                 raise ValueError(f"{slot.lower()}: a FieldTimeSeries at ({fld.LX.__name__}, {fld.LY.__name__}) with slices of the "
                                  f"interior shape {tuple(reversed(self.grid.interior_size(*fld.location)))} is needed, got one at "
                                  f"({fts.location[0].__name__}, {fts.location[1].__name__}) with {fts.interior_shape}")
             if slot in self._series:
                 raise ValueError(f"{slot.lower()}: two time series for one array")
-            nt, (ny, nx) = len(fts), fts.interior_shape
+            nt = len(fts)
             host = fts.backend.chunk_size is not None
-            keep = fts.data if host else torch.from_numpy(fts.data).to(self.device)      # (the caller's array: the library reads it)
-            ptr = keep.ctypes.data if host else keep.data_ptr()
-            st = _lib.TimeSeries(nt, fts.time_indexing.kind, _lib.SERIES_HOST if host else _lib.SERIES_DEVICE,
-                                 fts.backend.chunk_size or 0, fts.time_indexing.period, _dptr(fts.times), C.c_void_p(ptr), nx, nx * ny)
-            self._series[slot] = SimpleNamespace(series=fts, field=fld, struct=st, keep=keep, window=fts.backend.chunk_size or 0)
+            regridded = isinstance(fts, RegriddedTimeSeries)
+            keep, structs = [], []
+            for data in (fts.parts if regridded else (fts.data,)):      # (slices of the source shape for a regridded series)
+                ny, nx = data.shape[1:]
+                held = data if host else (self._series_arrays.get(id(data)) if regridded else None)
+                if held is None:                                        # (the two members of a pair share their two device arrays)
+                    held = self._series_arrays[id(data)] = torch.from_numpy(data).to(self.device)
+                ptr = held.ctypes.data if host else held.data_ptr()    # (the caller's array: the library reads it)
+                keep.append((held, data))
+                structs.append(_lib.TimeSeries(nt, fts.time_indexing.kind, _lib.SERIES_HOST if host else _lib.SERIES_DEVICE,
+                                               fts.backend.chunk_size or 0, fts.time_indexing.period, _dptr(fts.times), C.c_void_p(ptr), nx, nx * ny))
+            self._series[slot] = SimpleNamespace(series=fts, field=fld, struct=structs[0], other=structs[1] if len(structs) > 1 else None, keep=keep,
+                                                 map=self._regrid_map(fts.source, fld.location) if regridded else None,
+                                                 window=fts.backend.chunk_size or 0)
         self._pending_series = []
         if not self._series:
             return

@@ -600,6 +600,87 @@ int32_t csi_time_series_update(csi_context* ctx, double time);
  * slice uploads since csi_time_series_set.  Either pointer may be NULL. */
 int32_t csi_time_series_status(csi_context* ctx, int32_t field_id, int32_t* resident, int64_t* uploads);
 
+/* ---- forcing time series on a source grid of their own: regridded on the device -------------------------------------------------
+ * A series may be given on a RECTILINEAR source grid -- 1-D x nodes and 1-D y nodes in the coordinates of the model grid's nodes
+ * (degrees of longitude / latitude on a latitude-longitude or tripolar grid); x may be periodic -- instead of on the model grid.  At
+ * every csi_time_series_update ONE further launch (k_time_series_regrid, time_series_regrid.hip) serves all such slots: per target
+ * point it interpolates in time at the four surrounding source points, then bilinearly in space, rotates one component of a vector
+ * pair into the grid's local axes and writes the interior of the bound array.  Series on the model grid keep k_time_series.
+ *
+ * Per-axis rule (csi_regrid_plan_axis; pure host function, no context, no GPU): csi_time_series_plan (above) applied to space, and
+ * implemented by calling it.  nodes: n >= 2 values, strictly increasing and finite; x finite; otherwise CSI_ERR_INVALID_ARGUMENT.
+ *   periodic == 0: the CSI_TIME_CLAMP paragraph with times := nodes, t := x -- the end node outside the nodes, i0 == i1 and w = 0 at
+ *                  a node and beyond the ends (`period` is ignored);
+ *   periodic != 0: the CSI_TIME_CYCLICAL paragraph -- period <= 0 is inferred, a given one must exceed nodes[n-1] - nodes[0]; x is
+ *                  wrapped with fmod from nodes[0]; in the gap behind the last node i0 = n-1, i1 = 0,
+ *                  w = (x' - nodes[n-1]) / (period - (nodes[n-1] - nodes[0])).
+ * Output: 0-based i0, i1 and the weight w of node i1, 0 <= w < 1.
+ *
+ * Value per target point.  a_k, b_k: the source values of the two slices around the clock at corner k; w1, w2, same_t: the weights of
+ * k_time_series (w2 = frac, w1 = 1 - frac, formed on the host; same_t: n1 == n2).  Every line is two products and one sum,
+ * uncontracted, in this order; STRICT and FAST are the same code:
+ *     c_k  = same_t ? a_k : b_k * w2 + a_k * w1          k = 00, 10, 01, 11; c10 is the corner at (i1, j0)
+ *     lo   = c10 * wx + c00 * (1 - wx)
+ *     hi   = c11 * wx + c01 * (1 - wx)
+ *     val  = hi  * wy + lo  * (1 - wy)
+ * 1 - wx and 1 - wy are formed in the kernel.  Vector pair: a slot at (Face, Center) that is the x component of a pair forms val_E
+ * and val_N from the pair's two source series (each with ITS time weights) at its own point and writes val_E * cos + val_N * sin; a
+ * slot at (Center, Face) that is the y component writes val_N * cos - val_E * sin at its own point.  cos, sin: per-point arrays of the
+ * map, the bearing of the grid's x direction against east.
+ * Source values must be FINITE: a weight may be exactly 0, and 0 * Inf or 0 * NaN is NaN -- filling or masking the source
+ * (land points of an ocean product) is the caller's responsibility.
+ *
+ * A map (csi_regrid_map_create) is made for ONE location of the context's grid or tile: its interior extents nx, ny (a Face field on a
+ * Bounded side is one wider) and, per interior point, row-major and packed (point (i, j) at [j * nx + i]), the four 0-based source
+ * indices, the two weights and optionally cos and sin (both or neither; a vector pair needs them).  The library validates the extents
+ * against the grid, every index against the source extents and 0 <= w <= 1 (cos, sin: finite), and copies the map to the device; the
+ * caller's arrays are not needed after the call.  DEVICE LAYOUT, stated because it sets the limits and the traffic: three planes of
+ * 8-byte entries per point -- the four indices as uint16 {i0, i1, j0, j1}, wx, wy -- and two more (cos, sin) for a map with rotation:
+ * 24 or 40 bytes per point, read with 16-byte loads (two points at a time), rows padded so that a pair of points that is 16-byte
+ * aligned in the destination is 16-byte aligned in every plane.  Hence src_nx, src_ny <= 65536 (CSI_REGRID_MAX_SOURCE_EXTENT).
+ * Compulsory memory traffic per update and point: the map plus the 8-byte store, 32 bytes (scalar) or 48 bytes (vector component);
+ * the gathers (8 or 16 per point, 8 bytes each) go to a source slice that is small and shared by every workgroup.
+ * At most CSI_REGRID_MAX_MAPS (16) maps per context live at a time; csi_context_destroy frees them.  csi_regrid_map_destroy refuses a
+ * map that a slot still uses (CSI_ERR_INVALID_ARGUMENT).  csi_grid_set / csi_tile_set after a map was made leave it as it is: a slot
+ * set on it later is refused if the extents no longer match.
+ *
+ * NOT BUILT: conservative or higher-order remapping; curvilinear source grids; extrapolation beyond the clamp (and the front end's
+ * fill_missing); reading files; a per-slice source mask; rotation of pairs at (Center, Center). */
+int32_t csi_regrid_plan_axis(const double* nodes, int32_t n, int32_t periodic, double period, double x,
+                             int32_t* i0, int32_t* i1, double* w);
+typedef enum { CSI_REGRID_FACE_CENTER = 0, CSI_REGRID_CENTER_FACE = 1, CSI_REGRID_CENTER_CENTER = 2 } csi_regrid_location;
+enum { CSI_REGRID_MAX_MAPS = 16, CSI_REGRID_MAX_SOURCE_EXTENT = 65536 };
+typedef struct {
+    int32_t location;        /* csi_regrid_location of the target points */
+    int32_t nx, ny;          /* target interior extents */
+    int32_t src_nx, src_ny;  /* source extents, each 2 .. CSI_REGRID_MAX_SOURCE_EXTENT */
+    int32_t reserved;        /* 0 */
+    const int32_t* i0;       /* host arrays of ny * nx entries each */
+    const int32_t* i1;
+    const int32_t* j0;
+    const int32_t* j1;
+    const double* wx;
+    const double* wy;
+    const double* cos;       /* NULL (with sin): a map without rotation */
+    const double* sin;
+} csi_regrid_map;
+int32_t csi_regrid_map_create(csi_context* ctx, const csi_regrid_map* desc, int32_t* map_id);
+int32_t csi_regrid_map_destroy(csi_context* ctx, int32_t map_id);
+/* Set a REGRIDDED series on one of the nineteen slots of csi_time_series_set.  ts: a series whose slices have the SOURCE shape
+ * (src_ny rows of src_nx values; ld, slice_stride as before); both backends -- the HOST ring holds source-sized slices.  other == NULL:
+ * a scalar (component must be 0).  Otherwise ts is the EAST series and other the NORTH series of a vector pair (one ring each on the
+ * HOST backend; the two may have different times), component 0: the slot receives the x component and must lie at (Face, Center),
+ * 1: the y component, at (Center, Face).  map_id: a map made for the slot's location, with the source extents of the series; a
+ * source slice spans fewer than 2^31 doubles (ld * src_ny: the kernel forms 32-bit offsets).
+ * Setting a slot replaces whichever kind of series it had; csi_time_series_set(ctx, slot, NULL) removes either kind.  A slot whose
+ * bound array has changed its row stride or alignment since: csi_time_series_update fails; set the slot again. */
+int32_t csi_time_series_set_regridded(csi_context* ctx, int32_t field_id, const csi_time_series* ts, int32_t map_id,
+                                      const csi_time_series* other, int32_t component);
+/* For tests: launches of k_time_series_regrid so far (a context without regridded slots never launches it; one per update with any
+ * number of them) and the maps alive.  Either pointer may be NULL.  csi_time_series_status serves regridded slots too (a pair: the
+ * east series). */
+int32_t csi_regrid_stats(csi_context* ctx, int64_t* launches, int32_t* maps);
+
 /* ---- device diagnostics: advection timescale, integrals, extrema, finite check ------------------------------------------------------
  * Scalars computed from the bound fields ON THE DEVICE, in two launches on the context's stream (a pass over the interior that
  * leaves one partial record per block of 64 x 64 cells, and one block that folds the records), followed by a copy of the 21 result

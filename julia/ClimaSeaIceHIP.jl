@@ -51,6 +51,13 @@ struct CsiTimeSeries
     times::Ptr{Cdouble}; data::Ptr{Cvoid}
     ld::Int64; slice_stride::Int64
 end
+# csi_regrid_map (include/csi.h): one location's target points on a rectilinear source grid
+struct CsiRegridMap
+    location::Int32; nx::Int32; ny::Int32; src_nx::Int32; src_ny::Int32; reserved::Int32
+    i0::Ptr{Int32}; i1::Ptr{Int32}; j0::Ptr{Int32}; j1::Ptr{Int32}
+    wx::Ptr{Cdouble}; wy::Ptr{Cdouble}
+    cos::Ptr{Cdouble}; sin::Ptr{Cdouble}
+end
 struct CsiDiagnostics
     what::Int32; has_snow::Int32
     advection_timescale::Cdouble; inv_timescale_max::Cdouble; max_abs_u::Cdouble; max_abs_v::Cdouble
@@ -364,6 +371,66 @@ function time_series_status(ctx, slot, window)
     resident = fill(Int32(-1), max(window, 1)); uploads = Ref{Int64}(0)
     check(ctx, ccall((:csi_time_series_status, libcsi), Int32, (Ptr{Cvoid}, Int32, Ptr{Int32}, Ptr{Int64}), ctx.handle, slot, resident, uploads))
     return resident[1:window], uploads[]
+end
+
+# ---- series on a rectilinear source grid of their own (include/csi.h: csi_regrid_map_create, csi_time_series_set_regridded) ----------
+# (i0, i1, w) of coordinate x on a source axis: csi_time_series_plan applied to space (pure host function)
+function regrid_plan_axis(nodes::Vector{Float64}, periodic::Bool, period, x)
+    i0 = Ref{Int32}(0); i1 = Ref{Int32}(0); w = Ref{Cdouble}(0)
+    rc = ccall((:csi_regrid_plan_axis, libcsi), Int32, (Ptr{Cdouble}, Int32, Int32, Cdouble, Cdouble, Ptr{Int32}, Ptr{Int32}, Ptr{Cdouble}),
+               nodes, length(nodes), periodic, Float64(period), Float64(x), i0, i1, w)
+    rc == 0 || error("ClimaSeaIceHIP: csi_regrid_plan_axis: invalid input")
+    return i0[], i1[], w[]
+end
+
+# location: 0 (Face, Center), 1 (Center, Face), 2 (Center, Center).  X, Y: the (nx, ny) coordinates of the location's interior points in
+# the source grid's coordinates; cosθ, sinθ: the bearing of the grid's x direction there (nothing: a map for scalars only).  The
+# library copies everything; returns the map's id.
+function regrid_map_create(ctx, location, xs::Vector{Float64}, ys::Vector{Float64}, X, Y; periodic_x = false, period = 0.0, cosθ = nothing, sinθ = nothing)
+    nx, ny = size(X)
+    px = [regrid_plan_axis(xs, periodic_x, period, X[i, j]) for i in 1:nx, j in 1:ny]
+    py = [regrid_plan_axis(ys, false, 0.0, Y[i, j]) for i in 1:nx, j in 1:ny]
+    i0 = Int32[p[1] for p in px]; i1 = Int32[p[2] for p in px]; wx = Float64[p[3] for p in px]
+    j0 = Int32[p[1] for p in py]; j1 = Int32[p[2] for p in py]; wy = Float64[p[3] for p in py]
+    c = isnothing(cosθ) ? Float64[] : Float64.(cosθ); s = isnothing(sinθ) ? Float64[] : Float64.(sinθ)
+    id = Ref{Int32}(-1)
+    GC.@preserve i0 i1 j0 j1 wx wy c s begin
+        d = Ref(CsiRegridMap(location, nx, ny, length(xs), length(ys), 0, pointer(i0), pointer(i1), pointer(j0), pointer(j1), pointer(wx), pointer(wy),
+                             isempty(c) ? C_NULL : pointer(c), isempty(s) ? C_NULL : pointer(s)))
+        check(ctx, ccall((:csi_regrid_map_create, libcsi), Int32, (Ptr{Cvoid}, Ptr{CsiRegridMap}, Ptr{Int32}), ctx.handle, d, id))
+    end
+    return id[]
+end
+regrid_map_destroy(ctx, map) = check(ctx, ccall((:csi_regrid_map_destroy, libcsi), Int32, (Ptr{Cvoid}, Int32), ctx.handle, map))
+
+"""
+    attach_regridded_series!(ctx, slot, map, times, source_array; north = nothing, component = 0, device = false, window = 3, time_indexing, target)
+
+`source_array` holds slices of the SOURCE shape, (src_nx, src_ny, Nt): a host `Array` (CSI_SERIES_HOST, `window` slices on the device) or,
+with `device = true`, a device array (CSI_SERIES_DEVICE).  `north`: the northward series of a vector pair whose eastward series is
+`source_array`; `component` 0 writes the x component into a (Face, Center) slot, 1 the y component into a (Center, Face) slot.
+"""
+function attach_regridded_series!(ctx, slot, map, times, source_array; north = nothing, component = 0, device = false, window = 3,
+                                  time_indexing = Oceananigans.OutputReaders.Linear(), target = nothing)
+    isnothing(target) || bind!(ctx, slot, target)
+    nx, ny = size(source_array, 1), size(source_array, 2)
+    t = Float64.(collect(times))
+    kind, period = time_indexing_code(time_indexing)
+    series(a) = Ref(CsiTimeSeries(length(t), kind, device ? 0 : 1, device ? 0 : window, period, pointer(t), Ptr{Cvoid}(pointer(a)), nx, nx * ny))
+    GC.@preserve t source_array north begin
+        other = isnothing(north) ? C_NULL : series(north)
+        check(ctx, ccall((:csi_time_series_set_regridded, libcsi), Int32, (Ptr{Cvoid}, Int32, Ptr{CsiTimeSeries}, Int32, Ptr{CsiTimeSeries}, Int32),
+                         ctx.handle, slot, series(source_array), map, other, component))
+    end
+    push!(ctx.series, ((source_array, north), target))
+    return nothing
+end
+
+# (launches of the regridding kernel so far, maps alive)
+function regrid_stats(ctx)
+    launches = Ref{Int64}(0); maps = Ref{Int32}(0)
+    check(ctx, ccall((:csi_regrid_stats, libcsi), Int32, (Ptr{Cvoid}, Ptr{Int64}, Ptr{Int32}), ctx.handle, launches, maps))
+    return launches[], maps[]
 end
 
 # a Field is bound as it is, a FieldTimeSeries through the Field it writes into
