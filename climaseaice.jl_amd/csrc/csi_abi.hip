@@ -647,6 +647,16 @@ int32_t csi_fill_halo_local(csi_context* c, int32_t fid) {
     return fill_halo(c, fid);
 }
 
+// Every path of a whole step ends by imaging h, aice [, hs] (update_state!, or the tracer update's own stores) and, with dynamics, u and
+// v: a grid too narrow for one image per side (fill_width_check) is refused HERE, before the step has written anything -- not at its end,
+// and also where the fused stores would have skipped update_state!'s check.
+static int32_t step_width_check(csi_context* c, bool dynamics) {
+    int32_t rc;
+    if ((rc = fill_width_check(c, CSI_F_H))) return rc;          // (aice, hs: the same location)
+    if (dynamics && ((rc = fill_width_check(c, CSI_F_U)) || (rc = fill_width_check(c, CSI_F_V)))) return rc;
+    return CSI_OK;
+}
+
 int32_t csi_time_step_fe(csi_context* c, double dt, int32_t substeps, int32_t scheme, int32_t first_iteration) {
     if (!c) return CSI_ERR_INVALID_ARGUMENT;
     // dynamics = nothing (csi_evp_params_set never called): prescribed velocities, time_step_momentum! is a no-op
@@ -654,6 +664,7 @@ int32_t csi_time_step_fe(csi_context* c, double dt, int32_t substeps, int32_t sc
     const bool dynamics = has_dynamics(c);      // (or csi_dynamics_set(ctx, CSI_DYNAMICS_FREE_DRIFT))
     int32_t rc = dynamics ? need_momentum(c) : need(c, {CSI_F_H, CSI_F_A});
     if (rc) return rc;
+    if ((rc = step_width_check(c, dynamics))) return rc;
     if (first_iteration && (rc = do_update_state(c))) return rc;          // sea_ice_fe_step.jl:16
     if ((rc = do_tendencies_or_zero(c, scheme))) return rc;               // :19 (compute_tracer_tendencies!)
     if (dynamics && (rc = do_momentum_tendencies(c, dt))) return rc;      // :19 (compute_momentum_tendencies!: ExplicitSolver only)
@@ -717,6 +728,7 @@ int32_t csi_time_step_rk3(csi_context* c, double dt, int32_t substeps, int32_t s
     int32_t rc = dynamics ? need_momentum(c) : need(c, {CSI_F_H, CSI_F_A});
     if (rc) return rc;
     if ((rc = dynamics ? need(c, {CSI_F_HM, CSI_F_AM, CSI_F_UM, CSI_F_VM}) : need(c, {CSI_F_HM, CSI_F_AM}))) return rc;
+    if ((rc = step_width_check(c, dynamics))) return rc;
     if (c->ml_set && c->slab_set && (rc = need(c, {CSI_F_ML_TEMPERATURE, CSI_F_ML_TEMPERATURE_M}))) return rc;
     if (advect_stage_supported(c, scheme)) {
         const bool third = scheme == CSI_ADVECT_WENO3 || scheme == CSI_ADVECT_UPWIND3;

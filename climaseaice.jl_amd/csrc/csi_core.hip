@@ -216,7 +216,22 @@ Range interior_range(const csi_context* c) { return Range{1, c->Nx, 1, c->Ny}; }
 Range parent_range(const csi_context* c) { return Range{1 - c->Hx, c->Nx + c->Hx, 1 - c->Hy, c->Ny + c->Hy}; }
 
 
+// A local fill stores ONE image per side of a point (store_with_images): where a side wraps or mirrors, the grid must be at least as
+// wide as its halo in that direction, or part of the halo has no single source among the points.  The fold images rows Ny - Hy .. Ny - 1
+// of a Center-in-y field (Ny - Hy + 1 .. Ny of a Face-in-y one) and wraps them in x.  A direction whose sides have no image (Face on
+// walls, connected sides, ValueBoundaryCondition sides: one cell) is legal at any N >= 1.  The momentum step's wording (need_dynamics_common).
+int32_t fill_width_check(csi_context* c, int fid) {
+    const ImageSpec im = image_spec(c, fid);
+    auto images = [](int m) { return m == IMG_WRAP || m == IMG_MIRROR; };
+    bool narrow = ((images(im.xlo) || images(im.xhi)) && c->Nx < c->Hx) || ((images(im.ylo) || images(im.yhi)) && c->Ny < c->Hy);
+    if (im.yhi == IMG_FOLD) narrow = narrow || c->Nx < c->Hx || c->Ny < c->Hy + (im.fold_fy ? 0 : 1);
+    if (narrow) return fail(c, CSI_ERR_UNSUPPORTED, std::string("tile smaller than its halo: local halo fill of ") + kName[fid]);
+    return CSI_OK;
+}
+
 int32_t fill_halo(csi_context* c, int fid) {
+    int32_t rc;
+    if ((rc = fill_width_check(c, fid))) return rc;
     launch_fill_halo(ref_of(c, fid), c->g, image_spec(c, fid), c->stream);
     HIP_TRY(c, hipGetLastError());
     return CSI_OK;

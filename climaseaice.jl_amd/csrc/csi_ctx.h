@@ -480,6 +480,7 @@ int side_lo(int topo);
 int side_hi(int topo);
 int img_of(int side, int loc);
 ImageSpec image_spec(const csi_context* c, int fid);
+int32_t fill_width_check(csi_context* c, int fid);      // CSI_ERR_UNSUPPORTED where a local fill of this field would need more than one image per side
 FRef ref_of(const csi_context* c, int fid);
 int32_t need(csi_context* c, std::initializer_list<int> ids);
 // every id bound, or CSI_ERR_NOT_BOUND "<who>: <group>needs field <name> (not bound<hint>)" (group: empty, or with its trailing blank)

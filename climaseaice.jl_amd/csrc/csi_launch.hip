@@ -603,6 +603,11 @@ int32_t do_update_state(csi_context* c, bool in_step, bool tracers_filled) {
     // mask_immersed_field_xy! of every prognostic field, then their local halo fills in one batch (two launches)
     const bool snow = c->f[CSI_F_HS].p != nullptr;
     const bool vel = c->f[CSI_F_U].p && c->f[CSI_F_V].p && (!in_step || has_dynamics(c));
+    // (a grid narrower than its halo where a side has images: refused before anything is written, mask included)
+    if (!tracers_filled) {
+        if ((rc = fill_width_check(c, CSI_F_H))) return rc;      // (aice, hs: the same location)
+    }
+    if (vel && ((rc = fill_width_check(c, CSI_F_U)) || (rc = fill_width_check(c, CSI_F_V)))) return rc;
     launch_mask_center(ref_of(c, CSI_F_H), c->g, c->stream);
     launch_mask_center(ref_of(c, CSI_F_A), c->g, c->stream);
     if (snow) launch_mask_center(ref_of(c, CSI_F_HS), c->g, c->stream);

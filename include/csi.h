@@ -310,14 +310,23 @@ int32_t csi_weno_weight_dtype(csi_context* ctx, int32_t* dtype);
 int32_t csi_dynamic_step_tracers(csi_context* ctx, double dt, int32_t from_cache);
 /* cache_current_fields!(model), sea_ice_rk_substep.jl:29-42 */
 int32_t csi_cache_current_fields(csi_context* ctx);
-/* update_state!(model), sea_ice_model.jl:379-394: immersed masking + local halo fill of h, aice, u, v */
+/* update_state!(model), sea_ice_model.jl:379-394: immersed masking + local halo fill of h, aice, u, v.
+ * CSI_ERR_UNSUPPORTED ("tile smaller than its halo") where one of these fields could not be filled (csi_fill_halo_local below):
+ * refused as a whole, before the mask or any fill has written. */
 int32_t csi_update_state(csi_context* ctx);
 /* fill_halo_regions!(field; only_local_halos = true) for one bound field (a csi_field_id slot or CSI_F_FREE_DRIFT_U / _V; so
- * csi_halo_exchange) */
+ * csi_halo_exchange).  A halo cell is written only as the image of a point (Periodic wrap, no-flux mirror, ValueBoundaryCondition
+ * reflection, north fold; corners as the product of an x image and a y image): cells beyond a side without an image -- Face on a wall,
+ * a connected side, the deeper cells of a ValueBoundaryCondition side, and the corner cells whose column lies beyond such an x side --
+ * keep what they hold.  One image per side: in a direction where a side of this field wraps or mirrors the grid must be at least as wide
+ * as its halo (N >= H; below a north fold Nx >= Hx and Ny >= Hy, Ny >= Hy + 1 for a Center-in-y field) -- CSI_ERR_UNSUPPORTED ("tile
+ * smaller than its halo") otherwise, the parent untouched.  A direction whose sides have no image is legal at any N >= 1. */
 int32_t csi_fill_halo_local(csi_context* ctx, int32_t field_id);
 /* Whole model steps: FE (sea_ice_fe_step.jl:13-34) and the SplitRungeKutta3 stage loop around rk_substep!
  * (sea_ice_rk_substep.jl:81-94).  Without csi_evp_params_set and without csi_dynamics_set(ctx, CSI_DYNAMICS_FREE_DRIFT)
- * (dynamics = nothing) the velocities are prescribed and the momentum step is skipped: advection-only models.  Thermodynamics: csi_slab_params_set / csi_snow_params_set. */
+ * (dynamics = nothing) the velocities are prescribed and the momentum step is skipped: advection-only models.  Thermodynamics: csi_slab_params_set / csi_snow_params_set.
+ * A grid on which h, aice (with dynamics: u, v) cannot be imaged (csi_fill_halo_local: "tile smaller than its halo") is refused with
+ * CSI_ERR_UNSUPPORTED at the entry of the step, before anything is written. */
 int32_t csi_time_step_fe(csi_context* ctx, double dt, int32_t substeps, int32_t scheme, int32_t first_iteration);
 int32_t csi_time_step_rk3(csi_context* ctx, double dt, int32_t substeps, int32_t scheme);
 

@@ -18,7 +18,8 @@ def make_case(Nx=64, Ny=48, H=4, topo=("periodic", "periodic"), grid="rectilinea
               user_forcing=False, immersed_bc=None, coriolis_points=False, wind_drag=None,
               tripolar=None, ice_edge=None, ice_free_rows=None):
     rng = np.random.default_rng(seed)
-    c = dict(Nx=Nx, Ny=Ny, H=H, topo=topo, grid=grid, spacing=spacing, substeps=substeps, dt=dt, coriolis=coriolis,
+    Hx, Hy = (H, H) if np.isscalar(H) else (int(H[0]), int(H[1]))       # H: one halo width, or (Hx, Hy)
+    c = dict(Nx=Nx, Ny=Ny, H=H, Hx=Hx, Hy=Hy, topo=topo, grid=grid, spacing=spacing, substeps=substeps, dt=dt, coriolis=coriolis,
              top=top, bottom=bottom, ue=ue, ve=ve, pressure=pressure, field_forcing=field_forcing,
              free_drift=free_drift, beta=beta,     # beta: BetaPlane(f0 = coriolis, beta)
              noslip=noslip,                        # ValueBoundaryCondition(0) on the tangential velocity at every wall
@@ -36,11 +37,11 @@ def make_case(Nx=64, Ny=48, H=4, topo=("periodic", "periodic"), grid="rectilinea
     if grid == "tripolar":
         topo = ("periodic", "folded")
         c["topo"] = topo
-        g = csi.TripolarGrid((Nx, Ny), halo=(H, H), **(tripolar or {}))
+        g = csi.TripolarGrid((Nx, Ny), halo=(Hx, Hy), **(tripolar or {}))
     elif grid == "rectilinear":
-        g = csi.RectilinearGrid((Nx, Ny), x=(0.0, Nx * spacing), y=(0.0, Ny * spacing), topology=tt, halo=(H, H))
+        g = csi.RectilinearGrid((Nx, Ny), x=(0.0, Nx * spacing), y=(0.0, Ny * spacing), topology=tt, halo=(Hx, Hy))
     else:
-        g = csi.LatitudeLongitudeGrid((Nx, Ny), longitude=(0, 60), latitude=(20, 70), topology=tt, halo=(H, H))
+        g = csi.LatitudeLongitudeGrid((Nx, Ny), longitude=(0, 60), latitude=(20, 70), topology=tt, halo=(Hx, Hy))
     if curvilinear is not None:
         # the same grid described by twelve 2-D metric arrays (CSI_METRIC_FULL), optionally distorted by `curvilinear`
         g = csi.OrthogonalCurvilinearGrid.from_grid(g, distort=curvilinear, seed=seed)
@@ -106,8 +107,8 @@ def make_case(Nx=64, Ny=48, H=4, topo=("periodic", "periodic"), grid="rectilinea
     c.update(h=h, a=a, u=u, v=v)
     if coriolis_points and grid != "tripolar":
         # f(i, j) = f0 (1 + 0.3 sin cos) at the u / v nodes, metric-plane layout; halo entries image their points
-        n, ni = Ny + 2 * H + 1, Nx + 2 * H + 1
-        ia, ja = np.arange(ni) - (H - 1), np.arange(n) - (H - 1)
+        n, ni = Ny + 2 * Hy + 1, Nx + 2 * Hx + 1
+        ia, ja = np.arange(ni) - (Hx - 1), np.arange(n) - (Hy - 1)
         if topo[0] == "periodic":
             ia = (ia - 1) % Nx + 1
         if topo[1] == "periodic":
@@ -117,7 +118,7 @@ def make_case(Nx=64, Ny=48, H=4, topo=("periodic", "periodic"), grid="rectilinea
             X2, Y2 = (ia[None, :] - 1 + ox) / Nx, (ja[:, None] - 1 + oy) / Ny
             fpl = (coriolis or 1e-4) * (1.0 + 0.3 * np.sin(2 * np.pi * X2) * np.cos(np.pi * Y2))
             if topo[1] == "folded":
-                fpl = csi.fold_north(fpl, Nx, Ny, H, H, ox == 0.0, oy == 0.0, 1)     # f is a scalar: no sign change
+                fpl = csi.fold_north(fpl, Nx, Ny, Hx, Hy, ox == 0.0, oy == 0.0, 1)     # f is a scalar: no sign change
             planes.append(np.ascontiguousarray(fpl))
         c["f_points"] = tuple(planes)
     if user_forcing:

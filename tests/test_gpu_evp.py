@@ -131,11 +131,11 @@ def cmp_region(c, k, a):
     * diagnostics (alpha, zeta, Delta; written on the last sub-step, never read): the reference computes them on
       -H+2 : N+H-1; the two-sub-steps-per-launch kernel writes the interior plus all H periodic images and nothing
       beyond walls -> periodic directions without the outermost layer, bounded directions interior only."""
-    H = c["H"]
+    Hx, Hy = c.get("Hx", c["H"]), c.get("Hy", c["H"])                              # (make_case takes H as a number or as (Hx, Hy))
     if k == "s12" and ("bounded" in c["topo"] or "folded" in c["topo"]):
-        return a[H:a.shape[0] - H, H:a.shape[1] - H]
+        return a[Hy:a.shape[0] - Hy, Hx:a.shape[1] - Hx]
     if k in DIAG:
-        cut = [H if t in ("bounded", "folded") else 1 for t in c["topo"]]          # (x, y)
+        cut = [H if t in ("bounded", "folded") else 1 for t, H in zip(c["topo"], (Hx, Hy))]          # (x, y)
         return a[cut[1]:a.shape[0] - cut[1], cut[0]:a.shape[1] - cut[0]]
     return a
 
