@@ -5,6 +5,7 @@
 //   csi_fold.hip    north fold: the three-kernel band beside the pair launches
 //   csi_launch.hip  launch loops: sub-cycle, finalize, time_step_momentum!, tracer steps, update_state!, csi_profile_substeps
 //   csi_abi.hip     the C ABI (include/csi.h)
+//   csi_thermo.hip  thermodynamics: parameter structs, the choice of kernel and its binding checks, the mixed layer's launch, their entry points
 //   csi_time_series.hip   forcing time series: time indexing, the device ring of a host-resident series, the interpolation launch
 //   csi_diagnostics.hip   device diagnostics: the two launches, the result copy, the combine over the ranks of a decomposition
 //   csi_output.hip        device-side output: output sets, their staging slots, the copy stream and the slot events
@@ -298,7 +299,7 @@ struct csi_context {
     double vel_bc_value[2][2] = {{0, 0}, {0, 0}};
     bool snow_set = false;   // layered (snow + ice) step instead of the bare-ice one
     SnowDev snow{};
-    // csi_mixed_layer_set (csi_abi.hip, mixed_layer.hip): the slab-ocean mixed layer, stepped before the thermodynamic step of every stage
+    // csi_mixed_layer_set (csi_thermo.hip, mixed_layer.hip): the slab-ocean mixed layer, stepped before the thermodynamic step of every stage
     bool ml_set = false;
     csi_mixed_layer_params ml{};
     int64_t ml_launches = 0;             // csi_mixed_layer_stats
@@ -572,6 +573,7 @@ int32_t do_update_state(csi_context* c, bool in_step = false, bool tracers_fille
 int32_t do_tendencies(csi_context* c, int scheme);
 int32_t do_tendencies_or_zero(csi_context* c, int scheme);
 int32_t do_tracer_step(csi_context* c, double dt, int from_cache, bool fill_images = false);
+int32_t do_thermo(csi_context* c, double dt, int from_cache = 0);      // csi_thermo.hip: thermodynamic_time_step! of a stage (the mixed layer first, from Psi^- if from_cache)
 int extra_x(const csi_context* c, int fid);
 int extra_y(const csi_context* c, int fid);
 Range interior_range(const csi_context* c);

@@ -234,6 +234,8 @@ struct ShortwaveDev {
     FRef f{}, albedo_used{};
 };
 bool flux_has_emission(const FluxTermsDev& t);
+// the kernels read the cell's surface temperature (their LTU flag): the field -- CSI_F_TU / CSI_F_TUS -- must be bound exactly then
+bool flux_reads_surface_temperature(const HeatFluxDev& F, int sw_mode, int top_bc_kind);
 void launch_slab_flux_step(const SlabDev& S, const HeatFluxDev& F, const FluxFields& ff, const ShortwaveDev& sw, const GridDev& g,
                            const FRef& h, const FRef& a, const FRef& mf, int has_mf, double dt, hipStream_t s);
 void launch_layered_flux_step(const SlabDev& S, const SnowDev& W, const HeatFluxDev& F, const FluxFields& ff, const ShortwaveDev& sw,

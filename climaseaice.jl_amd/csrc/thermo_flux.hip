@@ -213,22 +213,19 @@ __global__ void __launch_bounds__(256) k_slab_flux(SlabDev s, HeatFluxDev F, Flu
     } else if (LTU) {              // PrescribedTemperature per cell
         Tu = tum;
     }
-    const double Eb = (SW != SW_NONE) ? lr.rho * latent_heat(lr, Tb) : s.rho_bulk * latent_heat(s, Tb);
-    const double Eu = (SW != SW_NONE) ? lr.rho * latent_heat(lr, Tu) : s.rho_bulk * latent_heat(s, Tu);
-    const double Qi_fun = (hn <= 0) ? 0.0 : -s.k * (Tu - Tb) / hn;
-    const double Qu = (s.top_flux_kind == 1) ? Qi_fun : Qx(Tu);
-    const double Qb = (SW != SW_NONE) ? Qb_pre : Qb_ext(Tu);
-    const double Qi = consolidated ? Qi_fun : 0.0;
-    const double wu = (Qu - Qi) / Eu;
-    const double wb = (Qi - Qb) / Eb;
-    double h1, a1;
-    ice_volume_update(wu + wb, hn, an, hc, dt, h1, a1);
-    a(i, j) = a1;
-    h(i, j) = h1;
-    if (has_mf) mf(i, j) = s.rho_bulk * (h1 * a1 - hn * an) / dt;
+    // (what follows the loop reads the copies made before it in the SHORTWAVE instantiations, the arguments themselves otherwise)
+    auto E = [&](double T) {
+        if constexpr (SW != SW_NONE) return lr.rho * latent_heat(lr, T);
+        else return s.rho_bulk * latent_heat(s, T);
+    };
+    auto Qb = [&](double T) {
+        if constexpr (SW != SW_NONE) return Qb_pre;
+        else return Qb_ext(T);
+    };
+    const UsedFluxes used = slab_from_surface(s, i, j, h, a, mf, has_mf, hn, an, hc, dt, Tb, Tu, E, Qx, Qb);
     if (s.top_bc_kind == 1 && ff.tu.p) ff.tu(i, j) = Tu;
-    if (ff.qtop_used.p) ff.qtop_used(i, j) = Qu;
-    if (ff.qbot_used.p) ff.qbot_used(i, j) = Qb;
+    if (ff.qtop_used.p) ff.qtop_used(i, j) = used.top;
+    if (ff.qbot_used.p) ff.qbot_used(i, j) = used.bottom;
     if (SW != SW_NONE && sw.albedo_used.p) sw.albedo_used(i, j) = albedo(sc, Tu);
 }
 
@@ -254,7 +251,6 @@ __global__ void __launch_bounds__(256) k_layered_flux(SlabDev s, SnowDev w, Heat
                                     : SwCell{in_vgpr(fsw), snowy ? sw.snow_cold : sw.cold, snowy ? sw.snow_warm : sw.warm,
                                              snowy ? sw.snow_thr : sw.thr, an, sw.weight};
     const double hc = (SW != SW_NONE) ? in_vgpr(s.hc) : s.hc;
-    const double Vin = hin * an, Vsn = hsn * an;
     const bool consolidated = hin >= hc;
     const double Tb = s.liq_T0 - s.liq_slope * Sb;
     double Tm = s.liq_T0 - s.liq_slope * s.ice_salinity;
@@ -262,21 +258,24 @@ __global__ void __launch_bounds__(256) k_layered_flux(SlabDev s, SnowDev w, Heat
     auto Qb_ext = [&](double T) {
         return (s.bot_flux_kind == 1) ? (-(1 - an)) * s.Qb : (F.bot.n ? flux_sum<false, LIN_NONE, SW_NONE>(F.bot, qb, T, lc, sc) : s.Qb);
     };
+    // what the step reads from the surface temperature on: the arguments themselves, or in the SHORTWAVE instantiations copies made
+    // before the loop
     TermRegs tr;
     LatentRegs lr;
-    double Qb_pre = 0.0, rs_pre = 0.0, rw_pre = 0.0, ki_pre = 0.0, dt_pre = 0.0, Ps_pre = 0.0;
+    double Qb_pre = 0.0;
+    LayeredNums n{w.rho, s.rho_l, ki, dt, Ps, s.rho_bulk, s.L0, hc};
     if constexpr (SW != SW_NONE) {
         load_terms<EMIT, LIN>(tr, F.top, qt, lc);
         lr = load_latent(s);
         Qb_pre = before_loop(Qb_ext(0.0));
-        rs_pre = before_loop(w.rho); rw_pre = before_loop(s.rho_l); ki_pre = before_loop(ki); dt_pre = before_loop(dt); Ps_pre = before_loop(Ps);
+        n = LayeredNums{before_loop(w.rho), before_loop(s.rho_l), before_loop(ki), before_loop(dt), before_loop(Ps), lr.rho, lr.L0, hc};
     }
     auto Qx = [&](double T) {
         if constexpr (SW != SW_NONE) return flux_sum_regs<EMIT, LIN, SW>(F.top, tr, T, lc, sc);      // (the term is in the tuple: n >= 1)
         else return F.top.n ? flux_sum<EMIT, LIN, SW>(F.top, qt, T, lc, sc) : s.Qu;
     };
     Tm = (hsn > 0) ? 0.0 : Tm;
-    const double R = hsn / ks + hin / ki;
+    const double Ri = hin / ki, Rs = hsn / ks, R = Rs + Ri;
     double Tus = w.Tu;
     if (w.top_bc_kind == 1) {
         double root = Tb;
@@ -292,64 +291,17 @@ __global__ void __launch_bounds__(256) k_layered_flux(SlabDev s, SnowDev w, Heat
     } else if (LTU) {
         Tus = tum;
     }
-    // (what follows the loop reads the copies made before it in the SHORTWAVE instantiations, the arguments themselves otherwise)
-    const double dtp = (SW != SW_NONE) ? dt_pre : dt, kip = (SW != SW_NONE) ? ki_pre : ki, Psp = (SW != SW_NONE) ? Ps_pre : Ps;
-    const double Ri = hin / ki, Rs = hsn / ks, Rt = Rs + Ri;
-    const double Tsi = (Rt <= 0) ? Tb : Tb + (Tus - Tb) * Ri / Rt;
-    const double Qic = (R <= 0) ? 0.0 : (Tb - Tus) / R;
-    const double Qis = consolidated ? Qic : 0.0;
-    const double Qui = Qx(Tus);
-    const double Qui_per_ice = (an > 0) ? Qui / an : 0.0;
-    const double dQ = Qui_per_ice - Qis;
-    const double melt_energy = jmax(0.0, -dQ);
-    const double rs = (SW != SW_NONE) ? rs_pre : w.rho, Ls = (SW != SW_NONE) ? lr.L0 : s.L0;
-    const double cap = rs * Ls * hsn / dtp;
-    const double Qs = jmin(melt_energy, cap);
-    const double Gsm = Qs / (rs * Ls);
-    const double ri = (SW != SW_NONE) ? lr.rho : s.rho_bulk, riL = ri * Ls;
-    const double Qbi = (SW != SW_NONE) ? Qb_pre : Qb_ext(Tus);
-    const double alpha = (Qui - Qbi) / riL, beta = Qs / riL;
-    const double Cm = (hin > 0) ? an / (2 * hin) : 0.0;
-    const double Cf = (hc > 0) ? (1 - an) / hc : 0.0;
-    const double Km = dtp * Cm, Kf = dtp * Cf;
-    const double eps = 2.220446049250313e-16;
-    const double Dm = 1 - Km * beta, Df = 1 - Kf * beta;
-    const double am = (fabs(Dm) > eps) ? (an + Km * alpha) / Dm : an + Km * alpha;
-    const double af = (fabs(Df) > eps) ? (an + Kf * alpha) / Df : an + Kf * alpha;
-    const double dtVm = alpha + beta * am;
-    const bool melting = dtVm < 0;
-    const double atmp = melting ? am : af;
-    const double Qeff = Qui + Qs * atmp;
-    const double Eb = ri * ((SW != SW_NONE) ? latent_heat(lr, Tb) : latent_heat(s, Tb));
-    const double Eu = ri * ((SW != SW_NONE) ? latent_heat(lr, Tsi) : latent_heat(s, Tsi));
-    const double Qii_fun = (hin <= 0) ? 0.0 : -kip * (Tsi - Tb) / hin;
-    const double Qii = consolidated ? Qii_fun : 0.0;
-    const double wu = (Qeff - Qii) / Eu, wb = (Qii - Qbi) / Eb;
-    double hi1, a1;
-    ice_volume_update(wu + wb, hin, an, hc, dtp, hi1, a1);
-    hsn = (a1 > 0) ? hsn * an / a1 : 0.0;
-    const double Gsp = (a1 > 0) ? Psp / rs : 0.0;
-    double hs1 = hsn + dtp * (Gsp - Gsm);
-    hs1 = jmax(0.0, hs1);
-    {
-        const double rw = (SW != SW_NONE) ? rw_pre : s.rho_l;
-        const double hf = hi1 * (1 - ri / rw) - hs1 * rs / rw;
-        double dhs = (hf < 0) ? -hf * ri / rs : 0.0;
-        const double hsp = jmax(0.0, hs1 - dhs);
-        dhs = hs1 - hsp;
-        hi1 = hi1 + dhs * rs / ri;
-        hs1 = hsp;
-    }
-    hs1 = (a1 <= 0) ? 0.0 : hs1;
-    a(i, j) = a1; h(i, j) = hi1; hs(i, j) = hs1;
-    const double Pabs = rs * Gsp * a1;
-    if (o.mf_ice.p) o.mf_ice(i, j) = ri * (hi1 * a1 - Vin) / dtp;
-    if (o.mf_snow.p) o.mf_snow(i, j) = rs * (hs1 * a1 - Vsn) / dtp - Pabs;
-    if (o.mf_int.p) o.mf_int(i, j) = Pabs;
-    if (o.tu_ice.p) o.tu_ice(i, j) = Tsi;
-    if (o.tu_snow.p) o.tu_snow(i, j) = Tus;
-    if (ff.qtop_used.p) ff.qtop_used(i, j) = Qui;
-    if (ff.qbot_used.p) ff.qbot_used(i, j) = Qbi;
+    auto latent = [&](double T) {
+        if constexpr (SW != SW_NONE) return latent_heat(lr, T);
+        else return latent_heat(s, T);
+    };
+    auto Qb = [&](double T) {
+        if constexpr (SW != SW_NONE) return Qb_pre;
+        else return Qb_ext(T);
+    };
+    const UsedFluxes used = layered_from_surface(n, i, j, h, a, hs, o, hin, an, hsn, Tb, Tus, Ri, R, latent, Qx, Qb);
+    if (ff.qtop_used.p) ff.qtop_used(i, j) = used.top;
+    if (ff.qbot_used.p) ff.qbot_used(i, j) = used.bottom;
     if (SW != SW_NONE && sw.albedo_used.p) sw.albedo_used(i, j) = albedo(sc, Tus);
 }
 
@@ -368,18 +320,15 @@ template <int SW> SlabFn slab_flux_entry(int b);
 template <int SW> LayeredFn layered_flux_entry(int b);
 
 namespace {
-constexpr int kBlockX = 64, kBlockY = 4;
-dim3 cells(const GridDev& g) { return dim3((unsigned)((g.Nx + kBlockX - 1) / kBlockX), (unsigned)((g.Ny + kBlockY - 1) / kBlockY)); }
-
 template <int B>
 void slab_inst(const SlabDev& S, const HeatFluxDev& F, const FluxFields& ff, const ShortwaveDev& sw, const GridDev& g, const FRef& h,
                const FRef& a, const FRef& mf, int has_mf, double dt, hipStream_t st) {
 #if CSI_FLUX_SW == 0
-    hipLaunchKernelGGL((k_slab_flux<(B & 1) != 0, (B & 2) != 0, (B & 4) != 0, (B & 8) != 0, (B / 16) % 3, (B / 48) != 0>), cells(g),
-                       dim3(kBlockX, kBlockY), 0, st, S, F, ff, g, h, a, mf, has_mf, dt);
+    hipLaunchKernelGGL((k_slab_flux<(B & 1) != 0, (B & 2) != 0, (B & 4) != 0, (B & 8) != 0, (B / 16) % 3, (B / 48) != 0>), thermo_grid(g),
+                       thermo_block(), 0, st, S, F, ff, g, h, a, mf, has_mf, dt);
 #else
     hipLaunchKernelGGL((k_slab_flux<(B & 1) != 0, (B & 2) != 0, (B & 4) != 0, (B & 8) != 0, (B / 16) % 3, (B / 48) != 0, CSI_FLUX_SW, ShortwaveDev>),
-                       cells(g), dim3(kBlockX, kBlockY), 0, st, S, F, ff, g, h, a, mf, has_mf, dt, sw);
+                       thermo_grid(g), thermo_block(), 0, st, S, F, ff, g, h, a, mf, has_mf, dt, sw);
 #endif
 }
 template <int... B>
@@ -393,11 +342,11 @@ void layered_inst(const SlabDev& S, const SnowDev& W, const HeatFluxDev& F, cons
                   const FRef& h, const FRef& a, const FRef& hs, const LayeredOut& o, double dt, hipStream_t st) {
 #if CSI_FLUX_SW == 0
     hipLaunchKernelGGL((k_layered_flux<(B & 1) != 0, (B & 2) != 0, (B & 4) != 0, (B & 8) != 0, (B & 16) != 0, (B / 32) % 3, (B / 96) != 0>),
-                       cells(g), dim3(kBlockX, kBlockY), 0, st, S, W, F, ff, g, h, a, hs, o, dt);
+                       thermo_grid(g), thermo_block(), 0, st, S, W, F, ff, g, h, a, hs, o, dt);
 #else
     hipLaunchKernelGGL((k_layered_flux<(B & 1) != 0, (B & 2) != 0, (B & 4) != 0, (B & 8) != 0, (B & 16) != 0, (B / 32) % 3, (B / 96) != 0,
                                        CSI_FLUX_SW, ShortwaveDev>),
-                       cells(g), dim3(kBlockX, kBlockY), 0, st, S, W, F, ff, g, h, a, hs, o, dt, sw);
+                       thermo_grid(g), thermo_block(), 0, st, S, W, F, ff, g, h, a, hs, o, dt, sw);
 #endif
 }
 template <int... B>
@@ -422,12 +371,17 @@ bool flux_has_emission(const FluxTermsDev& t) {
     return false;
 }
 
+bool flux_reads_surface_temperature(const HeatFluxDev& F, int sw_mode, int top_bc_kind) {
+    // PrescribedTemperature per cell, or Tu- of the secant: the flux balance has a term that depends on T
+    return (top_bc_kind == 0 && F.prescribed_array) ||
+           (top_bc_kind == 1 && (flux_has_emission(F.top) || F.lin != LIN_NONE || sw_mode != SW_NONE));
+}
+
 namespace {
 // template bits shared by both steps: which per-cell arrays a configuration reads
 int flux_bits(const HeatFluxDev& F, const FluxFields& ff, const ShortwaveDev& sw, int top_bc_kind) {
-    const bool emit = flux_has_emission(F.top);
-    const bool ltu = (top_bc_kind == 0 && F.prescribed_array) || (top_bc_kind == 1 && (emit || F.lin != LIN_NONE || sw.mode != SW_NONE));
-    return (ff.qtop.p ? 1 : 0) | (ff.qbot.p ? 2 : 0) | (emit ? 4 : 0) | (ltu ? 8 : 0);
+    return (ff.qtop.p ? 1 : 0) | (ff.qbot.p ? 2 : 0) | (flux_has_emission(F.top) ? 4 : 0) |
+           (flux_reads_surface_temperature(F, sw.mode, top_bc_kind) ? 8 : 0);
 }
 // the variants beyond them: the LINEAR term's three states, times the per-cell bottom salinity (6 per combination of bits), in each
 // of the SHORTWAVE term's three states.  Every one can be selected: with a SHORTWAVE term the flux balance always has LTU, and a

@@ -349,26 +349,32 @@ def test_header_is_the_definition():
 
 # ---- the kernels' generated code (the build keeps the compiler's resource-usage remarks beside the object) ---------------------------
 
-def _instantiations():
+def _remarks(*units):
+    """The resource-usage remarks of the kernels of these units (csrc/Makefile keeps them beside the objects): name -> figures."""
     csrc = os.path.join(ROOT, "climaseaice.jl_amd", "csrc")
     subprocess.check_call(["make", "-s", "-j8", "-C", csrc], stdout=subprocess.DEVNULL)      # (no-op when the library is up to date)
-    blocks = []
-    for unit in ("thermo_flux", "thermo_flux_sw1", "thermo_flux_sw2"):      # one object per state of the term (csrc/Makefile)
-        blocks += open(os.path.join(csrc, unit + ".res")).read().split("remark: Function Name: ")[1:]
     out = {}
-    for b in blocks:
-        name = b.split()[0]
+    for unit in units:
+        for b in open(os.path.join(csrc, unit + ".res")).read().split("remark: Function Name: ")[1:]:
+            g = lambda k: int(re.search(k + r"[^:]*: (\d+)", b).group(1))
+            out[b.split()[0]] = dict(scratch=g("ScratchSize"), vspill=g("VGPRs Spill"), sspill=g("SGPRs Spill"), lds=g("LDS Size"),
+                                     vgprs=g(r"    VGPRs"), occupancy=g("Occupancy"))
+    return out
+
+
+def _instantiations():
+    out = _remarks("thermo_flux", "thermo_flux_sw1", "thermo_flux_sw2")      # one object per state of the term (csrc/Makefile)
+    for name, v in out.items():
         m = re.search(r"k_(slab|layered)_fluxILb([01])ELb([01])ELb([01])ELb([01])E(?:Lb([01])E)?Li(\d)ELb([01])ELi(\d)EJ", name)
         assert m, name
-        g = lambda k: int(re.search(k + r"[^:]*: (\d+)", b).group(1))
-        out[name] = dict(kernel=m.group(1), sw=int(m.group(9)), scratch=g("ScratchSize"), vspill=g("VGPRs Spill"), sspill=g("SGPRs Spill"),
-                         lds=g("LDS Size"), vgprs=g(r"    VGPRs"), occupancy=g("Occupancy"))
+        v.update(kernel=m.group(1), sw=int(m.group(9)))
     return out
 
 
 def test_new_instantiations_have_no_scratch_and_no_spills():
     """csrc/thermo_flux*.res: 16 x 6 slab and 32 x 6 layered combinations of the older flags, each in three shortwave states.  The
-    number and per-cell states are new: 192 slab and 384 layered instantiations, none with scratch, spilled registers or LDS."""
+    number and per-cell states are new: 192 slab and 384 layered instantiations, none with scratch, spilled registers or LDS.
+    csrc/thermo.res: neither have k_slab and k_layered."""
     inst = _instantiations()
     count = lambda kernel, sw: sum(1 for v in inst.values() if v["kernel"] == kernel and v["sw"] == sw)
     assert [count("slab", k) for k in (0, 1, 2)] == [96, 96, 96] and [count("layered", k) for k in (0, 1, 2)] == [192, 192, 192]
@@ -378,6 +384,12 @@ def test_new_instantiations_have_no_scratch_and_no_spills():
     print("new instantiations: VGPRs %d ... %d, occupancy %d ... %d" % (min(v["vgprs"] for v in new.values()),
           max(v["vgprs"] for v in new.values()), min(v["occupancy"] for v in new.values()), max(v["occupancy"] for v in new.values())))
     assert max(v["vgprs"] for v in new.values()) <= 128
+    # csrc/thermo.res: the numeric kernels, which run each step's second half from the same functions (thermo_dev.h)
+    numeric = _remarks("thermo")
+    assert len(numeric) == 2 and all(re.search(r"\dk_(slab|layered)E", n) for n in numeric), list(numeric)
+    for n, v in numeric.items():
+        print(n, v)
+        assert v["scratch"] == 0 and v["vspill"] == 0 and v["sspill"] == 0, (n, v)
 
 
 # ---- front end -----------------------------------------------------------------------------------------------------------------------
