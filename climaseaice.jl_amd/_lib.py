@@ -106,7 +106,7 @@ SYMBOLS = ["csi_version", "csi_context_create", "csi_context_destroy", "csi_last
            "csi_output_snapshot", "csi_output_test", "csi_output_wait", "csi_output_release", "csi_output_destroy",
            "csi_derived_compute", "csi_budget_compute", "csi_derived_stats",
            "csi_momentum_terms_compute", "csi_momentum_budget_compute", "csi_momentum_terms_stats",
-           "csi_mixed_layer_set", "csi_mixed_layer_step", "csi_mixed_layer_stats", "csi_shortwave_set"]
+           "csi_mixed_layer_set", "csi_mixed_layer_step", "csi_mixed_layer_stats", "csi_shortwave_set", "csi_last_thermo"]
 DIAG_VELOCITY, DIAG_TRACERS, DIAG_ALL = 1, 2, 3
 OUT_F64, OUT_F32 = 0, 1
 DERIVED_ALL = 127
@@ -312,6 +312,7 @@ def load():
         "csi_mixed_layer_set": [vp, C.POINTER(MixedLayerParams)], "csi_mixed_layer_step": [vp, dbl, i32],
         "csi_mixed_layer_stats": [vp, C.POINTER(i64)],
         "csi_shortwave_set": [vp, C.POINTER(Shortwave)],
+        "csi_last_thermo": [vp, C.POINTER(i32), C.POINTER(i32), C.POINTER(i32)],
     }
     for name, args in sig.items():
         fn = getattr(L, name, None)
@@ -490,6 +491,13 @@ class Context:
         nt, tx, ty, st = C.c_int32(), C.c_int32(), C.c_int32(), C.c_int32()
         self.call("csi_last_advection", C.byref(nt), C.byref(tx), C.byref(ty), C.byref(st))
         return dict(tracers_per_thread=nt.value, tile_x=tx.value, tile_y=ty.value, stage_fused=st.value)
+
+    def last_thermo(self):
+        """csi_last_thermo: the kernel of the last thermodynamic launch -- step 0 none yet, 1 k_slab, 2 k_layered, 3 k_slab_flux,
+        4 k_layered_flux; shortwave 0 / 1 / 2 (no term / the flux a number / per cell); index within the family (-1: numeric kernels)."""
+        st, sw, b = C.c_int32(), C.c_int32(), C.c_int32()
+        self.call("csi_last_thermo", C.byref(st), C.byref(sw), C.byref(b))
+        return dict(step=st.value, shortwave=sw.value, index=b.value)
 
     def comm_count(self):
         """ranks of the RCCL communicator (ncclCommCount); 0 without one"""

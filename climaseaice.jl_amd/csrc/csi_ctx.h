@@ -348,6 +348,7 @@ struct csi_context {
     int last_fused = 0;
     AdvLayout last_adv{0, 0, 0};     // csi_last_advection: what the last tendency / stage launch of k_tendencies used (0: none yet)
     int last_adv_stage = 0;          // ... and whether it was a whole RK stage in one launch
+    ThermoLaunch last_thermo{0, 0, -1};      // csi_last_thermo: what the last thermodynamic launch used, as its launcher returned it (step 0: none yet)
     double ibc[2][4] = {{0, 0, 0, 0}, {0, 0, 0, 0}};   // csi_immersed_flux_bc_set: [u | v][west, east, south, north]
     int exch_k = 0;       // sub-steps per halo exchange (0 = auto: the largest k with 2k <= halo, at most 4)
     // Tile activity (csi_activity.hip, run_fused): the live-tile list of the current sub-cycle and, read back asynchronously, how many

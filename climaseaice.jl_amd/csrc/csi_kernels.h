@@ -194,10 +194,13 @@ struct SnowDev {
     int top_bc_kind;
 };
 struct LayeredOut { FRef mf_ice, mf_snow, mf_int, tu_ice, tu_snow; };   // optional outputs (p == nullptr: absent)
-void launch_layered_step(const SlabDev& S, const SnowDev& W, const GridDev& g, const FRef& h, const FRef& a, const FRef& hs,
-                         const LayeredOut& o, double dt, hipStream_t s);
-void launch_slab_step(const SlabDev& S, const GridDev& g, const FRef& h, const FRef& a, const FRef& mf, int has_mf,
-                      double dt, hipStream_t s);
+// what a thermodynamic launch used (csi_last_thermo): step 1 k_slab, 2 k_layered, 3 k_slab_flux, 4 k_layered_flux (0: none yet); the
+// table of the flux kernels it took the launcher from (SW_NONE / SW_NUMBER / SW_CELL); the index into that table (-1: the numeric kernels)
+struct ThermoLaunch { int step, sw, index; };
+ThermoLaunch launch_layered_step(const SlabDev& S, const SnowDev& W, const GridDev& g, const FRef& h, const FRef& a, const FRef& hs,
+                                 const LayeredOut& o, double dt, hipStream_t s);
+ThermoLaunch launch_slab_step(const SlabDev& S, const GridDev& g, const FRef& h, const FRef& a, const FRef& mf, int has_mf,
+                              double dt, hipStream_t s);
 
 // per-cell heat fluxes, RadiativeEmission, the surface-temperature solve (thermo_flux.hip; include/csi.h csi_heat_fluxes_set)
 constexpr int kMaxFluxTerms = 8;
@@ -236,11 +239,12 @@ struct ShortwaveDev {
 bool flux_has_emission(const FluxTermsDev& t);
 // the kernels read the cell's surface temperature (their LTU flag): the field -- CSI_F_TU / CSI_F_TUS -- must be bound exactly then
 bool flux_reads_surface_temperature(const HeatFluxDev& F, int sw_mode, int top_bc_kind);
-void launch_slab_flux_step(const SlabDev& S, const HeatFluxDev& F, const FluxFields& ff, const ShortwaveDev& sw, const GridDev& g,
-                           const FRef& h, const FRef& a, const FRef& mf, int has_mf, double dt, hipStream_t s);
-void launch_layered_flux_step(const SlabDev& S, const SnowDev& W, const HeatFluxDev& F, const FluxFields& ff, const ShortwaveDev& sw,
-                              const GridDev& g, const FRef& h, const FRef& a, const FRef& hs, const LayeredOut& o, double dt,
-                              hipStream_t s);
+// (both return the table and the index b they launched from)
+ThermoLaunch launch_slab_flux_step(const SlabDev& S, const HeatFluxDev& F, const FluxFields& ff, const ShortwaveDev& sw, const GridDev& g,
+                                   const FRef& h, const FRef& a, const FRef& mf, int has_mf, double dt, hipStream_t s);
+ThermoLaunch launch_layered_flux_step(const SlabDev& S, const SnowDev& W, const HeatFluxDev& F, const FluxFields& ff, const ShortwaveDev& sw,
+                                      const GridDev& g, const FRef& h, const FRef& a, const FRef& hs, const LayeredOut& o, double dt,
+                                      hipStream_t s);
 
 // the slab-ocean mixed layer (mixed_layer.hip; include/csi.h csi_mixed_layer_set).  rc = rho * c, C = rc * depth, grc = gamma * rc,
 // formed on the host in this order; Fo, K, Ta, Qd, S: the numbers a configuration without the array reads; nx, ny: the interior.

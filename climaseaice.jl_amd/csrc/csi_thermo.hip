@@ -83,9 +83,9 @@ static int32_t do_layered(csi_context* c, const SlabDev& S, const SnowDev& W, do
         FluxFields ff;
         ShortwaveDev sw;
         if ((rc = flux_fields(c, S, W.top_bc_kind, CSI_F_TUS, true, ff, sw))) return rc;
-        launch_layered_flux_step(S, W, c->heat, ff, sw, c->g, ref_of(c, CSI_F_H), ref_of(c, CSI_F_A), ref_of(c, CSI_F_HS), o, dt, c->stream);
+        c->last_thermo = launch_layered_flux_step(S, W, c->heat, ff, sw, c->g, ref_of(c, CSI_F_H), ref_of(c, CSI_F_A), ref_of(c, CSI_F_HS), o, dt, c->stream);
     } else {
-        launch_layered_step(S, W, c->g, ref_of(c, CSI_F_H), ref_of(c, CSI_F_A), ref_of(c, CSI_F_HS), o, dt, c->stream);
+        c->last_thermo = launch_layered_step(S, W, c->g, ref_of(c, CSI_F_H), ref_of(c, CSI_F_A), ref_of(c, CSI_F_HS), o, dt, c->stream);
     }
     HIP_TRY(c, hipGetLastError());
     return CSI_OK;
@@ -101,9 +101,9 @@ static int32_t do_slab(csi_context* c, const SlabDev& S, double dt) {
         ShortwaveDev sw;
         int32_t rc = flux_fields(c, S, S.top_bc_kind, CSI_F_TU, false, ff, sw);
         if (rc) return rc;
-        launch_slab_flux_step(S, c->heat, ff, sw, c->g, ref_of(c, CSI_F_H), ref_of(c, CSI_F_A), ref_of(c, CSI_F_MASS_FLUX), has_mf, dt, c->stream);
+        c->last_thermo = launch_slab_flux_step(S, c->heat, ff, sw, c->g, ref_of(c, CSI_F_H), ref_of(c, CSI_F_A), ref_of(c, CSI_F_MASS_FLUX), has_mf, dt, c->stream);
     } else {
-        launch_slab_step(S, c->g, ref_of(c, CSI_F_H), ref_of(c, CSI_F_A), ref_of(c, CSI_F_MASS_FLUX), has_mf, dt, c->stream);
+        c->last_thermo = launch_slab_step(S, c->g, ref_of(c, CSI_F_H), ref_of(c, CSI_F_A), ref_of(c, CSI_F_MASS_FLUX), has_mf, dt, c->stream);
     }
     HIP_TRY(c, hipGetLastError());
     return CSI_OK;
@@ -196,6 +196,14 @@ int32_t csi_slab_params_set(csi_context* c, const csi_slab_params* p) {
     if (!c) return CSI_ERR_INVALID_ARGUMENT;
     c->slab_set = p != nullptr;
     if (p) c->slab = slab_dev(p);
+    return CSI_OK;
+}
+
+int32_t csi_last_thermo(csi_context* c, int32_t* step, int32_t* shortwave, int32_t* index) {
+    if (!c) return CSI_ERR_INVALID_ARGUMENT;
+    if (step) *step = c->last_thermo.step;
+    if (shortwave) *shortwave = c->last_thermo.sw;
+    if (index) *index = c->last_thermo.index;
     return CSI_OK;
 }
 

@@ -51,14 +51,16 @@ __global__ void __launch_bounds__(256) k_layered(SlabDev s, SnowDev w, GridDev g
                          [&](double) { return Qu; }, [&](double) { return (s.bot_flux_kind == 1) ? (-(1 - an)) * s.Qb : s.Qb; });
 }
 
-void launch_layered_step(const SlabDev& S, const SnowDev& W, const GridDev& g, const FRef& h, const FRef& a, const FRef& hs,
-                         const LayeredOut& o, double dt, hipStream_t s) {
+ThermoLaunch launch_layered_step(const SlabDev& S, const SnowDev& W, const GridDev& g, const FRef& h, const FRef& a, const FRef& hs,
+                                 const LayeredOut& o, double dt, hipStream_t s) {
     hipLaunchKernelGGL(k_layered, thermo_grid(g), thermo_block(), 0, s, S, W, g, h, a, hs, o, dt);
+    return ThermoLaunch{2, SW_NONE, -1};
 }
 
-void launch_slab_step(const SlabDev& S, const GridDev& g, const FRef& h, const FRef& a, const FRef& mf, int has_mf,
-                      double dt, hipStream_t s) {
+ThermoLaunch launch_slab_step(const SlabDev& S, const GridDev& g, const FRef& h, const FRef& a, const FRef& mf, int has_mf,
+                              double dt, hipStream_t s) {
     hipLaunchKernelGGL(k_slab, thermo_grid(g), thermo_block(), 0, s, S, g, h, a, mf, has_mf, dt);
+    return ThermoLaunch{1, SW_NONE, -1};
 }
 
 }  // namespace csi

@@ -385,24 +385,30 @@ int flux_bits(const HeatFluxDev& F, const FluxFields& ff, const ShortwaveDev& sw
 }
 // the variants beyond them: the LINEAR term's three states, times the per-cell bottom salinity (6 per combination of bits), in each
 // of the SHORTWAVE term's three states.  Every one can be selected: with a SHORTWAVE term the flux balance always has LTU, and a
-// PrescribedTemperature top has it exactly when the temperature is per cell.
+// PrescribedTemperature top has it exactly when the temperature is per cell.  tests/test_thermo_flux_matrix_table.py proves it --
+// tests/thermo_flux_matrix.py restates this rule and builds a configuration for each of the 864 --, and tests/test_gpu_thermo_flux_matrix.py
+// runs every one with the launch reported by csi_last_thermo.
 int flux_variant(const HeatFluxDev& F) { return F.lin + 3 * (F.bottom_salinity_array ? 1 : 0); }
 }  // namespace
 
-void launch_slab_flux_step(const SlabDev& S, const HeatFluxDev& F, const FluxFields& ff, const ShortwaveDev& sw, const GridDev& g,
-                           const FRef& h, const FRef& a, const FRef& mf, int has_mf, double dt, hipStream_t s) {
+ThermoLaunch launch_slab_flux_step(const SlabDev& S, const HeatFluxDev& F, const FluxFields& ff, const ShortwaveDev& sw, const GridDev& g,
+                                   const FRef& h, const FRef& a, const FRef& mf, int has_mf, double dt, hipStream_t s) {
     const int b = flux_bits(F, ff, sw, S.top_bc_kind) + 16 * flux_variant(F);
-    const SlabFn fn = sw.mode == SW_CELL ? slab_flux_entry<SW_CELL>(b) : (sw.mode == SW_NUMBER ? slab_flux_entry<SW_NUMBER>(b) : slab_flux_entry<SW_NONE>(b));
+    const int table = sw.mode == SW_CELL ? SW_CELL : (sw.mode == SW_NUMBER ? SW_NUMBER : SW_NONE);
+    const SlabFn fn = table == SW_CELL ? slab_flux_entry<SW_CELL>(b) : (table == SW_NUMBER ? slab_flux_entry<SW_NUMBER>(b) : slab_flux_entry<SW_NONE>(b));
     fn(S, F, ff, sw, g, h, a, mf, has_mf, dt, s);
+    return ThermoLaunch{3, table, b};
 }
 
-void launch_layered_flux_step(const SlabDev& S, const SnowDev& W, const HeatFluxDev& F, const FluxFields& ff, const ShortwaveDev& sw,
-                              const GridDev& g, const FRef& h, const FRef& a, const FRef& hs, const LayeredOut& o, double dt,
-                              hipStream_t s) {
+ThermoLaunch launch_layered_flux_step(const SlabDev& S, const SnowDev& W, const HeatFluxDev& F, const FluxFields& ff, const ShortwaveDev& sw,
+                                      const GridDev& g, const FRef& h, const FRef& a, const FRef& hs, const LayeredOut& o, double dt,
+                                      hipStream_t s) {
     const int b = (flux_bits(F, ff, sw, W.top_bc_kind) | (F.snowfall_array ? 16 : 0)) + 32 * flux_variant(F);
-    const LayeredFn fn = sw.mode == SW_CELL ? layered_flux_entry<SW_CELL>(b)
-                                            : (sw.mode == SW_NUMBER ? layered_flux_entry<SW_NUMBER>(b) : layered_flux_entry<SW_NONE>(b));
+    const int table = sw.mode == SW_CELL ? SW_CELL : (sw.mode == SW_NUMBER ? SW_NUMBER : SW_NONE);
+    const LayeredFn fn = table == SW_CELL ? layered_flux_entry<SW_CELL>(b)
+                                          : (table == SW_NUMBER ? layered_flux_entry<SW_NUMBER>(b) : layered_flux_entry<SW_NONE>(b));
     fn(S, W, F, ff, sw, g, h, a, hs, o, dt, s);
+    return ThermoLaunch{4, table, b};
 }
 #endif
 

@@ -1337,6 +1337,17 @@ int32_t csi_last_path(csi_context* ctx, int32_t* fused, int32_t* exchange_interv
  * the launch was a whole RK stage of an advection-only model (tendencies + tracer update, 1) or the tendencies alone (0).  What the
  * launch code used, recorded when it launched; all zero before the first one.  Any pointer may be NULL. */
 int32_t csi_last_advection(csi_context* ctx, int32_t* tracers_per_thread, int32_t* tile_x, int32_t* tile_y, int32_t* stage_fused);
+/* The kernel of the last thermodynamic launch (csi_slab_thermo_step, csi_layered_thermo_step, a time step with thermodynamics).
+ * step: 0 none yet, 1 k_slab, 2 k_layered (the numeric kernels), 3 k_slab_flux, 4 k_layered_flux (the flux-term kernels, which run once
+ * a side has terms, the prescribed temperature, the snowfall or the bottom salinity is an array, or a used-flux output is bound).
+ * shortwave: the SHORTWAVE term's state the kernel was compiled for -- 0 none, 1 the flux a number, 2 the flux per cell.  index: the
+ * kernel's number within that family (-1 for the numeric kernels),
+ *     slab      flux_bits                       + 16 * (linear + 3 * per-cell bottom salinity)
+ *     layered   (flux_bits | per-cell snowfall << 4) + 32 * (linear + 3 * per-cell bottom salinity)
+ * flux_bits = top ARRAY term | bottom ARRAY term << 1 | RadiativeEmission << 2 | per-cell surface temperature read << 3; linear: 0 no
+ * LINEAR term, 1 its K and Ta numbers, 2 per cell.  What the launch code used, returned by the launcher when it launched.  Any pointer
+ * may be NULL. */
+int32_t csi_last_thermo(csi_context* ctx, int32_t* step, int32_t* shortwave, int32_t* index);
 /* Kernel launches and sub-steps of the last fused sub-cycle (sub-steps / launches = sub-steps per launch). */
 int32_t csi_last_launches(csi_context* ctx, int32_t* launches, int32_t* substeps);
 /* Number of kernel launches issued for one sub-step in the current configuration (upper bound). */

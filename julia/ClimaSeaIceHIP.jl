@@ -587,6 +587,13 @@ function last_advection(ctx)
     check(ctx, ccall((:csi_last_advection, libcsi), Int32, (Ptr{Cvoid}, Ref{Int32}, Ref{Int32}, Ref{Int32}, Ref{Int32}), ctx.handle, nt, tx, ty, st))
     return (tracers_per_thread = Int(nt[]), tile_x = Int(tx[]), tile_y = Int(ty[]), stage_fused = st[] != 0)
 end
+# The kernel of the last thermodynamic launch (include/csi.h: csi_last_thermo): step 0 none yet, 1 k_slab, 2 k_layered, 3 k_slab_flux,
+# 4 k_layered_flux; the SHORTWAVE term's state it was compiled for (0 / 1 / 2); its index within the family (-1: the numeric kernels)
+function last_thermo(ctx)
+    st, sw, b = Ref{Int32}(0), Ref{Int32}(0), Ref{Int32}(0)
+    check(ctx, ccall((:csi_last_thermo, libcsi), Int32, (Ptr{Cvoid}, Ref{Int32}, Ref{Int32}, Ref{Int32}), ctx.handle, st, sw, b))
+    return (step = Int(st[]), shortwave = Int(sw[]), index = Int(b[]))
+end
 set_row_constant!(ctx, on::Bool, rtol::Real = 0.0) =
     check(ctx, ccall((:csi_set_row_constant, libcsi), Int32, (Ptr{Cvoid}, Int32, Cdouble), ctx.handle, on ? 1 : 0, rtol))
 function row_constant_rows(ctx)
