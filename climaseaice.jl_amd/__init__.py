@@ -25,5 +25,6 @@ from .time_series import (Clamp, Cyclical, FieldTimeSeries, InMemory, Linear, Re
 from .model import (FieldBoundaryConditions, FluxBoundaryCondition, ImmersedBoundaryCondition, MeltingConstrainedFluxBalance, ValueBoundaryCondition, PrescribedTemperature, RadiativeEmission, LinearHeatFlux, bulk_sensible_heat_flux, SteppedAlbedo, ShortwaveRadiation, SeaIceModel, SlabThermodynamics, SnowSlabThermodynamics,
                     snow_slab_thermodynamics, UpwindBiased, WENO, set_, time_step, time_step_momentum, compute_momentum_tendencies, update_state,
                     prognostic_state, restore_prognostic_state)
+from .enthalpy import ColumnField, ColumnGrid, ColumnTimeSeries, EnthalpyMethodSeaIceModel, MolecularDiffusivity
 
 __all__ = [n for n in dir() if not n.startswith("_")]

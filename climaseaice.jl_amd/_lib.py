@@ -106,7 +106,16 @@ SYMBOLS = ["csi_version", "csi_context_create", "csi_context_destroy", "csi_last
            "csi_output_snapshot", "csi_output_test", "csi_output_wait", "csi_output_release", "csi_output_destroy",
            "csi_derived_compute", "csi_budget_compute", "csi_derived_stats",
            "csi_momentum_terms_compute", "csi_momentum_budget_compute", "csi_momentum_terms_stats",
-           "csi_mixed_layer_set", "csi_mixed_layer_step", "csi_mixed_layer_stats", "csi_shortwave_set", "csi_last_thermo"]
+           "csi_mixed_layer_set", "csi_mixed_layer_step", "csi_mixed_layer_stats", "csi_shortwave_set", "csi_last_thermo",
+           "csi_enthalpy_plan", "csi_enthalpy_create", "csi_enthalpy_destroy", "csi_enthalpy_bind", "csi_enthalpy_boundary_set",
+           "csi_enthalpy_set", "csi_enthalpy_update_state", "csi_enthalpy_time_step", "csi_enthalpy_last_launch",
+           "csi_enthalpy_ice_thickness"]
+# the enthalpy-method column model (include/csi.h): csi_enthalpy_array, csi_enthalpy_side, csi_enthalpy_bc_kind, the two forms, the rule's constants
+ENTH_H, ENTH_T, ENTH_PHI, ENTH_KAPPA = 0, 1, 2, 3
+ENTH_T_BOTTOM, ENTH_T_TOP, ENTH_H_BOTTOM, ENTH_H_TOP = 0, 1, 2, 3
+ENTH_BC_NONE, ENTH_BC_NUMBER, ENTH_BC_ARRAY, ENTH_BC_SERIES_SCALAR, ENTH_BC_SERIES_PLANE, ENTH_BC_FLUX, ENTH_BC_GRADIENT = range(7)
+ENTH_PER_STEP, ENTH_ON_CHIP = 1, 2
+ENTH_MAX_SUBSTEPS, ENTH_MIN_WAVES_PER_CU, ENTH_LDS_PER_CU = 64, 2, 163840
 DIAG_VELOCITY, DIAG_TRACERS, DIAG_ALL = 1, 2, 3
 OUT_F64, OUT_F32 = 0, 1
 DERIVED_ALL = 127
@@ -220,6 +229,18 @@ class OutputField(C.Structure):
                 ("fill_value", C.c_double)]
 
 
+class EnthalpyParams(C.Structure):
+    """csi_enthalpy_params (include/csi.h): the enthalpy-method column model's extents, faces and parameters."""
+    _fields_ = [("Nx", C.c_int32), ("Ny", C.c_int32), ("Nz", C.c_int32), ("reserved", C.c_int32), ("z_faces", C.POINTER(C.c_double)),
+                ("ice_heat_capacity", C.c_double), ("water_heat_capacity", C.c_double), ("fusion_enthalpy", C.c_double),
+                ("kappa_ice", C.c_double), ("kappa_water", C.c_double)]
+
+
+class EnthalpyLaunch(C.Structure):
+    """csi_enthalpy_launch (include/csi.h): what the last csi_enthalpy_time_step launched."""
+    _fields_ = [("form", C.c_int32), ("launches", C.c_int32), ("substeps_per_launch", C.c_int32), ("lds_bytes", C.c_int32)]
+
+
 class CsiError(RuntimeError):
     def __init__(self, code, msg):
         super().__init__(f"libcsi_hip error {code}: {msg}")
@@ -313,6 +334,13 @@ def load():
         "csi_mixed_layer_stats": [vp, C.POINTER(i64)],
         "csi_shortwave_set": [vp, C.POINTER(Shortwave)],
         "csi_last_thermo": [vp, C.POINTER(i32), C.POINTER(i32), C.POINTER(i32)],
+        "csi_enthalpy_plan": [i32, i32, C.POINTER(i32), C.POINTER(i64), C.POINTER(i32), C.POINTER(i32)],
+        "csi_enthalpy_create": [vp, C.POINTER(EnthalpyParams), C.POINTER(vp)], "csi_enthalpy_destroy": [vp],
+        "csi_enthalpy_bind": [vp, i32, vp],
+        "csi_enthalpy_boundary_set": [vp, i32, i32, dbl, vp, C.POINTER(TimeSeries)],
+        "csi_enthalpy_set": [vp, i32, dbl], "csi_enthalpy_update_state": [vp, dbl],
+        "csi_enthalpy_time_step": [vp, dbl, i32, dbl, C.POINTER(dbl)],
+        "csi_enthalpy_last_launch": [vp, C.POINTER(EnthalpyLaunch)], "csi_enthalpy_ice_thickness": [vp, dbl, vp],
     }
     for name, args in sig.items():
         fn = getattr(L, name, None)
@@ -361,6 +389,16 @@ def time_series_plan(times, indexing, period, t):
     if rc != OK:
         raise CsiError(rc, "csi_time_series_plan: invalid input")
     return n1.value, n2.value, frac.value
+
+
+def enthalpy_plan(Nz, forced_path=0):
+    """csi_enthalpy_plan as a dict: the form of the enthalpy-method column model's step kernel for columns of Nz levels (pure host
+    function; CsiError on invalid input and for a forced on-chip form that does not fit)."""
+    form, lds, waves, cap = C.c_int32(), C.c_int64(), C.c_int32(), C.c_int32()
+    rc = load().csi_enthalpy_plan(int(Nz), int(forced_path), C.byref(form), C.byref(lds), C.byref(waves), C.byref(cap))
+    if rc != OK:
+        raise CsiError(rc, "csi_enthalpy_plan: invalid input, or the forced on-chip form does not fit")
+    return dict(form=form.value, lds_bytes=lds.value, waves_per_cu=waves.value, max_substeps=cap.value)
 
 
 def regrid_plan_axis(nodes, periodic, period, x):

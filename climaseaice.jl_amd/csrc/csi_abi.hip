@@ -34,6 +34,14 @@ int32_t csi_context_create(int32_t device_id, void* hip_stream, csi_context** ou
             return fail(nullptr, CSI_ERR_INVALID_ARGUMENT, std::string("CSI_ADV_SHAPE=") + e + ": 0 (by grid size), 1 (64 x 8), 2 (63 x 7) or 3 (63 x 11)");
         adv_shape = (int)v;
     }
+    int enth_path = 0;
+    if (const char* e = getenv("CSI_ENTH_PATH"); e && *e) {
+        char* end = nullptr;
+        const long v = strtol(e, &end, 10);
+        if (*end || v < 0 || v > 2)
+            return fail(nullptr, CSI_ERR_INVALID_ARGUMENT, std::string("CSI_ENTH_PATH=") + e + ": 0 (by the rule of csi_enthalpy_plan), 1 (per step) or 2 (on chip)");
+        enth_path = (int)v;
+    }
     csi_context* c = new csi_context();
     c->device = device_id;
     if (hip_stream) {
@@ -55,6 +63,7 @@ int32_t csi_context_create(int32_t device_id, void* hip_stream, csi_context** ou
         c->tune.peer_edge = env_int("CSI_PEER_EDGE");          // rows the chunks next to a peer-connected y side are shorter by (default 4; 0: uniform chunks)
         c->tune.write_through = env_int("CSI_WRITE_THROUGH");  // 0 / 1: never / always store the pair kernel's results write-through (default: by grid size)
         c->tune.adv_nt = env_int("CSI_ADV_NT"); c->tune.pair_target = env_int("CSI_PAIR_TARGET");
+        c->tune.enth_path = enth_path;                         // form of the enthalpy-method column model's step kernel (checked above)
         c->tune.adv_shape = adv_shape;                         // block shape of the advection kernel's two-tracer layout (checked above)
         { const char* e = getenv("CSI_ADV_STAGE_MAX_CELLS"); if (e && *e) c->tune.adv_stage_max_cells = atol(e); }      // A/B: largest grid that takes one launch per RK stage
         { const int v = env_int("CSI_ROW_TARGET_1024"); if (v >= 0) c->tune.row_target_1024 = v; }      // 0: per-row coefficients keep 1536 tiles (rounds 3-5a)
@@ -74,6 +83,7 @@ int32_t csi_context_destroy(csi_context* c) {
     peer_release(c);
     series_release(c);
     output_release(c);
+    enthalpy_release(c);
     for (auto& e : c->ring_ev) if (e) hipEventDestroy(e);
     if (c->band_ev_pair) hipEventDestroy(c->band_ev_pair);
     if (c->band_ev_band) hipEventDestroy(c->band_ev_band);

@@ -11,6 +11,7 @@
 //   csi_output.hip        device-side output: output sets, their staging slots, the copy stream and the slot events
 //   csi_derived.hip       derived fields and energy budget integrals: binding checks, the launches, the budget's combine over the ranks
 //   csi_momentum_terms.hip   momentum balance terms and their power: binding checks, the launches, the power sums' combine over the ranks
+//   csi_enthalpy.hip      the enthalpy-method column model: the choosing rule, the model object, its launches
 //   csi_mem.h       DeviceBuf / PinnedBuf: the owner of every allocation the library makes
 #pragma once
 #include "../../include/csi.h"
@@ -333,6 +334,8 @@ struct csi_context {
     // csi_output_* (csi_output.hip): the sets and the copy stream their records leave on, made at the first csi_output_create
     OutputSet out_sets[kMaxOutputSets];
     hipStream_t out_stream = nullptr;
+    // csi_enthalpy_create (csi_enthalpy.hip): the column models made from this context that have not been destroyed yet
+    std::vector<csi_enthalpy*> enthalpies;
     long grid_gen = 0;                   // csi_grid_set calls so far
     int weno_w32 = 0;     // csi_set_weno_weight_dtype: 1 = WENO weights in single precision (upstream's FT2 = Float32, recalled)
     // csi_rheology_set / csi_momentum_solver_set (csi_momentum.hip): ViscousRheology, ExplicitSolver
@@ -386,6 +389,7 @@ struct csi_context {
                     adv_shape = -1,        // CSI_ADV_SHAPE: block shape where two tracers share a thread (1 / 2 / 3: 64 x 8 / 63 x 7 / 63 x 11; default by grid size)
                     band_fused = -1,      // CSI_BAND_FUSED=0: the fold band on the three kernels + two copies per step (rounds 4-6a); default: six launches per step without copies, loads hoisted (csi_fold.hip band_substeps_fused)
                     band_event_flags = -1,   // CSI_BAND_EVENT_FLAGS (csi_fold.hip ensure_band)
+                    enth_path = 0,         // CSI_ENTH_PATH: the form of the enthalpy-method column model's step kernel (0 by the rule, 1 per step, 2 on chip)
                     no_geom_sig = -1;      // debugging aid (CSI_DEBUG_NO_GEOM_SIG=1): skip the launch-geometry check of the peer set-up (tests/test_gpu_local_tiles.py)
       long adv_stage_max_cells = 1L << 40;      // advection-only models: one launch per RK stage up to this many cells (advect_stage_supported; no cut since round 6)
     } tune;
@@ -586,6 +590,7 @@ static inline const Bound& band_bound(const csi_context* c, int q) { return c->f
 int32_t series_prefetch(csi_context* c);                 // ... the look-ahead uploads of the newest csi_time_series_update, once (no-op otherwise)
 void series_release(csi_context* c);                     // csi_time_series.hip: events, copy stream, rings (the streams have been drained)
 bool series_drives(const csi_context* c, int fid);       // ... a series of either kind (model grid, regridded) is set on the slot
+void enthalpy_release(csi_context* c);                   // csi_enthalpy.hip: every surviving column model (the context's stream has been drained)
 void output_release(csi_context* c);                     // csi_output.hip: every set, the copy stream (the context's stream has been drained)
 int32_t peer_check_entry(csi_context* c);      // (csi_abi.hip: the error word of the peer transport, checked at every entry point)
 

@@ -126,18 +126,22 @@ def _is_number(x):
 
 
 class ValueBoundaryCondition:
-    """Oceananigans ValueBoundaryCondition(value): on a tangential velocity at a wall, value 0 is no-slip."""
+    """Oceananigans ValueBoundaryCondition(value): on a tangential velocity at a wall, value 0 is no-slip.  A number becomes a float;
+    anything else -- an (Ny, Nx) array, a FieldTimeSeries: the boundary temperatures of EnthalpyMethodSeaIceModel -- is kept as it
+    is, and the velocity conditions of SeaIceModel refuse it by name."""
 
     def __init__(self, value=0.0):
-        self.value = float(value)
+        self.value = float(value) if np.isscalar(value) else value
 
 
 class FieldBoundaryConditions:
-    """FieldBoundaryConditions(north =, south =, west =, east =): sides left out keep the default (no-flux for the
-    tangential velocity, impenetrable for the normal one).  Used as SeaIceModel(boundary_conditions = dict(u =, v =))."""
+    """FieldBoundaryConditions(north =, south =, west =, east =, top =, bottom =): sides left out keep the default (no-flux for the
+    tangential velocity, impenetrable for the normal one; no-flux for the column model's temperature).  Used as
+    SeaIceModel(boundary_conditions = dict(u =, v =)) and EnthalpyMethodSeaIceModel(boundary_conditions = dict(T =))."""
 
-    def __init__(self, north=None, south=None, west=None, east=None, immersed=None):
+    def __init__(self, north=None, south=None, west=None, east=None, immersed=None, top=None, bottom=None):
         self.north, self.south, self.west, self.east, self.immersed = north, south, west, east, immersed
+        self.top, self.bottom = top, bottom
 
 
 class FluxBoundaryCondition:
@@ -536,6 +540,9 @@ class SeaIceModel:
                 bc = getattr(bcs, side, None) if bcs is not None else None
                 if bc is not None and not isinstance(bc, ValueBoundaryCondition):
                     raise NotImplementedError("velocity boundary conditions: ValueBoundaryCondition or the default")
+                if bc is not None and not isinstance(bc.value, float):
+                    raise NotImplementedError("velocity boundary conditions: ValueBoundaryCondition(number); an array or a FieldTimeSeries "
+                                              "is accepted by the enthalpy-method column model's temperature only")
                 self.ctx.call("csi_velocity_bc_set", _lib.F[name], k, 0 if bc is None else 1, 0.0 if bc is None else bc.value)
             imm = getattr(bcs, "immersed", None) if bcs is not None else None
             self.ctx.call("csi_immersed_flux_bc_set", _lib.F[name], *(imm.values() if imm is not None else (0.0, 0.0, 0.0, 0.0)))

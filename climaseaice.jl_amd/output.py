@@ -310,6 +310,9 @@ class OutputWriter:
             raise ValueError("OutputWriter: dtype must be 'f32' or 'f64'")
         if int(slots) < 1:
             raise ValueError("OutputWriter: slots >= 1")
+        if type(model).__name__ == "EnthalpyMethodSeaIceModel":
+            raise NotImplementedError("OutputWriter: an output writer over the column fields of an EnthalpyMethodSeaIceModel is not built; "
+                                      "read them with ColumnField.interior_numpy() between time_steps calls")
         recorder = recorder or DeviceRecorder
         from .derived import DERIVED_NAMES, name_of_slot
         if not isinstance(outputs, dict) and hasattr(model, "derived_field"):

@@ -1353,6 +1353,122 @@ int32_t csi_last_launches(csi_context* ctx, int32_t* launches, int32_t* substeps
 /* Number of kernel launches issued for one sub-step in the current configuration (upper bound). */
 int32_t csi_launches_per_substep(csi_context* ctx, int32_t* n);
 
+/* ---- enthalpy-method column model: sub-steps fused on chip ----------------------------------------------------------------------------
+ * The reference's EnthalpyMethodSeaIceModel with MolecularDiffusivity (src/EnthalpyMethodSeaIceModel.jl;
+ * examples/diffusive_ice_column_model.jl; test/runtests.jl:9-28): Nx * Ny independent columns of Nz levels, stepped explicitly.  A
+ * model of its own: an opaque csi_enthalpy made from a context for its device, stream and error text; it shares nothing else with the
+ * context's sea-ice model, and a process that never creates one launches what it launched before.  Every entry runs on the context's
+ * stream and none waits for the device.
+ *
+ * ARRAYS.  H, T, phi, kappa: caller-owned, contiguous (Nz + 2, Ny, Nx) doubles in device memory; level k = 1 .. Nz is the interior,
+ * levels 0 and Nz + 1 are the z halos.  The library never reads (or writes) the halo levels of H and phi.  There are no horizontal
+ * halos: the model has no horizontal operator.  Parameters: ice_heat_capacity c, water_heat_capacity (stored, never read, as in the
+ * reference), fusion_enthalpy L, kappa_ice, kappa_water.
+ *
+ * SEMANTICS, mirrored from the reference on purpose (none of these is a fix):
+ *   set T          (set!(model; T), :80-98, :146-159)  H[k] = c * T[k] + L * phi[k] with the phi held at that moment (zero for a
+ *                  fresh model); two products and a sum.  T's halos are not touched.
+ *   set H          (set!(model; H), :132-144)          T[k] = H[k] / c, then T's halos from its boundary conditions at `time`.
+ *   Neither set updates phi or kappa: a fresh model has kappa = 0 until update_state runs, and a bare time step of it changes nothing.
+ *   update_state   (:161-166), in this order:  T[k] = H[k] / c and T's halos at `time` (latent heat is ignored here, as upstream
+ *                  ignores it);  phi[k] = (T[k] < 0) ? 1 : 0;  kappa[k] = kappa_ice * (1 - phi[k]) + kappa_water * phi[k], then
+ *                  kappa[0] = kappa[1], kappa[Nz + 1] = kappa[Nz].  Frozen cells (phi = 1) take kappa_WATER: the reference's assignment.
+ *   time step      (:168-185)  G from the current T and kappa, halos included; H[k] = H[k] + dt * G[k]; update_state at the time the
+ *                  step STARTED from; then the clock t = t + dt, one addition per step.  So the boundary values that enter T's halos
+ *                  after step s are those of the step's start time, not of the time it ends at.  H's own boundary conditions are
+ *                  the default zero flux and contribute nothing.
+ * OPERATORS (STATUS: RECALLED -- Oceananigans is not vendored; this statement is the definition, like the time indexing and the
+ * fold), k = 1 .. Nz, faces k = 1 .. Nz + 1, zf the Nz + 1 faces given at creation:
+ *   zc[k]   = (zf[k] + zf[k + 1]) / 2                 dzc[k] = zf[k + 1] - zf[k]
+ *   dzf[k]  = zc[k] - zc[k - 1] inside the column;    dzf[1] = dzc[1] and dzf[Nz + 1] = dzc[Nz] (a Bounded stretched grid repeats its
+ *                                                     end spacing)
+ *   flux[k] = ((kappa[k] + kappa[k - 1]) / 2) * ((T[k] - T[k - 1]) / dzf[k])
+ *   G[k]    = (flux[k + 1] - flux[k]) / dzc[k]
+ *   value condition Tb at the bottom / Tt at the top:  T[0] = 2 * Tb - T[1],  T[Nz + 1] = 2 * Tt - T[Nz];  no condition (no flux):
+ *   the halo takes its neighbour's value.
+ * No contraction, IEEE division (three per cell and step), one arithmetic for both library modes (STRICT = FAST, as for the time
+ * series and the diagnostics).
+ *
+ * BOUNDARY TEMPERATURES, per side: none, a number, a (Ny, Nx) device array, or a time series whose slices are scalars or (Ny, Nx)
+ * planes in device memory (CSI_SERIES_DEVICE; the HOST ring backend is refused by name).  For a series the host evaluates
+ * csi_time_series_plan at every sub-step's start time and hands the kernel (n1, n2, frac) per sub-step and side as kernel
+ * arguments; the kernel forms (n1 == n2) ? psi_1 : psi_2 * frac + psi_1 * (1 - frac).  Any condition on H, and a flux or gradient
+ * condition on T, is CSI_ERR_UNSUPPORTED.
+ *
+ * KERNEL FORMS (enthalpy.hip, k_enthalpy_steps: one thread per column, lanes along x, every level one coalesced plane; a thread
+ * marches k upward in place, carrying the lower face's flux and the old T[k], kappa[k] in registers; no barrier, no cross-lane
+ * operation):
+ *   CSI_ENTH_ON_CHIP   H[1 .. Nz] and T[0 .. Nz + 1] of a wave's 64 columns live in LDS as [level][lane], (2 Nz + 2) * 512 bytes
+ *                      per wave (one wave per block); one launch runs up to CSI_ENTH_MAX_SUBSTEPS sub-steps, longer requests loop
+ *                      launches.  The first sub-step of a launch reads kappa from memory (the held kappa need not be the one T
+ *                      implies), later ones derive it from T; after the last, H, T, phi, kappa are stored once, the halo levels
+ *                      of T and kappa included.  Memory sees the state once in and once out per launch.
+ *   CSI_ENTH_PER_STEP  the same body on the caller's arrays, one launch per step, for columns too deep for LDS.
+ * CHOOSING RULE (csi_enthalpy_plan; pure host function, no context, no GPU): lds = (2 Nz + 2) * 512; waves = floor(163840 / lds),
+ * the waves a CU's 160 KiB hold; ON_CHIP iff waves >= CSI_ENTH_MIN_WAVES_PER_CU = 2 (Nz <= 79): the smallest residency taken is two
+ * waves per CU, half a wave per SIMD -- the sub-step loop is a dependent chain of IEEE divisions, and what is bought is the absent
+ * memory traffic, not latency hiding.  The compiler's register count allows 8 waves per SIMD for every kernel of the unit; on chip
+ * the LDS image sets the residency: waves per CU as above (Nz = 20: 7).  forced_path (the environment's CSI_ENTH_PATH, read when the
+ * CONTEXT is created: 0 auto, 1 per step, 2 on chip; any other value fails csi_context_create) overrides the rule;
+ * 2 where waves < 1 is CSI_ERR_UNSUPPORTED.
+ *
+ * ICE THICKNESS (k_enthalpy_thickness; one thread per column, a (Ny, Nx) array).  The example's diagnostic
+ * (diffusive_ice_column_model.jl:115-127) made total -- this definition is OURS: kw = the number of levels from the bottom up whose
+ * T >= Tm, stopping at the first that is not.  kw == 0: -zf[1].  kw == Nz: 0.  Otherwise, with ki = kw + 1,
+ *   dTdz = (T[ki] - T[kw]) / dzf[ki];   z = zc[kw] + (Tm - T[kw]) / dTdz;   thickness = -z.
+ * On profiles that decrease monotonically upward it equals the example's binary search.
+ *
+ * ERRORS: unbound arrays CSI_ERR_NOT_BOUND; dt not finite, n < 1, faces not finite or not strictly increasing, extents < 1, a
+ * parameter that is not finite, c == 0: CSI_ERR_INVALID_ARGUMENT; the conditions above CSI_ERR_UNSUPPORTED.
+ * csi_context_destroy frees the models that survive; a csi_enthalpy must not be used after its context is gone.
+ * NOT BUILT: horizontal coupling; tiles or multi-GPU; output sets over column fields; a reciprocal-multiply FAST arithmetic; a
+ * register-resident variant templated on Nz; the HOST series backend; any coupling to the sea-ice model of the context. */
+typedef struct csi_enthalpy csi_enthalpy;
+typedef enum { CSI_ENTH_H = 0, CSI_ENTH_T = 1, CSI_ENTH_PHI = 2, CSI_ENTH_KAPPA = 3 } csi_enthalpy_array;
+typedef enum { CSI_ENTH_T_BOTTOM = 0, CSI_ENTH_T_TOP = 1, CSI_ENTH_H_BOTTOM = 2, CSI_ENTH_H_TOP = 3 } csi_enthalpy_side;
+typedef enum {
+    CSI_ENTH_BC_NONE = 0,            /* the default: no flux, halo = neighbour */
+    CSI_ENTH_BC_NUMBER = 1,
+    CSI_ENTH_BC_ARRAY = 2,           /* dev_array: (Ny, Nx) doubles */
+    CSI_ENTH_BC_SERIES_SCALAR = 3,   /* ts: nt scalars, slice_stride doubles apart (ld is ignored) */
+    CSI_ENTH_BC_SERIES_PLANE = 4,    /* ts: nt (Ny, Nx) planes, rows ld apart, slices slice_stride apart */
+    CSI_ENTH_BC_FLUX = 5,            /* refused: CSI_ERR_UNSUPPORTED */
+    CSI_ENTH_BC_GRADIENT = 6         /* refused: CSI_ERR_UNSUPPORTED */
+} csi_enthalpy_bc_kind;
+enum { CSI_ENTH_PER_STEP = 1, CSI_ENTH_ON_CHIP = 2 };
+enum { CSI_ENTH_MAX_SUBSTEPS = 64, CSI_ENTH_MIN_WAVES_PER_CU = 2, CSI_ENTH_LDS_PER_CU = 163840 };
+typedef struct {
+    int32_t Nx, Ny, Nz;                /* each >= 1 */
+    int32_t reserved;                  /* 0 */
+    const double* z_faces;             /* host, Nz + 1 values, strictly increasing; copied */
+    double ice_heat_capacity;          /* c */
+    double water_heat_capacity;        /* stored, never read */
+    double fusion_enthalpy;            /* L */
+    double kappa_ice, kappa_water;
+} csi_enthalpy_params;
+typedef struct {
+    int32_t form;                      /* CSI_ENTH_PER_STEP | CSI_ENTH_ON_CHIP; 0: no time step yet */
+    int32_t launches;                  /* of the last csi_enthalpy_time_step */
+    int32_t substeps_per_launch;       /* of its first launch: min(n, CSI_ENTH_MAX_SUBSTEPS) on chip, 1 per step */
+    int32_t lds_bytes;                 /* per block; 0 per step */
+} csi_enthalpy_launch;
+/* The choosing rule.  Any output pointer may be NULL.  Nz < 1 or forced_path outside 0 .. 2: CSI_ERR_INVALID_ARGUMENT. */
+int32_t csi_enthalpy_plan(int32_t Nz, int32_t forced_path, int32_t* form, int64_t* lds_bytes, int32_t* waves_per_cu,
+                          int32_t* max_substeps);
+int32_t csi_enthalpy_create(csi_context* ctx, const csi_enthalpy_params* p, csi_enthalpy** out);
+int32_t csi_enthalpy_destroy(csi_enthalpy* e);
+int32_t csi_enthalpy_bind(csi_enthalpy* e, int32_t which, void* dev);
+/* kind NUMBER reads `number`, ARRAY `dev_array`, the SERIES kinds `ts` (times are copied; the data stay the caller's). */
+int32_t csi_enthalpy_boundary_set(csi_enthalpy* e, int32_t side, int32_t kind, double number, const void* dev_array,
+                                  const csi_time_series* ts);
+/* which: CSI_ENTH_T or CSI_ENTH_H -- the set semantics above, applied to what the caller wrote into that bound array. */
+int32_t csi_enthalpy_set(csi_enthalpy* e, int32_t which, double time);
+int32_t csi_enthalpy_update_state(csi_enthalpy* e, double time);
+/* n steps of dt from `time`; *time_out (may be NULL): the clock after them, n additions. */
+int32_t csi_enthalpy_time_step(csi_enthalpy* e, double dt, int32_t n, double time, double* time_out);
+int32_t csi_enthalpy_last_launch(csi_enthalpy* e, csi_enthalpy_launch* out);
+int32_t csi_enthalpy_ice_thickness(csi_enthalpy* e, double Tm, void* dev_out);
+
 #ifdef __cplusplus
 }
 #endif

@@ -1071,6 +1071,102 @@ function close_output!(sink, model::HIPSeaIceModel, set::OutputSet)
     return nothing
 end
 
+# ---- the enthalpy-method column model (include/csi.h, "enthalpy-method column model") ------------------------------------------------
+# csi_enthalpy_array, csi_enthalpy_side, csi_enthalpy_bc_kind and the two kernel forms
+const ENTHALPY = (H=0, T=1, PHI=2, KAPPA=3)
+const ENTHALPY_SIDE = (T_BOTTOM=0, T_TOP=1, H_BOTTOM=2, H_TOP=3)
+const ENTHALPY_BC = (NONE=0, NUMBER=1, ARRAY=2, SERIES_SCALAR=3, SERIES_PLANE=4, FLUX=5, GRADIENT=6)
+const CSI_ENTH_PER_STEP = 1
+const CSI_ENTH_ON_CHIP = 2
+const CSI_ENTH_MAX_SUBSTEPS = 64
+# csi_enthalpy_params: extents, the Nz + 1 faces (host), c, c_water (stored, never read), L, kappa_ice, kappa_water
+struct CsiEnthalpyParams
+    Nx::Int32; Ny::Int32; Nz::Int32; reserved::Int32
+    z_faces::Ptr{Cdouble}
+    ice_heat_capacity::Cdouble; water_heat_capacity::Cdouble; fusion_enthalpy::Cdouble
+    kappa_ice::Cdouble; kappa_water::Cdouble
+end
+@assert sizeof(CsiEnthalpyParams) == 64 && fieldoffset(CsiEnthalpyParams, 5) == 16      # the layout gcc gives csi_enthalpy_params
+# csi_enthalpy_launch: what the last csi_enthalpy_time_step launched
+struct CsiEnthalpyLaunch
+    form::Int32; launches::Int32; substeps_per_launch::Int32; lds_bytes::Int32
+end
+@assert sizeof(CsiEnthalpyLaunch) == 16
+
+mutable struct EnthalpyContext
+    ctx::Context
+    handle::Ptr{Cvoid}
+    keep::Vector{Any}
+end
+
+# the number of a ValueBoundaryCondition, `nothing` for the default; everything else raises by name
+function enthalpy_boundary_number(bc, side)
+    (bc === nothing || nameof(typeof(bc.classification)) in (:Flux, :NoFlux) && bc.condition === nothing) && return nothing
+    nameof(typeof(bc.classification)) in (:Flux, :Gradient) &&
+        error("ClimaSeaIceHIP: attach(::EnthalpyMethodSeaIceModel): a flux or gradient condition on T ($side) is not supported; ValueBoundaryCondition(number) or the default")
+    nameof(typeof(bc.classification)) === :Value ||
+        error("ClimaSeaIceHIP: attach(::EnthalpyMethodSeaIceModel): the $side condition on T is a ValueBoundaryCondition or the default")
+    bc.condition isa Number ||
+        error("ClimaSeaIceHIP: attach(::EnthalpyMethodSeaIceModel): the $side temperature is a function, an array or a time series; this stub passes Numbers only (the C ABI takes arrays and series: csi_enthalpy_boundary_set)")
+    return Float64(bc.condition)
+end
+
+# attach_enthalpy(ctx, column_model): a csi_enthalpy for a horizontally Flat EnthalpyMethodSeaIceModel with MolecularDiffusivity and
+# number-valued or absent T conditions.  The library addresses levels 0 .. Nz + 1 of the parents directly: one halo level each side.
+function attach_enthalpy(ctx::Context, column)
+    grid = column.grid
+    Nx, Ny, Nz = size(grid)
+    (Nx == 1 && Ny == 1) ||
+        error("ClimaSeaIceHIP: attach(::EnthalpyMethodSeaIceModel): a horizontally Flat grid is needed (parents with horizontal halos are not contiguous planes)")
+    nameof(typeof(column.closure)) === :MolecularDiffusivity ||
+        error("ClimaSeaIceHIP: attach(::EnthalpyMethodSeaIceModel): closure is a MolecularDiffusivity")
+    Hz = grid.Hz
+    zf = Float64[grid.z.cᵃᵃᶠ[k] for k in 1:Nz+1]
+    p = Ref(CsiEnthalpyParams(Nx, Ny, Nz, 0, pointer(zf), column.ice_heat_capacity, column.water_heat_capacity, column.fusion_enthalpy,
+                              column.closure.κ_ice, column.closure.κ_water))
+    h = Ref{Ptr{Cvoid}}(C_NULL)
+    GC.@preserve zf check(ctx, ccall((:csi_enthalpy_create, libcsi), Int32, (Ptr{Cvoid}, Ref{CsiEnthalpyParams}, Ptr{Ptr{Cvoid}}), ctx.handle, p, h))
+    e = EnthalpyContext(ctx, h[], Any[column])
+    for (which, f) in ((ENTHALPY.H, column.state.H), (ENTHALPY.T, column.state.T), (ENTHALPY.PHI, column.state.ϕ), (ENTHALPY.KAPPA, column.closure.κ))
+        check(ctx, ccall((:csi_enthalpy_bind, libcsi), Int32, (Ptr{Cvoid}, Int32, Ptr{Cvoid}), e.handle, which, Ptr{Cvoid}(pointer(parent(f)) + 8 * (Hz - 1))))
+    end
+    for name in (:H, :ϕ), side in (:bottom, :top)
+        enthalpy_boundary_number(getproperty(getproperty(column.state, name).boundary_conditions, side), side) === nothing ||
+            error("ClimaSeaIceHIP: attach(::EnthalpyMethodSeaIceModel): a boundary condition on $name is not supported")
+    end
+    for (side, name) in ((ENTHALPY_SIDE.T_BOTTOM, :bottom), (ENTHALPY_SIDE.T_TOP, :top))
+        v = enthalpy_boundary_number(getproperty(column.state.T.boundary_conditions, name), name)
+        check(ctx, ccall((:csi_enthalpy_boundary_set, libcsi), Int32, (Ptr{Cvoid}, Int32, Int32, Cdouble, Ptr{Cvoid}, Ptr{Cvoid}), e.handle, side,
+                         v === nothing ? ENTHALPY_BC.NONE : ENTHALPY_BC.NUMBER, v === nothing ? 0.0 : v, C_NULL, C_NULL))
+    end
+    return e
+end
+
+enthalpy_set!(e::EnthalpyContext, which, time) =
+    check(e.ctx, ccall((:csi_enthalpy_set, libcsi), Int32, (Ptr{Cvoid}, Int32, Cdouble), e.handle, which, time))
+enthalpy_update_state!(e::EnthalpyContext, time) =
+    check(e.ctx, ccall((:csi_enthalpy_update_state, libcsi), Int32, (Ptr{Cvoid}, Cdouble), e.handle, time))
+# n steps of Δt from `time`: the clock after them
+function enthalpy_time_step!(e::EnthalpyContext, Δt, n, time)
+    t = Ref{Cdouble}(0.0)
+    check(e.ctx, ccall((:csi_enthalpy_time_step, libcsi), Int32, (Ptr{Cvoid}, Cdouble, Int32, Cdouble, Ptr{Cdouble}), e.handle, Δt, n, time, t))
+    return t[]
+end
+function enthalpy_last_launch(e::EnthalpyContext)
+    r = Ref(CsiEnthalpyLaunch(0, 0, 0, 0))
+    check(e.ctx, ccall((:csi_enthalpy_last_launch, libcsi), Int32, (Ptr{Cvoid}, Ref{CsiEnthalpyLaunch}), e.handle, r))
+    return r[]
+end
+enthalpy_ice_thickness!(e::EnthalpyContext, out, Tm = -0.1) =
+    check(e.ctx, ccall((:csi_enthalpy_ice_thickness, libcsi), Int32, (Ptr{Cvoid}, Cdouble, Ptr{Cvoid}), e.handle, Tm, Ptr{Cvoid}(pointer(out))))
+function enthalpy_plan(Nz, forced = 0)
+    form = Ref{Int32}(0); lds = Ref{Int64}(0); waves = Ref{Int32}(0); cap = Ref{Int32}(0)
+    rc = ccall((:csi_enthalpy_plan, libcsi), Int32, (Int32, Int32, Ptr{Int32}, Ptr{Int64}, Ptr{Int32}, Ptr{Int32}), Nz, forced, form, lds, waves, cap)
+    rc == 0 || error("libcsi_hip error $rc: csi_enthalpy_plan")
+    return (form = form[], lds_bytes = lds[], waves_per_cu = waves[], max_substeps = cap[])
+end
+detach_enthalpy!(e::EnthalpyContext) = (check(e.ctx, ccall((:csi_enthalpy_destroy, libcsi), Int32, (Ptr{Cvoid},), e.handle)); e.handle = C_NULL; nothing)
+
 # Checkpointing (sea_ice_model.jl:414-445: prognostic_state / restore_prognostic_state!) needs nothing from the library: the
 # state lives in the Oceananigans Fields, restore writes into the same parents, and the library holds pointers only.  If a
 # restore REPLACES parents (new arrays), drop the context so that the next step re-attaches:
