@@ -26,5 +26,6 @@ from .model import (FieldBoundaryConditions, FluxBoundaryCondition, ImmersedBoun
                     snow_slab_thermodynamics, UpwindBiased, WENO, set_, time_step, time_step_momentum, compute_momentum_tendencies, update_state,
                     prognostic_state, restore_prognostic_state)
 from .enthalpy import ColumnField, ColumnGrid, ColumnTimeSeries, EnthalpyMethodSeaIceModel, MolecularDiffusivity
+from .drifters import Drifters, DrifterWriter, load_tracks
 
 __all__ = [n for n in dir() if not n.startswith("_")]

@@ -109,7 +109,11 @@ SYMBOLS = ["csi_version", "csi_context_create", "csi_context_destroy", "csi_last
            "csi_mixed_layer_set", "csi_mixed_layer_step", "csi_mixed_layer_stats", "csi_shortwave_set", "csi_last_thermo",
            "csi_enthalpy_plan", "csi_enthalpy_create", "csi_enthalpy_destroy", "csi_enthalpy_bind", "csi_enthalpy_boundary_set",
            "csi_enthalpy_set", "csi_enthalpy_update_state", "csi_enthalpy_time_step", "csi_enthalpy_last_launch",
-           "csi_enthalpy_ice_thickness"]
+           "csi_enthalpy_ice_thickness",
+           "csi_drifters_locate", "csi_drifters_advance", "csi_drifters_sample", "csi_drifters_stats"]
+# Lagrangian ice drifters (include/csi.h): the status bits of csi_drifters_advance, the column bits of csi_drifters_sample
+DRIFTER_CLAMPED_X, DRIFTER_CLAMPED_Y, DRIFTER_HELD, DRIFTER_LOST, DRIFTER_INACTIVE = 1, 2, 4, 8, 16
+DRIFTER_COL_XI, DRIFTER_COL_ETA, DRIFTER_COL_U, DRIFTER_COL_V, DRIFTER_COL_H, DRIFTER_COL_A, DRIFTER_COL_HS, DRIFTER_COL_ALL = 1, 2, 4, 8, 16, 32, 64, 127
 # the enthalpy-method column model (include/csi.h): csi_enthalpy_array, csi_enthalpy_side, csi_enthalpy_bc_kind, the two forms, the rule's constants
 ENTH_H, ENTH_T, ENTH_PHI, ENTH_KAPPA = 0, 1, 2, 3
 ENTH_T_BOTTOM, ENTH_T_TOP, ENTH_H_BOTTOM, ENTH_H_TOP = 0, 1, 2, 3
@@ -241,6 +245,11 @@ class EnthalpyLaunch(C.Structure):
     _fields_ = [("form", C.c_int32), ("launches", C.c_int32), ("substeps_per_launch", C.c_int32), ("lds_bytes", C.c_int32)]
 
 
+class Drifters(C.Structure):
+    """csi_drifters (include/csi.h): the caller's device arrays of n drifters."""
+    _fields_ = [("n", C.c_int64), ("xi", C.c_void_p), ("eta", C.c_void_p), ("status", C.c_void_p)]
+
+
 class CsiError(RuntimeError):
     def __init__(self, code, msg):
         super().__init__(f"libcsi_hip error {code}: {msg}")
@@ -341,6 +350,9 @@ def load():
         "csi_enthalpy_set": [vp, i32, dbl], "csi_enthalpy_update_state": [vp, dbl],
         "csi_enthalpy_time_step": [vp, dbl, i32, dbl, C.POINTER(dbl)],
         "csi_enthalpy_last_launch": [vp, C.POINTER(EnthalpyLaunch)], "csi_enthalpy_ice_thickness": [vp, dbl, vp],
+        "csi_drifters_locate": [i32, i32, dbl, dbl, C.POINTER(i32), C.POINTER(dbl)],
+        "csi_drifters_advance": [vp, C.POINTER(Drifters), dbl, i32], "csi_drifters_sample": [vp, C.POINTER(Drifters), i32, vp, i64],
+        "csi_drifters_stats": [vp, C.POINTER(i64)],
     }
     for name, args in sig.items():
         fn = getattr(L, name, None)
@@ -399,6 +411,16 @@ def enthalpy_plan(Nz, forced_path=0):
     if rc != OK:
         raise CsiError(rc, "csi_enthalpy_plan: invalid input, or the forced on-chip form does not fit")
     return dict(form=form.value, lds_bytes=lds.value, waves_per_cu=waves.value, max_substeps=cap.value)
+
+
+def drifters_locate(Nx, Ny, xi, eta):
+    """csi_drifters_locate as a dict: the stencils and weights of one index-space position (pure host function; any xi, eta is accepted,
+    CsiError for extents < 1)."""
+    idx, w = (C.c_int32 * 6)(), (C.c_double * 4)()
+    rc = load().csi_drifters_locate(int(Nx), int(Ny), float(xi), float(eta), idx, w)
+    if rc != OK:
+        raise CsiError(rc, "csi_drifters_locate: Nx >= 1 and Ny >= 1 are needed")
+    return dict(ia=idx[0], ja=idx[1], ib=idx[2], jb=idx[3], ic=idx[4], jc=idx[5], sx=w[0], sy=w[1], rx=w[2], ry=w[3])
 
 
 def regrid_plan_axis(nodes, periodic, period, x):
@@ -623,6 +645,21 @@ class Context:
         a, b = C.c_int64(), C.c_int64()
         self.call("csi_derived_stats", C.byref(a), C.byref(b))
         return a.value, b.value
+
+    # ---- Lagrangian ice drifters (include/csi.h, csi_drifters_*) --------------------------------------------------------------------
+    def drifters_advance(self, d, dt, substeps=1):
+        """csi_drifters_advance: `substeps` midpoint sub-steps of dt / substeps in ONE launch on the context's stream (nothing is waited for)."""
+        self.call("csi_drifters_advance", C.byref(d), float(dt), int(substeps))
+
+    def drifters_sample(self, d, columns, dev_out, ld):
+        """csi_drifters_sample: the columns of the mask at dev_out[k * ld + q], ONE launch (nothing is waited for)."""
+        self.call("csi_drifters_sample", C.byref(d), int(columns), C.c_void_p(dev_out) if dev_out else None, int(ld))
+
+    def drifters_stats(self):
+        """Launches of the two drifter kernels made on this context so far."""
+        n = C.c_int64()
+        self.call("csi_drifters_stats", C.byref(n))
+        return n.value
 
     # ---- momentum balance terms, interface stresses and their power (include/csi.h) ------------------------------------------------
     def momentum_terms_compute(self, mask):

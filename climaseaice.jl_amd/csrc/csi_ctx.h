@@ -12,6 +12,7 @@
 //   csi_derived.hip       derived fields and energy budget integrals: binding checks, the launches, the budget's combine over the ranks
 //   csi_momentum_terms.hip   momentum balance terms and their power: binding checks, the launches, the power sums' combine over the ranks
 //   csi_enthalpy.hip      the enthalpy-method column model: the choosing rule, the model object, its launches
+//   csi_drifters.hip      Lagrangian ice drifters: the locate rule on the host, argument and binding checks, the two launches
 //   csi_mem.h       DeviceBuf / PinnedBuf: the owner of every allocation the library makes
 #pragma once
 #include "../../include/csi.h"
@@ -330,6 +331,7 @@ struct csi_context {
     DeviceBuf<uint8_t> gather_buf;
     // the calls made so far (csi_derived_stats, csi_momentum_terms_stats)
     int64_t derived_launches = 0, budget_calls = 0;
+    int64_t drifter_launches = 0;        // csi_drifters_advance / _sample (csi_drifters.hip): launches of the two kernels
     int64_t mterm_launches = 0, mterm_budget_calls = 0;
     // csi_output_* (csi_output.hip): the sets and the copy stream their records leave on, made at the first csi_output_create
     OutputSet out_sets[kMaxOutputSets];

@@ -386,4 +386,18 @@ struct OutputTable { int n; int mask_ld; double w; const unsigned char* mask; Ou
 void launch_output_accumulate(const OutputTable& T, hipStream_t s);
 void launch_output_pack(const OutputTable& T, hipStream_t s);
 
+// Lagrangian ice drifters (drifters.hip; include/csi.h csi_drifters_advance / csi_drifters_sample): one thread per drifter.  xi, eta,
+// status: the caller's arrays of n entries.  advance: m sub-steps of tau in ONE launch; sample: the columns of `columns` at
+// out[k * ld + q]; hs.p == nullptr where the HS column is not requested (h, a likewise).
+struct DriftersDev {
+    GridDev g;
+    FRef u, v, h, a, hs;
+    double* xi;
+    double* eta;
+    int32_t* status;
+    long n;
+};
+void launch_drifters_advance(const DriftersDev& D, double tau, int m, hipStream_t s);
+void launch_drifters_sample(const DriftersDev& D, int columns, double* out, long ld, hipStream_t s);
+
 }  // namespace csi

@@ -457,6 +457,7 @@ class SeaIceModel:
             self.ice_top_temperature = CenterField(grid, dev, "Tu")
         self.clock = SimpleNamespace(time=0.0, iteration=0)
         self.output_writers = OrderedDict()      # key -> output.OutputWriter, driven by time_step (empty: nothing is called)
+        self.drifters = None                     # a drifters.Drifters: time_step advances them with the step's dt (None: no call)
         self._keep = []
         self._stress_fields = {}
         self._free_drift_fields = {}
@@ -1182,6 +1183,8 @@ def prognostic_state(model):
         model.synchronize()
     state = {k: f.numpy().copy() for k, f in _state_fields(model).items()}
     state["clock"] = (model.clock.time, model.clock.iteration)
+    if getattr(model, "drifters", None) is not None:      # drifters.xi, drifters.eta, drifters.status: only when drifters are set
+        state.update(model.drifters.state())
     return state
 
 
@@ -1192,6 +1195,8 @@ def restore_prognostic_state(model, state):
         if k in state:
             model.copy_to_field(f, state[k])
     model.clock.time, model.clock.iteration = state["clock"]
+    if getattr(model, "drifters", None) is not None and "drifters.xi" in state:
+        model.drifters.restore(state, model)
     return model
 
 
@@ -1241,5 +1246,8 @@ def time_step(model, dt):
     # it -- what the Julia stub does in the update_state! that ends time_step! (julia/ClimaSeaIceHIP.jl)
     if isinstance(model.grid, TileGrid):
         model.ctx.validate_all()
+    # Lagrangian drifters move with the velocities the step leaves, one launch, before the writers sample them (drifters.py)
+    if getattr(model, "drifters", None) is not None:
+        model.drifters.advance(model, float(dt), model.drifters.substeps)
     for writer in model.output_writers.values():
         writer.after_step(model, float(dt))

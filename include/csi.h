@@ -1469,6 +1469,99 @@ int32_t csi_enthalpy_time_step(csi_enthalpy* e, double dt, int32_t n, double tim
 int32_t csi_enthalpy_last_launch(csi_enthalpy* e, csi_enthalpy_launch* out);
 int32_t csi_enthalpy_ice_thickness(csi_enthalpy* e, double Tm, void* dev_out);
 
+/* ---- Lagrangian ice drifters --------------------------------------------------------------------------------------------------------
+ * Points that move with the ice: buoy tracks, "where did this floe come from".  Oceananigans gives its ocean models LagrangianParticles;
+ * SeaIceModel has no counterpart in the reference, so THIS COMMENT IS THE DEFINITION (tests/drifters_ref.py restates it in NumPy, and
+ * csrc/drifters_dev.h, a host-and-device header, is the one C statement of it: the kernels and the host function below call it).
+ * Nothing here changes another entry point: a context that never makes these calls launches exactly what it launched before.  One code
+ * serves STRICT and FAST, compiled without contraction; every division below is an IEEE division: both modes give the same bits.
+ *
+ * POSITION.  A drifter has an index-space position (xi, eta) in doubles, xi in [0, Nx], eta in [0, Ny].  Cell (i, j) (1-based, as
+ * everywhere) covers [i - 1, i) x [j - 1, j); u[i, j] sits at (i - 1, j - 1/2), v[i, j] at (i - 1/2, j - 1), cell centres at
+ * (i - 1/2, j - 1/2).  The arrays xi, eta (double) and status (int32) are the CALLER's device arrays, n entries each, handed over in a
+ * csi_drifters at every call: the library keeps no drifter state.
+ *
+ * RATES, in cells per second:  A[i, j] = u[i, j] / dx^fc[i, j],  B[i, j] = v[i, j] / dy^cf[i, j]  (the metrics every operator reads at
+ * the u and v points, at all three metric kinds).  Each is ONE correctly rounded division of two stored doubles, so its value does not
+ * depend on whether it is formed where it is used (as the kernel does) or in a pass of its own.
+ *
+ * LOCATE.  With fl(x, lo, hi) = fmin(fmax(floor(x), lo), hi) -- the clamps are applied to the DOUBLE, before the conversion to an
+ * integer, and fmax / fmin return their other argument for a NaN, so every input value, NaN and +-Inf included, gives an index inside
+ * the one ring named below.  This is part of the contract, not an optimisation.
+ *   A at (xi, eta):  fx = fl(xi, 0, Nx - 1), sx = xi - fx;  t = eta - 0.5, fy = fl(t, -1, Ny - 1), sy = t - fy;
+ *                    columns ia = fx + 1, ia + 1;  rows ja = fy + 1, ja + 1  (rows 0 and Ny + 1, the first halo ring, are read);
+ *                    a = (1 - sy) * ((1 - sx) * A[ia, ja] + sx * A[ia + 1, ja]) + sy * ((1 - sx) * A[ia, ja + 1] + sx * A[ia + 1, ja + 1])
+ *   B at (xi, eta):  the same with the roles of x and y exchanged:  gy = fl(eta, 0, Ny - 1), ry = eta - gy;  s = xi - 0.5,
+ *                    gx = fl(s, -1, Nx - 1), rx = s - gx;  columns ib = gx + 1, ib + 1;  rows jb = gy + 1, jb + 1;
+ *                    b = (1 - rx) * ((1 - ry) * B[ib, jb] + ry * B[ib, jb + 1]) + rx * ((1 - ry) * B[ib + 1, jb] + ry * B[ib + 1, jb + 1])
+ *   rate(xi, eta) = (a, b).  Every product and sum is rounded on its own, in the order written (no contraction).
+ *   The CONTAINING CELL of (xi, eta) is (ic, jc) = (fl(xi, 0, Nx - 1) + 1, fl(eta, 0, Ny - 1) + 1): a point on the last face belongs
+ *   to the last cell.
+ * csi_drifters_locate(Nx, Ny, xi, eta, idx, w) is that rule as a pure host function (no context, no GPU): idx[6] = {ia, ja, ib, jb, ic,
+ * jc}, w[4] = {sx, sy, rx, ry}.  Nx < 1 or Ny < 1 or a NULL pointer: CSI_ERR_INVALID_ARGUMENT; any xi, eta is accepted.
+ *
+ * NORM, of one coordinate x in a direction of N cells; it returns the coordinate and may raise a status bit.
+ *   Periodic:  r = x - N * floor(x / N);  where r >= N or r < 0, r = 0.  (A tiny negative x gives r == N exactly after rounding, and a
+ *              quotient that rounds up to a whole number gives a tiny negative r: both stand for the seam, 0.  A NaN stays a NaN.)
+ *   Bounded:   r = x < 0 ? 0 : (x > N ? N : x);  CSI_DRIFTER_CLAMPED_X / _Y is raised when r != x.  (A NaN stays a NaN, no bit.)
+ *
+ * ONE SUB-STEP of length tau (midpoint rule; the velocities are frozen at the state the call finds):
+ *   (a1, b1) = rate(xi, eta)
+ *   xm = norm_x(xi + (tau / 2) * a1),  ym = norm_y(eta + (tau / 2) * b1)
+ *   (a2, b2) = rate(xm, ym)
+ *   X = xi + tau * a2,  Y = eta + tau * b2;  xn = norm_x(X),  yn = norm_y(Y)          (the bits of all four norms are kept)
+ *   LOST:  where X, Y, xn or yn is not finite, the drifter becomes (NaN, NaN), CSI_DRIFTER_LOST is raised and the advance ends for it.
+ *   LAND:  otherwise, with a mask set (csi_mask_set), if the byte of the containing cell of (xn, yn) is 0 the drifter keeps (xi, eta)
+ *          and CSI_DRIFTER_HELD is raised; each sub-step is judged on its own.  Otherwise (xi, eta) = (xn, yn).
+ * csi_drifters_advance(ctx, d, dt, substeps) runs m = substeps sub-steps of tau = dt / m (formed once, on the host) in ONE launch on
+ * the context's stream, one thread per drifter: position and status are read once and stored once.  A drifter with a non-finite
+ * coordinate at entry is INACTIVE: nothing is read for it, its position is left as it is and its status becomes CSI_DRIFTER_INACTIVE.
+ * For every other drifter status becomes the OR of the bits its sub-steps raised (0: it moved freely).  Hence, for the POSITIONS,
+ * advance(dt, m) gives the bits of m calls advance(dt / m, 1) while the velocities stand still.
+ *
+ * HALO ELEMENTS READ (the entry points fill none): u and dx^fc at columns 1 .. Nx + 1, rows 0 .. Ny + 1; v and dy^cf at columns
+ * 0 .. Nx + 1, rows 1 .. Ny + 1; the mask, h, aice, hs at the interior only.  On a Bounded high side column Nx + 1 / row Ny + 1 of a
+ * Face field is its last face, elsewhere the first halo element.  Nothing else outside the interior is read, whatever it holds.
+ * csi_update_state and every step entry point leave these elements valid, as stated for csi_derived_compute above.
+ *
+ * SAMPLING.  csi_drifters_sample(ctx, d, columns, dev_out, ld) writes, in ONE launch, the requested columns at the current positions:
+ * column k (the k-th set bit of `columns`, counted from bit 0) of drifter q at dev_out[k * ld + q], doubles, ld >= n: the layout is a
+ * function of the column mask alone.  XI, ETA: the position.  U, V: the bilinear form above with the weights of A / of B applied to
+ * u / to v themselves (m/s along the grid's local directions).  H, A, HS: the containing cell's value of CSI_F_H, CSI_F_A, CSI_F_HS,
+ * copied.  An inactive drifter (non-finite coordinate) receives NaN in every column.
+ *
+ * Neither entry waits for the device.  n == 0 is a no-op without a launch.  csi_drifters_stats: launches of the two kernels made on
+ * the context so far (tests; the pointer may be NULL).
+ * ERRORS, by name.  CSI_ERR_NOT_BOUND: the grid; u or v; h, aice or hs where their column is requested.  CSI_ERR_INVALID_ARGUMENT:
+ * d == NULL, n < 0, a NULL array with n > 0, dt not finite, substeps < 1, columns == 0 or an unknown bit, dev_out == NULL, ld < n, a
+ * grid with halo < 1.  CSI_ERR_UNSUPPORTED: a tiled context (a drifter would have to migrate between ranks) and the RIGHT_FOLDED
+ * topologies (crossing the fold re-orients the drifter).
+ * NOT BUILT: tiles; the fold; sorting or binning the drifters by cell; deformation from drifter triplets; sampling of derived or
+ * momentum term fields; asynchronous staging of the sampled records. */
+#define CSI_DRIFTER_CLAMPED_X 1
+#define CSI_DRIFTER_CLAMPED_Y 2
+#define CSI_DRIFTER_HELD 4
+#define CSI_DRIFTER_LOST 8
+#define CSI_DRIFTER_INACTIVE 16
+#define CSI_DRIFTER_COL_XI 1
+#define CSI_DRIFTER_COL_ETA 2
+#define CSI_DRIFTER_COL_U 4
+#define CSI_DRIFTER_COL_V 8
+#define CSI_DRIFTER_COL_H 16
+#define CSI_DRIFTER_COL_A 32
+#define CSI_DRIFTER_COL_HS 64
+#define CSI_DRIFTER_COL_ALL 127
+typedef struct {
+    int64_t n;                         /* drifters; >= 0 */
+    double* xi;                        /* device, n doubles */
+    double* eta;                       /* device, n doubles */
+    int32_t* status;                   /* device, n int32: rewritten by every advance */
+} csi_drifters;
+int32_t csi_drifters_locate(int32_t Nx, int32_t Ny, double xi, double eta, int32_t* idx, double* w);
+int32_t csi_drifters_advance(csi_context* ctx, const csi_drifters* d, double dt, int32_t substeps);
+int32_t csi_drifters_sample(csi_context* ctx, const csi_drifters* d, int32_t columns, void* dev_out, int64_t ld);
+int32_t csi_drifters_stats(csi_context* ctx, int64_t* launches);
+
 #ifdef __cplusplus
 }
 #endif

@@ -1167,6 +1167,48 @@ function enthalpy_plan(Nz, forced = 0)
 end
 detach_enthalpy!(e::EnthalpyContext) = (check(e.ctx, ccall((:csi_enthalpy_destroy, libcsi), Int32, (Ptr{Cvoid},), e.handle)); e.handle = C_NULL; nothing)
 
+# ---- Lagrangian ice drifters (include/csi.h, "Lagrangian ice drifters": csi_drifters_advance, csi_drifters_sample) ----------------------
+# Index-space positions xi in [0, Nx], eta in [0, Ny] and an Int32 status per drifter, in DEVICE arrays the caller owns (ROCArrays): the
+# library keeps no drifter state.  advance_drifters!(model, xi, eta, status, Δt; substeps) moves them with the velocities the model holds,
+# ONE launch on the context's stream, nothing copied or waited for -- call it after time_step!(model, Δt) (whose update_state! leaves the
+# one halo ring of u, v valid that the call reads), before anything samples the positions.  Not supported: Distributed grids, tripolar grids.
+const DRIFTER_STATUS = (CLAMPED_X=1, CLAMPED_Y=2, HELD=4, LOST=8, INACTIVE=16)
+const DRIFTER_COLUMNS = (XI=1, ETA=2, U=4, V=8, H=16, A=32, HS=64)
+# csi_drifters: n and the three device arrays
+struct CsiDrifters
+    n::Int64
+    xi::Ptr{Cdouble}
+    eta::Ptr{Cdouble}
+    status::Ptr{Int32}
+end
+@assert sizeof(CsiDrifters) == 32      # the layout gcc gives csi_drifters
+
+function advance_drifters!(model::HIPSeaIceModel, xi, eta, status, Δt; substeps = 1)
+    ctx = context(model)
+    length(xi) == length(eta) == length(status) || error("advance_drifters!: xi, eta and status need one length")
+    d = Ref(CsiDrifters(length(xi), Ptr{Cdouble}(pointer(xi)), Ptr{Cdouble}(pointer(eta)), Ptr{Int32}(pointer(status))))
+    GC.@preserve model xi eta status check(ctx, ccall((:csi_drifters_advance, libcsi), Int32, (Ptr{Cvoid}, Ref{CsiDrifters}, Cdouble, Int32),
+                                                      ctx.handle, d, Float64(Δt), Int32(substeps)))
+    return nothing
+end
+
+# sample_drifters!(out, model, xi, eta, status; columns): column k of the mask (DRIFTER_COLUMNS) of drifter q at out[q, k], a device matrix
+# with at least length(xi) rows
+function sample_drifters!(out, model::HIPSeaIceModel, xi, eta, status; columns = DRIFTER_COLUMNS.XI | DRIFTER_COLUMNS.ETA)
+    ctx = context(model)
+    d = Ref(CsiDrifters(length(xi), Ptr{Cdouble}(pointer(xi)), Ptr{Cdouble}(pointer(eta)), Ptr{Int32}(pointer(status))))
+    GC.@preserve model out xi eta status check(ctx, ccall((:csi_drifters_sample, libcsi), Int32, (Ptr{Cvoid}, Ref{CsiDrifters}, Int32, Ptr{Cvoid}, Int64),
+                                                          ctx.handle, d, Int32(columns), Ptr{Cvoid}(pointer(out)), Int64(size(out, 1))))
+    return out
+end
+
+function drifter_launches(model::HIPSeaIceModel)
+    ctx = context(model)
+    n = Ref{Int64}(0)
+    check(ctx, ccall((:csi_drifters_stats, libcsi), Int32, (Ptr{Cvoid}, Ref{Int64}), ctx.handle, n))
+    return n[]
+end
+
 # Checkpointing (sea_ice_model.jl:414-445: prognostic_state / restore_prognostic_state!) needs nothing from the library: the
 # state lives in the Oceananigans Fields, restore writes into the same parents, and the library holds pointers only.  If a
 # restore REPLACES parents (new arrays), drop the context so that the next step re-attaches:
