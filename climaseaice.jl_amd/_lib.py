@@ -9,6 +9,8 @@ import os
 
 import numpy as np
 
+from .grids import Center, Face
+
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("CSI_HIP_LIBRARY", os.path.join(_HERE, "libcsi_hip.so"))   # override: A/B runs of two builds
 
@@ -16,45 +18,62 @@ LIB_PATH = os.environ.get("CSI_HIP_LIBRARY", os.path.join(_HERE, "libcsi_hip.so"
 OK = 0
 PERIODIC, BOUNDED, FULLY_CONNECTED, LEFT_CONNECTED, RIGHT_CONNECTED, RIGHT_FOLDED, LEFT_CONNECTED_RIGHT_FOLDED = 0, 1, 2, 3, 4, 5, 6
 METRIC_UNIFORM, METRIC_PER_J, METRIC_FULL = 0, 1, 2
-FIELD_IDS = ["U", "V", "H", "A", "S11", "S22", "S12", "UN", "VN", "P", "ALPHA", "DELTA", "ZETA_F", "ZETA_C",
-             "GH", "GA", "HM", "AM", "UM", "VM", "TOP_U", "TOP_V", "BOT_U", "BOT_V", "MASS_FLUX",
-             "HS", "GHS", "HSM", "MASS_FLUX_SNOW", "SNOWFALL_INTERCEPTED", "TU", "TUS", "FORCING_U", "FORCING_V", "GU", "GV"]
-THERMO_FIELD_IDS = ["TOP_HEAT_FLUX", "BOTTOM_HEAT_FLUX", "SNOWFALL"]     # csi_thermo_field_id: numbered from CSI_F_COUNT on
-FREE_DRIFT_FIELD_IDS = ["FREE_DRIFT_U", "FREE_DRIFT_V"]                  # csi_free_drift_field_id: numbered from CSI_F_COUNT_ALL on
-F = {n: k for k, n in enumerate(FIELD_IDS + THERMO_FIELD_IDS + FREE_DRIFT_FIELD_IDS)}
-# csi_derived_field_id: the seven derived (c,c) fields, numbered from CSI_F_COUNT_TOTAL = len(F) on (F itself keeps its extent)
-DERIVED_FIELD_IDS = ["D_DIVERGENCE", "D_SHEAR", "D_DEFORMATION", "D_SPEED", "D_SIGMA_I", "D_SIGMA_II", "D_STRESS_POWER"]
-F_DERIVED = {n: len(F) + k for k, n in enumerate(DERIVED_FIELD_IDS)}
-# csi_momentum_term_field_id: the ten momentum term fields, _X / _Y of each term, numbered from CSI_F_COUNT_DERIVED on
-MOMENTUM_TERM_FIELD_IDS = ["M_CORIOLIS_X", "M_CORIOLIS_Y", "M_TOP_X", "M_TOP_Y", "M_BOTTOM_X", "M_BOTTOM_Y", "M_INTERNAL_X", "M_INTERNAL_Y",
-                           "M_FORCING_X", "M_FORCING_Y"]
-F_MOMENTUM_TERMS = {n: len(F) + len(F_DERIVED) + k for k, n in enumerate(MOMENTUM_TERM_FIELD_IDS)}
-F_COUNT_BINDABLE = len(F) + len(F_DERIVED) + len(F_MOMENTUM_TERMS)
-# csi_thermo_linear_field_id: the LINEAR term's per-cell K and Ta, the per-cell bottom salinity and the two used-flux outputs, numbered
-# from CSI_F_COUNT_BINDABLE on
-THERMO_LINEAR_FIELD_IDS = ["FLUX_COEFFICIENT", "FLUX_REFERENCE_TEMPERATURE", "BOTTOM_SALINITY", "TOP_HEAT_FLUX_USED",
-                           "BOTTOM_HEAT_FLUX_USED"]
-F_THERMO_LINEAR = {n: F_COUNT_BINDABLE + k for k, n in enumerate(THERMO_LINEAR_FIELD_IDS)}
-F_COUNT_THERMO = F_COUNT_BINDABLE + len(F_THERMO_LINEAR)
-# csi_mixed_layer_field_id: the slab-ocean mixed layer's temperature, its Psi^- copy, its four inputs and the open-water flux it used,
-# numbered from CSI_F_COUNT_THERMO on
-MIXED_LAYER_FIELD_IDS = ["ML_TEMPERATURE", "ML_TEMPERATURE_M", "ML_SURFACE_HEAT_FLUX", "ML_COEFFICIENT", "ML_REFERENCE_TEMPERATURE",
-                         "ML_DEEP_HEAT_FLUX", "ML_SURFACE_FLUX_USED"]
-F_MIXED_LAYER = {n: F_COUNT_THERMO + k for k, n in enumerate(MIXED_LAYER_FIELD_IDS)}
-F_COUNT_MIXED_LAYER = F_COUNT_THERMO + len(F_MIXED_LAYER)
-# csi_shortwave_field_id: the SHORTWAVE top term's per-cell flux and the albedo a step used, numbered from CSI_F_COUNT_MIXED_LAYER on
-SHORTWAVE_FIELD_IDS = ["SHORTWAVE", "ALBEDO_USED"]
-F_SHORTWAVE = {n: F_COUNT_MIXED_LAYER + k for k, n in enumerate(SHORTWAVE_FIELD_IDS)}
-F_COUNT_SHORTWAVE = F_COUNT_MIXED_LAYER + len(F_SHORTWAVE)
+# ---- the field slots of csi_field_bind: include/csi.h's eight chained enums; csrc/csi_slots.h states the same table for the library ----
+# One row per slot, in id order: (NAME, the name the library's messages print, (LX, LY), roles).  A new slot is one row here.
+SLOT_HALO, SLOT_PEER, SLOT_FORCING, SLOT_SERIES = 1, 2, 4, 8      # csrc/csi_slots.h: what each role means
+_H, _HP, _HFS, _S = SLOT_HALO, SLOT_HALO | SLOT_PEER, SLOT_HALO | SLOT_FORCING | SLOT_SERIES, SLOT_SERIES
+_cc, _fc, _cf, _ff = (Center, Center), (Face, Center), (Center, Face), (Face, Face)
+SLOTS = [
+    ("U", "u", _fc, _HP), ("V", "v", _cf, _HP), ("H", "h", _cc, _H), ("A", "aice", _cc, _H), ("S11", "sigma11", _cc, _HP),
+    ("S22", "sigma22", _cc, _HP), ("S12", "sigma12", _ff, _HP), ("UN", "un", _fc, _H), ("VN", "vn", _cf, _H), ("P", "P", _cc, _H),
+    ("ALPHA", "alpha", _cc, _HP), ("DELTA", "Delta", _cc, _HP), ("ZETA_F", "zeta_f", _ff, _HP), ("ZETA_C", "zeta_c", _cc, _HP),
+    ("GH", "Gh", _cc, _H), ("GA", "Gaice", _cc, _H), ("HM", "h-", _cc, _H), ("AM", "aice-", _cc, _H), ("UM", "u-", _fc, _H), ("VM", "v-", _cf, _H),
+    ("TOP_U", "top_u", _fc, _HFS), ("TOP_V", "top_v", _cf, _HFS), ("BOT_U", "bottom_u", _fc, _HFS), ("BOT_V", "bottom_v", _cf, _HFS),
+    ("MASS_FLUX", "mass_flux", _cc, _H), ("HS", "hs", _cc, _H), ("GHS", "Ghs", _cc, _H), ("HSM", "hs-", _cc, _H),
+    ("MASS_FLUX_SNOW", "mass_flux_snow", _cc, _H), ("SNOWFALL_INTERCEPTED", "intercepted_snowfall", _cc, _H), ("TU", "Tu", _cc, _H),
+    ("TUS", "Tu_snow", _cc, _H), ("FORCING_U", "forcing_u", _fc, _HFS), ("FORCING_V", "forcing_v", _cf, _HFS), ("GU", "Gu", _fc, _H),
+    ("GV", "Gv", _cf, _H), ("TOP_HEAT_FLUX", "top_heat_flux", _cc, _S), ("BOTTOM_HEAT_FLUX", "bottom_heat_flux", _cc, _S),
+    ("SNOWFALL", "snowfall", _cc, _S), ("FREE_DRIFT_U", "free_drift_u", _fc, _HFS), ("FREE_DRIFT_V", "free_drift_v", _cf, _HFS),
+    ("D_DIVERGENCE", "divergence", _cc, 0), ("D_SHEAR", "shear", _cc, 0), ("D_DEFORMATION", "deformation", _cc, 0), ("D_SPEED", "speed", _cc, 0),
+    ("D_SIGMA_I", "sigma_I", _cc, 0), ("D_SIGMA_II", "sigma_II", _cc, 0), ("D_STRESS_POWER", "stress_power", _cc, 0),
+    ("M_CORIOLIS_X", "coriolis_x", _fc, 0), ("M_CORIOLIS_Y", "coriolis_y", _cf, 0), ("M_TOP_X", "top_x", _fc, 0), ("M_TOP_Y", "top_y", _cf, 0),
+    ("M_BOTTOM_X", "bottom_x", _fc, 0), ("M_BOTTOM_Y", "bottom_y", _cf, 0), ("M_INTERNAL_X", "internal_x", _fc, 0),
+    ("M_INTERNAL_Y", "internal_y", _cf, 0), ("M_FORCING_X", "forcing_x", _fc, 0), ("M_FORCING_Y", "forcing_y", _cf, 0),
+    ("FLUX_COEFFICIENT", "flux_coefficient", _cc, _S), ("FLUX_REFERENCE_TEMPERATURE", "flux_reference_temperature", _cc, _S),
+    ("BOTTOM_SALINITY", "bottom_salinity", _cc, _S), ("TOP_HEAT_FLUX_USED", "top_heat_flux_used", _cc, 0),
+    ("BOTTOM_HEAT_FLUX_USED", "bottom_heat_flux_used", _cc, 0), ("ML_TEMPERATURE", "ocean_temperature", _cc, 0),
+    ("ML_TEMPERATURE_M", "ocean_temperature-", _cc, 0), ("ML_SURFACE_HEAT_FLUX", "ocean_surface_heat_flux", _cc, _S),
+    ("ML_COEFFICIENT", "ocean_coefficient", _cc, _S), ("ML_REFERENCE_TEMPERATURE", "ocean_reference_temperature", _cc, _S),
+    ("ML_DEEP_HEAT_FLUX", "ocean_deep_heat_flux", _cc, _S), ("ML_SURFACE_FLUX_USED", "ocean_surface_flux_used", _cc, 0),
+    ("SHORTWAVE", "shortwave", _cc, _S), ("ALBEDO_USED", "albedo_used", _cc, 0)]
+_NAMES = [row[0] for row in SLOTS]
+_ID = {n: k for k, n in enumerate(_NAMES)}
+_DISPLAY = {row[1]: row[0] for row in SLOTS}
+# the eight enums, each from its first enumerator to the next one's; the last four cuts are the counts from CSI_F_COUNT_BINDABLE on
+_cut = [_ID[n] for n in ("U", "TOP_HEAT_FLUX", "FREE_DRIFT_U", "D_DIVERGENCE", "M_CORIOLIS_X", "FLUX_COEFFICIENT", "ML_TEMPERATURE", "SHORTWAVE")] + [len(SLOTS)]
+(FIELD_IDS, THERMO_FIELD_IDS, FREE_DRIFT_FIELD_IDS, DERIVED_FIELD_IDS, MOMENTUM_TERM_FIELD_IDS, THERMO_LINEAR_FIELD_IDS,
+ MIXED_LAYER_FIELD_IDS, SHORTWAVE_FIELD_IDS) = (_NAMES[a:b] for a, b in zip(_cut, _cut[1:]))
+F, F_DERIVED, F_MOMENTUM_TERMS, F_THERMO_LINEAR, F_MIXED_LAYER, F_SHORTWAVE = ({n: _ID[n] for n in _NAMES[a:b]} for a, b in zip([0] + _cut[3:], _cut[3:]))
+F_COUNT_BINDABLE, F_COUNT_THERMO, F_COUNT_MIXED_LAYER, F_COUNT_SHORTWAVE = _cut[5:]
+# the slots a time series may drive (csi_time_series_set): of F the forcing slots first, then the others; the younger enums' in their own lists
+_series = [row[0] for row in SLOTS if row[3] & SLOT_SERIES]
+SERIES_SLOTS = sorted((n for n in _series if n in F), key=lambda n: not SLOTS[_ID[n]][3] & SLOT_FORCING)
+THERMO_SERIES_SLOTS, MIXED_LAYER_SERIES_SLOTS, SHORTWAVE_SERIES_SLOTS = ([n for n in _series if n in t] for t in (F_THERMO_LINEAR, F_MIXED_LAYER, F_SHORTWAVE))
 
 
 def slot_id(name):
-    """The number of a csi_field_bind slot by name: F, or one of the derived fields', momentum term fields', thermodynamic or
-    mixed-layer and shortwave slots."""
-    for table in (F, F_DERIVED, F_MOMENTUM_TERMS, F_MIXED_LAYER, F_SHORTWAVE):
-        if name in table:
-            return table[name]
-    return F_THERMO_LINEAR[name]
+    """The number of a csi_field_bind slot by name."""
+    return _ID[name]
+
+
+def slot_location(name):
+    """(LX, LY) of a slot by name: grids.Center / grids.Face."""
+    return SLOTS[_ID[name]][2]
+
+
+def slot_of_display_name(display):
+    """The slot's name ("ML_COEFFICIENT") for the name the library's messages print ("ocean_coefficient")."""
+    return _DISPLAY[display]
 
 
 STRESS_NONE, STRESS_CONST, STRESS_FIELD, STRESS_SEMI_IMPLICIT = 0, 1, 2, 3
@@ -76,15 +95,6 @@ TIME_CLAMP, TIME_CYCLICAL, TIME_LINEAR = 0, 1, 2
 SERIES_DEVICE, SERIES_HOST = 0, 1
 REGRID_FACE_CENTER, REGRID_CENTER_FACE, REGRID_CENTER_CENTER = 0, 1, 2      # csi_regrid_location
 REGRID_MAX_MAPS, REGRID_MAX_SOURCE_EXTENT = 16, 65536
-# the eleven slots a time series may drive (csi_time_series_set)
-SERIES_SLOTS = ["TOP_U", "TOP_V", "BOT_U", "BOT_V", "FORCING_U", "FORCING_V", "FREE_DRIFT_U", "FREE_DRIFT_V",
-                "TOP_HEAT_FLUX", "BOTTOM_HEAT_FLUX", "SNOWFALL"]
-# ... and the three thermodynamic inputs that joined them (slot_id names them): fourteen in all
-THERMO_SERIES_SLOTS = ["FLUX_COEFFICIENT", "FLUX_REFERENCE_TEMPERATURE", "BOTTOM_SALINITY"]
-# ... and the mixed layer's four inputs: eighteen
-MIXED_LAYER_SERIES_SLOTS = ["ML_SURFACE_HEAT_FLUX", "ML_COEFFICIENT", "ML_REFERENCE_TEMPERATURE", "ML_DEEP_HEAT_FLUX"]
-# ... and the shortwave flux: nineteen
-SHORTWAVE_SERIES_SLOTS = ["SHORTWAVE"]
 ML_SURFACE_ARRAY, ML_BULK_ARRAYS, ML_DEEP_ARRAY, ML_HAS_SURFACE, ML_HAS_BULK = 1, 2, 4, 8, 16      # csi_mixed_layer_params.flags
 
 # every symbol include/csi.h declares (checked by tests/test_abi.py against the header text)

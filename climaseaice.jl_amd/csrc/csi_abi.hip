@@ -302,20 +302,18 @@ int32_t csi_mask_set(csi_context* c, const uint8_t* dev_mask, int64_t ld) {
 int32_t csi_field_bind(csi_context* c, int32_t fid, void* dev_ptr, int64_t ld, int32_t ni, int32_t nj) {
     if (!c) return CSI_ERR_INVALID_ARGUMENT;
     if (!c->grid_set) return fail(c, CSI_ERR_NOT_BOUND, "csi_grid_set has not been called");
-    if (fid < 0 || fid >= CSI_F_COUNT_SHORTWAVE) return fail(c, CSI_ERR_INVALID_ARGUMENT, "unknown field id");
+    if (!slot_known(fid)) return fail(c, CSI_ERR_INVALID_ARGUMENT, "unknown field id");
     if (!dev_ptr) { c->f[fid] = Bound{}; return CSI_OK; }
     const int eni = c->Nx + 2 * c->Hx + extra_x(c, fid), enj = c->Ny + 2 * c->Hy + extra_y(c, fid);
     if (ni != eni || nj != enj || ld < ni) {
         char buf[256];
         snprintf(buf, sizeof buf, "field %s: parent extents (%d, %d, ld %lld) do not match the grid (expected %d x %d)",
-                 kName[fid], ni, nj, (long long)ld, eni, enj);
+                 slot_name(fid), ni, nj, (long long)ld, eni, enj);
         return fail(c, CSI_ERR_INVALID_ARGUMENT, buf);
     }
     if (ld > 0x7fffffff) return fail(c, CSI_ERR_INVALID_ARGUMENT, "ld too large");
     if (((uintptr_t)dev_ptr) & 7) return fail(c, CSI_ERR_INVALID_ARGUMENT, "field pointer must be 8-byte aligned");
-    const bool peer_field = fid == CSI_F_U || fid == CSI_F_V || fid == CSI_F_S11 || fid == CSI_F_S22 || fid == CSI_F_S12 || fid == CSI_F_ALPHA ||
-                            fid == CSI_F_ZETA_C || fid == CSI_F_ZETA_F || fid == CSI_F_DELTA;
-    if (peer_field && c->f[fid].p != (double*)dev_ptr && c->peer.ready) {
+    if (slot_has(fid, SLOT_PEER) && c->f[fid].p != (double*)dev_ptr && c->peer.ready) {
         // the neighbours hold mappings of the OLD array: the next sub-cycle sets the peer transport up again.  That set-up is
         // collective -- on a tiled model, re-binding one of these nine arrays is something every rank has to do between the same
         // two steps (include/csi.h)
@@ -457,7 +455,7 @@ int32_t csi_cache_current_fields(csi_context* c) {
     B.aligned16 = 1;
     auto add = [&](int dst, int src) -> int32_t {
         const Bound &d = c->f[dst], &q = c->f[src];
-        if (d.ld != q.ld || d.nj != q.nj) return fail(c, CSI_ERR_INVALID_ARGUMENT, std::string("parent shape mismatch: ") + kName[dst] + " vs " + kName[src]);
+        if (d.ld != q.ld || d.nj != q.nj) return fail(c, CSI_ERR_INVALID_ARGUMENT, std::string("parent shape mismatch: ") + slot_name(dst) + " vs " + slot_name(src));
         B.src[B.count] = q.p; B.dst[B.count] = d.p; B.n[B.count] = (long)d.ld * d.nj; ++B.count;
         if ((((uintptr_t)q.p) | ((uintptr_t)d.p)) & 15) B.aligned16 = 0;
         return CSI_OK;
@@ -477,9 +475,6 @@ int32_t csi_cache_current_fields(csi_context* c) {
     return CSI_OK;
 }
 
-// the slots csi_fill_halo_local / csi_halo_exchange take: csi_field_id and the prescribed free-drift velocity fields
-static bool halo_slot(int32_t fid) { return (fid >= 0 && fid < CSI_F_COUNT) || fid == CSI_F_FREE_DRIFT_U || fid == CSI_F_FREE_DRIFT_V; }
-
 int32_t csi_update_state(csi_context* c) {
     if (!c) return CSI_ERR_INVALID_ARGUMENT;
     const int32_t rc = do_update_state(c);
@@ -488,7 +483,7 @@ int32_t csi_update_state(csi_context* c) {
 
 int32_t csi_fill_halo_local(csi_context* c, int32_t fid) {
     if (!c) return CSI_ERR_INVALID_ARGUMENT;
-    if (!halo_slot(fid)) return fail(c, CSI_ERR_INVALID_ARGUMENT, "unknown field id");
+    if (!slot_has(fid, SLOT_HALO)) return fail(c, CSI_ERR_INVALID_ARGUMENT, "unknown field id");
     int32_t rc = need(c, {fid});
     if (rc) return rc;
     return fill_halo(c, fid);
@@ -598,13 +593,18 @@ int32_t csi_time_step_rk3(csi_context* c, double dt, int32_t substeps, int32_t s
     return finish_step(c, CSI_OK);
 }
 
+// what csi_tile_set and every csi_comm_init* share: the peer transport's mappings go, and with them what made it fail or abort; a
+// csi_comm_init* first leaves the RCCL communicator / host-channel group the context was in
+static void peer_reset(csi_context* c) { peer_release(c); c->peer.failed = false; c->peer.aborted = false; if (c->peer.err_host) *c->peer.err_host.get() = 0; }
+static void leave_groups(csi_context* c) { if (c->comm) { ncclCommDestroy(c->comm); c->comm = nullptr; } if (c->hostg) { hostgroup_leave(c->hostg); c->hostg = nullptr; } }
+
 int32_t csi_tile_set(csi_context* c, int32_t rx, int32_t ry, int32_t Rx, int32_t Ry, int32_t periodic_x, int32_t periodic_y) {
     if (!c) return CSI_ERR_INVALID_ARGUMENT;
     if (Rx < 1 || Ry < 1 || rx < 0 || rx >= Rx || ry < 0 || ry >= Ry) return fail(c, CSI_ERR_INVALID_ARGUMENT, "tile coordinates out of range");
     c->tile.rx = rx; c->tile.ry = ry; c->tile.Rx = Rx; c->tile.Ry = Ry;
     c->tile.periodic_x = periodic_x != 0; c->tile.periodic_y = periodic_y != 0;
     c->tile.set = true;
-    peer_release(c); c->peer.failed = false; c->peer.aborted = false; if (c->peer.err_host) *c->peer.err_host.get() = 0;           // (the neighbours may be other ranks now)
+    peer_reset(c);      // (the neighbours may be other ranks now)
     return CSI_OK;
 }
 
@@ -622,10 +622,9 @@ int32_t csi_comm_init(csi_context* c, int32_t world_size, int32_t rank, const ui
     if (!c || !id128) return CSI_ERR_INVALID_ARGUMENT;
     if (world_size < 1 || rank < 0 || rank >= world_size) return fail(c, CSI_ERR_INVALID_ARGUMENT, "rank / world_size out of range");
     HIP_TRY(c, hipSetDevice(c->device));
-    if (c->comm) { ncclCommDestroy(c->comm); c->comm = nullptr; }
-    if (c->hostg) { hostgroup_leave(c->hostg); c->hostg = nullptr; }
+    leave_groups(c);
     c->local = nullptr;
-    peer_release(c); c->peer.failed = false; c->peer.aborted = false; if (c->peer.err_host) *c->peer.err_host.get() = 0;           // (mappings of the previous communicator's neighbours)
+    peer_reset(c);      // (mappings of the previous communicator's neighbours)
     ncclUniqueId id;
     memcpy(&id, id128, 128);
     NCCL_TRY(c, ncclCommInitRank(&c->comm, world_size, id, rank));
@@ -649,9 +648,8 @@ void csi_local_group_destroy(csi_local_group* G) { delete G; }
 int32_t csi_comm_init_local(csi_context* c, csi_local_group* G, int32_t rank) {
     if (!c || !G) return CSI_ERR_INVALID_ARGUMENT;
     if (rank < 0 || rank >= G->world) return fail(c, CSI_ERR_INVALID_ARGUMENT, "rank out of range for this group");
-    if (c->comm) { ncclCommDestroy(c->comm); c->comm = nullptr; }
-    if (c->hostg) { hostgroup_leave(c->hostg); c->hostg = nullptr; }
-    peer_release(c); c->peer.failed = false; c->peer.aborted = false; if (c->peer.err_host) *c->peer.err_host.get() = 0;
+    leave_groups(c);
+    peer_reset(c);
     c->local = G;
     c->world = G->world; c->rank = rank;
     // The peer transport's kernels wait for flags the OTHER tiles' kernels of this process publish.  HIP maps streams onto
@@ -676,10 +674,9 @@ int32_t csi_comm_init_host(csi_context* c, const char* shm_name, int32_t world_s
     if (!c || !shm_name) return CSI_ERR_INVALID_ARGUMENT;
     if (world_size < 2 || rank < 0 || rank >= world_size) return fail(c, CSI_ERR_INVALID_ARGUMENT, "rank / world_size out of range (a host-channel group has at least two ranks)");
     HIP_TRY(c, hipSetDevice(c->device));
-    if (c->comm) { ncclCommDestroy(c->comm); c->comm = nullptr; }
-    if (c->hostg) { hostgroup_leave(c->hostg); c->hostg = nullptr; }
+    leave_groups(c);
     c->local = nullptr;
-    peer_release(c); c->peer.failed = false; c->peer.aborted = false; if (c->peer.err_host) *c->peer.err_host.get() = 0;
+    peer_reset(c);
     std::string e;
     c->hostg = hostgroup_join(shm_name, world_size, rank, &e);
     if (!c->hostg) return fail(c, CSI_ERR_COMM, e);
@@ -703,7 +700,7 @@ int32_t csi_halo_exchange(csi_context* c, const int32_t* field_ids, int32_t nfie
     if (!c || !field_ids) return CSI_ERR_INVALID_ARGUMENT;
     if (!c->grid_set) return fail(c, CSI_ERR_NOT_BOUND, "csi_grid_set has not been called");
     for (int k = 0; k < nfields; ++k)
-        if (!halo_slot(field_ids[k])) return fail(c, CSI_ERR_INVALID_ARGUMENT, "unknown field id");
+        if (!slot_has(field_ids[k], SLOT_HALO)) return fail(c, CSI_ERR_INVALID_ARGUMENT, "unknown field id");
     return exchange(c, field_ids, nfields, width);
 }
 

@@ -40,17 +40,17 @@ int img_of(int side, int loc) {
 }
 ImageSpec image_spec(const csi_context* c, int fid) {
     ImageSpec im;
-    im.xlo = img_of(c->g.xlo, kLoc[fid][0]);
-    im.xhi = img_of(c->g.xhi, kLoc[fid][0]);
-    im.ylo = img_of(c->g.ylo, kLoc[fid][1]);
-    im.yhi = img_of(c->g.yhi, kLoc[fid][1]);
-    im.ex = (kLoc[fid][0] == LOC_F && c->g.xhi == SIDE_WALL) ? 1 : 0;
-    im.ey = (kLoc[fid][1] == LOC_F && c->g.yhi == SIDE_WALL) ? 1 : 0;
+    im.xlo = img_of(c->g.xlo, slot_loc(fid, 0));
+    im.xhi = img_of(c->g.xhi, slot_loc(fid, 0));
+    im.ylo = img_of(c->g.ylo, slot_loc(fid, 1));
+    im.yhi = img_of(c->g.yhi, slot_loc(fid, 1));
+    im.ex = (slot_loc(fid, 0) == LOC_F && c->g.xhi == SIDE_WALL) ? 1 : 0;
+    im.ey = (slot_loc(fid, 1) == LOC_F && c->g.yhi == SIDE_WALL) ? 1 : 0;
     im.vxlo = im.vxhi = im.vylo = im.vyhi = 0.0;
     // Zipper (north fold): vector components change sign (sea_ice_model.jl:57-64 for u, v; the stress / ocean-velocity /
     // forcing arrays at the velocity points are built with the same boundary conditions, test/distributed_tests_utils.jl:196-197)
-    im.fold_fx = kLoc[fid][0] == LOC_F; im.fold_fy = kLoc[fid][1] == LOC_F;
-    im.fold_sign = (kLoc[fid][0] != kLoc[fid][1]) ? -1 : 1;       // (f,c) and (c,f) fields are all velocity-like here
+    im.fold_fx = slot_loc(fid, 0) == LOC_F; im.fold_fy = slot_loc(fid, 1) == LOC_F;
+    im.fold_sign = (slot_loc(fid, 0) != slot_loc(fid, 1)) ? -1 : 1;       // (f,c) and (c,f) fields are all velocity-like here
     // ValueBoundaryCondition on the tangential velocity at a wall replaces the no-flux mirror (one halo cell)
     if (fid == CSI_F_U) {
         if (im.ylo == IMG_MIRROR && c->vel_bc_on[0][0]) { im.ylo = IMG_VALUE; im.vylo = c->vel_bc_value[0][0]; }
@@ -62,8 +62,8 @@ ImageSpec image_spec(const csi_context* c, int fid) {
     return im;
 }
 // a Face-located field has one extra point where the HIGH side of that direction is a wall
-int extra_x(const csi_context* c, int fid) { return (kLoc[fid][0] == LOC_F && c->g.xhi == SIDE_WALL) ? 1 : 0; }
-int extra_y(const csi_context* c, int fid) { return (kLoc[fid][1] == LOC_F && c->g.yhi == SIDE_WALL) ? 1 : 0; }
+int extra_x(const csi_context* c, int fid) { return (slot_loc(fid, 0) == LOC_F && c->g.xhi == SIDE_WALL) ? 1 : 0; }
+int extra_y(const csi_context* c, int fid) { return (slot_loc(fid, 1) == LOC_F && c->g.yhi == SIDE_WALL) ? 1 : 0; }
 
 FRef ref_of(const csi_context* c, int fid) {
     FRef r;
@@ -75,7 +75,7 @@ FRef ref_of(const csi_context* c, int fid) {
 int32_t need(csi_context* c, std::initializer_list<int> ids) {
     if (!c->grid_set) return fail(c, CSI_ERR_NOT_BOUND, "csi_grid_set has not been called");
     for (int id : ids)
-        if (!c->f[id].p) return fail(c, CSI_ERR_NOT_BOUND, std::string("field not bound: ") + kName[id]);
+        if (!c->f[id].p) return fail(c, CSI_ERR_NOT_BOUND, std::string("field not bound: ") + slot_name(id));
     return CSI_OK;
 }
 
@@ -93,8 +93,8 @@ int32_t check_stress_fields(csi_context* c, int side) {
     int fu = side == CSI_STRESS_TOP ? CSI_F_TOP_U : CSI_F_BOT_U, fv = side == CSI_STRESS_TOP ? CSI_F_TOP_V : CSI_F_BOT_V;
     bool need_u = s.kind == CSI_STRESS_FIELD || (s.kind == CSI_STRESS_SEMI_IMPLICIT && s.ue_kind == CSI_VEL_FIELD);
     bool need_v = s.kind == CSI_STRESS_FIELD || (s.kind == CSI_STRESS_SEMI_IMPLICIT && s.ve_kind == CSI_VEL_FIELD);
-    if (need_u && !c->f[fu].p) return fail(c, CSI_ERR_NOT_BOUND, std::string("stress field not bound: ") + kName[fu]);
-    if (need_v && !c->f[fv].p) return fail(c, CSI_ERR_NOT_BOUND, std::string("stress field not bound: ") + kName[fv]);
+    if (need_u && !c->f[fu].p) return fail(c, CSI_ERR_NOT_BOUND, std::string("stress field not bound: ") + slot_name(fu));
+    if (need_v && !c->f[fv].p) return fail(c, CSI_ERR_NOT_BOUND, std::string("stress field not bound: ") + slot_name(fv));
     return CSI_OK;
 }
 
@@ -225,7 +225,7 @@ int32_t fill_width_check(csi_context* c, int fid) {
     auto images = [](int m) { return m == IMG_WRAP || m == IMG_MIRROR; };
     bool narrow = ((images(im.xlo) || images(im.xhi)) && c->Nx < c->Hx) || ((images(im.ylo) || images(im.yhi)) && c->Ny < c->Hy);
     if (im.yhi == IMG_FOLD) narrow = narrow || c->Nx < c->Hx || c->Ny < c->Hy + (im.fold_fy ? 0 : 1);
-    if (narrow) return fail(c, CSI_ERR_UNSUPPORTED, std::string("tile smaller than its halo: local halo fill of ") + kName[fid]);
+    if (narrow) return fail(c, CSI_ERR_UNSUPPORTED, std::string("tile smaller than its halo: local halo fill of ") + slot_name(fid));
     return CSI_OK;
 }
 
@@ -239,7 +239,7 @@ int32_t fill_halo(csi_context* c, int fid) {
 
 int32_t copy_parent(csi_context* c, int dst, int src) {
     const Bound &d = c->f[dst], &s = c->f[src];
-    if (d.ld != s.ld || d.nj != s.nj) return fail(c, CSI_ERR_INVALID_ARGUMENT, std::string("parent shape mismatch: ") + kName[dst] + " vs " + kName[src]);
+    if (d.ld != s.ld || d.nj != s.nj) return fail(c, CSI_ERR_INVALID_ARGUMENT, std::string("parent shape mismatch: ") + slot_name(dst) + " vs " + slot_name(src));
     HIP_TRY(c, hipMemcpyAsync(d.p, s.p, sizeof(double) * (size_t)d.ld * (size_t)d.nj, hipMemcpyDeviceToDevice, c->stream));
     return CSI_OK;
 }
@@ -349,6 +349,7 @@ bool offsets_fit_32bit(int Nx, int Ny, int Hx, int Hy, int64_t max_ld) {
 }
 int64_t max_bound_ld(const csi_context* c) {
     int64_t m = 0;
+    // (not kSlotCount: the slots the fused kernels address and the derived fields, as ever -- this set decides pair_supported)
     for (int k = 0; k < CSI_F_COUNT_DERIVED; ++k) if (c->f[k].p && c->f[k].ld > m) m = c->f[k].ld;
     if (c->g.has_mask && c->g.mask_ld > m) m = c->g.mask_ld;
     return m;

@@ -13,10 +13,12 @@
 //   csi_momentum_terms.hip   momentum balance terms and their power: binding checks, the launches, the power sums' combine over the ranks
 //   csi_enthalpy.hip      the enthalpy-method column model: the choosing rule, the model object, its launches
 //   csi_drifters.hip      Lagrangian ice drifters: the locate rule on the host, argument and binding checks, the two launches
+//   csi_slots.h     the field slots: id, display name, location and roles of each, one row per slot
 //   csi_mem.h       DeviceBuf / PinnedBuf: the owner of every allocation the library makes
 #pragma once
 #include "../../include/csi.h"
 #include "csi_dev.h"
+#include "csi_slots.h"
 #include "csi_kernels.h"
 #include "momentum_dev.h"
 #include "csi_hostgroup.h"
@@ -46,42 +48,6 @@ struct Bound {
     int64_t ld = 0;
     int ni = 0, nj = 0;
 };
-
-// (x, y) location of every field slot
-static const int kLoc[CSI_F_COUNT_SHORTWAVE][2] = {
-    {LOC_F, LOC_C}, {LOC_C, LOC_F}, {LOC_C, LOC_C}, {LOC_C, LOC_C},   // U V H A
-    {LOC_C, LOC_C}, {LOC_C, LOC_C}, {LOC_F, LOC_F},                   // S11 S22 S12
-    {LOC_F, LOC_C}, {LOC_C, LOC_F}, {LOC_C, LOC_C}, {LOC_C, LOC_C}, {LOC_C, LOC_C},  // UN VN P ALPHA DELTA
-    {LOC_F, LOC_F}, {LOC_C, LOC_C},                                   // ZETA_F ZETA_C
-    {LOC_C, LOC_C}, {LOC_C, LOC_C}, {LOC_C, LOC_C}, {LOC_C, LOC_C},   // GH GA HM AM
-    {LOC_F, LOC_C}, {LOC_C, LOC_F},                                   // UM VM
-    {LOC_F, LOC_C}, {LOC_C, LOC_F}, {LOC_F, LOC_C}, {LOC_C, LOC_F},   // TOP_U TOP_V BOT_U BOT_V
-    {LOC_C, LOC_C},                                                   // MASS_FLUX
-    {LOC_C, LOC_C}, {LOC_C, LOC_C}, {LOC_C, LOC_C},                   // HS GHS HSM
-    {LOC_C, LOC_C}, {LOC_C, LOC_C}, {LOC_C, LOC_C}, {LOC_C, LOC_C},   // MASS_FLUX_SNOW SNOWFALL_INTERCEPTED TU TUS
-    {LOC_F, LOC_C}, {LOC_C, LOC_F},                                   // FORCING_U FORCING_V
-    {LOC_F, LOC_C}, {LOC_C, LOC_F},                                   // GU GV
-    {LOC_C, LOC_C}, {LOC_C, LOC_C}, {LOC_C, LOC_C},                   // TOP_HEAT_FLUX BOTTOM_HEAT_FLUX SNOWFALL
-    {LOC_F, LOC_C}, {LOC_C, LOC_F},                                   // FREE_DRIFT_U FREE_DRIFT_V
-    {LOC_C, LOC_C}, {LOC_C, LOC_C}, {LOC_C, LOC_C}, {LOC_C, LOC_C}, {LOC_C, LOC_C}, {LOC_C, LOC_C}, {LOC_C, LOC_C},    // the seven derived fields
-    {LOC_F, LOC_C}, {LOC_C, LOC_F}, {LOC_F, LOC_C}, {LOC_C, LOC_F}, {LOC_F, LOC_C}, {LOC_C, LOC_F}, {LOC_F, LOC_C}, {LOC_C, LOC_F},
-    {LOC_F, LOC_C}, {LOC_C, LOC_F},                                   // the ten momentum term fields: _X, _Y of each term
-    {LOC_C, LOC_C}, {LOC_C, LOC_C}, {LOC_C, LOC_C}, {LOC_C, LOC_C}, {LOC_C, LOC_C},    // FLUX_COEFFICIENT .. BOTTOM_HEAT_FLUX_USED
-    {LOC_C, LOC_C}, {LOC_C, LOC_C}, {LOC_C, LOC_C}, {LOC_C, LOC_C}, {LOC_C, LOC_C}, {LOC_C, LOC_C}, {LOC_C, LOC_C},    // ML_TEMPERATURE .. ML_SURFACE_FLUX_USED
-    {LOC_C, LOC_C}, {LOC_C, LOC_C}};                                  // SHORTWAVE ALBEDO_USED
-static const char* const kName[CSI_F_COUNT_SHORTWAVE] = {"u", "v", "h", "aice", "sigma11", "sigma22", "sigma12", "un", "vn", "P", "alpha",
-                                  "Delta", "zeta_f", "zeta_c", "Gh", "Gaice", "h-", "aice-", "u-", "v-",
-                                  "top_u", "top_v", "bottom_u", "bottom_v", "mass_flux",
-                                  "hs", "Ghs", "hs-", "mass_flux_snow", "intercepted_snowfall", "Tu", "Tu_snow", "forcing_u", "forcing_v", "Gu", "Gv",
-                                  "top_heat_flux", "bottom_heat_flux", "snowfall", "free_drift_u", "free_drift_v",
-                                  "divergence", "shear", "deformation", "speed", "sigma_I", "sigma_II", "stress_power",
-                                  "coriolis_x", "coriolis_y", "top_x", "top_y", "bottom_x", "bottom_y", "internal_x", "internal_y",
-                                  "forcing_x", "forcing_y",
-                                  "flux_coefficient", "flux_reference_temperature", "bottom_salinity", "top_heat_flux_used",
-                                  "bottom_heat_flux_used",
-                                  "ocean_temperature", "ocean_temperature-", "ocean_surface_heat_flux", "ocean_coefficient",
-                                  "ocean_reference_temperature", "ocean_deep_heat_flux", "ocean_surface_flux_used",
-                                  "shortwave", "albedo_used"};
 
 extern std::string g_create_error;      // csi_context_create failures (no context to hold the message)
 
@@ -214,7 +180,7 @@ struct csi_context {
     long fcor2_ld = 0, fcor2_plane = 0;
     bool cor_dirty = true;               // Coriolis columns of the FAST table need (re)building
     double cor_synced = 0.0;             // FPlane value they were built with
-    Bound f[CSI_F_COUNT_SHORTWAVE];
+    Bound f[kSlotCount];
     csi_evp_params evp{};
     csi_stress stress[2]{};
     int mode = CSI_MODE_STRICT;
@@ -428,9 +394,6 @@ static inline int nxf_of(int k) { return k > 1 ? 5 : 2; }     // sigma travels w
 struct FoldBand;
 // ---- functions shared by the translation units (definitions: see the list at the top) ----
 static const int kPing[5] = {CSI_F_U, CSI_F_V, CSI_F_S11, CSI_F_S22, CSI_F_S12};
-// update_external_stress!: the arrays at the velocity points whose halos the library fills (and exchanges between tiles) before a momentum step
-static const int kForcingFields[8] = {CSI_F_TOP_U, CSI_F_TOP_V, CSI_F_BOT_U, CSI_F_BOT_V, CSI_F_FORCING_U, CSI_F_FORCING_V,
-                                      CSI_F_FREE_DRIFT_U, CSI_F_FREE_DRIFT_V};
 // (elo / ehi: rows of the FIRST / LAST chunk where they differ from `rows` -- shorter tiles next to a peer-connected y side,
 //  pair_geom; elo == rows and ehi == 0: every chunk `rows` rows, the last one what is left)
 struct FusedGeom { Range rs; int nstrips, nchunks, rows; int elo = 0, ehi = 0; int wt = 0; };      // wt: write-through result stores (FI_WT)

@@ -57,7 +57,7 @@ int32_t csi_derived_compute(csi_context* c, int32_t mask) {
     for (int k = 0; k < DV_COUNT; ++k) {
         if (!(mask & (1 << k))) continue;
         const int id = CSI_F_D_DIVERGENCE + k;
-        if (!c->f[id].p) return fail(c, CSI_ERR_NOT_BOUND, std::string("derived: field ") + kName[id] + " is requested but no array is bound to its slot");
+        if (!c->f[id].p) return fail(c, CSI_ERR_NOT_BOUND, std::string("derived: field ") + slot_name(id) + " is requested but no array is bound to its slot");
         D.out[k] = ref_of(c, id);
     }
     HIP_TRY(c, hipSetDevice(c->device));

@@ -8,7 +8,10 @@
 namespace csi {
 
 enum : int { SIDE_PERIODIC = 0, SIDE_WALL = 1, SIDE_CONNECTED = 2, SIDE_FOLD = 3 };   // SIDE_FOLD: north fold of a TripolarGrid (yhi only)
+#ifndef CSI_LOC_DEFINED      // csi_slots.h states the same two for host code built without HIP
+#define CSI_LOC_DEFINED
 enum : int { LOC_C = 0, LOC_F = 1 };
+#endif
 enum : int { IMG_NONE = 0, IMG_WRAP = 1, IMG_MIRROR = 2, IMG_VALUE = 3, IMG_FOLD = 4 };
 
 struct FRef {

@@ -15,7 +15,7 @@ static_assert(DQ_COUNT >= BQ_COUNT && DQ_COUNT >= MQ_COUNT, "the reduction buffe
 
 int32_t need_named(csi_context* c, const char* who, const char* group, std::initializer_list<int> ids, const char* hint) {
     for (int id : ids)
-        if (!c->f[id].p) return fail(c, CSI_ERR_NOT_BOUND, std::string(who) + ": " + group + "needs field " + kName[id] + " (not bound" + hint + ")");
+        if (!c->f[id].p) return fail(c, CSI_ERR_NOT_BOUND, std::string(who) + ": " + group + "needs field " + slot_name(id) + " (not bound" + hint + ")");
     return CSI_OK;
 }
 
@@ -69,10 +69,10 @@ static int32_t diag_local(csi_context* c, int32_t what, double thr, double* slot
     const bool vel = what & CSI_DIAG_VELOCITY, trc = what & CSI_DIAG_TRACERS;
     if (vel)
         for (int id : {CSI_F_U, CSI_F_V})
-            if (!c->f[id].p) return fail(c, CSI_ERR_NOT_BOUND, std::string("diagnostics: the velocity group needs field ") + kName[id] + " (not bound: a model without dynamics supports CSI_DIAG_TRACERS only)");
+            if (!c->f[id].p) return fail(c, CSI_ERR_NOT_BOUND, std::string("diagnostics: the velocity group needs field ") + slot_name(id) + " (not bound: a model without dynamics supports CSI_DIAG_TRACERS only)");
     if (trc)
         for (int id : {CSI_F_H, CSI_F_A})
-            if (!c->f[id].p) return fail(c, CSI_ERR_NOT_BOUND, std::string("diagnostics: the tracer group needs field ") + kName[id] + " (not bound)");
+            if (!c->f[id].p) return fail(c, CSI_ERR_NOT_BOUND, std::string("diagnostics: the tracer group needs field ") + slot_name(id) + " (not bound)");
     DiagDev D{};
     D.g = c->g;
     D.u = ref_of(c, CSI_F_U); D.v = ref_of(c, CSI_F_V); D.h = ref_of(c, CSI_F_H); D.a = ref_of(c, CSI_F_A); D.hs = ref_of(c, CSI_F_HS);

@@ -70,7 +70,7 @@ int32_t csi_drifters_sample(csi_context* c, const csi_drifters* d, int32_t colum
     const struct { int bit, fid; FRef* ref; } cell[3] = {{CSI_DRIFTER_COL_H, CSI_F_H, &D.h}, {CSI_DRIFTER_COL_A, CSI_F_A, &D.a}, {CSI_DRIFTER_COL_HS, CSI_F_HS, &D.hs}};
     for (const auto& k : cell) {
         if (!(columns & k.bit)) continue;
-        if (!c->f[k.fid].p) return fail(c, CSI_ERR_NOT_BOUND, std::string("drifters sample: field ") + kName[k.fid] + " is requested as a column but not bound");
+        if (!c->f[k.fid].p) return fail(c, CSI_ERR_NOT_BOUND, std::string("drifters sample: field ") + slot_name(k.fid) + " is requested as a column but not bound");
         *k.ref = ref_of(c, k.fid);
     }
     if (D.n == 0) return CSI_OK;

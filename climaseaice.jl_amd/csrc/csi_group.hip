@@ -11,7 +11,7 @@ int32_t exchange(csi_context* c, const int* fids, int nf, int W) {
     if (nf > MAX_EX_FIELDS) return fail(c, CSI_ERR_INVALID_ARGUMENT, "too many fields in one exchange");
     FRef fr[MAX_EX_FIELDS];
     for (int k = 0; k < nf; ++k) {
-        if (!c->f[fids[k]].p) return fail(c, CSI_ERR_NOT_BOUND, std::string("field not bound: ") + kName[fids[k]]);
+        if (!c->f[fids[k]].p) return fail(c, CSI_ERR_NOT_BOUND, std::string("field not bound: ") + slot_name(fids[k]));
         fr[k] = ref_of(c, fids[k]);
     }
     return exchange_refs(c, fr, nf, W);

@@ -553,7 +553,7 @@ int32_t need_dynamics_common(csi_context* c) {
     if (c->Hx < 2 || c->Hy < 2) return fail(c, CSI_ERR_INVALID_ARGUMENT, "the momentum step needs halo >= 2");
     if (c->free_drift == CSI_FREE_DRIFT_FIELDS && (!c->f[CSI_F_FREE_DRIFT_U].p || !c->f[CSI_F_FREE_DRIFT_V].p))      // free_drift = (u, v)
         return fail(c, CSI_ERR_NOT_BOUND, std::string("prescribed free-drift velocity field not bound: ") +
-                                              kName[c->f[CSI_F_FREE_DRIFT_U].p ? CSI_F_FREE_DRIFT_V : CSI_F_FREE_DRIFT_U]);
+                                              slot_name(c->f[CSI_F_FREE_DRIFT_U].p ? CSI_F_FREE_DRIFT_V : CSI_F_FREE_DRIFT_U));
     if (c->free_drift == CSI_FREE_DRIFT_STRESS_BALANCE) {   // stress_balance_free_drift.jl:21-35: exactly one of the two stresses is a SemiImplicitStress
         const bool ts = c->stress[CSI_STRESS_TOP].kind == CSI_STRESS_SEMI_IMPLICIT, bs = c->stress[CSI_STRESS_BOTTOM].kind == CSI_STRESS_SEMI_IMPLICIT;
         if (ts == bs) return fail(c, CSI_ERR_INVALID_ARGUMENT, "StressBalanceFreeDrift needs exactly one SemiImplicitStress (top or bottom)");

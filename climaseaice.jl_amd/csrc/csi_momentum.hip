@@ -85,7 +85,7 @@ int32_t reset_velocities(csi_context* c) {
 // update_external_stress! (split_explicit_momentum_equations.jl:133-134): local halos of the stress / forcing arrays
 int32_t fill_forcing_halos(csi_context* c) {
     int32_t rc;
-    for (int id : kForcingFields)
+    for (int id : slots_with(SLOT_FORCING))
         if (c->f[id].p && (rc = fill_halo(c, id))) return rc;
     return CSI_OK;
 }
@@ -99,7 +99,7 @@ int32_t update_external_stress(csi_context* c) {
         // (every rank binds the same slots, so every rank issues the same batches: one exchange takes at most MAX_EX_FIELDS fields,
         //  which the six older slots fill; with the two free-drift fields on top of them a second batch follows)
         int ff[8], n = 0;
-        for (int id : kForcingFields) if (c->f[id].p) ff[n++] = id;
+        for (int id : slots_with(SLOT_FORCING)) if (c->f[id].p) ff[n++] = id;
         const int W = c->Hx < c->Hy ? c->Hx : c->Hy;
         for (int at = 0; at < n; at += MAX_EX_FIELDS)
             if ((rc = exchange(c, ff + at, std::min(n - at, MAX_EX_FIELDS), W))) return rc;

@@ -72,7 +72,7 @@ int32_t csi_momentum_terms_compute(csi_context* c, int32_t mask) {
         if (!(mask & (1 << t))) continue;
         for (int q = 0; q < 2; ++q) {
             const int id = CSI_F_M_CORIOLIS_X + 2 * t + q;
-            if (!c->f[id].p) return fail(c, CSI_ERR_NOT_BOUND, std::string("momentum terms: field ") + kName[id] + " is requested but no array is bound to its slot");
+            if (!c->f[id].p) return fail(c, CSI_ERR_NOT_BOUND, std::string("momentum terms: field ") + slot_name(id) + " is requested but no array is bound to its slot");
             T.out[2 * t + q] = ref_of(c, id);
         }
     }

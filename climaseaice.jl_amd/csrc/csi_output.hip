@@ -56,7 +56,7 @@ static OutputSet* set_of(csi_context* c, int32_t handle, bool check = true) {
         const Bound& b = c->f[S->f[k].field_id];
         const Bound& s = S->sig[k];
         if (b.p != s.p || b.ld != s.ld || b.ni != s.ni || b.nj != s.nj) {
-            fail(c, CSI_ERR_INVALID_ARGUMENT, std::string("output: field ") + kName[S->f[k].field_id] +
+            fail(c, CSI_ERR_INVALID_ARGUMENT, std::string("output: field ") + slot_name(S->f[k].field_id) +
                                                   " was re-bound after csi_output_create -- the set is invalid; destroy it and create it again");
             return nullptr;
         }
@@ -102,13 +102,13 @@ int32_t csi_output_create(csi_context* c, const csi_output_field* fields, int32_
     int32_t nx[kMaxOutputFields], ny[kMaxOutputFields], dt[kMaxOutputFields];
     for (int k = 0; k < n; ++k) {
         const csi_output_field& f = fields[k];
-        if (f.field_id < 0 || f.field_id >= CSI_F_COUNT_SHORTWAVE) return fail(c, CSI_ERR_INVALID_ARGUMENT, "output: unknown field id at position " + std::to_string(k));
+        if (!slot_known(f.field_id)) return fail(c, CSI_ERR_INVALID_ARGUMENT, "output: unknown field id at position " + std::to_string(k));
         if (f.dtype != CSI_OUT_F64 && f.dtype != CSI_OUT_F32)
-            return fail(c, CSI_ERR_INVALID_ARGUMENT, std::string("output: field ") + kName[f.field_id] + ": unknown dtype (CSI_OUT_F64 or CSI_OUT_F32)");
-        if (f.masked && (kLoc[f.field_id][0] != LOC_C || kLoc[f.field_id][1] != LOC_C))
-            return fail(c, CSI_ERR_INVALID_ARGUMENT, std::string("output: field ") + kName[f.field_id] + ": masking is for (Center, Center) fields only");
+            return fail(c, CSI_ERR_INVALID_ARGUMENT, std::string("output: field ") + slot_name(f.field_id) + ": unknown dtype (CSI_OUT_F64 or CSI_OUT_F32)");
+        if (f.masked && (slot_loc(f.field_id, 0) != LOC_C || slot_loc(f.field_id, 1) != LOC_C))
+            return fail(c, CSI_ERR_INVALID_ARGUMENT, std::string("output: field ") + slot_name(f.field_id) + ": masking is for (Center, Center) fields only");
         const Bound& b = c->f[f.field_id];
-        if (!b.p) return fail(c, CSI_ERR_NOT_BOUND, std::string("output: field ") + kName[f.field_id] + " is not bound");
+        if (!b.p) return fail(c, CSI_ERR_NOT_BOUND, std::string("output: field ") + slot_name(f.field_id) + " is not bound");
         nx[k] = b.ni - 2 * c->Hx; ny[k] = b.nj - 2 * c->Hy; dt[k] = f.dtype;
     }
     int at = -1;

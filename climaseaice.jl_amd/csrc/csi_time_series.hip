@@ -27,14 +27,6 @@
 
 namespace csi_host {
 
-static bool series_slot(int fid) {
-    for (int id : kForcingFields) if (fid == id) return true;
-    return fid == CSI_F_TOP_HEAT_FLUX || fid == CSI_F_BOTTOM_HEAT_FLUX || fid == CSI_F_SNOWFALL || fid == CSI_F_FLUX_COEFFICIENT ||
-           fid == CSI_F_FLUX_REFERENCE_TEMPERATURE || fid == CSI_F_BOTTOM_SALINITY || fid == CSI_F_ML_SURFACE_HEAT_FLUX ||
-           fid == CSI_F_ML_COEFFICIENT || fid == CSI_F_ML_REFERENCE_TEMPERATURE || fid == CSI_F_ML_DEEP_HEAT_FLUX ||
-           fid == CSI_F_SHORTWAVE;
-}
-
 static int find_series(const csi_context* c, int fid) {
     for (size_t k = 0; k < c->series.size(); ++k) if (c->series[k].fid == fid) return (int)k;
     return -1;
@@ -173,10 +165,11 @@ static int32_t upload(csi_context* c, TimeSeries& S, int slot, int slice) {
 
 // ---- what csi_time_series_set and csi_time_series_set_regridded share ------------------------------------------------------------------
 static int32_t slot_check(csi_context* c, int fid, bool setting) {
-    if (fid < 0 || fid >= CSI_F_COUNT_SHORTWAVE || !series_slot(fid))
-        return fail(c, CSI_ERR_INVALID_ARGUMENT, "time series: the slot is not one of the eleven forcing slots (stress / external-velocity arrays, model.forcing, "
-                                                 "free-drift fields, top / bottom heat flux, snowfall) nor one of the eight per-cell inputs that joined them: the LinearHeatFlux "
-                                                 "coefficient and reference temperature, the bottom salinity, the mixed layer's four inputs, the shortwave flux");
+    if (!slot_has(fid, SLOT_SERIES)) {
+        std::string names;
+        for (int id : slots_with(SLOT_SERIES)) names += std::string(names.empty() ? "" : ", ") + slot_name(id);
+        return fail(c, CSI_ERR_INVALID_ARGUMENT, "time series: the slot is not one a series may drive (" + names + ")");
+    }
     if (setting && fid == CSI_F_BOTTOM_HEAT_FLUX && c->ml_set)
         return fail(c, CSI_ERR_INVALID_ARGUMENT, "time series on bottom_heat_flux: the mixed layer (csi_mixed_layer_set) writes that array at every step");
     return CSI_OK;
@@ -209,7 +202,7 @@ static int32_t describe_series(csi_context* c, TimeSeries& S, int fid, const csi
     if (!ts->times || !ts->data) return fail(c, CSI_ERR_INVALID_ARGUMENT, "time series: times and data must not be NULL");
     if (((uintptr_t)ts->data) & 7) return fail(c, CSI_ERR_INVALID_ARGUMENT, "time series: data must be 8-byte aligned");
     if (S.ld < S.nx || S.slice_stride < S.ld * (int64_t)(S.ny - 1) + S.nx)
-        return fail(c, CSI_ERR_INVALID_ARGUMENT, std::string("time series of ") + kName[fid] + ": ld / slice_stride too small for slices of " + shape);
+        return fail(c, CSI_ERR_INVALID_ARGUMENT, std::string("time series of ") + slot_name(fid) + ": ld / slice_stride too small for slices of " + shape);
     int n1, n2;
     double frac;
     if (ts->nt < 2 || plan(ts->times, ts->nt, ts->indexing, ts->period, ts->times[0], &n1, &n2, &frac))
@@ -292,7 +285,7 @@ static int32_t series_at(csi_context* c, TimeSeries& S, double t, const double**
     double frac;
     int32_t rc;
     if ((rc = plan(S.times.data(), S.nt, S.indexing, S.period, t, &n1, &n2, &frac)))
-        return fail(c, rc, std::string("time series of ") + kName[S.fid] + ": the time is not a finite number");
+        return fail(c, rc, std::string("time series of ") + slot_name(S.fid) + ": the time is not a finite number");
     *w2 = frac; *w1 = 1.0 - frac;
     *same = n1 == n2;
     if (S.backend == CSI_SERIES_DEVICE) {
@@ -320,13 +313,13 @@ static int32_t do_series_update(csi_context* c, double t) {
         SeriesTable T{};
         for (TimeSeries& S : c->series) {
             const Bound& b = c->f[S.fid];
-            if (!b.p) return fail(c, CSI_ERR_NOT_BOUND, std::string("time series: field ") + kName[S.fid] + " is no longer bound");
+            if (!b.p) return fail(c, CSI_ERR_NOT_BOUND, std::string("time series: field ") + slot_name(S.fid) + " is no longer bound");
             SeriesDesc& D = T.d[T.n];
             D.dst = b.p + c->Hx + (int64_t)c->Hy * b.ld;
             D.ldd = (long)b.ld;
             D.nx = S.nx; D.ny = S.ny;
             if (S.backend == CSI_SERIES_HOST && (b.ld != S.ring_ld || (((uintptr_t)D.dst ^ (uintptr_t)ring_slice(S, 0)) & 15)))
-                return fail(c, CSI_ERR_INVALID_ARGUMENT, std::string("time series of ") + kName[S.fid] + ": the field was re-bound with another row stride or alignment; call csi_time_series_set again");
+                return fail(c, CSI_ERR_INVALID_ARGUMENT, std::string("time series of ") + slot_name(S.fid) + ": the field was re-bound with another row stride or alignment; call csi_time_series_set again");
             if ((rc = series_at(c, S, t, &D.a, &D.b, &D.lda, &D.w1, &D.w2, &D.same))) return rc;
             D.ldb = D.lda;
             ++T.n;
@@ -338,13 +331,13 @@ static int32_t do_series_update(csi_context* c, double t) {
         RegridTable T{};
         for (RegridSeries& R : c->regrid) {
             const Bound& b = c->f[R.fid];
-            if (!b.p) return fail(c, CSI_ERR_NOT_BOUND, std::string("time series: field ") + kName[R.fid] + " is no longer bound");
+            if (!b.p) return fail(c, CSI_ERR_NOT_BOUND, std::string("time series: field ") + slot_name(R.fid) + " is no longer bound");
             const RegridMap& M = c->maps[R.map];
             RegridDesc& D = T.d[T.n];
             D.dst = b.p + c->Hx + (int64_t)c->Hy * b.ld;
             D.ldd = (long)b.ld;
             if (b.ld != R.dst_ld || regrid_variant(D.dst, b.ld) != R.variant || b.ni - 2 * c->Hx != M.nx || b.nj - 2 * c->Hy != M.ny)
-                return fail(c, CSI_ERR_INVALID_ARGUMENT, std::string("regridded time series of ") + kName[R.fid] + ": the field was re-bound with another shape, row stride or alignment; call csi_time_series_set_regridded again");
+                return fail(c, CSI_ERR_INVALID_ARGUMENT, std::string("regridded time series of ") + slot_name(R.fid) + ": the field was re-bound with another shape, row stride or alignment; call csi_time_series_set_regridded again");
             D.nx = M.nx; D.ny = M.ny;
             D.map = M.dev[R.variant].get(); D.mld = (long)M.mld; D.plane = (long)M.plane;
             D.pair = R.parts == 2; D.component = R.component;
@@ -397,7 +390,7 @@ int32_t csi_time_series_set(csi_context* c, int32_t fid, const csi_time_series* 
     if ((rc = slot_check(c, fid, ts != nullptr)) || (rc = slot_clear(c, fid))) return rc;
     if (!ts) return CSI_OK;
     const Bound& b = c->f[fid];
-    if (!c->grid_set || !b.p) return fail(c, CSI_ERR_NOT_BOUND, std::string("time series: bind field ") + kName[fid] + " first (the series writes into the bound array)");
+    if (!c->grid_set || !b.p) return fail(c, CSI_ERR_NOT_BOUND, std::string("time series: bind field ") + slot_name(fid) + " first (the series writes into the bound array)");
     TimeSeries S;
     // the interior: field_size minus halos (a Face field on a Bounded side is one wider)
     if ((rc = describe_series(c, S, fid, ts, b.ni - 2 * c->Hx, b.nj - 2 * c->Hy, "the field's interior shape"))) return rc;
@@ -477,7 +470,7 @@ int32_t csi_regrid_map_destroy(csi_context* c, int32_t map_id) {
     if (!c) return CSI_ERR_INVALID_ARGUMENT;
     if (map_id < 0 || map_id >= (int)c->maps.size() || !c->maps[map_id].live) return fail(c, CSI_ERR_INVALID_ARGUMENT, "regrid map: unknown map");
     for (const RegridSeries& R : c->regrid)
-        if (R.map == map_id) return fail(c, CSI_ERR_INVALID_ARGUMENT, std::string("regrid map: the series of ") + kName[R.fid] + " still uses the map");
+        if (R.map == map_id) return fail(c, CSI_ERR_INVALID_ARGUMENT, std::string("regrid map: the series of ") + slot_name(R.fid) + " still uses the map");
     HIP_TRY(c, hipStreamSynchronize(c->stream));                // (a launch that read it may still run)
     c->maps[map_id] = RegridMap{};
     return CSI_OK;
@@ -491,16 +484,16 @@ int32_t csi_time_series_set_regridded(csi_context* c, int32_t fid, const csi_tim
     if (map_id < 0 || map_id >= (int)c->maps.size() || !c->maps[map_id].live) return fail(c, CSI_ERR_INVALID_ARGUMENT, "regridded time series: unknown map");
     RegridMap& M = c->maps[map_id];
     const Bound& b = c->f[fid];
-    if (!c->grid_set || !b.p) return fail(c, CSI_ERR_NOT_BOUND, std::string("time series: bind field ") + kName[fid] + " first (the series writes into the bound array)");
-    if (kLoc[fid][0] != kLoc[kLocationField[M.location]][0] || kLoc[fid][1] != kLoc[kLocationField[M.location]][1] ||
+    if (!c->grid_set || !b.p) return fail(c, CSI_ERR_NOT_BOUND, std::string("time series: bind field ") + slot_name(fid) + " first (the series writes into the bound array)");
+    if (slot_loc(fid, 0) != slot_loc(kLocationField[M.location], 0) || slot_loc(fid, 1) != slot_loc(kLocationField[M.location], 1) ||
         b.ni - 2 * c->Hx != M.nx || b.nj - 2 * c->Hy != M.ny)
-        return fail(c, CSI_ERR_INVALID_ARGUMENT, std::string("regridded time series of ") + kName[fid] + ": wrong location -- the map was made for another location (or another grid) than the slot's");
+        return fail(c, CSI_ERR_INVALID_ARGUMENT, std::string("regridded time series of ") + slot_name(fid) + ": wrong location -- the map was made for another location (or another grid) than the slot's");
     if (component != 0 && component != 1) return fail(c, CSI_ERR_INVALID_ARGUMENT, "regridded time series: component is 0 (x) or 1 (y)");
     if (!other && component != 0) return fail(c, CSI_ERR_INVALID_ARGUMENT, "regridded time series: component without other -- a scalar series has component 0");
     if (other) {
         if (!M.rotation) return fail(c, CSI_ERR_INVALID_ARGUMENT, "regridded time series: a vector pair needs a map with cos and sin");
-        if (kLoc[fid][0] != (component == 0 ? LOC_F : LOC_C) || kLoc[fid][1] != (component == 0 ? LOC_C : LOC_F))
-            return fail(c, CSI_ERR_INVALID_ARGUMENT, std::string("regridded time series of ") + kName[fid] + ": the x component of a pair drives a slot at (Face, Center), the y component one at (Center, Face)");
+        if (slot_loc(fid, 0) != (component == 0 ? LOC_F : LOC_C) || slot_loc(fid, 1) != (component == 0 ? LOC_C : LOC_F))
+            return fail(c, CSI_ERR_INVALID_ARGUMENT, std::string("regridded time series of ") + slot_name(fid) + ": the x component of a pair drives a slot at (Face, Center), the y component one at (Center, Face)");
     }
     RegridSeries R;
     R.fid = fid; R.map = map_id; R.parts = other ? 2 : 1; R.component = component;

@@ -18,7 +18,7 @@ from . import _lib
 
 DERIVED_NAMES = ("divergence", "shear", "deformation", "speed", "sigma_I", "sigma_II", "stress_power")
 STRESS_GROUP = ("sigma_I", "sigma_II", "stress_power")
-_SLOT = dict(zip(DERIVED_NAMES, _lib.DERIVED_FIELD_IDS))
+_SLOT = {n: _lib.slot_of_display_name(n) for n in DERIVED_NAMES}
 _BIT = {n: 1 << k for k, n in enumerate(DERIVED_NAMES)}
 _GROUPS = {"stress": _lib.BUDGET_STRESS, "kinetic": _lib.BUDGET_KINETIC, "all": _lib.BUDGET_ALL}
 

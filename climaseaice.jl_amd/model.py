@@ -26,18 +26,16 @@ from .grids import (METRIC_NAMES, Bounded, Center, Face, FullyConnected, LeftCon
 
 _OWN = object()      # SlabThermodynamics.params: use the object's own fluxes
 
-# the name _cell_field gives a per-cell input's field -> the slot of csi_time_series_set a FieldTimeSeries in its place drives
-_SERIES_SLOT_OF = {"top_heat_flux": "TOP_HEAT_FLUX", "bottom_heat_flux": "BOTTOM_HEAT_FLUX", "snowfall": "SNOWFALL",
-                   "flux_coefficient": "FLUX_COEFFICIENT", "flux_reference_temperature": "FLUX_REFERENCE_TEMPERATURE",
-                   "bottom_salinity": "BOTTOM_SALINITY", "ocean_surface_heat_flux": "ML_SURFACE_HEAT_FLUX",
-                   "ocean_coefficient": "ML_COEFFICIENT", "ocean_reference_temperature": "ML_REFERENCE_TEMPERATURE",
-                   "ocean_deep_heat_flux": "ML_DEEP_HEAT_FLUX"}
-_SHORTWAVE_SERIES_SLOT_OF = {"shortwave": "SHORTWAVE"}      # ... and the ShortwaveRadiation term's flux
+# the name _cell_field gives a per-cell input's field -> its series slot, for the inputs older than the shortwave flux
+_SERIES_SLOT_OF = {_lib.SLOTS[_lib.slot_id(n)][1]: n for n in _lib.SERIES_SLOTS[8:] + _lib.THERMO_SERIES_SLOTS + _lib.MIXED_LAYER_SERIES_SLOTS}
 
 
 def series_slot_of(name):
-    """The csi_time_series_set slot that a FieldTimeSeries given for the per-cell input `name` drives."""
-    return _SERIES_SLOT_OF[name] if name in _SERIES_SLOT_OF else _SHORTWAVE_SERIES_SLOT_OF[name]
+    """The csi_time_series_set slot that a FieldTimeSeries given for the per-cell input `name` drives (KeyError: none does)."""
+    slot = _lib.slot_of_display_name(name)
+    if not _lib.SLOTS[_lib.slot_id(slot)][3] & _lib.SLOT_SERIES:
+        raise KeyError(name)
+    return slot
 
 
 def _cell_shape_ok(value, grid):
@@ -471,6 +469,7 @@ class SeaIceModel:
         self.shortwave_flux = None
         self._albedo_used = None
         self._heat_fluxes_used = None
+        self._lazy_fields = {}              # slot -> the output field allocated and bound the first time it was asked for (_lazy_slot_field)
         self.ctx = _lib.Context(dev.index or 0, stream)
         self._configure()
         self._attach_pending_series()
@@ -481,6 +480,32 @@ class SeaIceModel:
     # ---- plumbing: describe the problem to the library -----------------------------------------
     def _bind(self, name, fld):
         self.ctx.call("csi_field_bind", _lib.slot_id(name), C.c_void_p(fld.data.data_ptr()), fld.ni, fld.ni, fld.nj)
+
+    def _slot_field(self, slot, value=None, name=None, bind=True):
+        """The device field of a slot, at the slot's location (_lib.SLOTS), bound to it: a Field is used in place (moved to the device if
+        needed), a FieldTimeSeries gets a new field it writes into, a number, array or function a new field set to it, None a zero field."""
+        if isinstance(value, Field):
+            fld = value
+            if fld.data.device != self.device:
+                fld.data = fld.data.to(self.device)
+        else:
+            fld = Field(_lib.slot_location(slot), self.grid, self.device, slot.lower() if name is None else name)
+            if isinstance(value, FieldTimeSeries):
+                self._pending_series.append((slot, value, fld))
+            elif value is not None:
+                fld.set(value)
+        if bind:
+            self._bind(slot, fld)
+        return fld
+
+    def _lazy_slot_field(self, slot, name):
+        """An output field the library fills once its slot is bound: allocated, bound and kept the first time it is asked for."""
+        if slot not in self._lazy_fields:
+            fld = Field(_lib.slot_location(slot), self.grid, self.device, name)
+            torch.cuda.synchronize(self.device)      # (the zero fill ran on torch's stream)
+            self._bind(slot, fld)
+            self._lazy_fields[slot] = fld
+        return self._lazy_fields[slot]
 
     def _configure(self):
         g = self.grid
@@ -549,15 +574,7 @@ class SeaIceModel:
             self.ctx.call("csi_immersed_flux_bc_set", _lib.F[name], *(imm.values() if imm is not None else (0.0, 0.0, 0.0, 0.0)))
         # model.forcing = (u = array, v = array): user forcing of the velocity tendencies (sum_of_forcing_u / _v)
         if self.forcing is not None:
-            fu, fv = self.forcing["u"], self.forcing["v"]
-            self.forcing_fields = SimpleNamespace(u=XFaceField(g, self.device, "forcing_u"), v=YFaceField(g, self.device, "forcing_v"))
-            for fld, val, slot in ((self.forcing_fields.u, fu, "FORCING_U"), (self.forcing_fields.v, fv, "FORCING_V")):
-                if isinstance(val, FieldTimeSeries):
-                    self._pending_series.append((slot, val, fld))
-                else:
-                    fld.set(val)
-            self._bind("FORCING_U", self.forcing_fields.u)
-            self._bind("FORCING_V", self.forcing_fields.v)
+            self.forcing_fields = SimpleNamespace(u=self._slot_field("FORCING_U", self.forcing["u"]), v=self._slot_field("FORCING_V", self.forcing["v"]))
             torch.cuda.synchronize(self.device)
             self.ctx.call("csi_fill_halo_local", _lib.F["FORCING_U"])
             self.ctx.call("csi_fill_halo_local", _lib.F["FORCING_V"])
@@ -618,16 +635,11 @@ class SeaIceModel:
         """A (Center, Center) field on the model grid from a CenterField (used as it is: writes into it reach the next step) or an
         (Ny, Nx) array -- on a TileGrid also one of the global grid's shape, of which the tile's part is taken."""
         g = self.grid
-        if isinstance(value, Field):
-            if value.location != (Center, Center) or (value.ni, value.nj) != tuple(g.field_size(Center, Center)):
-                raise ValueError(f"{name}: a CenterField on the model's grid is needed")
-            if value.data.device != self.device:
-                value.data = value.data.to(self.device)
-            return value
-        if isinstance(value, FieldTimeSeries):      # the series writes into a new field (bound by the caller, registered after it)
-            fld = CenterField(g, self.device, name)
-            self._pending_series.append((series_slot_of(name), value, fld))
-            return fld
+        if isinstance(value, Field) and (value.location != (Center, Center) or (value.ni, value.nj) != tuple(g.field_size(Center, Center))):
+            raise ValueError(f"{name}: a CenterField on the model's grid is needed")
+        slot = series_slot_of(name) if isinstance(value, FieldTimeSeries) else _lib.slot_of_display_name(name)
+        if isinstance(value, (Field, FieldTimeSeries)):      # (a series writes into a new field; every field is bound by the caller)
+            return self._slot_field(slot, value, name, bind=False)
         arr = np.asarray(value, dtype=np.float64)
         if arr.ndim == 0:                           # a number beside a per-cell partner (LinearHeatFlux): broadcast
             arr = np.full((g.Ny, g.Nx), float(arr))
@@ -635,9 +647,7 @@ class SeaIceModel:
             arr = arr[g.j_off:g.j_off + g.Ny, g.i_off:g.i_off + g.Nx]
         if arr.shape != (g.Ny, g.Nx):
             raise ValueError(f"{name}: an array of shape (Ny, Nx) = {(g.Ny, g.Nx)} is needed, got {arr.shape}")
-        fld = CenterField(g, self.device, name)
-        fld.set(arr)
-        return fld
+        return self._slot_field(slot, arr, name, bind=False)
 
     def _heat_terms(self, spec, side):
         """getflux's forms (boundary_fluxes.jl:8-22, 98-127) as csi_heat_flux_term entries: None for the numeric path (None, a
@@ -771,19 +781,7 @@ class SeaIceModel:
 
     def _stress_field(self, slot, comp, value):
         """materialize_stress (sea_ice_external_stress.jl:63-69,132-137): a device copy on the model grid."""
-        mk = XFaceField if comp == "U" else YFaceField
-        if isinstance(value, Field):
-            fld = value
-            if fld.data.device != self.device:
-                fld.data = fld.data.to(self.device)
-        elif isinstance(value, FieldTimeSeries):
-            fld = mk(self.grid, self.device, f"{slot}_{comp}".lower())
-            self._pending_series.append((f"{slot}_{comp}", value, fld))
-        else:
-            fld = mk(self.grid, self.device, f"{slot}_{comp}".lower())
-            fld.set(value)
-        self._stress_fields[f"{slot}_{comp}"] = fld
-        self._bind(f"{slot}_{comp}", fld)
+        fld = self._stress_fields[f"{slot}_{comp}"] = self._slot_field(f"{slot}_{comp}", value)
         return fld
 
     def _set_stress(self, side, stress, slot):
@@ -822,12 +820,8 @@ class SeaIceModel:
         if self.ice_thermodynamics is None:
             raise ValueError("heat_fluxes_used needs ice_thermodynamics")
         if self._heat_fluxes_used is None:
-            top = CenterField(self.grid, self.device, "top_heat_flux_used")
-            bottom = CenterField(self.grid, self.device, "bottom_heat_flux_used")
-            torch.cuda.synchronize(self.device)      # (the zero fill ran on torch's stream)
-            self._bind("TOP_HEAT_FLUX_USED", top)
-            self._bind("BOTTOM_HEAT_FLUX_USED", bottom)
-            self._heat_fluxes_used = SimpleNamespace(top=top, bottom=bottom)
+            self._heat_fluxes_used = SimpleNamespace(top=self._lazy_slot_field("TOP_HEAT_FLUX_USED", "top_heat_flux_used"),
+                                                     bottom=self._lazy_slot_field("BOTTOM_HEAT_FLUX_USED", "bottom_heat_flux_used"))
         return self._heat_fluxes_used
 
     @property
@@ -837,11 +831,7 @@ class SeaIceModel:
         (synchronize() first); in an RK3 step it holds the last stage's values."""
         if self.shortwave is None:
             raise ValueError("albedo_used needs a ShortwaveRadiation term in top_heat_flux")
-        if self._albedo_used is None:
-            fld = CenterField(self.grid, self.device, "albedo_used")
-            torch.cuda.synchronize(self.device)      # (the zero fill ran on torch's stream)
-            self._bind("ALBEDO_USED", fld)
-            self._albedo_used = fld
+        self._albedo_used = self._lazy_slot_field("ALBEDO_USED", "albedo_used")
         return self._albedo_used
 
     def external_stress_field(self, slot, comp):
@@ -850,19 +840,7 @@ class SeaIceModel:
     def _free_drift_field(self, comp, value):
         """One component of `free_drift = (u, v)` on the device, like _stress_field: a field of the grid is used as it is, a number or
         an interior-shaped array fills a new one.  The library fills the halos at every momentum step."""
-        mk = XFaceField if comp == "U" else YFaceField
-        if isinstance(value, Field):
-            fld = value
-            if fld.data.device != self.device:
-                fld.data = fld.data.to(self.device)
-        elif isinstance(value, FieldTimeSeries):
-            fld = mk(self.grid, self.device, f"free_drift_{comp}".lower())
-            self._pending_series.append((f"FREE_DRIFT_{comp}", value, fld))
-        else:
-            fld = mk(self.grid, self.device, f"free_drift_{comp}".lower())
-            fld.set(value)
-        self._free_drift_fields[comp] = fld
-        self._bind(f"FREE_DRIFT_{comp}", fld)
+        fld = self._free_drift_fields[comp] = self._slot_field(f"FREE_DRIFT_{comp}", value)
         return fld
 
     def free_drift_field(self, comp):
@@ -1040,13 +1018,8 @@ class SeaIceModel:
         """The (Center, Center) field of a derived quantity -- "divergence", "shear", "deformation", "speed", "sigma_I", "sigma_II",
         "stress_power" --, allocated and bound to its slot the first time it is asked for.  compute_derived fills its interior."""
         from .derived import slot_of
-        if name not in self._derived_fields:
-            slot = slot_of(name)
-            fld = CenterField(self.grid, self.device, name)
-            torch.cuda.synchronize(self.device)      # (the zero fill ran on torch's stream)
-            self._bind(slot, fld)
-            self._derived_fields[name] = fld
-        return self._derived_fields[name]
+        fld = self._derived_fields[name] = self._lazy_slot_field(slot_of(name), name)
+        return fld
 
     def compute_derived(self, *names):
         """Fill the named derived fields from the current state, all in ONE launch on the library's stream (no copy, no wait: an
@@ -1070,14 +1043,9 @@ class SeaIceModel:
         """The field of one component of a momentum balance term -- "coriolis_x", "top_y", "bottom_x", "internal_y", "forcing_x", ...: a
         force per unit area at the u (_x) or v (_y) points --, allocated and bound to its slot the first time it is asked for.
         compute_momentum_terms fills its interior."""
-        from .momentum_terms import location_of, slot_of
-        if name not in self._momentum_term_fields:
-            slot = slot_of(name)
-            fld = Field(location_of(name), self.grid, self.device, name)
-            torch.cuda.synchronize(self.device)      # (the zero fill ran on torch's stream)
-            self._bind(slot, fld)
-            self._momentum_term_fields[name] = fld
-        return self._momentum_term_fields[name]
+        from .momentum_terms import slot_of
+        fld = self._momentum_term_fields[name] = self._lazy_slot_field(slot_of(name), name)
+        return fld
 
     def compute_momentum_terms(self, *names):
         """Fill the named term fields from the current state, all in ONE launch on the library's stream (no copy, no wait;

@@ -19,11 +19,10 @@ import math
 from dataclasses import dataclass
 
 from . import _lib
-from .grids import Center, Face
 
 MOMENTUM_TERMS = ("coriolis", "top", "bottom", "internal", "forcing")
 TERM_FIELD_NAMES = tuple(f"{t}_{c}" for t in MOMENTUM_TERMS for c in ("x", "y"))
-_SLOT = dict(zip(TERM_FIELD_NAMES, _lib.MOMENTUM_TERM_FIELD_IDS))
+_SLOT = {n: _lib.slot_of_display_name(n) for n in TERM_FIELD_NAMES}
 _BIT = {t: 1 << k for k, t in enumerate(MOMENTUM_TERMS)}
 _GROUPS = {"external": _lib.MBUDGET_EXTERNAL, "body": _lib.MBUDGET_BODY, "internal": _lib.MBUDGET_INTERNAL, "all": _lib.MBUDGET_ALL}
 _GROUP_MEMBERS = (("external", ("top", "bottom")), ("body", ("coriolis", "forcing")), ("internal", ("internal",)))
@@ -38,8 +37,7 @@ def slot_of(name):
 
 def location_of(name):
     """(Face, Center) for an _x field, (Center, Face) for an _y field."""
-    slot_of(name)
-    return (Face, Center) if name.endswith("_x") else (Center, Face)
+    return _lib.slot_location(slot_of(name))
 
 
 def name_of_slot(slot):

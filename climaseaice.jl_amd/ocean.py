@@ -6,7 +6,6 @@ definition, csrc/mixed_layer.hip the kernel.  This module only describes the lay
 import ctypes as C
 
 import numpy as np
-import torch
 
 from . import _lib
 from .fields import CenterField, Field
@@ -159,12 +158,7 @@ class SlabOceanMixedLayer:
         Allocated and bound the first time it is asked for.  Read it after the step (synchronize() first)."""
         if self._model is None:
             raise ValueError("surface_flux_used needs a model: SeaIceModel(grid, ..., ocean=this)")
-        if self._surface_flux_used is None:
-            m = self._model
-            fld = CenterField(m.grid, m.device, "ocean_surface_flux_used")
-            torch.cuda.synchronize(m.device)      # (the zero fill ran on torch's stream)
-            m._bind("ML_SURFACE_FLUX_USED", fld)
-            self._surface_flux_used = fld
+        self._surface_flux_used = self._model._lazy_slot_field("ML_SURFACE_FLUX_USED", "ocean_surface_flux_used")
         return self._surface_flux_used
 
     def state_fields(self):

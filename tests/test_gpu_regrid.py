@@ -293,7 +293,7 @@ def test_abi_refusals():
         set_("TOP_U", st, rot_map, st, 1)
     with pytest.raises(csi.CsiError, match="ts must not be NULL"):
         set_("TOP_U", None, fc_map)
-    with pytest.raises(csi.CsiError, match="eleven forcing slots"):
+    with pytest.raises(csi.CsiError, match="not one a series may drive"):
         set_("H", st, fc_map)
     small = d.series([0.0, 1.0], data[:, :3, :], L.TIME_CLAMP)            # slices smaller than the map's source
     small.slice_stride = 3 * src.shape[1] - 1
