@@ -359,8 +359,8 @@ constexpr int TX = CSI_ADV_TX, TY2 = CSI_ADV_TY, TY3 = 4;      // rows of a flux
 // the tracers used to share a thread -- four WENO7 reconstructions behind 28 dependent loads; at 512^2 the launch lasts as long
 // as one block, so halving the chain per thread is what shortens it.)
 // store_with_images for a tracer on a grid with N >= 2 H and no fold: a cell is within H of at most one side per direction, so it
-// has at most one x image, one y image and their corner -- scalars instead of store_with_images' index lists (which live in
-// scratch memory: inside the tendency kernel they cost more than the separate update launch they were meant to save)
+// has at most one x image, one y image and their corner -- scalars instead of store_with_images' four slots (a specialisation
+// under that precondition, kept because it sits in the advection hot loop)
 __device__ __forceinline__ void store_tracer_images(const FRef& f, const GridDev& g, const ImageSpec& im, int i, int j, double val) {
     f(i, j) = val;
     int ix = 0, jy = 0;

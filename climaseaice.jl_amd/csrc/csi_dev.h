@@ -200,9 +200,11 @@ __device__ __forceinline__ int image_hi(int mode, int i, int N, int H, bool& has
     if (mode == IMG_VALUE) { has = (i == N); return N + 1; }
     has = false; return 0;
 }
-// (momentum_free_drift.hip store_point_and_images restates these stores with fixed image slots instead of the run-time lists below,
-//  which live in scratch memory: a change of the image semantics here has to be made there too.  tests/test_gpu_free_drift.py compares
-//  that kernel's parents, halos included, with the oracle's fills on every topology.)
+// The store rule, stated once for every kernel that stores a prognostic field: the point, its north-fold image, its x images, its
+// y images and their corners.  A point has at most one image per side (csi_core.hip checks the grid is wide enough), so the images
+// sit in four fixed slots -- x low, x high, y low, y high -- and nothing is indexed at run time: the rule needs no scratch memory.
+// An IMG_VALUE side reflects what it copies about twice its value, x before y.
+__device__ __forceinline__ double image_value(int mode, double bc, double w) { return mode == IMG_VALUE ? 2 * bc - w : w; }
 __device__ __forceinline__ void store_with_images(const FRef& f, const GridDev& g, const ImageSpec& im, int i, int j, double val) {
     f(i, j) = val;
     // Elements within H of an edge have halo images; the test is cheap and almost always false.
@@ -228,30 +230,21 @@ __device__ __forceinline__ void store_with_images(const FRef& f, const GridDev& 
             if (it > g.Nx - g.Hx) f(it - g.Nx, jt) = w;
         }
     }
-    int xi[3], yj[3];
-    double cx[3], cy[3];          // image value = c - val (c = 2 * bc value on an IMG_VALUE side), or val itself (c = NaN marker unused)
-    bool fx[3], fy[3];            // the image is a ValueBoundaryCondition reflection
-    int nx = 0, ny = 0;
-    xi[nx] = i; fx[nx] = false; cx[nx++] = 0.0;
-    yj[ny] = j; fy[ny] = false; cy[ny++] = 0.0;
-    bool has;
-    int t;
-    if (in_x) {
-        t = image_lo(im.xlo, i, g.Nx, g.Hx, has); if (has) { xi[nx] = t; fx[nx] = im.xlo == IMG_VALUE; cx[nx++] = 2 * im.vxlo; }
-        t = image_hi(im.xhi, i, g.Nx, g.Hx, has); if (has) { xi[nx] = t; fx[nx] = im.xhi == IMG_VALUE; cx[nx++] = 2 * im.vxhi; }
-    }
-    if (in_y) {
-        t = image_lo(im.ylo, j, g.Ny, g.Hy, has); if (has) { yj[ny] = t; fy[ny] = im.ylo == IMG_VALUE; cy[ny++] = 2 * im.vylo; }
-        t = image_hi(im.yhi, j, g.Ny, g.Hy, has); if (has) { yj[ny] = t; fy[ny] = im.yhi == IMG_VALUE; cy[ny++] = 2 * im.vyhi; }
-    }
-    for (int b = 0; b < ny; ++b)
-        for (int a = 0; a < nx; ++a)
-            if (a | b) {
-                double w = val;
-                if (fx[a]) w = cx[a] - w;
-                if (fy[b]) w = cy[b] - w;
-                f(xi[a], yj[b]) = w;
-            }
+    bool hxl, hxh, hyl, hyh;
+    const int xl = image_lo(im.xlo, i, g.Nx, g.Hx, hxl), xh = image_hi(im.xhi, i, g.Nx, g.Hx, hxh);
+    const int yl = image_lo(im.ylo, j, g.Ny, g.Hy, hyl), yh = image_hi(im.yhi, j, g.Ny, g.Hy, hyh);
+    hxl &= in_x; hxh &= in_x; hyl &= in_y; hyh &= in_y;
+    const double wl = image_value(im.xlo, im.vxlo, val), wh = image_value(im.xhi, im.vxhi, val);
+    if (hxl) f(xl, j) = wl;
+    if (hxh) f(xh, j) = wh;
+    // a y image of the point, and of its x images: the corners
+    auto row = [&](int mode, double bc, int y) {
+        f(i, y) = image_value(mode, bc, val);
+        if (hxl) f(xl, y) = image_value(mode, bc, wl);
+        if (hxh) f(xh, y) = image_value(mode, bc, wh);
+    };
+    if (hyl) row(im.ylo, im.vylo, yl);
+    if (hyh) row(im.yhi, im.vyhi, yh);
 }
 
 }  // namespace csi

@@ -5,6 +5,15 @@
 
 namespace csi {
 
+// one thread per point of a Range in blocks of b: the thread's (i, j), and the grid that covers the range
+#define CELL_OF_RANGE(r)                                                   \
+    const int i = (r).i0 + (int)(blockIdx.x * blockDim.x + threadIdx.x);   \
+    const int j = (r).j0 + (int)(blockIdx.y * blockDim.y + threadIdx.y);   \
+    if (i > (r).i1 || j > (r).j1) return;
+static inline dim3 grid_for(const Range& r, dim3 b) {
+    return dim3((unsigned)((r.i1 - r.i0 + 1 + b.x - 1) / b.x), (unsigned)((r.j1 - r.j0 + 1 + b.y - 1) / b.y), 1);
+}
+
 // STRICT mode: one kernel per reference @kernel (evp_strict.hip)
 void launch_strict_init(const EvpDev& P, const Range& r, hipStream_t s);
 void launch_strict_visc(const EvpDev& P, const Range& r, hipStream_t s);
@@ -12,7 +21,7 @@ void launch_strict_stress(const EvpDev& P, const Range& r, hipStream_t s);
 void launch_strict_ustep(const EvpDev& P, const Range& r, const ImageSpec& im, hipStream_t s);
 void launch_strict_vstep(const EvpDev& P, const Range& r, const ImageSpec& im, hipStream_t s);
 
-// free-drift velocities of marginal ice (StressBalanceFreeDrift), once per sub-cycle, both modes (evp_strict.hip)
+// free-drift velocities of marginal ice (StressBalanceFreeDrift), once per sub-cycle, both modes (momentum_free_drift.hip)
 void launch_free_drift(const EvpDev& P, const Range& r, hipStream_t s);
 // StressBalanceFreeDrift as the model's dynamics (momentum_free_drift.hip): u and v over r, each with its halo images, in one launch
 void launch_free_drift_step(const EvpDev& P, const Range& r, const ImageSpec& imu, const ImageSpec& imv, hipStream_t s);

@@ -1,7 +1,8 @@
 // derived_dev.h -- the reference's strict-order operators, stated ONCE for every kernel that evaluates them on fields: the strain rates
 // (elasto_visco_plastic_rheology.jl:360-375), the four-point interpolations, the masked stress accessors and the stress divergence
-// (ice_stress_divergence.jl:16-51).  Users: the STRICT stepping kernels (evp_strict.hip), the derived-field and energy-budget kernels
-// (derived.hip, budget.hip) and, for the divergence arithmetic on gathered values, momentum_dev.h div1 / div2.
+// (ice_stress_divergence.jl:16-51).  Users: the STRICT viscosity and stress kernels (evp_strict.hip k_visc, k_stress), the derived-field and
+// energy-budget kernels (derived.hip, budget.hip) and, for the divergence arithmetic on gathered values, momentum_dev.h div1 / div2
+// (every point-wise velocity step, the STRICT EVP ones included).
 //
 // Every operator takes the bare grid and field references and the metric kind as a template parameter: MK = 0 uniform (two numbers),
 // 1 per row (vectors indexed by j), 2 per point (twelve planes) -- decided when the kernel is chosen (derived.hip, budget.hip) -- or

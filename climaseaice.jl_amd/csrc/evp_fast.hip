@@ -625,10 +625,6 @@ __global__ void __launch_bounds__(64) k_band_vel(EvpDev P, Range r, ImageSpec im
 
 }  // namespace fast
 
-static inline dim3 grid_for(const Range& r, dim3 b) {
-    return dim3((unsigned)((r.i1 - r.i0 + 1 + b.x - 1) / b.x), (unsigned)((r.j1 - r.j0 + 1 + b.y - 1) / b.y), 1);
-}
-
 // cross component of an array-valued external velocity averaged to the velocity points (what stress_x / stress_y
 // compute per call): vbar at u points from fv, ubar at v points from fu; same avg4, so the values are identical
 __global__ void __launch_bounds__(256) k_forcing_bars(FRef fu, FRef fv, FRef ubar_v, FRef vbar_u, int has_u, int has_v, Range r) {

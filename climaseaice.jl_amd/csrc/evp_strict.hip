@@ -9,14 +9,13 @@
 //   k_stress    _compute_evp_stresses!     :294-354 (+ ice_pressure :282-289)
 //   k_ustep     _u_velocity_step!          SeaIceDynamics/split_explicit_momentum_equations.jl:197-229
 //   k_vstep     _v_velocity_step!          :231-264
-// with u/v_velocity_tendency (momentum_tendencies_kernel_functions.jl:11-74), the stress
-// divergence (Rheologies/ice_stress_divergence.jl:16-51) and the external stresses
-// (sea_ice_external_stress.jl:8-27,176-202) inlined.  The strain rates, the four-point interpolations and the stress divergence
-// are derived_dev.h's, with the metric kind decided at run time (dv::MK_RUNTIME).  The local halo fill that follows each
-// velocity kernel in the reference (:180-187) is fused into the store (store_with_images).
-#include "csi_dev.h"
+// The strain rates and the four-point interpolations of k_visc / k_stress are derived_dev.h's, with the metric kind decided at run
+// time (dv::MK_RUNTIME).  The velocity steps are momentum_dev.h's point-wise sub-step -- gather, u/v_velocity_tendency
+// (momentum_tendencies_kernel_functions.jl:11-74) on the stored stresses, implicit coefficient, closing part -- instantiated with
+// strict arithmetic; the local halo fill that follows each of them in the reference (:180-187) is fused into the store
+// (store_with_images).  The free-drift velocities of marginal ice are momentum_free_drift.hip's.
 #include "csi_kernels.h"
-#include "derived_dev.h"
+#include "momentum_dev.h"
 
 namespace csi {
 namespace strict {
@@ -38,20 +37,15 @@ __device__ __forceinline__ double exx(const EvpDev& P, int i, int j) { return e_
 __device__ __forceinline__ double eyy(const EvpDev& P, int i, int j) { return e_yy<MK>(P.g, P.u, P.v, i, j); }
 __device__ __forceinline__ double exy(const EvpDev& P, int i, int j) { return e_xy<MK>(P.g, P.u, P.v, i, j); }
 
-#define CELL_IJ(r)                                              \
-    const int i = (r).i0 + (int)(blockIdx.x * blockDim.x + threadIdx.x); \
-    const int j = (r).j0 + (int)(blockIdx.y * blockDim.y + threadIdx.y); \
-    if (i > (r).i1 || j > (r).j1) return;
-
 __global__ void k_init(EvpDev P, Range r, FRef un, FRef vn) {
-    CELL_IJ(r)
+    CELL_OF_RANGE(r)
     P.P(i, j) = P.P_star * P.h(i, j) * exp(-P.C_star * (1 - P.a(i, j)));   // ice_strength :219
     un(i, j) = P.u(i, j);
     vn(i, j) = P.v(i, j);
 }
 
 __global__ void k_visc(EvpDev P, Range r) {
-    CELL_IJ(r)
+    CELL_OF_RANGE(r)
     const double ie = 1.0 / P.ecc;
     const double em2 = ie * ie;
     const double Dm = P.Dmin;
@@ -77,7 +71,7 @@ __global__ void k_visc(EvpDev P, Range r) {
 __device__ __forceinline__ double clampd(double x, double lo, double hi) { return x > hi ? hi : (x < lo ? lo : x); }
 
 __global__ void k_stress(EvpDev P, Range r) {
-    CELL_IJ(r)
+    CELL_OF_RANGE(r)
     const GridDev& g = P.g;
     const double ie = 1.0 / P.ecc;
     const double em2 = ie * ie;
@@ -116,152 +110,34 @@ __global__ void k_stress(EvpDev P, Range r) {
     P.al(i, j) = gc;
 }
 
-// ---- external stresses, sea_ice_external_stress.jl:8-27,176-202 ------------------------------
-__device__ __forceinline__ double ext_ue(const StressDev& s, int i, int j) {
-    return s.ue_kind == 2 ? s.fu(i, j) : (s.ue_kind == 1 ? s.ue : 0.0);
-}
-__device__ __forceinline__ double ext_ve(const StressDev& s, int i, int j) {
-    return s.ve_kind == 2 ? s.fv(i, j) : (s.ve_kind == 1 ? s.ve : 0.0);
-}
-
-__device__ __forceinline__ double drag_norm_u(const EvpDev& P, const StressDev& s, int i, int j) {
-    double du = ext_ue(s, i, j) - P.u(i, j);
-    double dv = avg4_fc([&](int ii, int jj) { return ext_ve(s, ii, jj); }, i, j) - avg4_fc(P.v, i, j);
-    return sqrt(du * du + dv * dv);
-}
-__device__ __forceinline__ double drag_norm_v(const EvpDev& P, const StressDev& s, int i, int j) {
-    double dv = ext_ve(s, i, j) - P.v(i, j);
-    double du = avg4_cf([&](int ii, int jj) { return ext_ue(s, ii, jj); }, i, j) - avg4_cf(P.u, i, j);
-    return sqrt(du * du + dv * dv);
-}
-__device__ __forceinline__ double explicit_tau_x(const EvpDev& P, const StressDev& s, int i, int j) {
-    switch (s.kind) {
-        case 1: return s.tau_u;
-        case 2: return s.fu(i, j);
-        case 3: return s.rho_e * s.Cd * drag_norm_u(P, s, i, j) * ext_ue(s, i, j);
-        default: return 0.0;
-    }
-}
-__device__ __forceinline__ double explicit_tau_y(const EvpDev& P, const StressDev& s, int i, int j) {
-    switch (s.kind) {
-        case 1: return s.tau_v;
-        case 2: return s.fv(i, j);
-        case 3: return s.rho_e * s.Cd * drag_norm_v(P, s, i, j) * ext_ve(s, i, j);
-        default: return 0.0;
-    }
-}
-// ---- StressBalanceFreeDrift closed forms, stress_balance_free_drift.jl:61-129 --------------------------------
-// exactly one stress is a SemiImplicitStress (checked on the host); the other one gives tau.  The result depends on
-// the forcing only, so it is evaluated once per sub-cycle into ufd / vfd (strict arithmetic in both modes).
-__device__ __forceinline__ double free_drift_u(const EvpDev& P, int i, int j) {
-    const StressDev& semi = P.bot.kind == 3 ? P.bot : P.top;
-    const StressDev& expl = P.bot.kind == 3 ? P.top : P.bot;
-    const double tx = explicit_tau_x(P, expl, i, j);
-    const double ty = avg4_fc([&](int ii, int jj) { return explicit_tau_y(P, expl, ii, jj); }, i, j);
-    return stress_balance_velocity(ext_ue(semi, i, j), tx, tx, ty, semi.rho_e * semi.Cd);
-}
-__device__ __forceinline__ double free_drift_v(const EvpDev& P, int i, int j) {
-    const StressDev& semi = P.bot.kind == 3 ? P.bot : P.top;
-    const StressDev& expl = P.bot.kind == 3 ? P.top : P.bot;
-    const double tx = avg4_cf([&](int ii, int jj) { return explicit_tau_x(P, expl, ii, jj); }, i, j);
-    const double ty = explicit_tau_y(P, expl, i, j);
-    return stress_balance_velocity(ext_ve(semi, i, j), ty, tx, ty, semi.rho_e * semi.Cd);
+// ---- the velocity steps: momentum_dev.h's point-wise sub-step with strict arithmetic on the stored stresses (FAST = false,
+// VISC = false), stored in place.  dtau = dt / Ix(alpha), also the Delta t of sum_of_forcing (evp:391-401)
+__global__ void __launch_bounds__(256) k_ustep(EvpDev P, Range r, ImageSpec im) {
+    CELL_OF_RANGE(r)
+    mom::UPoint q;
+    mom::gather_u<false>(P, P.u, P.v, i, j, q);
+    const double dtau = P.dt / ((q.alw + q.ale) / 2);
+    double mi, ai;
+    const double G = mom::u_tendency<false, false>(P, 0.0, q, i, j, dtau, mi, ai);
+    const double tau_i = mom::implicit_coef<false>(P, q.top, q.bot, q.uc, q.v4, mi, ai);
+    const bool peripheral = q.c.inact[3] | q.c.inact[2];               // peripheral_node (f, c, c): cells (i, j), (i - 1, j)
+    store_with_images(P.u, P.g, im, i, j, mom::close_substep<false, true>(P, q.uc, G, tau_i, dtau, q.fd, mi, ai, peripheral));
 }
 
-__device__ __forceinline__ double implicit_tau_x(const EvpDev& P, const StressDev& s, int i, int j) {
-    return s.kind == 3 ? s.rho_e * s.Cd * drag_norm_u(P, s, i, j) : 0.0;
-}
-__device__ __forceinline__ double implicit_tau_y(const EvpDev& P, const StressDev& s, int i, int j) {
-    return s.kind == 3 ? s.rho_e * s.Cd * drag_norm_v(P, s, i, j) : 0.0;
-}
-
-#define EPS64 2.220446049250313e-16
-
-__global__ void k_ustep(EvpDev P, Range r, ImageSpec im) {
-    CELL_IJ(r)
-    const double dt = P.dt;
-    double mi = (ice_mass(P, i - 1, j) + ice_mass(P, i, j)) / 2;
-    double ai = (P.a(i - 1, j) + P.a(i, j)) / 2;
-    double abar = (P.al(i - 1, j) + P.al(i, j)) / 2;
-    double dtau = dt / abar;
-    // u_velocity_tendency, momentum_tendencies_kernel_functions.jl:11-41
-    double cor = 0.0;
-    if (P.has_cor) {
-        cor = -fcor_at_u(P, i, j) * avg4_fc(P.v, i, j);     // FPlane / BetaPlane (f at this row's u points) / per-point f
-    }
-    const double user = P.has_forcing ? P.forcing_u(i, j) : 0.0;    // model.forcing.u as an array
-    double forcing = user + (P.un(i, j) - P.u(i, j)) / dtau / abar;  // sum_of_forcing_u, evp:391-395
-    double imm = immersed_div_sigma_1(P, i, j) / mi;                  // zero(grid) / FluxBoundaryCondition numbers, isd:57-85
-    double G = (-cor
-                - explicit_tau_x(P, P.top, i, j) / mi * ai
-                + explicit_tau_x(P, P.bot, i, j) / mi * ai
-                + div_sigma_1<MK>(P.g, Sigma{P.s11, P.s22, P.s12}, i, j) / mi
-                + imm
-                + forcing);
-    G = (mi <= 0) ? 0.0 : G;
-    double tau_i = (implicit_tau_x(P, P.bot, i, j) - implicit_tau_x(P, P.top, i, j)) / mi * ai;
-    tau_i = (mi <= 0) ? 0.0 : tau_i;
-    double uD = (P.u(i, j) + dtau * G) / (1 + dtau * tau_i);
-    double uF = P.free_drift ? P.ufd(i, j) : 0.0;                       // free_drift_u, :219
-    bool marginal = (mi > EPS64) & (ai > EPS64);
-    bool active_ice = (mi >= P.min_mass) & (ai >= P.min_conc);
-    // `... * active` with a Julia Bool: false is a strong zero (sign kept), :228
-    double sel = active_ice ? uD : (marginal ? uF : 0.0);
-    double res = peripheral_u(P.g, i, j) ? copysign(0.0, sel) : sel;
-    store_with_images(P.u, P.g, im, i, j, res);
-}
-
-__global__ void k_vstep(EvpDev P, Range r, ImageSpec im) {
-    CELL_IJ(r)
-    const double dt = P.dt;
-    double mi = (ice_mass(P, i, j - 1) + ice_mass(P, i, j)) / 2;
-    double ai = (P.a(i, j - 1) + P.a(i, j)) / 2;
-    double abar = (P.al(i, j - 1) + P.al(i, j)) / 2;
-    double dtau = dt / abar;
-    double cor = 0.0;
-    if (P.has_cor) {
-        cor = fcor_at_v(P, i, j) * avg4_cf(P.u, i, j);
-    }
-    const double user = P.has_forcing ? P.forcing_v(i, j) : 0.0;
-    double forcing = user + (P.vn(i, j) - P.v(i, j)) / dtau / abar;
-    double imm = immersed_div_sigma_2(P, i, j) / mi;
-    double G = (-cor
-                - explicit_tau_y(P, P.top, i, j) / mi * ai
-                + explicit_tau_y(P, P.bot, i, j) / mi * ai
-                + div_sigma_2<MK>(P.g, Sigma{P.s11, P.s22, P.s12}, i, j) / mi
-                + imm
-                + forcing);
-    G = (mi <= 0) ? 0.0 : G;
-    double tau_i = (implicit_tau_y(P, P.bot, i, j) - implicit_tau_y(P, P.top, i, j)) / mi * ai;
-    tau_i = (mi <= 0) ? 0.0 : tau_i;
-    double vD = (P.v(i, j) + dtau * G) / (1 + dtau * tau_i);
-    double vF = P.free_drift ? P.vfd(i, j) : 0.0;
-    bool marginal = (mi > EPS64) & (ai > EPS64);
-    bool active_ice = (mi >= P.min_mass) & (ai >= P.min_conc);
-    double sel = active_ice ? vD : (marginal ? vF : 0.0);
-    double res = peripheral_v(P.g, i, j) ? copysign(0.0, sel) : sel;
-    store_with_images(P.v, P.g, im, i, j, res);
+__global__ void __launch_bounds__(256) k_vstep(EvpDev P, Range r, ImageSpec im) {
+    CELL_OF_RANGE(r)
+    mom::VPoint q;
+    mom::gather_v<false>(P, P.u, P.v, i, j, q);
+    const double dtau = P.dt / ((q.als + q.aln) / 2);
+    double mi, ai;
+    const double G = mom::v_tendency<false, false>(P, 0.0, q, i, j, dtau, mi, ai);
+    const double tau_i = mom::implicit_coef<false>(P, q.top, q.bot, q.vc, q.u4, mi, ai);
+    const bool peripheral = q.c.inact[4] | q.c.inact[1];               // peripheral_node (c, f, c): cells (i, j), (i, j - 1)
+    store_with_images(P.v, P.g, im, i, j, mom::close_substep<false, true>(P, q.vc, G, tau_i, dtau, q.fd, mi, ai, peripheral));
 }
 
 }  // namespace strict
 
-static inline dim3 grid_for(const Range& r, dim3 b) {
-    return dim3((unsigned)((r.i1 - r.i0 + 1 + b.x - 1) / b.x), (unsigned)((r.j1 - r.j0 + 1 + b.y - 1) / b.y), 1);
-}
-
-namespace strict {
-__global__ void __launch_bounds__(256) k_free_drift(EvpDev P, Range r) {
-    const int i = r.i0 + (int)(blockIdx.x * blockDim.x + threadIdx.x), j = r.j0 + (int)(blockIdx.y * blockDim.y + threadIdx.y);
-    if (i > r.i1 || j > r.j1) return;
-    P.ufd(i, j) = free_drift_u(P, i, j);
-    P.vfd(i, j) = free_drift_v(P, i, j);
-}
-}  // namespace strict
-
-void launch_free_drift(const EvpDev& P, const Range& r, hipStream_t s) {
-    dim3 b(64, 4);
-    hipLaunchKernelGGL(strict::k_free_drift, grid_for(r, b), b, 0, s, P, r);
-}
 void launch_strict_init(const EvpDev& P, const Range& r, hipStream_t s) {
     dim3 b(64, 4);
     hipLaunchKernelGGL(strict::k_init, grid_for(r, b), b, 0, s, P, r, P.un, P.vn);

@@ -1,5 +1,6 @@
-// momentum_dev.h -- the velocity tendencies of ViscousRheology and of the ExplicitSolver (momentum_viscous.hip,
-// momentum_explicit.hip).  gfx950 only.
+// momentum_dev.h -- the point-wise velocity sub-step: the tendencies and the closing part.  Users: the STRICT EVP velocity steps
+// (evp_strict.hip, FAST = false, VISC = false), ViscousRheology (momentum_viscous.hip), the ExplicitSolver (momentum_explicit.hip),
+// the momentum balance terms (momentum_terms.hip, the front half) and, for the gather helpers, momentum_free_drift.hip.  gfx950 only.
 //
 //   u_velocity_tendency / v_velocity_tendency   SeaIceDynamics/momentum_tendencies_kernel_functions.jl:11-74
 //   ViscousRheology stresses                    Rheologies/viscous_rheology.jl:15-22 (nu a Number)
@@ -205,10 +206,12 @@ struct VPoint {
     Cells c;                            // cells (i-1..i+1) x (j-1..j)
 };
 
-// U: the u array the point reads (the launch's input), V: the current v
+// U: the u array the point reads (the launch's input), V: the current v.  Only the viscous stencil reads the own component at the
+// four neighbours: the EVP steps store in place, and those are cells that other threads are writing
 template <bool VISC>
 __device__ __forceinline__ void gather_u(const EvpDev& P, const FRef& U, const FRef& V, int i, int j, UPoint& q) {
-    q.uc = U(i, j); q.uw = U(i - 1, j); q.ue = U(i + 1, j); q.us = U(i, j - 1); q.un = U(i, j + 1);
+    q.uc = U(i, j);
+    if (VISC) { q.uw = U(i - 1, j); q.ue = U(i + 1, j); q.us = U(i, j - 1); q.un = U(i, j + 1); }
     q.v4[0] = V(i - 1, j); q.v4[1] = V(i, j); q.v4[2] = V(i - 1, j + 1); q.v4[3] = V(i, j + 1);
     q.hw = P.h(i - 1, j); q.he = P.h(i, j); q.aw = P.a(i - 1, j); q.ae = P.a(i, j);
     if (!VISC) {
@@ -232,7 +235,8 @@ __device__ __forceinline__ void gather_u(const EvpDev& P, const FRef& U, const F
 }
 template <bool VISC>
 __device__ __forceinline__ void gather_v(const EvpDev& P, const FRef& U, const FRef& V, int i, int j, VPoint& q) {
-    q.vc = V(i, j); q.vs = V(i, j - 1); q.vn = V(i, j + 1); q.vw = V(i - 1, j); q.ve = V(i + 1, j);
+    q.vc = V(i, j);
+    if (VISC) { q.vs = V(i, j - 1); q.vn = V(i, j + 1); q.vw = V(i - 1, j); q.ve = V(i + 1, j); }
     q.u4[0] = U(i, j - 1); q.u4[1] = U(i + 1, j - 1); q.u4[2] = U(i, j); q.u4[3] = U(i + 1, j);
     q.hs = P.h(i, j - 1); q.hn = P.h(i, j); q.as_ = P.a(i, j - 1); q.an = P.a(i, j);
     if (!VISC) {
@@ -376,6 +380,25 @@ template <bool FAST>
 __device__ __forceinline__ double implicit_coef(const EvpDev& P, const StressPt& top, const StressPt& bot, double own, const double* x4, double mi, double ai) {
     const double d = implicit_tau(P.bot, bot, own, x4) - implicit_tau(P.top, top, own, x4);
     return FAST ? d * ((1.0 / mi) * ai) : d / mi * ai;
+}
+
+// ---- the closing part of a sub-step, once for both components and every stepping kernel (split_explicit_momentum_equations.jl:215-228,
+// :249-263; explicit_momentum_equations.jl:40-82) ----------------------------------------------------------------------------------
+// x: the velocity the step starts from (the point's own; u^- / v^- for the ExplicitSolver), G its tendency, tau_i the implicit
+// coefficient, fd the free-drift value, mi / ai the interpolated mass and concentration.  The semi-implicit solve, then the select:
+// active ice takes the solve, marginal ice the free drift, the rest zero.
+// SPLIT: the split-explicit kernels guard tau_i where m <= 0 and multiply by `active` -- a Julia Bool, so a peripheral point gets a
+// strong zero that keeps the sign (:228).  The ExplicitSolver's steps have neither (momentum_explicit.hip's header): SPLIT = false
+template <bool FAST, bool SPLIT>
+__device__ __forceinline__ double close_substep(const EvpDev& P, double x, double G, double tau_i, double dtau, double fd, double mi, double ai,
+                                                bool peripheral) {
+    if (SPLIT) tau_i = (mi <= 0) ? 0.0 : tau_i;
+    const double xD = FAST ? fma(dtau, G, x) / fma(dtau, tau_i, 1.0) : (x + dtau * G) / (1 + dtau * tau_i);
+    const double xF = P.free_drift ? fd : 0.0;
+    const bool marginal = (mi > MOM_EPS64) & (ai > MOM_EPS64);
+    const bool active_ice = (mi >= P.min_mass) & (ai >= P.min_conc);
+    const double sel = active_ice ? xD : (marginal ? xF : 0.0);
+    return (SPLIT && peripheral) ? copysign(0.0, sel) : sel;
 }
 
 }  // namespace mom

@@ -10,18 +10,14 @@
 // at four points -- and, unlike the split-explicit kernels, have no `* active` factor and no m <= 0 guard on tau_i.  Each writes
 // the halo images of its component with its stores: the fill_halo_regions! that follows it (:33, :36).
 #include "momentum_dev.h"
+#include "csi_kernels.h"
 
 namespace csi {
 namespace mom {
 
-#define MOM_CELL(r)                                                            \
-    const int i = (r).i0 + (int)(blockIdx.x * blockDim.x + threadIdx.x);       \
-    const int j = (r).j0 + (int)(blockIdx.y * blockDim.y + threadIdx.y);       \
-    if (i > (r).i1 || j > (r).j1) return;
-
 template <bool FAST, bool VISC>
 __global__ void __launch_bounds__(256) k_tendencies(MomDev M, Range r) {
-    MOM_CELL(r)
+    CELL_OF_RANGE(r)
     const EvpDev& P = M.P;
     UPoint qu;
     VPoint qv;
@@ -34,7 +30,7 @@ __global__ void __launch_bounds__(256) k_tendencies(MomDev M, Range r) {
 
 template <bool FAST>
 __global__ void __launch_bounds__(256) k_expl_ustep(MomDev M, Range r, ImageSpec im) {
-    MOM_CELL(r)
+    CELL_OF_RANGE(r)
     const EvpDev& P = M.P;
     // gather: h, aice at (i-1, j), (i, j); u^-, G, u at the point; v at the four points of the cross average; stresses; free drift
     const double hw = P.h(i - 1, j), he = P.h(i, j), aw = P.a(i - 1, j), ae = P.a(i, j);
@@ -46,18 +42,13 @@ __global__ void __launch_bounds__(256) k_expl_ustep(MomDev M, Range r, ImageSpec
     const double fd = ld_sel(P.free_drift, addr(P.ufd, i, j), addr(P.u, i, j), 0.0);
     const double ai = (aw + ae) / 2;
     const double mi = (hw * P.rho * aw + he * P.rho * ae) / 2;
-    const double dt = P.dt;
     const double tau_i = implicit_coef<FAST>(P, top, bot, uc, v4, mi, ai);
-    const double uD = FAST ? fma(dt, G, um) / fma(dt, tau_i, 1.0) : (um + dt * G) / (1 + dt * tau_i);
-    const double uF = P.free_drift ? fd : 0.0;
-    const bool marginal = (mi > MOM_EPS64) & (ai > MOM_EPS64);
-    const bool active_ice = (mi >= P.min_mass) & (ai >= P.min_conc);
-    store_with_images(M.out, P.g, im, i, j, active_ice ? uD : (marginal ? uF : 0.0));
+    store_with_images(M.out, P.g, im, i, j, close_substep<FAST, false>(P, um, G, tau_i, P.dt, fd, mi, ai, false));
 }
 
 template <bool FAST>
 __global__ void __launch_bounds__(256) k_expl_vstep(MomDev M, Range r, ImageSpec im) {
-    MOM_CELL(r)
+    CELL_OF_RANGE(r)
     const EvpDev& P = M.P;
     const double hs = P.h(i, j - 1), hn = P.h(i, j), as_ = P.a(i, j - 1), an = P.a(i, j);
     const double vm = M.vm(i, j), G = M.Gv(i, j), vc = P.v(i, j);
@@ -68,40 +59,31 @@ __global__ void __launch_bounds__(256) k_expl_vstep(MomDev M, Range r, ImageSpec
     const double fd = ld_sel(P.free_drift, addr(P.vfd, i, j), addr(P.v, i, j), 0.0);
     const double ai = (as_ + an) / 2;
     const double mi = (hs * P.rho * as_ + hn * P.rho * an) / 2;
-    const double dt = P.dt;
     const double tau_i = implicit_coef<FAST>(P, top, bot, vc, u4, mi, ai);
-    const double vD = FAST ? fma(dt, G, vm) / fma(dt, tau_i, 1.0) : (vm + dt * G) / (1 + dt * tau_i);
-    const double vF = P.free_drift ? fd : 0.0;
-    const bool marginal = (mi > MOM_EPS64) & (ai > MOM_EPS64);
-    const bool active_ice = (mi >= P.min_mass) & (ai >= P.min_conc);
-    store_with_images(M.out, P.g, im, i, j, active_ice ? vD : (marginal ? vF : 0.0));
+    store_with_images(M.out, P.g, im, i, j, close_substep<FAST, false>(P, vm, G, tau_i, P.dt, fd, mi, ai, false));
 }
 
 }  // namespace mom
 
-static inline dim3 mom_grid(const Range& r, dim3 b) {
-    return dim3((unsigned)((r.i1 - r.i0 + 1 + b.x - 1) / b.x), (unsigned)((r.j1 - r.j0 + 1 + b.y - 1) / b.y), 1);
-}
-
 void launch_explicit_tendencies(const MomDev& M, const Range& r, int viscous, int fast, hipStream_t s) {
     const dim3 b(64, 4);
     if (fast) {
-        if (viscous) hipLaunchKernelGGL((mom::k_tendencies<true, true>), mom_grid(r, b), b, 0, s, M, r);
-        else hipLaunchKernelGGL((mom::k_tendencies<true, false>), mom_grid(r, b), b, 0, s, M, r);
+        if (viscous) hipLaunchKernelGGL((mom::k_tendencies<true, true>), grid_for(r, b), b, 0, s, M, r);
+        else hipLaunchKernelGGL((mom::k_tendencies<true, false>), grid_for(r, b), b, 0, s, M, r);
     } else {
-        if (viscous) hipLaunchKernelGGL((mom::k_tendencies<false, true>), mom_grid(r, b), b, 0, s, M, r);
-        else hipLaunchKernelGGL((mom::k_tendencies<false, false>), mom_grid(r, b), b, 0, s, M, r);
+        if (viscous) hipLaunchKernelGGL((mom::k_tendencies<false, true>), grid_for(r, b), b, 0, s, M, r);
+        else hipLaunchKernelGGL((mom::k_tendencies<false, false>), grid_for(r, b), b, 0, s, M, r);
     }
 }
 void launch_explicit_ustep(const MomDev& M, const Range& r, const ImageSpec& im, int fast, hipStream_t s) {
     const dim3 b(64, 4);
-    if (fast) hipLaunchKernelGGL(mom::k_expl_ustep<true>, mom_grid(r, b), b, 0, s, M, r, im);
-    else hipLaunchKernelGGL(mom::k_expl_ustep<false>, mom_grid(r, b), b, 0, s, M, r, im);
+    if (fast) hipLaunchKernelGGL(mom::k_expl_ustep<true>, grid_for(r, b), b, 0, s, M, r, im);
+    else hipLaunchKernelGGL(mom::k_expl_ustep<false>, grid_for(r, b), b, 0, s, M, r, im);
 }
 void launch_explicit_vstep(const MomDev& M, const Range& r, const ImageSpec& im, int fast, hipStream_t s) {
     const dim3 b(64, 4);
-    if (fast) hipLaunchKernelGGL(mom::k_expl_vstep<true>, mom_grid(r, b), b, 0, s, M, r, im);
-    else hipLaunchKernelGGL(mom::k_expl_vstep<false>, mom_grid(r, b), b, 0, s, M, r, im);
+    if (fast) hipLaunchKernelGGL(mom::k_expl_vstep<true>, grid_for(r, b), b, 0, s, M, r, im);
+    else hipLaunchKernelGGL(mom::k_expl_vstep<false>, grid_for(r, b), b, 0, s, M, r, im);
 }
 
 }  // namespace csi

@@ -14,70 +14,50 @@
 // STRICT (FAST = false): the reference's operation order, compiled without contraction: bit-for-bit the test-side restatement
 // (tests/momentum_ref.py).  FAST: explicit FMAs, reciprocals of the mass and the metrics; both gather every load of a point first.
 #include "momentum_dev.h"
+#include "csi_kernels.h"
 
 namespace csi {
 namespace mom {
 
-#define MOM_CELL(r)                                                            \
-    const int i = (r).i0 + (int)(blockIdx.x * blockDim.x + threadIdx.x);       \
-    const int j = (r).j0 + (int)(blockIdx.y * blockDim.y + threadIdx.y);       \
-    if (i > (r).i1 || j > (r).j1) return;
-
 template <bool FAST>
 __global__ void __launch_bounds__(256) k_visc_ustep(MomDev M, Range r, ImageSpec im) {
-    MOM_CELL(r)
+    CELL_OF_RANGE(r)
     const EvpDev& P = M.P;
     UPoint q;
     gather_u<true>(P, P.u, P.v, i, j, q);
     const double dtau = P.dt;                                          // Delta t / substeps (host), Rheologies.jl:49
     double mi, ai;
     const double G = u_tendency<FAST, true>(P, M.nu, q, i, j, 0.0, mi, ai);
-    double tau_i = implicit_coef<FAST>(P, q.top, q.bot, q.uc, q.v4, mi, ai);
-    tau_i = (mi <= 0) ? 0.0 : tau_i;
-    const double uD = FAST ? fma(dtau, G, q.uc) / fma(dtau, tau_i, 1.0) : (q.uc + dtau * G) / (1 + dtau * tau_i);
-    const double uF = P.free_drift ? q.fd : 0.0;
-    const bool marginal = (mi > MOM_EPS64) & (ai > MOM_EPS64);
-    const bool active_ice = (mi >= P.min_mass) & (ai >= P.min_conc);
-    const double sel = active_ice ? uD : (marginal ? uF : 0.0);
+    const double tau_i = implicit_coef<FAST>(P, q.top, q.bot, q.uc, q.v4, mi, ai);
     const bool peripheral = q.c.inact[3] | q.c.inact[2];               // peripheral_node (f, c, c): cells (i, j), (i - 1, j)
-    store_with_images(M.out, P.g, im, i, j, peripheral ? copysign(0.0, sel) : sel);   // `* active` with a Bool, :228
+    store_with_images(M.out, P.g, im, i, j, close_substep<FAST, true>(P, q.uc, G, tau_i, dtau, q.fd, mi, ai, peripheral));
 }
 
 template <bool FAST>
 __global__ void __launch_bounds__(256) k_visc_vstep(MomDev M, Range r, ImageSpec im) {
-    MOM_CELL(r)
+    CELL_OF_RANGE(r)
     const EvpDev& P = M.P;
     VPoint q;
     gather_v<true>(P, P.u, P.v, i, j, q);
     const double dtau = P.dt;
     double mi, ai;
     const double G = v_tendency<FAST, true>(P, M.nu, q, i, j, 0.0, mi, ai);
-    double tau_i = implicit_coef<FAST>(P, q.top, q.bot, q.vc, q.u4, mi, ai);
-    tau_i = (mi <= 0) ? 0.0 : tau_i;
-    const double vD = FAST ? fma(dtau, G, q.vc) / fma(dtau, tau_i, 1.0) : (q.vc + dtau * G) / (1 + dtau * tau_i);
-    const double vF = P.free_drift ? q.fd : 0.0;
-    const bool marginal = (mi > MOM_EPS64) & (ai > MOM_EPS64);
-    const bool active_ice = (mi >= P.min_mass) & (ai >= P.min_conc);
-    const double sel = active_ice ? vD : (marginal ? vF : 0.0);
+    const double tau_i = implicit_coef<FAST>(P, q.top, q.bot, q.vc, q.u4, mi, ai);
     const bool peripheral = q.c.inact[4] | q.c.inact[1];               // peripheral_node (c, f, c): cells (i, j), (i, j - 1)
-    store_with_images(M.out, P.g, im, i, j, peripheral ? copysign(0.0, sel) : sel);
+    store_with_images(M.out, P.g, im, i, j, close_substep<FAST, true>(P, q.vc, G, tau_i, dtau, q.fd, mi, ai, peripheral));
 }
 
 }  // namespace mom
 
-static inline dim3 mom_grid(const Range& r, dim3 b) {
-    return dim3((unsigned)((r.i1 - r.i0 + 1 + b.x - 1) / b.x), (unsigned)((r.j1 - r.j0 + 1 + b.y - 1) / b.y), 1);
-}
-
 void launch_viscous_ustep(const MomDev& M, const Range& r, const ImageSpec& im, int fast, hipStream_t s) {
     const dim3 b(64, 4);
-    if (fast) hipLaunchKernelGGL(mom::k_visc_ustep<true>, mom_grid(r, b), b, 0, s, M, r, im);
-    else hipLaunchKernelGGL(mom::k_visc_ustep<false>, mom_grid(r, b), b, 0, s, M, r, im);
+    if (fast) hipLaunchKernelGGL(mom::k_visc_ustep<true>, grid_for(r, b), b, 0, s, M, r, im);
+    else hipLaunchKernelGGL(mom::k_visc_ustep<false>, grid_for(r, b), b, 0, s, M, r, im);
 }
 void launch_viscous_vstep(const MomDev& M, const Range& r, const ImageSpec& im, int fast, hipStream_t s) {
     const dim3 b(64, 4);
-    if (fast) hipLaunchKernelGGL(mom::k_visc_vstep<true>, mom_grid(r, b), b, 0, s, M, r, im);
-    else hipLaunchKernelGGL(mom::k_visc_vstep<false>, mom_grid(r, b), b, 0, s, M, r, im);
+    if (fast) hipLaunchKernelGGL(mom::k_visc_vstep<true>, grid_for(r, b), b, 0, s, M, r, im);
+    else hipLaunchKernelGGL(mom::k_visc_vstep<false>, grid_for(r, b), b, 0, s, M, r, im);
 }
 
 }  // namespace csi

@@ -1,6 +1,6 @@
 """The local halo fill (fill_halo_regions!(...; only_local_halos = true)) in GATHER form, in numpy.  TEST INFRASTRUCTURE ONLY.
 
-The device code (csrc/csi_dev.h store_with_images and its restatements) states which halo images an interior cell HAS and stores
+The device code (csrc/csi_dev.h store_with_images and its specialisations) states which halo images an interior cell HAS and stores
 them from the owner's thread.  This module states the same rule the other way round: for every parent column (row) a 1-D table says
 which interior column (row) its value comes from and how it is changed on the way -- copied, or reflected about a
 ValueBoundaryCondition number (2 * value - c) -- and the passes are applied as whole-array gathers in the oracle's and upstream's order:

@@ -174,8 +174,45 @@ def test_strict_bitwise_vs_oracle(name, oracle_lib):
         assert np.array_equal(g[k], p.f[k]), f"{name}: {k} differs, max abs diff {np.abs(g[k] - p.f[k]).max():.3e}"
 
 
+# The operand combinations of the strict velocity steps that no case of CASES reaches (there the bottom stress is a SemiImplicitStress
+# or a pair of arrays, and a SemiImplicitStress on top always has an air velocity): case keywords, the keywords of the momentum
+# equation that replace the case's, and the same stress set on the oracle
+STRICT_STRESS_KINDS = {
+    "bottom_nothing": (dict(bottom=None), {}, None),
+    "bottom_numbers": (dict(bottom=None), dict(bottom_momentum_stress=(0.004, -0.003)), ("bottom", 1, dict(tau=(0.004, -0.003)))),
+    "top_semi_at_rest": (dict(top=None), dict(top_momentum_stress=csi.SemiImplicitStress(rho_e=1.3, Cd=1.2e-3)),
+                         ("top", 3, dict(rho_e=1.3, Cd=1.2e-3))),
+}
+
+
+@pytest.mark.parametrize("substeps", [3, 4])
+@pytest.mark.parametrize("name", list(STRICT_STRESS_KINDS))
+def test_strict_bitwise_vs_oracle_remaining_stress_kinds(name, substeps, oracle_lib):
+    kw, override, ora = STRICT_STRESS_KINDS[name]
+    c = cases.make_case(Nx=12, Ny=10, H=3, substeps=substeps, random_uv=0.05, **kw)
+    p = cases.oracle_problem(c)
+    if ora is not None:
+        p.set_stress(ora[0], ora[1], **ora[2])
+    orig = csi.SeaIceMomentumEquation
+    csi.SeaIceMomentumEquation = lambda g, **k: orig(g, **dict(k, **override))
+    try:
+        m = cases.csi_model(c, mode="strict")
+    finally:
+        csi.SeaIceMomentumEquation = orig
+    p.initialize_rheology()
+    m.ctx.call("csi_evp_initialize")
+    m.copy_to_field(m.dynamics.auxiliaries.fields.P, p.f["P"])      # (P uses exp(): continue from the oracle's, as above)
+    p.L.ora_fill_halo_u(p.ptr); p.L.ora_fill_halo_v(p.ptr)
+    p.subcycle(c["dt"], 1, substeps)
+    m.ctx.call("csi_evp_subcycle", c["dt"], substeps, 1)
+    g = gpu_fields(m)
+    for k in ("u", "v"):                                            # whole parents
+        assert np.all(np.isfinite(g[k])) and np.abs(g[k]).max() > 0, k
+        assert np.array_equal(g[k], p.f[k]), f"{name}: {k} differs, max abs diff {np.abs(g[k] - p.f[k]).max():.3e}"
+
+
 FAST_TOL_VEL, FAST_TOL_SIG = 1e-12, 1e-11
-_TOL_BRANCH = {}        # case -> {field: "stated" | "10x sensitivity"}: which bound each full-cycle comparison needed
+_TOL_BRANCH = {}       # case -> {field: "stated" | "10x sensitivity"}: which bound each full-cycle comparison needed
 
 
 def oracle_self_sensitivity(c, fields=("u", "v", "s11", "s22", "s12")):

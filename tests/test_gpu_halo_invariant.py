@@ -1,7 +1,7 @@
 """Every store path leaves filled halos behind.
 
-Every kernel that stores a prognostic field also writes that value's halo images (csrc/csi_dev.h store_with_images and its
-restatements in momentum_free_drift.hip, advect.hip, evp_fused2.hip, evp_fused_common.h).  After a public entry that advances a field,
+Every kernel that stores a prognostic field also writes that value's halo images (csrc/csi_dev.h store_with_images, which every
+velocity kernel and the fills call, and its specialisations in advect.hip and evp_fused2.hip).  After a public entry that advances a field,
 the returned parent must therefore be its own fill: tests/halo_ref.py's fill of the parent equals the parent on every SPECIFIED cell,
 BIT FOR BIT.  Two conditions keep that from passing emptily: every point within H of an edge (a source of some image) changed its bits
 between input and output, and that is asserted -- the inputs are chosen for it: ice everywhere above the minimum mass with
@@ -204,7 +204,7 @@ VARIANTS = {
 @pytest.mark.parametrize("path", list(VARIANTS))
 def test_momentum_variants_leave_filled_halos(path, topo, halo):
     """The viscous sub-cycle, the explicit u and v steps (momentum_viscous.hip, momentum_explicit.hip) and StressBalanceFreeDrift as the
-    dynamics (momentum_free_drift.hip store_point_and_images, which restates the store rule with fixed image slots)."""
+    dynamics (momentum_free_drift.hip): all of them store through store_with_images."""
     spec = VARIANTS[path]
     for N in sizes_of(halo, topo):
         n = spec.get("n", 4)

@@ -125,8 +125,9 @@ HIPCC = shutil.which("hipcc") or "/opt/rocm/bin/hipcc"
 # kernel-name fragment -> (loads in flight before the first vector-memory wait -- None: EVERY load of the kernel --, most
 # `load ... vmcnt(0)` drains tolerated).  The viscous sub-step kernels gather all operands of a point -- velocities, h, aice, metrics,
 # mask bytes, Coriolis parameter, stress arrays, forcing, free drift -- with unconditional loads from selected addresses
-# (csrc/momentum_dev.h), so no load waits for another; the explicit steps issue their point loads first (the rest are the stores'
-# halo-image reloads).
+# (csrc/momentum_dev.h), so no load waits for another; the explicit steps issue their point loads first (the rest belong to the
+# stress gather; none is waited for alone).  No gated kernel touches scratch memory: the halo images of store_with_images
+# (csrc/csi_dev.h) sit in fixed slots.
 GATED = {
     ("momentum_viscous", "12k_visc_ustepILb1E"): (None, 0), ("momentum_viscous", "12k_visc_vstepILb1E"): (None, 0),
     ("momentum_viscous", "12k_visc_ustepILb0E"): (None, 0), ("momentum_viscous", "12k_visc_vstepILb0E"): (None, 0),
@@ -174,3 +175,4 @@ def test_fast_kernels_issue_the_point_loads_before_the_first_wait(asm, key):
     assert seq[:first_wait].count("L") >= need, f"{names[0]}: {''.join(seq)[:200]}"
     drains = sum(1 for a, b in zip(seq, seq[1:]) if a == "L" and b == "W0")
     assert drains <= drains_allowed, f"{names[0]}: {drains} single-load round trips"
+    assert not any(ln.strip().startswith("scratch_") for ln in asm[src][names[0]]), f"{names[0]} touches scratch memory"
