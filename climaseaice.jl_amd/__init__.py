@@ -27,5 +27,6 @@ from .model import (FieldBoundaryConditions, FluxBoundaryCondition, ImmersedBoun
                     prognostic_state, restore_prognostic_state)
 from .enthalpy import ColumnField, ColumnGrid, ColumnTimeSeries, EnthalpyMethodSeaIceModel, MolecularDiffusivity
 from .drifters import Drifters, DrifterWriter, load_tracks
+from .regions import RegionalDiagnostics, RegionalSeriesWriter, Regions, load_regional_series
 
 __all__ = [n for n in dir() if not n.startswith("_")]

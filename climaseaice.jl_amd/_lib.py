@@ -120,7 +120,10 @@ SYMBOLS = ["csi_version", "csi_context_create", "csi_context_destroy", "csi_last
            "csi_enthalpy_plan", "csi_enthalpy_create", "csi_enthalpy_destroy", "csi_enthalpy_bind", "csi_enthalpy_boundary_set",
            "csi_enthalpy_set", "csi_enthalpy_update_state", "csi_enthalpy_time_step", "csi_enthalpy_last_launch",
            "csi_enthalpy_ice_thickness",
-           "csi_drifters_locate", "csi_drifters_advance", "csi_drifters_sample", "csi_drifters_stats"]
+           "csi_drifters_locate", "csi_drifters_advance", "csi_drifters_sample", "csi_drifters_stats",
+           "csi_regions_layout", "csi_regions_compute", "csi_regions_stats"]
+# per-region ice integrals and extrema (include/csi.h): the most regions one call takes
+REGIONS_MAX = 64
 # Lagrangian ice drifters (include/csi.h): the status bits of csi_drifters_advance, the column bits of csi_drifters_sample
 DRIFTER_CLAMPED_X, DRIFTER_CLAMPED_Y, DRIFTER_HELD, DRIFTER_LOST, DRIFTER_INACTIVE = 1, 2, 4, 8, 16
 DRIFTER_COL_XI, DRIFTER_COL_ETA, DRIFTER_COL_U, DRIFTER_COL_V, DRIFTER_COL_H, DRIFTER_COL_A, DRIFTER_COL_HS, DRIFTER_COL_ALL = 1, 2, 4, 8, 16, 32, 64, 127
@@ -260,6 +263,17 @@ class Drifters(C.Structure):
     _fields_ = [("n", C.c_int64), ("xi", C.c_void_p), ("eta", C.c_void_p), ("status", C.c_void_p)]
 
 
+class Regions(C.Structure):
+    """csi_regions (include/csi.h): the caller's device id map, laid out like a (c,c) parent."""
+    _fields_ = [("ids", C.c_void_p), ("ld", C.c_int64), ("n_regions", C.c_int32), ("reserved", C.c_int32)]
+
+
+class RegionRecord(C.Structure):
+    """csi_region_record (include/csi.h): the tracer group of one region; snow members hold NaN without a snow layer."""
+    _fields_ = ([(n, C.c_double) for n in ("ice_volume", "ice_area", "ice_extent", "snow_volume", "region_area",
+                                           "min_h", "max_h", "min_aice", "max_aice", "max_hs")] + [("cells", C.c_int64)])
+
+
 class CsiError(RuntimeError):
     def __init__(self, code, msg):
         super().__init__(f"libcsi_hip error {code}: {msg}")
@@ -363,6 +377,9 @@ def load():
         "csi_drifters_locate": [i32, i32, dbl, dbl, C.POINTER(i32), C.POINTER(dbl)],
         "csi_drifters_advance": [vp, C.POINTER(Drifters), dbl, i32], "csi_drifters_sample": [vp, C.POINTER(Drifters), i32, vp, i64],
         "csi_drifters_stats": [vp, C.POINTER(i64)],
+        "csi_regions_layout": [i32, i32, i32, C.POINTER(i64), C.POINTER(i64)],
+        "csi_regions_compute": [vp, C.POINTER(Regions), dbl, C.POINTER(RegionRecord), C.POINTER(i64)],
+        "csi_regions_stats": [vp, C.POINTER(i64)],
     }
     for name, args in sig.items():
         fn = getattr(L, name, None)
@@ -431,6 +448,16 @@ def drifters_locate(Nx, Ny, xi, eta):
     if rc != OK:
         raise CsiError(rc, "csi_drifters_locate: Nx >= 1 and Ny >= 1 are needed")
     return dict(ia=idx[0], ja=idx[1], ib=idx[2], jb=idx[3], ic=idx[4], jc=idx[5], sx=w[0], sy=w[1], rx=w[2], ry=w[3])
+
+
+def regions_layout(Nx, Ny, n_regions):
+    """csi_regions_layout: (records, bytes) of the partial buffer of csi_regions_compute (pure host function; CsiError for extents < 1
+    and for n_regions outside 1 .. REGIONS_MAX)."""
+    rec, nb = C.c_int64(), C.c_int64()
+    rc = load().csi_regions_layout(int(Nx), int(Ny), int(n_regions), C.byref(rec), C.byref(nb))
+    if rc != OK:
+        raise CsiError(rc, "csi_regions_layout: Nx >= 1, Ny >= 1 and 1 <= n_regions <= 64 are needed")
+    return rec.value, nb.value
 
 
 def regrid_plan_axis(nodes, periodic, period, x):
@@ -669,6 +696,22 @@ class Context:
         """Launches of the two drifter kernels made on this context so far."""
         n = C.c_int64()
         self.call("csi_drifters_stats", C.byref(n))
+        return n.value
+
+    # ---- per-region ice integrals and extrema (include/csi.h, csi_regions_*) ---------------------------------------------------------
+    def regions_compute(self, ids_ptr, ld, n_regions, extent_threshold, reserved=0):
+        """csi_regions_compute: (the n_regions filled csi_region_record, unassigned_cells); two launches and one small copy, waits for
+        the context's stream; collective on a tiled context.  ids_ptr: the device address of the map's parent."""
+        r = Regions(C.c_void_p(ids_ptr) if ids_ptr else None, int(ld), int(n_regions), int(reserved))
+        out = (RegionRecord * max(1, min(int(n_regions), REGIONS_MAX)))()
+        stray = C.c_int64(-1)
+        self.call("csi_regions_compute", C.byref(r), float(extent_threshold), out, C.byref(stray))
+        return out, stray.value
+
+    def regions_stats(self):
+        """Launches made by csi_regions_compute on this context so far (two per call)."""
+        n = C.c_int64()
+        self.call("csi_regions_stats", C.byref(n))
         return n.value
 
     # ---- momentum balance terms, interface stresses and their power (include/csi.h) ------------------------------------------------

@@ -13,6 +13,7 @@
 //   csi_momentum_terms.hip   momentum balance terms and their power: binding checks, the launches, the power sums' combine over the ranks
 //   csi_enthalpy.hip      the enthalpy-method column model: the choosing rule, the model object, its launches
 //   csi_drifters.hip      Lagrangian ice drifters: the locate rule on the host, argument and binding checks, the two launches
+//   csi_regions.hip       per-region ice integrals: argument and binding checks, the two launches, the combine over the ranks
 //   csi_slots.h     the field slots: id, display name, location and roles of each, one row per slot
 //   csi_mem.h       DeviceBuf / PinnedBuf: the owner of every allocation the library makes
 #pragma once
@@ -298,6 +299,11 @@ struct csi_context {
     // the calls made so far (csi_derived_stats, csi_momentum_terms_stats)
     int64_t derived_launches = 0, budget_calls = 0;
     int64_t drifter_launches = 0;        // csi_drifters_advance / _sample (csi_drifters.hip): launches of the two kernels
+    // csi_regions_compute (csi_regions.hip): the partial records followed by the folded slots (sized by csi_regions_layout, only
+    // grows), ONE page-locked copy of the folded slots, the launches made so far (csi_regions_stats).  Empty until the first call
+    DeviceBuf<double> regions_part;
+    PinnedBuf<double> regions_host;
+    int64_t region_launches = 0;
     int64_t mterm_launches = 0, mterm_budget_calls = 0;
     // csi_output_* (csi_output.hip): the sets and the copy stream their records leave on, made at the first csi_output_create
     OutputSet out_sets[kMaxOutputSets];

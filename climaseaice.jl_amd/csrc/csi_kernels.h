@@ -409,4 +409,31 @@ struct DriftersDev {
 void launch_drifters_advance(const DriftersDev& D, double tau, int m, hipStream_t s);
 void launch_drifters_sample(const DriftersDev& D, int columns, double* out, long ld, hipStream_t s);
 
+// per-region ice integrals and extrema (regions.hip; include/csi.h csi_regions_compute): the diagnostics' tracer group restricted to the
+// cells of each region of the caller's id map.  One 8-byte slot per quantity, in this order, in every record; RQ_CELLS is an int64 bit
+// pattern.  Records: slot q of region r of block b at part[((long)r * RQ_COUNT + q) * nrec + b] -- contiguous per region and slot, so
+// red::finish_records' block r reads region r as the diagnostics' single block reads its own.  Region index n_regions is the record of
+// the cells that belong to NO region: identities, and their number in RQ_CELLS.
+enum : int { RQ_VOLUME = 0, RQ_AREA, RQ_EXTENT, RQ_SNOW_VOLUME, RQ_REGION_AREA, RQ_MIN_H, RQ_MAX_H, RQ_MIN_AICE, RQ_MAX_AICE, RQ_MAX_HS,
+             RQ_CELLS, RQ_COUNT };
+constexpr int kRegionsMax = 64;
+struct RegionKinds {
+    __host__ __device__ static constexpr int kind(int q) {
+        return (q == RQ_MAX_H || q == RQ_MAX_AICE || q == RQ_MAX_HS) ? K_MAX : (q == RQ_MIN_H || q == RQ_MIN_AICE) ? K_MIN : q == RQ_CELLS ? K_CNT : K_SUM;
+    }
+};
+struct RegionsDev {
+    GridDev g;
+    FRef h, a, hs;
+    const int32_t* ids;        // element (0, 0)-offset like the mask: the id of cell (i, j) at ids[i + j * ids_ld]
+    long ids_ld;
+    int n_regions;             // 1 .. kRegionsMax
+    int has_hs;
+    double threshold;
+    double* part;
+    long nrec;
+};
+// the two launches: records into D.part, the (n_regions + 1) x RQ_COUNT folded slots into out (device memory)
+void launch_regions(const RegionsDev& D, double* out, hipStream_t s);
+
 }  // namespace csi

@@ -1,5 +1,6 @@
 // ordered_reduce.h -- the ONE device-side statement of the ordered reduction that csi_diagnostics_compute, csi_budget_compute and
-// csi_momentum_budget_compute share (diagnostics.hip, budget.hip, momentum_terms.hip).  gfx950 only.
+// csi_momentum_budget_compute share (diagnostics.hip, budget.hip, momentum_terms.hip), and csi_regions_compute with one record per region
+// and block (regions.hip).  gfx950 only.
 //
 // Two launches on one stream: a partial kernel of 64 x 4 threads per block of 64 x 64 cells writes one record per block (plain stores,
 // one slot per quantity: slot q of record r at part[q * nrec + r]); ONE block (finish_records) folds the records into the result.  The
@@ -75,12 +76,16 @@ __device__ __forceinline__ void block_fold(double (&acc)[N], int lane, int wave,
         dst[(long)q * stride] = x;
     }
 }
-// the finishing kernel: one block of kFinishThreads.  UNROLL: the record loop's unroll count (0: the compiler's choice).  The loop is
+// the finishing kernel: one block of kFinishThreads per SEGMENT -- block b folds the records at part + b * N * nrec into out + b * N.
+// The diagnostics and the budgets launch one block (their one segment: b = 0, the pointers as given); csi_regions_compute one per region
+// (regions.hip), each in the order stated above.  UNROLL: the record loop's unroll count (0: the compiler's choice).  The loop is
 // written out under both branches: behind a helper function the compiler unrolls it differently (more loads in flight than the
 // registers of the 21-slot instantiations hold at their occupancy).  The two loops are ONE statement: an edit to one is an edit to both
 template <int N, int Q0, int Q1, class Kinds, int UNROLL>
 __global__ void __launch_bounds__(kFinishThreads) finish_records(const double* __restrict__ part, long nrec, double* __restrict__ out) {
     const int t = (int)threadIdx.x;
+    part += (long)blockIdx.x * N * nrec;
+    out += (long)blockIdx.x * N;
     double acc[N];
     set_identity<N, Kinds>(acc);
     if constexpr (UNROLL > 0) {
@@ -98,8 +103,8 @@ __global__ void __launch_bounds__(kFinishThreads) finish_records(const double* _
     block_fold<N, Q0, Q1, Kinds>(acc, t & 63, t >> 6, t, out, 1);
 }
 template <int N, int Q0, int Q1, class Kinds, int UNROLL>
-inline void launch_finish(const double* part, long nrec, double* out, hipStream_t s) {
-    hipLaunchKernelGGL((finish_records<N, Q0, Q1, Kinds, UNROLL>), dim3(1), dim3(kFinishThreads), 0, s, part, nrec, out);
+inline void launch_finish(const double* part, long nrec, double* out, hipStream_t s, int segments = 1) {
+    hipLaunchKernelGGL((finish_records<N, Q0, Q1, Kinds, UNROLL>), dim3((unsigned)segments), dim3(kFinishThreads), 0, s, part, nrec, out);
 }
 
 }  // namespace red

@@ -1013,6 +1013,13 @@ class SeaIceModel:
         from .diagnostics import diagnostics
         return diagnostics(self, what, extent_threshold)
 
+    def regional_diagnostics(self, regions, extent_threshold=0.15):
+        """The tracer group of diagnostics() per region of a csi.Regions map -- volume, area, extent, snow volume, region area, extrema
+        and cell counts as one vector per quantity --, reduced on the device in the diagnostics' summation order (regions.py,
+        include/csi.h csi_regions_compute).  Waits for the library's stream; collective on a tiled model."""
+        from .regions import regional_diagnostics
+        return regional_diagnostics(self, regions, extent_threshold)
+
     # ---- derived fields and energy budget integrals (derived.py; include/csi.h csi_derived_compute / csi_budget_compute) ----------
     def derived_field(self, name):
         """The (Center, Center) field of a derived quantity -- "divergence", "shear", "deformation", "speed", "sigma_I", "sigma_II",

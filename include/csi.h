@@ -1562,6 +1562,66 @@ int32_t csi_drifters_advance(csi_context* ctx, const csi_drifters* d, double dt,
 int32_t csi_drifters_sample(csi_context* ctx, const csi_drifters* d, int32_t columns, void* dev_out, int64_t ld);
 int32_t csi_drifters_stats(csi_context* ctx, int64_t* launches);
 
+/* ---- per-region ice integrals and extrema ---------------------------------------------------------------------------------------------
+ * The tracer group of csi_diagnostics_compute, per region of a caller-supplied map, in ONE call: Arctic and Antarctic extent, extent and
+ * volume per basin, totals per latitude band.  Stands where users of the reference copy h, aice, hs and the metrics to the host and bin
+ * them there (a wait for the stream, whole parents over the bus, sums in the host library's order).
+ *
+ * A REGION MAP is a device array of int32 laid out like a (c,c) parent with leading dimension ld -- as the mask of csi_mask_set is: the
+ * id of cell (i, j) at ids[(i + Hx - 1) + (j + Hy - 1) * ld].  Only i = 1 .. Nx, j = 1 .. Ny are read, whatever the halo elements hold.
+ * n_regions is between 1 and CSI_REGIONS_MAX = 64.  A cell BELONGS TO REGION r when its id equals r and it is active (no mask set, or
+ * its mask byte != 0).  An id outside 0 .. n_regions - 1 -- negative ids, INT32_MIN and INT32_MAX included -- belongs to no region; the
+ * ACTIVE cells with such an id are counted in *unassigned_cells.  No id value forms an address: ids are compared, never used as an index.
+ * The caller's array is passed at every call; the library keeps no map (as with csi_drifters).
+ *
+ * out[r], r = 0 .. n_regions - 1 (HOST memory), holds the tracer group restricted to the cells of region r:
+ *   ice_volume = sum (h * aice) * Az     ice_area = sum aice * Az     ice_extent = sum Az over cells with aice >= extent_threshold
+ *   snow_volume = sum (hs * aice) * Az   region_area = sum Az         (Az = Az^cc; products in the order written, uncontracted)
+ *   min_h, max_h, min_aice, max_aice, max_hs   (NaN elements are skipped; -0.0 and +0.0 compare equal and either may be returned)
+ *   cells               the number of cells of r
+ * exactly as stated for CSI_DIAG_TRACERS above.  snow_volume and max_hs without a bound CSI_F_HS hold the "not computed" value NaN.
+ * A region with no cell returns +0.0 for the sums, +Inf for the minima, -Inf for the maxima and 0 for cells.
+ *
+ * SUMMATION ORDER: the one stated for csi_diagnostics_compute above, a function of (Nx, Ny) alone -- it does not depend on the map.  A
+ * cell that does not belong to r contributes the identity to r's record: +0.0 to a sum, +Inf to a minimum, -Inf to a maximum, 0 to
+ * cells.  Hence out[r] equals, BIT FOR BIT, what csi_diagnostics_compute(CSI_DIAG_TRACERS) returns on the same fields when the mask is
+ * replaced by `mask AND (id == r)` (region_area = its active_area, cells = its active_cells).
+ *
+ * Two launches on the context's stream -- a pass over the interior that leaves, per block of 64 x 64 cells, one record per region (a
+ * block folds only the regions that occur in its tile; the others get identity records) and a finishing launch of n_regions + 1 blocks,
+ * block r folding region r's records as step 4 above, the last one the count of the cells of no region --, one copy of the folded slots
+ * to page-locked host memory and one wait for the stream.  No atomics in device memory, no flags, no hand-off between workgroups inside
+ * a launch: the same bits from call to call, in STRICT and FAST mode.  The record buffer is the context's, allocated at the first call
+ * and only growing; csi_regions_layout(Nx, Ny, n_regions, &records, &bytes) is its size as a pure host function (no context, no GPU):
+ *   records = ceil(Nx / 64) * ceil(Ny / 64)     bytes = records * (n_regions + 1) * 11 * 8
+ * (Nx < 1, Ny < 1 or n_regions outside 1 .. 64: CSI_ERR_INVALID_ARGUMENT; either output pointer may be NULL.)  csi_regions_stats:
+ * launches made by csi_regions_compute on this context so far (two per call); a model that never asks makes none.
+ *
+ * Tiled contexts: the call is COLLECTIVE, exactly like csi_diagnostics_compute.  Each rank passes ITS piece of the map (laid out like
+ * its own (c,c) parents), reduces its own interior, the ranks all-gather n_regions x 11 slots and the count, and every rank combines
+ * them on the host in rank order: all ranks return the same bits, and sums differ from the untiled run's by rounding only.  A rank that
+ * fails locally still takes part in the all-gather; then every rank returns an error.
+ *
+ * Errors, by name: CSI_ERR_NOT_BOUND for a missing h or aice (and the grid); CSI_ERR_INVALID_ARGUMENT for r == NULL, NULL ids or out,
+ * n_regions outside 1 .. 64, ld < Nx + 2 Hx, an extent_threshold that is negative or not finite, reserved != 0.
+ * NOT BUILT: more than 64 regions per call (call again with another map); overlapping regions; the velocity group or the non-finite
+ * counts per region; regional energy or momentum budgets; region maps as bound slots or as time series. */
+#define CSI_REGIONS_MAX 64
+typedef struct {
+    const int32_t* ids;                /* device, laid out like a (c,c) parent */
+    int64_t ld;                        /* >= Nx + 2 Hx */
+    int32_t n_regions;                 /* 1 .. CSI_REGIONS_MAX */
+    int32_t reserved;                  /* 0 */
+} csi_regions;
+typedef struct {
+    double ice_volume, ice_area, ice_extent, snow_volume, region_area;
+    double min_h, max_h, min_aice, max_aice, max_hs;
+    int64_t cells;
+} csi_region_record;
+int32_t csi_regions_layout(int32_t Nx, int32_t Ny, int32_t n_regions, int64_t* records, int64_t* bytes);
+int32_t csi_regions_compute(csi_context* ctx, const csi_regions* r, double extent_threshold, csi_region_record* out, int64_t* unassigned_cells);
+int32_t csi_regions_stats(csi_context* ctx, int64_t* launches);
+
 #ifdef __cplusplus
 }
 #endif

@@ -1209,6 +1209,61 @@ function drifter_launches(model::HIPSeaIceModel)
     return n[]
 end
 
+# ---- per-region ice integrals and extrema (include/csi.h: csi_regions_compute) -----------------------------------------------------------
+# regional_diagnostics(model, ids, n): the tracer group of diagnostics(model) per region of `ids`, a DEVICE matrix of Int32 laid out
+# like the parent of a (Center, Center) field (ROCArray, size(ids, 1) >= Nx + 2Hx): a cell with id r in 0 .. n - 1 belongs to region r,
+# any other id to none.  Two launches and one small copy on the context's stream, which the call waits for; sums in the library's
+# summation order.  Returns (records::Vector{CsiRegionRecord}, unassigned_cells).  Distributed grids: collective, each rank its piece.
+const REGIONS_MAX = 64
+# csi_regions: the caller's map
+struct CsiRegions
+    ids::Ptr{Int32}
+    ld::Int64
+    n_regions::Int32
+    reserved::Int32
+end
+@assert sizeof(CsiRegions) == 24      # the layout gcc gives csi_regions
+# csi_region_record: one region's values (snow_volume, max_hs: NaN without a snow layer)
+struct CsiRegionRecord
+    ice_volume::Cdouble
+    ice_area::Cdouble
+    ice_extent::Cdouble
+    snow_volume::Cdouble
+    region_area::Cdouble
+    min_h::Cdouble
+    max_h::Cdouble
+    min_aice::Cdouble
+    max_aice::Cdouble
+    max_hs::Cdouble
+    cells::Int64
+end
+@assert sizeof(CsiRegionRecord) == 88
+
+function regional_diagnostics(model::HIPSeaIceModel, ids, n; extent_threshold = 0.15)
+    ctx = context(model)
+    1 <= n <= REGIONS_MAX || error("regional_diagnostics: between 1 and $REGIONS_MAX regions per call")
+    r = Ref(CsiRegions(Ptr{Int32}(pointer(ids)), Int64(size(ids, 1)), Int32(n), Int32(0)))
+    out = Vector{CsiRegionRecord}(undef, n)
+    unassigned = Ref{Int64}(0)
+    GC.@preserve model ids out check(ctx, ccall((:csi_regions_compute, libcsi), Int32, (Ptr{Cvoid}, Ref{CsiRegions}, Cdouble, Ptr{CsiRegionRecord}, Ref{Int64}),
+                                                ctx.handle, r, Float64(extent_threshold), pointer(out), unassigned))
+    return out, unassigned[]
+end
+
+function regions_layout(Nx, Ny, n)
+    records, bytes = Ref{Int64}(0), Ref{Int64}(0)
+    rc = ccall((:csi_regions_layout, libcsi), Int32, (Int32, Int32, Int32, Ref{Int64}, Ref{Int64}), Int32(Nx), Int32(Ny), Int32(n), records, bytes)
+    rc == 0 || error("csi_regions_layout: Nx >= 1, Ny >= 1 and 1 <= n <= $REGIONS_MAX are needed")
+    return records[], bytes[]
+end
+
+function region_launches(model::HIPSeaIceModel)
+    ctx = context(model)
+    n = Ref{Int64}(0)
+    check(ctx, ccall((:csi_regions_stats, libcsi), Int32, (Ptr{Cvoid}, Ref{Int64}), ctx.handle, n))
+    return n[]
+end
+
 # Checkpointing (sea_ice_model.jl:414-445: prognostic_state / restore_prognostic_state!) needs nothing from the library: the
 # state lives in the Oceananigans Fields, restore writes into the same parents, and the library holds pointers only.  If a
 # restore REPLACES parents (new arrays), drop the context so that the next step re-attaches:
