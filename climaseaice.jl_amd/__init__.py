@@ -28,5 +28,6 @@ from .model import (FieldBoundaryConditions, FluxBoundaryCondition, ImmersedBoun
 from .enthalpy import ColumnField, ColumnGrid, ColumnTimeSeries, EnthalpyMethodSeaIceModel, MolecularDiffusivity
 from .drifters import Drifters, DrifterWriter, load_tracks
 from .regions import RegionalDiagnostics, RegionalSeriesWriter, Regions, load_regional_series
+from .tracers import IceAge, Tracer
 
 __all__ = [n for n in dir() if not n.startswith("_")]

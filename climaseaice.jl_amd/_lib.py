@@ -62,12 +62,16 @@ THERMO_SERIES_SLOTS, MIXED_LAYER_SERIES_SLOTS, SHORTWAVE_SERIES_SLOTS = ([n for 
 
 
 def slot_id(name):
-    """The number of a csi_field_bind slot by name."""
+    """The number of a csi_field_bind slot by name; "TRACER:k" is tracer k as an output field, CSI_TRACER_FIELD(k) (no slot)."""
+    if name.startswith("TRACER:"):
+        return 4096 + int(name[7:])
     return _ID[name]
 
 
 def slot_location(name):
     """(LX, LY) of a slot by name: grids.Center / grids.Face."""
+    if name.startswith("TRACER:"):
+        return SLOTS[_ID["H"]][2]
     return SLOTS[_ID[name]][2]
 
 
@@ -121,7 +125,8 @@ SYMBOLS = ["csi_version", "csi_context_create", "csi_context_destroy", "csi_last
            "csi_enthalpy_set", "csi_enthalpy_update_state", "csi_enthalpy_time_step", "csi_enthalpy_last_launch",
            "csi_enthalpy_ice_thickness",
            "csi_drifters_locate", "csi_drifters_advance", "csi_drifters_sample", "csi_drifters_stats",
-           "csi_regions_layout", "csi_regions_compute", "csi_regions_stats"]
+           "csi_regions_layout", "csi_regions_compute", "csi_regions_stats",
+           "csi_tracers_set", "csi_tracers_tendencies", "csi_tracers_update", "csi_tracers_stats", "csi_tracers_last"]
 # per-region ice integrals and extrema (include/csi.h): the most regions one call takes
 REGIONS_MAX = 64
 # Lagrangian ice drifters (include/csi.h): the status bits of csi_drifters_advance, the column bits of csi_drifters_sample
@@ -274,6 +279,21 @@ class RegionRecord(C.Structure):
                                            "min_h", "max_h", "min_aice", "max_aice", "max_hs")] + [("cells", C.c_int64)])
 
 
+TRACERS_MAX = 8
+TRACER_PLAIN, TRACER_BY_CONCENTRATION = 0, 1
+
+
+def tracer_field(k):
+    """CSI_TRACER_FIELD(k) (include/csi.h): tracer k as an output field id."""
+    return 4096 + int(k)
+
+
+class Tracers(C.Structure):
+    """csi_tracers (include/csi.h): the caller's tracer arrays (parent shape of h), optional tendency arrays and per-tracer flags."""
+    _fields_ = [("n", C.c_int32), ("c", C.c_void_p * TRACERS_MAX), ("G", C.c_void_p * TRACERS_MAX),
+                ("weighting", C.c_int32 * TRACERS_MAX), ("nonnegative", C.c_int32 * TRACERS_MAX), ("source", C.c_double * TRACERS_MAX)]
+
+
 class CsiError(RuntimeError):
     def __init__(self, code, msg):
         super().__init__(f"libcsi_hip error {code}: {msg}")
@@ -380,6 +400,9 @@ def load():
         "csi_regions_layout": [i32, i32, i32, C.POINTER(i64), C.POINTER(i64)],
         "csi_regions_compute": [vp, C.POINTER(Regions), dbl, C.POINTER(RegionRecord), C.POINTER(i64)],
         "csi_regions_stats": [vp, C.POINTER(i64)],
+        "csi_tracers_set": [vp, C.POINTER(Tracers)], "csi_tracers_tendencies": [vp, i32, dbl, i32], "csi_tracers_update": [vp, dbl],
+        "csi_tracers_stats": [vp, C.POINTER(i64), C.POINTER(i64)],
+        "csi_tracers_last": [vp, C.POINTER(i32), C.POINTER(i32), C.POINTER(i32), C.POINTER(i32)],
     }
     for name, args in sig.items():
         fn = getattr(L, name, None)
@@ -713,6 +736,31 @@ class Context:
         n = C.c_int64()
         self.call("csi_regions_stats", C.byref(n))
         return n.value
+
+    # ---- advected ice tracers (include/csi.h, csi_tracers_*) --------------------------------------------------------------------------
+    def tracers_set(self, t):
+        """csi_tracers_set: the library copies the Tracers struct (None removes the tracers)."""
+        self.call("csi_tracers_set", None if t is None else C.byref(t))
+
+    def tracers_tendencies(self, scheme, dt, from_cache=False):
+        """csi_tracers_tendencies: the first half of a stage for every tracer, one launch (nothing is waited for)."""
+        self.call("csi_tracers_tendencies", int(scheme), float(dt), int(bool(from_cache)))
+
+    def tracers_update(self, dt):
+        """csi_tracers_update: the second half of a stage for every tracer, one launch (nothing is waited for)."""
+        self.call("csi_tracers_update", float(dt))
+
+    def tracers_stats(self):
+        """(launches of the tracer stencil kernel, launches of the point-wise tracer kernels) made on this context so far."""
+        a, b = C.c_int64(), C.c_int64()
+        self.call("csi_tracers_stats", C.byref(a), C.byref(b))
+        return a.value, b.value
+
+    def tracers_last(self):
+        """csi_tracers_last: the layout of the last tracer stencil launch (all zero before the first one)."""
+        v = [C.c_int32() for _ in range(4)]
+        self.call("csi_tracers_last", *[C.byref(x) for x in v])
+        return dict(tracers_per_thread=v[0].value, tile_x=v[1].value, tile_y=v[2].value, groups=v[3].value)
 
     # ---- momentum balance terms, interface stresses and their power (include/csi.h) ------------------------------------------------
     def momentum_terms_compute(self, mask):

@@ -62,7 +62,7 @@ int32_t csi_context_create(int32_t device_id, void* hip_stream, csi_context** ou
         c->tune.pair_common = env_int("CSI_PAIR_COMMON"); c->tune.no_geom_sig = env_int("CSI_DEBUG_NO_GEOM_SIG");
         c->tune.peer_edge = env_int("CSI_PEER_EDGE");          // rows the chunks next to a peer-connected y side are shorter by (default 4; 0: uniform chunks)
         c->tune.write_through = env_int("CSI_WRITE_THROUGH");  // 0 / 1: never / always store the pair kernel's results write-through (default: by grid size)
-        c->tune.adv_nt = env_int("CSI_ADV_NT"); c->tune.pair_target = env_int("CSI_PAIR_TARGET");
+        c->tune.adv_nt = env_int("CSI_ADV_NT"); c->tune.trc_ntr = env_int("CSI_TRACERS_NTR"); c->tune.pair_target = env_int("CSI_PAIR_TARGET");
         c->tune.enth_path = enth_path;                         // form of the enthalpy-method column model's step kernel (checked above)
         c->tune.adv_shape = adv_shape;                         // block shape of the advection kernel's two-tracer layout (checked above)
         { const char* e = getenv("CSI_ADV_STAGE_MAX_CELLS"); if (e && *e) c->tune.adv_stage_max_cells = atol(e); }      // A/B: largest grid that takes one launch per RK stage
@@ -472,6 +472,7 @@ int32_t csi_cache_current_fields(csi_context* c) {
     if (c->f[CSI_F_ML_TEMPERATURE].p && c->f[CSI_F_ML_TEMPERATURE_M].p && (rc = add(CSI_F_ML_TEMPERATURE_M, CSI_F_ML_TEMPERATURE))) return rc;
     launch_copy_batch(B, c->stream);
     HIP_TRY(c, hipGetLastError());
+    if (c->trc.set && (rc = tracers_cache(c))) return rc;      // (advected tracers: c -> c^-, a batch of their own)
     return CSI_OK;
 }
 
@@ -509,12 +510,14 @@ int32_t csi_time_step_fe(csi_context* c, double dt, int32_t substeps, int32_t sc
     if ((rc = step_width_check(c, dynamics))) return rc;
     if (first_iteration && (rc = do_update_state(c))) return rc;          // sea_ice_fe_step.jl:16
     if ((rc = do_tendencies_or_zero(c, scheme))) return rc;               // :19 (compute_tracer_tendencies!)
+    if (c->trc.set && (rc = tracers_first_half(c, scheme, dt, 0))) return rc;      // (advected tracers: the first half, include/csi.h)
     if (dynamics && (rc = do_momentum_tendencies(c, dt))) return rc;      // :19 (compute_momentum_tendencies!: ExplicitSolver only)
     if (dynamics && (rc = do_momentum(c, dt, substeps, 0))) return rc;    // :22
     // without a mask and without a thermodynamic step the tracer update's stores write the halo images themselves
     const bool fused_fill = !c->g.has_mask && !c->slab_set;
     if ((rc = do_tracer_step(c, dt, 0, fused_fill))) return rc;           // :25
     if ((rc = do_thermo(c, dt))) return rc;                               // :28 thermodynamic_time_step!
+    if (c->trc.set && (rc = tracers_second_half(c, dt))) return rc;       // (advected tracers: the second half)
     if ((rc = do_update_state(c, true, fused_fill))) return rc;           // :31
     return finish_step(c, CSI_OK);
 }
@@ -534,6 +537,7 @@ bool advect_stage_supported(const csi_context* c, int scheme) {
     // separate update streams another 7 arrays per stage, which the fused stage never touches: no cut any more (A/B knob:
     // CSI_ADV_STAGE_MAX_CELLS)
     if ((long)c->Nx * c->Ny > c->tune.adv_stage_max_cells) return false;
+    if (c->trc.set) return false;      // (advected tracers take the general stage loop)
     return !has_dynamics(c) && scheme != 0 && c->fusion && !c->slab_set && !c->g.has_mask && !is_tiled(c) &&
            c->f[CSI_F_HS].p == nullptr && c->f[CSI_F_H].ld == c->f[CSI_F_HM].ld && c->f[CSI_F_A].ld == c->f[CSI_F_AM].ld;
 }
@@ -583,11 +587,13 @@ int32_t csi_time_step_rk3(csi_context* c, double dt, int32_t substeps, int32_t s
     for (int beta = 3; beta >= 1; --beta) {                               // upstream stage loop
         const double dtau = dt / beta;
         if ((rc = do_tendencies_or_zero(c, scheme))) return rc;           // :84
+        if (c->trc.set && (rc = tracers_first_half(c, scheme, dtau, 1))) return rc;      // (advected tracers: from Psi^-)
         if (dynamics && (rc = do_momentum_tendencies(c, dtau))) return rc;               // :84 (ExplicitSolver only)
         if (dynamics && (rc = do_momentum(c, dtau, substeps, 1))) return rc;             // :87
         const bool fused_fill = !c->g.has_mask && !c->slab_set;
         if ((rc = do_tracer_step(c, dtau, 1, fused_fill))) return rc;     // :89
         if ((rc = do_thermo(c, dtau, 1))) return rc;                      // :91 thermodynamic_time_step! (the mixed layer: from Psi^-)
+        if (c->trc.set && (rc = tracers_second_half(c, dtau))) return rc;
         if ((rc = do_update_state(c, true, fused_fill))) return rc;
     }
     return finish_step(c, CSI_OK);
@@ -601,6 +607,7 @@ static void leave_groups(csi_context* c) { if (c->comm) { ncclCommDestroy(c->com
 int32_t csi_tile_set(csi_context* c, int32_t rx, int32_t ry, int32_t Rx, int32_t Ry, int32_t periodic_x, int32_t periodic_y) {
     if (!c) return CSI_ERR_INVALID_ARGUMENT;
     if (Rx < 1 || Ry < 1 || rx < 0 || rx >= Rx || ry < 0 || ry >= Ry) return fail(c, CSI_ERR_INVALID_ARGUMENT, "tile coordinates out of range");
+    if (c->trc.set) return fail(c, CSI_ERR_UNSUPPORTED, "csi_tile_set: advected tracers are not supported on tiled contexts (csi_tracers_set was called on this context)");
     c->tile.rx = rx; c->tile.ry = ry; c->tile.Rx = Rx; c->tile.Ry = Ry;
     c->tile.periodic_x = periodic_x != 0; c->tile.periodic_y = periodic_y != 0;
     c->tile.set = true;

@@ -14,6 +14,7 @@
 //   csi_enthalpy.hip      the enthalpy-method column model: the choosing rule, the model object, its launches
 //   csi_drifters.hip      Lagrangian ice drifters: the locate rule on the host, argument and binding checks, the two launches
 //   csi_regions.hip       per-region ice integrals: argument and binding checks, the two launches, the combine over the ranks
+//   csi_tracers.hip       advected ice tracers: argument checks, the library-owned c* and Psi^- arrays, the two halves of a stage
 //   csi_slots.h     the field slots: id, display name, location and roles of each, one row per slot
 //   csi_mem.h       DeviceBuf / PinnedBuf: the owner of every allocation the library makes
 #pragma once
@@ -304,6 +305,23 @@ struct csi_context {
     DeviceBuf<double> regions_part;
     PinnedBuf<double> regions_host;
     int64_t region_launches = 0;
+    // csi_tracers_set (csi_tracers.hip): the caller's description, the parent of h it was checked against, the dense c* of a stage and
+    // the Psi^- copies c^- (n parents), both allocated by csi_tracers_set; the launches so far and the last stencil launch's layout
+    struct Tracers {
+        bool set = false;
+        csi_tracers t{};
+        Bound shape;
+        long grid_gen = 0;
+        DeviceBuf<double> star, base;
+        DeviceBuf<double> free_;             // RK3: the stage before, without its source (n parents; empty while no tracer has a source)
+        bool free_valid = false;             // ... has been written since csi_cache_current_fields (the second stage on)
+        bool star_from_cache = false;        // the pending first half was an RK3 stage's
+        int64_t star_ld = 0, star_plane = 0;
+        bool star_valid = false;             // a first half has run since the last second half
+        bool base_valid = false;             // csi_cache_current_fields has copied c -> c^- since csi_tracers_set
+        int64_t stencil_launches = 0, update_launches = 0;
+        TracerLayout last{0, 0, 0, 0};
+    } trc;
     int64_t mterm_launches = 0, mterm_budget_calls = 0;
     // csi_output_* (csi_output.hip): the sets and the copy stream their records leave on, made at the first csi_output_create
     OutputSet out_sets[kMaxOutputSets];
@@ -364,6 +382,7 @@ struct csi_context {
                     band_fused = -1,      // CSI_BAND_FUSED=0: the fold band on the three kernels + two copies per step (rounds 4-6a); default: six launches per step without copies, loads hoisted (csi_fold.hip band_substeps_fused)
                     band_event_flags = -1,   // CSI_BAND_EVENT_FLAGS (csi_fold.hip ensure_band)
                     enth_path = 0,         // CSI_ENTH_PATH: the form of the enthalpy-method column model's step kernel (0 by the rule, 1 per step, 2 on chip)
+                    trc_ntr = -1,          // CSI_TRACERS_NTR: tracers per thread of the tracer stencil kernel (1 / 2 / 4; default by the number of tracers)
                     no_geom_sig = -1;      // debugging aid (CSI_DEBUG_NO_GEOM_SIG=1): skip the launch-geometry check of the peer set-up (tests/test_gpu_local_tiles.py)
       long adv_stage_max_cells = 1L << 40;      // advection-only models: one launch per RK stage up to this many cells (advect_stage_supported; no cut since round 6)
     } tune;
@@ -563,6 +582,14 @@ void series_release(csi_context* c);                     // csi_time_series.hip:
 bool series_drives(const csi_context* c, int fid);       // ... a series of either kind (model grid, regridded) is set on the slot
 void enthalpy_release(csi_context* c);                   // csi_enthalpy.hip: every surviving column model (the context's stream has been drained)
 void output_release(csi_context* c);                     // csi_output.hip: every set, the copy stream (the context's stream has been drained)
+// csi_tracers.hip: the halves of a stage (include/csi.h), the Psi^- copies, update_state!'s mask and halo fill outside a step, and
+// CSI_TRACER_FIELD(k) as an output field
+int32_t tracers_first_half(csi_context* c, int scheme, double dt, int from_cache);
+int32_t tracers_second_half(csi_context* c, double dt);
+int32_t tracers_cache(csi_context* c);
+int32_t tracers_update_state(csi_context* c);
+bool tracer_field_id(int32_t id, int* k);
+Bound tracer_bound(const csi_context* c, int k);
 int32_t peer_check_entry(csi_context* c);      // (csi_abi.hip: the error word of the peer transport, checked at every entry point)
 
 }  // namespace csi_host

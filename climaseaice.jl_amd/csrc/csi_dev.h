@@ -205,16 +205,22 @@ __device__ __forceinline__ int image_hi(int mode, int i, int N, int H, bool& has
 // sit in four fixed slots -- x low, x high, y low, y high -- and nothing is indexed at run time: the rule needs no scratch memory.
 // An IMG_VALUE side reflects what it copies about twice its value, x before y.
 __device__ __forceinline__ double image_value(int mode, double bc, double w) { return mode == IMG_VALUE ? 2 * bc - w : w; }
+// whether element (i, j) has any image at all: within H of an edge (one row more below a north fold).  The test is cheap and almost
+// always false; kernels that store several elements at once (tracers.hip) ask it before they choose a wide store.
+__device__ __forceinline__ bool has_halo_images(const GridDev& g, const ImageSpec& im, int i, int j) {
+    const bool in_x = (i >= 1) & (i <= g.Nx), in_y = (j >= 1) & (j <= g.Ny);
+    const bool near_x = in_x & ((i <= g.Hx) | (i > g.Nx - g.Hx));
+    const bool near_y = in_y & ((j <= g.Hy) | (j > g.Ny - g.Hy - (im.yhi == IMG_FOLD ? 1 : 0)));
+    return near_x | near_y;
+}
 __device__ __forceinline__ void store_with_images(const FRef& f, const GridDev& g, const ImageSpec& im, int i, int j, double val) {
     f(i, j) = val;
-    // Elements within H of an edge have halo images; the test is cheap and almost always false.
+    // Elements within H of an edge have halo images (has_halo_images).
     // x-images exist for interior columns (any row, including the ring rows a tile recomputes for
     // its neighbours), y-images for interior rows; corners are the product of the two.
     const bool in_x = (i >= 1) & (i <= g.Nx), in_y = (j >= 1) & (j <= g.Ny);
-    const bool near_x = in_x & ((i <= g.Hx) | (i > g.Nx - g.Hx));
     const bool fold = im.yhi == IMG_FOLD;
-    const bool near_y = in_y & ((j <= g.Hy) | (j > g.Ny - g.Hy - (fold ? 1 : 0)));
-    if (!(near_x | near_y)) return;
+    if (!has_halo_images(g, im, i, j)) return;
     if (fold & in_x & in_y) {
         // North fold (Zipper; recalled upstream semantics, oracle/csi_oracle.c fold_north): the owner of (i, j) writes
         //   c[it, 2 Ny - j] (Center in y, rows Ny-Hy .. Ny-1) / c[it, 2 Ny + 1 - j] (Face in y, rows Ny-Hy+1 .. Ny)

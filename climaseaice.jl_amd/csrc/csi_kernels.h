@@ -436,4 +436,37 @@ struct RegionsDev {
 // the two launches: records into D.part, the (n_regions + 1) x RQ_COUNT folded slots into out (device memory)
 void launch_regions(const RegionsDev& D, double* out, hipStream_t s);
 
+// advected ice tracers (tracers.hip; include/csi.h csi_tracers_tendencies / csi_tracers_update).  Every tracer array has the row stride
+// ld of the array bound to CSI_F_H: c, cb (the base c^-: the tracer itself under FE, the library's Psi^- copy under RK3) and G are
+// (0, 0)-offset addresses, G[k] == nullptr where the tendency is not stored.  cin: what the stencil reads -- the tracer itself, or under RK3
+// from the second stage on, for a tracer with a source, the library's source-free copy of the stage before; cfree: where the second half
+// stores that copy (nullptr: not stored).  star: the dense c* of the stage -- tracer k, cell (i, j)
+// at star[k * star_plane + (i - 1) + (j - 1) * star_ld], star_ld and star_plane even, so that a pair of cells (odd i, i + 1) is 16-byte aligned.
+constexpr int kTracersMax = 8;
+struct TracersDev {
+    GridDev g;
+    FRef u, v;
+    FRef a;                    // the concentration of the stage's input (the weight of the stencil values) / of its end (second half)
+    FRef ab, Ga;               // the base aice^- and the tendency just written (BY_CONCENTRATION)
+    ImageSpec im;
+    int n, scheme, w32, pad_;
+    double dt;
+    long ld;
+    double* c[kTracersMax];
+    double* cin[kTracersMax];
+    double* cfree[kTracersMax];
+    double* cb[kTracersMax];
+    double* G[kTracersMax];
+    double* star;
+    long star_ld, star_plane;
+    int weighting[kTracersMax], nonnegative[kTracersMax];
+    double source[kTracersMax];
+};
+static_assert(sizeof(TracersDev) <= 4096, "the description travels by value as the kernel argument");
+// what a stencil launch used (csi_tracers_last): tracers per thread, the cells of a flux tile, tracer groups on blockIdx.z
+struct TracerLayout { int ntr, tx, ty, groups; };
+TracerLayout launch_tracers_tendencies(const TracersDev& T, int mode, int force_ntr, hipStream_t s);
+void launch_tracers_star_noadv(const TracersDev& T, hipStream_t s);
+void launch_tracers_finish(const TracersDev& T, hipStream_t s);
+
 }  // namespace csi

@@ -626,6 +626,8 @@ int32_t do_update_state(csi_context* c, bool in_step, bool tracers_filled) {
     if (vel) { add(CSI_F_U); add(CSI_F_V); }
     launch_fill_halo_batch(B, c->g, c->stream);
     HIP_TRY(c, hipGetLastError());
+    // advected tracers: masked and imaged like hs; inside a step the second half's stores have done both (csi_tracers.hip)
+    if (c->trc.set && !in_step && (rc = tracers_update_state(c))) return rc;
     if (is_tiled(c)) {                                      // the MPI part of fill_halo_regions!, sea_ice_model.jl:383
         int ff[5] = {CSI_F_H, CSI_F_A, CSI_F_U, CSI_F_V, CSI_F_HS};
         int n = vel ? 4 : 2;

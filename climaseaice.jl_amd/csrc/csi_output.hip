@@ -40,6 +40,13 @@ void output_release(csi_context* c) {
     if (c->out_stream) { hipStreamDestroy(c->out_stream); c->out_stream = nullptr; }
 }
 
+// A field of a set: a slot, or CSI_TRACER_FIELD(k) once tracers are set (a (Center, Center) array of h's shape; csi_tracers.hip).  Its
+// binding now, its name in messages, whether the id names anything, and whether it is a (Center, Center) field.
+static Bound out_bound(const csi_context* c, int32_t id) { int k; return tracer_field_id(id, &k) ? tracer_bound(c, k) : c->f[id]; }
+static std::string out_name(int32_t id) { int k; return tracer_field_id(id, &k) ? "tracer " + std::to_string(k) : std::string(slot_name(id)); }
+static bool out_known(int32_t id) { int k; return tracer_field_id(id, &k) || slot_known(id); }
+static bool out_center(int32_t id) { int k; return tracer_field_id(id, &k) || (slot_loc(id, 0) == LOC_C && slot_loc(id, 1) == LOC_C); }
+
 // the set of a handle (null + error: a bad handle); `check`: also refuse a set whose fields or grid have changed since it was made
 static OutputSet* set_of(csi_context* c, int32_t handle, bool check = true) {
     if (handle < 1 || handle > kMaxOutputSets || !c->out_sets[handle - 1].live) {
@@ -53,10 +60,10 @@ static OutputSet* set_of(csi_context* c, int32_t handle, bool check = true) {
         return nullptr;
     }
     for (int k = 0; k < S->n; ++k) {
-        const Bound& b = c->f[S->f[k].field_id];
+        const Bound b = out_bound(c, S->f[k].field_id);
         const Bound& s = S->sig[k];
         if (b.p != s.p || b.ld != s.ld || b.ni != s.ni || b.nj != s.nj) {
-            fail(c, CSI_ERR_INVALID_ARGUMENT, std::string("output: field ") + slot_name(S->f[k].field_id) +
+            fail(c, CSI_ERR_INVALID_ARGUMENT, std::string("output: field ") + out_name(S->f[k].field_id) +
                                                   " was re-bound after csi_output_create -- the set is invalid; destroy it and create it again");
             return nullptr;
         }
@@ -102,13 +109,13 @@ int32_t csi_output_create(csi_context* c, const csi_output_field* fields, int32_
     int32_t nx[kMaxOutputFields], ny[kMaxOutputFields], dt[kMaxOutputFields];
     for (int k = 0; k < n; ++k) {
         const csi_output_field& f = fields[k];
-        if (!slot_known(f.field_id)) return fail(c, CSI_ERR_INVALID_ARGUMENT, "output: unknown field id at position " + std::to_string(k));
+        if (!out_known(f.field_id)) return fail(c, CSI_ERR_INVALID_ARGUMENT, "output: unknown field id at position " + std::to_string(k));
         if (f.dtype != CSI_OUT_F64 && f.dtype != CSI_OUT_F32)
-            return fail(c, CSI_ERR_INVALID_ARGUMENT, std::string("output: field ") + slot_name(f.field_id) + ": unknown dtype (CSI_OUT_F64 or CSI_OUT_F32)");
-        if (f.masked && (slot_loc(f.field_id, 0) != LOC_C || slot_loc(f.field_id, 1) != LOC_C))
-            return fail(c, CSI_ERR_INVALID_ARGUMENT, std::string("output: field ") + slot_name(f.field_id) + ": masking is for (Center, Center) fields only");
-        const Bound& b = c->f[f.field_id];
-        if (!b.p) return fail(c, CSI_ERR_NOT_BOUND, std::string("output: field ") + slot_name(f.field_id) + " is not bound");
+            return fail(c, CSI_ERR_INVALID_ARGUMENT, std::string("output: field ") + out_name(f.field_id) + ": unknown dtype (CSI_OUT_F64 or CSI_OUT_F32)");
+        if (f.masked && !out_center(f.field_id))
+            return fail(c, CSI_ERR_INVALID_ARGUMENT, std::string("output: field ") + out_name(f.field_id) + ": masking is for (Center, Center) fields only");
+        const Bound b = out_bound(c, f.field_id);
+        if (!b.p) return fail(c, CSI_ERR_NOT_BOUND, std::string("output: field ") + out_name(f.field_id) + " is not bound");
         nx[k] = b.ni - 2 * c->Hx; ny[k] = b.nj - 2 * c->Hy; dt[k] = f.dtype;
     }
     int at = -1;
@@ -121,7 +128,7 @@ int32_t csi_output_create(csi_context* c, const csi_output_field* fields, int32_
     plan_layout(nx, ny, dt, n, S.off, &S.record_bytes);
     int64_t acc = 0;
     for (int k = 0; k < n; ++k) {
-        S.f[k] = fields[k]; S.sig[k] = c->f[fields[k].field_id]; S.nx[k] = nx[k]; S.ny[k] = ny[k];
+        S.f[k] = fields[k]; S.sig[k] = out_bound(c, fields[k].field_id); S.nx[k] = nx[k]; S.ny[k] = ny[k];
         S.acc_off[k] = acc;
         if (fields[k].averaged) { S.any_averaged = true; acc += ((int64_t)nx[k] * ny[k] + 1) / 2 * 2; }
     }

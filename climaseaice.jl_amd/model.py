@@ -392,8 +392,11 @@ class SeaIceModel:
     def __init__(self, grid, dynamics=None, advection=None, timestepper="SplitRungeKutta3", sea_ice_density=900.0,
                  ice_thermodynamics=None, snow_thermodynamics=None, snow_density=330.0, snowfall=0.0,
                  boundary_conditions=None, forcing=None, device="cuda:0", mode="fast", stream=None, top_heat_flux=None,
-                 bottom_heat_flux=None, ocean=None):
+                 bottom_heat_flux=None, ocean=None, tracers=None):
         self.grid = grid
+        # tracers: names or csi.Tracer / csi.IceAge specs, advected on the device (tracers.py; include/csi.h); refused before anything is allocated
+        from .tracers import tracer_specs
+        self.tracer_specs = tracer_specs(tracers, grid)
         # dynamics: None (prescribed velocities), a SeaIceMomentumEquation, or StressBalanceFreeDrift(top_momentum_stress = ...,
         # bottom_momentum_stress = ...) as the whole dynamics (stress_balance_free_drift.jl:131-151)
         if isinstance(dynamics, StressBalanceFreeDrift):
@@ -453,6 +456,11 @@ class SeaIceModel:
                                                intercepted_snowfall=CenterField(grid, dev, "intercepted_snowfall"))
             self.snow_top_temperature = CenterField(grid, dev, "Tu_snow")
             self.ice_top_temperature = CenterField(grid, dev, "Tu")
+        # advected tracers: name -> CenterField, in the order given (model.tracer(name)); their tendencies in Gn.<name> and csi_tracers_set
+        # in _configure.  Empty: none of the tracer calls is ever made
+        self.tracers = OrderedDict((t.name, CenterField(grid, dev, t.name)) for t in self.tracer_specs)
+        for t in self.tracer_specs:
+            setattr(Gn, t.name, CenterField(grid, dev, "G" + t.name))
         self.clock = SimpleNamespace(time=0.0, iteration=0)
         self.output_writers = OrderedDict()      # key -> output.OutputWriter, driven by time_step (empty: nothing is called)
         self.drifters = None                     # a drifters.Drifters: time_step advances them with the step's dt (None: no call)
@@ -473,6 +481,9 @@ class SeaIceModel:
         self.ctx = _lib.Context(dev.index or 0, stream)
         self._configure()
         self._attach_pending_series()
+        if self.tracer_specs:
+            from .tracers import attach
+            attach(self)
         self.set_mode(mode)
         self.ctx.call("csi_set_weno_weight_dtype", 1 if getattr(advection, "weight_dtype", "f64") == "f32" else 0)
         torch.cuda.synchronize(self.device)   # field initialisation ran on torch's stream
@@ -1082,6 +1093,12 @@ class SeaIceModel:
         from .momentum_terms import momentum_budget
         return momentum_budget(self, what)
 
+    def tracer(self, name):
+        """The CenterField of an advected tracer by name (SeaIceModel(..., tracers = ...); tracers.py)."""
+        if name not in self.tracers:
+            raise KeyError(f"tracer: the model has no tracer named {name!r} (it has: {', '.join(self.tracers) or 'none'})")
+        return self.tracers[name]
+
     def synchronize(self):
         """Wait for the library's stream (call before reading fields with torch / numpy)."""
         self.ctx.call("csi_sync")
@@ -1100,6 +1117,7 @@ def set_(model, **kw):
              "\u05d0": model.ice_concentration, "u": model.velocities.u, "v": model.velocities.v}
     if model.snow_thickness is not None:
         names["hs"] = model.snow_thickness
+    names.update(getattr(model, "tracers", {}))
     for k, val in kw.items():
         if k not in names:
             raise KeyError(f"set!: unknown field {k}")
@@ -1117,11 +1135,14 @@ def update_state(model):
 def _state_fields(model):
     """name -> Field of what Oceananigans.prognostic_state(model) saves (sea_ice_model.jl:414-426): velocities, ice
     thickness / concentration, snow thickness, the time stepper's G^n and Psi^-, the dynamics' auxiliary fields, the mass fluxes,
-    the thermodynamics' top surface temperatures.  Not mirrored: `tracers` (the HIP path advects h, aice, hs only; a model with
-    further tracers is not attached) and the clock's fields beyond (time, iteration)."""
+    the thermodynamics' top surface temperatures, and "tracers.<name>" for the advected tracers of a model that has them (tracers.py;
+    their tendencies travel with G^n, and the library's Psi^- copies are rebuilt by every RK3 step).  Not mirrored: the clock's fields
+    beyond (time, iteration)."""
     out = {"u": model.velocities.u, "v": model.velocities.v, "h": model.ice_thickness, "aice": model.ice_concentration}
     if model.snow_thickness is not None:
         out["hs"] = model.snow_thickness
+    for name, f in getattr(model, "tracers", {}).items():
+        out["tracers." + name] = f
     for k, f in vars(model.timestepper.Gn).items():
         out["Gn." + k] = f
     if model.timestepper.Psi_minus is not None:

@@ -217,6 +217,8 @@ def bound_fields(model):
     from .momentum_terms import slot_of as term_slot_of
     for name, f in getattr(model, "_momentum_term_fields", {}).items():      # momentum term fields, once allocated (model.momentum_term)
         out[name] = (f, term_slot_of(name))
+    for k, (name, f) in enumerate(getattr(model, "tracers", {}).items()):      # advected tracers (tracers.py): CSI_TRACER_FIELD(k), no slot
+        out[name] = (f, f"TRACER:{k}")
     return out
 
 

@@ -1622,6 +1622,88 @@ int32_t csi_regions_layout(int32_t Nx, int32_t Ny, int32_t n_regions, int64_t* r
 int32_t csi_regions_compute(csi_context* ctx, const csi_regions* r, double extent_threshold, csi_region_record* out, int64_t* unassigned_cells);
 int32_t csi_regions_stats(csi_context* ctx, int64_t* launches);
 
+/* ---- advected ice tracers and ice age ---------------------------------------------------------------------------------------------------
+ * Properties carried WITH the ice: a dye, the age of the ice.  SeaIceModel(grid; tracers = ...) of the reference makes its tracers
+ * prognostic fields (sea_ice_model.jl:151, 164-189) but never steps them: its tendency kernel ignores the argument
+ * (tracer_tendency_kernel_functions.jl:27-45).  So THIS COMMENT IS THE DEFINITION.  It is not free-floating: the reference has exactly
+ * one generic third tracer, the snow thickness hs -- tendency -horizontal_div_Uc(hs) (:49-52), update max(0, hs^- + dt G), zero where
+ * aice <= 0 (sea_ice_fe_step.jl:86-94) -- and a PLAIN tracer follows that rule statement for statement; tests/tracers_ref.py restates
+ * both halves below in NumPy with G taken from the oracle's hs.
+ * Nothing here changes another entry point: a context without tracers launches exactly what it launched before.
+ *
+ * Up to CSI_TRACERS_MAX = 8 tracers.  Each is a (Center, Center) device array of the CALLER's with the parent shape of the array bound to
+ * CSI_F_H (same leading dimension, rows, halos); G[k], where given, likewise.  Per tracer:
+ *   weighting    CSI_TRACER_PLAIN (0) | CSI_TRACER_BY_CONCENTRATION (1)
+ *   nonnegative  0 | 1
+ *   source       a rate per second (finite)
+ *
+ * One stage with stage step dtau uses BASE fields c^-, aice^-: under RK3 (from_cache) the base is Psi^- -- c^- a library-owned copy
+ * made by csi_cache_current_fields, aice^- = CSI_F_AM --, under FE the current fields.
+ *
+ * FIRST HALF (csi_tracers_tendencies).  It runs where compute_tracer_tendencies! runs: after the h / aice tendency launch and BEFORE the
+ * momentum step, so it sees the velocities, scheme, weight dtype and mode h sees.
+ *   PLAIN:             G = -horizontal_div_Uc(c);   c* = c^- + dtau * G
+ *   BY_CONCENTRATION:  q = aice * c at every stencil point (ONE rounded product, never contracted into the reconstruction);
+ *                      G = -horizontal_div_Uc(q);
+ *                      aice* = aice^- + dtau * Ga, Ga the array bound to CSI_F_GA as just written: the tracer update's own expression
+ *                      BEFORE its clips;
+ *                      c* = aice* > 0 ? ((aice^- * c^-) + dtau * G) / aice* : 0, an IEEE division in both modes.
+ *                      Ridging (aice* > 1 -> 1) therefore leaves c unchanged.
+ *   c* goes to a library-owned interior array; G goes to the caller's G[k] where one is given (NULL: not stored).
+ *   scheme == 0: G = 0 and no stencil launch is made (c* is formed by one point-wise launch, counted with the update launches).
+ * SECOND HALF (csi_tracers_update).  It runs at the end of the stage, after the thermodynamic step and before update_state!, and reads
+ * the stage-final aice:
+ *   x = nonnegative ? jmax(0, c*) : c*           (jmax: Julia's max, NaN if either is NaN)
+ *   c = (aice > 0 and the cell is active) ? x + dtau * source : 0
+ *   and the store writes the local halo images, as hs gets them.
+ * Without thermodynamics and with source = 0, nonnegative = 1, PLAIN this is dynamic_step_snow! followed by update_state!'s mask, bit
+ * for bit.  STRICT: the oracle's operations; FAST: the reconstructions of the FAST h / aice tendencies (|dG| <= 1e-12 max|G|), the
+ * update's arithmetic the same code in both modes.
+ * RK3: every stage restarts from Psi^- with its own dtau, so the LAST stage is the step's result and a source accrues dt per step, not
+ * 11/6 of it (the argument made for the mixed layer above).  For that to hold for ice that MOVES as well, the source of one stage must not
+ * travel with the next stage's fluxes: from the second stage on, the stencil of a tracer with source != 0 reads the stage before WITHOUT
+ * its source -- the second half also stores  (aice > 0 and the cell is active) ? x : 0  with its halo images into a library-owned array,
+ * and that array is the stencil's input until the next csi_cache_current_fields.  (Otherwise ice that enters an ice-free cell brings the
+ * earlier stages' increments with it and ends the step with 11/6 dt of age.)  The first stage, ForwardEuler and tracers without a source
+ * read the tracer itself.  Hence 0 <= age <= t under both steppers for a scheme whose reconstruction is a convex combination, and to the
+ * WENO-Z inhomogeneity (about 2e-8 per stencil evaluation for WENO7) otherwise.
+ * STATED LIMITS.  Growth does not dilute c.  There is no volume weighting: V = h aice is not transported conservatively by the
+ * reference, so q / V would not keep a uniform field uniform.  PLAIN tracers are densities: in divergent flow a uniform plain tracer
+ * does not stay uniform -- the reference's hs behaviour.
+ *
+ * csi_tracers_set(ctx, t) copies the struct (t == NULL removes the tracers).  csi_time_step_fe / _rk3 then run both halves where
+ * stated, csi_cache_current_fields also copies c -> c^- (a copy batch of its own), csi_update_state images and masks the tracers as it
+ * does hs, and a context with tracers takes the general stage loop (csi_last_advection reports stage_fused = 0).
+ * csi_tracers_stats: launches of the stencil kernel / of the point-wise kernels so far; csi_tracers_last: what the last stencil launch
+ * used -- tracers per thread (1, 2 or 4), the cells of a flux tile, the tracer groups (blockIdx.z).  Results do not depend on them.
+ * Output: csi_output_field.field_id also accepts CSI_TRACER_FIELD(k) once tracers are set (snapshot, average, masked fill, as for any
+ * (Center, Center) field); csi_tracers_set after csi_output_create invalidates such a set, like a re-bind.
+ * ERRORS, by name.  CSI_ERR_INVALID_ARGUMENT: n outside 1 .. 8, a NULL c[k], an unknown weighting or nonnegative value, a non-finite
+ * source, arrays that alias each other or h, aice, hs as bound at the call (fields bound later and the tendency arrays Gh, Ga are not
+ * checked), an array whose device allocation ends before a whole parent of h behind the pointer -- a sub-allocating allocator's large
+ * blocks pass this test: it catches a gross mistake, not every short array --, a dt that is not finite.  CSI_ERR_NOT_BOUND: the grid, h, aice (their shape is
+ * the tracers'), and at a step u, v, CSI_F_GA (BY_CONCENTRATION), CSI_F_AM (from_cache).  CSI_ERR_UNSUPPORTED: tiled contexts, whichever
+ * of csi_tile_set / csi_tracers_set comes second.
+ * NOT BUILT: tiles and multi-GPU; tracer integrals in diagnostics or regions; per-tracer schemes; time-series or array-valued sources;
+ * volume weighting; tracers in the fused advection-only stage launch; tracers as bound slots. */
+#define CSI_TRACERS_MAX 8
+#define CSI_TRACER_PLAIN 0
+#define CSI_TRACER_BY_CONCENTRATION 1
+#define CSI_TRACER_FIELD(k) (4096 + (k))
+typedef struct {
+    int32_t n;                             /* 1 .. CSI_TRACERS_MAX */
+    double* c[CSI_TRACERS_MAX];            /* device, parent shape of CSI_F_H */
+    double* G[CSI_TRACERS_MAX];            /* device, the same shape; NULL: the tendency is not stored */
+    int32_t weighting[CSI_TRACERS_MAX];
+    int32_t nonnegative[CSI_TRACERS_MAX];
+    double source[CSI_TRACERS_MAX];
+} csi_tracers;
+int32_t csi_tracers_set(csi_context* ctx, const csi_tracers* t);
+int32_t csi_tracers_tendencies(csi_context* ctx, int32_t scheme, double dt, int32_t from_cache);
+int32_t csi_tracers_update(csi_context* ctx, double dt);
+int32_t csi_tracers_stats(csi_context* ctx, int64_t* stencil_launches, int64_t* update_launches);
+int32_t csi_tracers_last(csi_context* ctx, int32_t* tracers_per_thread, int32_t* tile_x, int32_t* tile_y, int32_t* groups);
+
 #ifdef __cplusplus
 }
 #endif

@@ -440,11 +440,11 @@ const ArrayLike = Union{Field, FieldTimeSeries}
 stress_struct(τ::NamedTuple{(:u, :v), <:Tuple{ArrayLike, ArrayLike}}) = CsiStress(2, 0, 0, 0, 0, 0, 0, 0, 0, 0)
 
 """
-    attach!(model) -> Context
+    attach!(model; tracer_specs = nothing) -> Context
 
 Describe `model` to the library once (grid, fields, parameters).  Field memory stays owned by Julia.
 """
-function attach!(model::SeaIceModel)
+function attach!(model::SeaIceModel; tracer_specs = nothing)
     ctx = Context()
     dyn = model.dynamics
     grid = model.velocities.u.grid
@@ -535,6 +535,8 @@ function attach!(model::SeaIceModel)
     end
     check(ctx, ccall((:csi_set_mode, libcsi), Int32, (Ptr{Cvoid}, Int32), ctx.handle, 1))   # CSI_MODE_FAST
     check(ctx, ccall((:csi_set_fusion, libcsi), Int32, (Ptr{Cvoid}, Int32), ctx.handle, 2)) # two sub-steps per launch (default)
+    # user tracers: the reference never steps them; with specs the library advects them, without the attach raises by name
+    attach_tracers!(ctx, model, tracer_specs)
     return ctx
 end
 
@@ -634,7 +636,7 @@ wrap_row(grid, j) = topology(grid, 2) == Periodic ? mod1(j, grid.Ny) : j
 
 # One context per model, created on first use.
 const CONTEXTS = IdDict{Any, Context}()
-context(model) = get!(() -> attach!(model), CONTEXTS, model)
+context(model; tracer_specs = nothing) = get!(() -> attach!(model; tracer_specs), CONTEXTS, model)      # (tracer_specs: read by the attach only -- call context(model; tracer_specs = ...) before the first step)
 
 # ---- a solver tag that selects the HIP path by dispatch -------------------------------------------
 """
@@ -1262,6 +1264,69 @@ function region_launches(model::HIPSeaIceModel)
     n = Ref{Int64}(0)
     check(ctx, ccall((:csi_regions_stats, libcsi), Int32, (Ptr{Cvoid}, Ref{Int64}), ctx.handle, n))
     return n[]
+end
+
+# ---- advected ice tracers and ice age (include/csi.h: csi_tracers_set, "advected ice tracers and ice age") -----------------------------------
+# SeaIceModel(grid; tracers = ...) makes its tracers prognostic fields (sea_ice_model.jl:151, 164-189) and never steps them: the tendency
+# kernel ignores the argument (tracer_tendency_kernel_functions.jl:27-45).  attach_tracers!(ctx, model, specs) hands them to the library,
+# which then advects them inside csi_time_step_fe / _rk3 by the rule include/csi.h states.  `specs`: a NamedTuple name => (weighting =
+# :plain | :concentration, nonnegative = true | false, source = a rate per second), one entry per tracer of model.tracers, in its order.
+# Give them once, before the model's first step: ClimaSeaIceHIP.context(model; tracer_specs = specs).
+# A model with user tracers and NO specs raises by name: an attach must not start stepping what the reference leaves alone, silently.
+const TRACERS_MAX = 8
+const TRACER_PLAIN = Int32(0)
+const TRACER_BY_CONCENTRATION = Int32(1)
+tracer_field(k) = Int32(4096 + k)       # CSI_TRACER_FIELD(k): tracer k (0-based) as a csi_output_field id
+# csi_tracers: the caller's arrays (parent shape of h) and per-tracer flags
+struct CsiTracers
+    n::Int32
+    pad::Int32
+    c::NTuple{8, Ptr{Cdouble}}
+    G::NTuple{8, Ptr{Cdouble}}
+    weighting::NTuple{8, Int32}
+    nonnegative::NTuple{8, Int32}
+    source::NTuple{8, Cdouble}
+end
+@assert sizeof(CsiTracers) == 264      # the layout gcc gives csi_tracers
+
+ice_age_spec(; units = :s) = (weighting = :concentration, nonnegative = true, source = units == :days ? 1 / 86400 : 1.0)
+
+function attach_tracers!(ctx, model, specs = nothing)
+    names = keys(model.tracers)
+    isempty(names) && return nothing
+    isnothing(specs) && error("attach_tracers!: the model has tracers $(names), which the reference never steps; give specs " *
+                              "(name = (weighting = :plain | :concentration, nonnegative = true, source = 0.0), ...) to have the library advect them")
+    length(names) <= TRACERS_MAX || error("attach_tracers!: at most $TRACERS_MAX tracers, the model has $(length(names))")
+    keys(specs) == names || error("attach_tracers!: specs name $(keys(specs)), the model's tracers are $(names)")
+    pad(v, z) = ntuple(k -> k <= length(v) ? v[k] : z, 8)
+    null = Ptr{Cdouble}(C_NULL)
+    c = [Ptr{Cdouble}(pointer(parent(model.tracers[n]))) for n in names]
+    G = [haskey(model.timestepper.Gⁿ, n) ? Ptr{Cdouble}(pointer(parent(model.timestepper.Gⁿ[n]))) : null for n in names]
+    w = [specs[n].weighting == :concentration ? TRACER_BY_CONCENTRATION :
+         specs[n].weighting == :plain ? TRACER_PLAIN : error("attach_tracers!: tracer $n: weighting must be :plain or :concentration") for n in names]
+    nn = [Int32(specs[n].nonnegative ? 1 : 0) for n in names]
+    src = [Float64(specs[n].source) for n in names]
+    t = Ref(CsiTracers(Int32(length(names)), Int32(0), pad(c, null), pad(G, null), pad(w, Int32(0)), pad(nn, Int32(0)), pad(src, 0.0)))
+    GC.@preserve model check(ctx, ccall((:csi_tracers_set, libcsi), Int32, (Ptr{Cvoid}, Ref{CsiTracers}), ctx.handle, t))
+    return nothing
+end
+detach_tracers!(ctx) = check(ctx, ccall((:csi_tracers_set, libcsi), Int32, (Ptr{Cvoid}, Ptr{Cvoid}), ctx.handle, C_NULL))
+
+# the two halves of a stage, stand-alone (the step entries run them where include/csi.h states)
+tracers_tendencies!(ctx, scheme, Δt, from_cache = false) =
+    check(ctx, ccall((:csi_tracers_tendencies, libcsi), Int32, (Ptr{Cvoid}, Int32, Cdouble, Int32), ctx.handle, Int32(scheme), Float64(Δt), Int32(from_cache)))
+tracers_update!(ctx, Δt) = check(ctx, ccall((:csi_tracers_update, libcsi), Int32, (Ptr{Cvoid}, Cdouble), ctx.handle, Float64(Δt)))
+
+function tracer_launches(ctx)
+    a, b = Ref{Int64}(0), Ref{Int64}(0)
+    check(ctx, ccall((:csi_tracers_stats, libcsi), Int32, (Ptr{Cvoid}, Ref{Int64}, Ref{Int64}), ctx.handle, a, b))
+    return (stencil = a[], update = b[])
+end
+
+function last_tracer_launch(ctx)
+    nt, tx, ty, g = Ref{Int32}(0), Ref{Int32}(0), Ref{Int32}(0), Ref{Int32}(0)
+    check(ctx, ccall((:csi_tracers_last, libcsi), Int32, (Ptr{Cvoid}, Ref{Int32}, Ref{Int32}, Ref{Int32}, Ref{Int32}), ctx.handle, nt, tx, ty, g))
+    return (tracers_per_thread = Int(nt[]), tile_x = Int(tx[]), tile_y = Int(ty[]), groups = Int(g[]))
 end
 
 # Checkpointing (sea_ice_model.jl:414-445: prognostic_state / restore_prognostic_state!) needs nothing from the library: the
