@@ -18,8 +18,17 @@ Within a component the viscous sub-step is Jacobi: every point reads the OLD val
 deliberate departure from the reference's in-place kernel, whose result depends on scheduling; include/csi.h); between the
 components it is Gauss-Seidel in the parity order of split_explicit_momentum_equations.jl:178.
 Arrays are (nj, ni), element (i, j) (1-based) at a[j + Hy - 1, i + Hx - 1], as in oracle_np.py.
+
+The number type is a parameter.  Ref(p, ..., num=float) is the restatement above.  Ref(p, ..., num=fast_math_ref.CTX) evaluates the
+same expressions, in the same order, in that `decimal` context (80 digits, one rounding per operation, the square root of the drag
+norm included): every input is the same double, converted exactly, so the result is the truth that STRICT and FAST both approximate.
+What a step stores goes into the problem's double arrays rounded once (the next launch reads doubles); the unrounded values of the
+last tendency / component step are kept in `self.q` ("u", "v", "Gu", "Gv": object arrays over the interior).  The exact path has no
+free drift: that value comes from the C oracle, in double.
 """
+import contextlib
 import ctypes as C
+import decimal
 import math
 
 import numpy as np
@@ -30,24 +39,48 @@ EPS64 = 2.220446049250313e-16
 CC, FC, CF, FF = (O.CENTER, O.CENTER), (O.FACE, O.CENTER), (O.CENTER, O.FACE), (O.FACE, O.FACE)
 
 
+def rel_error(Q, exact, ctx):
+    """max|Q - exact| / max|exact| over the interior: Q an array of doubles, exact the object array of Decimals of Ref.q (evaluated in
+    `ctx`, the differences formed there before anything is rounded to double).  A non-finite Q gives inf."""
+    Q = np.asarray(Q, dtype=np.float64)
+    assert Q.shape == exact.shape
+    if not np.all(np.isfinite(Q)):
+        return math.inf
+    with decimal.localcontext(ctx):
+        worst = max(abs(decimal.Decimal(float(a)) - b) for a, b in zip(Q.ravel(), exact.ravel()))
+        scale = max(abs(b) for b in exact.ravel())
+        return float(worst / scale)
+
+
 class Ref:
-    def __init__(self, p, nu=1000.0, viscous=True):
-        self.p, self.s, self.nu, self.viscous = p, p.s, float(nu), viscous
+    def __init__(self, p, nu=1000.0, viscous=True, num=float):
+        self.p, self.s, self.viscous = p, p.s, viscous
         s = p.s
+        if num is float:
+            self.N, self.sqrt, self.nan, self.ctx = float, math.sqrt, math.nan, contextlib.nullcontext
+            self.szero = lambda x: math.copysign(0.0, x)
+        else:                                             # a decimal.Context: a double converts exactly, whatever the precision
+            assert isinstance(num, decimal.Context) and not s.free_drift_kind, "the exact path has no free drift"
+            self.N, self.sqrt, self.nan = (lambda x: decimal.Decimal(float(x))), (lambda x: x.sqrt()), decimal.Decimal("NaN")
+            self.ctx = lambda: decimal.localcontext(num)
+            self.szero = lambda x: decimal.Decimal(0).copy_sign(x)
+        self.zero = self.N(0.0)
+        self.nu = self.N(nu)
         self.Nx, self.Ny, self.Hx, self.Hy = s.Nx, s.Ny, s.Hx, s.Hy
         # metrics at every location over the parent index range (Ny + 2Hy + 1) x (Nx + 2Hx + 1), from the oracle's own operators
         ni, nj = s.Nx + 2 * s.Hx + 1, s.Ny + 2 * s.Hy + 1
         self.met = {}
         for w, fn in (("dx", p.L.ora_dx), ("dy", p.L.ora_dy), ("az", p.L.ora_az)):
             for loc in (CC, FC, CF, FF):
-                self.met[w, loc] = [[fn(p.ptr, loc[0], loc[1], i - s.Hx + 1, j - s.Hy + 1) for i in range(ni)] for j in range(nj)]
+                self.met[w, loc] = [[self.N(fn(p.ptr, loc[0], loc[1], i - s.Hx + 1, j - s.Hy + 1)) for i in range(ni)] for j in range(nj)]
         self.mask = p._mask if s.has_mask else None
         self.Gu = np.zeros_like(p.f["u"])
         self.Gv = np.zeros_like(p.f["v"])
+        self.q = {k: np.full((s.Ny, s.Nx), self.zero, dtype=object) for k in ("u", "v", "Gu", "Gv")}
 
     # ---- access ----------------------------------------------------------------------------------------------------------------
     def at(self, a, i, j):
-        return float(a[j + self.Hy - 1, i + self.Hx - 1])
+        return self.N(a[j + self.Hy - 1, i + self.Hx - 1])
 
     def m(self, w, loc, i, j):
         return self.met[w, loc][j + self.Hy - 1][i + self.Hx - 1]
@@ -83,19 +116,19 @@ class Ref:
     # ---- stresses (viscous_rheology.jl / stored sigma) behind conditional_flux_ccc / _ffc ----------------------------------------
     def ux(self, u, i, j):
         val = self.nu * (self.at(u, i + 1, j) - self.at(u, i, j)) if self.viscous else self.at(self.p.f["s11"], i, j)
-        return 0.0 if self.ipcc(i, j) else val
+        return self.zero if self.ipcc(i, j) else val
 
     def vy(self, v, i, j):
         val = self.nu * (self.at(v, i, j + 1) - self.at(v, i, j)) if self.viscous else self.at(self.p.f["s22"], i, j)
-        return 0.0 if self.ipcc(i, j) else val
+        return self.zero if self.ipcc(i, j) else val
 
     def uy(self, u, i, j):
         val = self.nu * (self.at(u, i, j) - self.at(u, i, j - 1)) if self.viscous else self.at(self.p.f["s12"], i, j)
-        return 0.0 if self.ipff(i, j) else val
+        return self.zero if self.ipff(i, j) else val
 
     def vx(self, v, i, j):
         val = self.nu * (self.at(v, i, j) - self.at(v, i - 1, j)) if self.viscous else self.at(self.p.f["s12"], i, j)
-        return 0.0 if self.ipff(i, j) else val
+        return self.zero if self.ipff(i, j) else val
 
     # ---- divergence, ice_stress_divergence.jl:36-51 ------------------------------------------------------------------------------
     def div1(self, u, v, i, j):
@@ -122,22 +155,22 @@ class Ref:
 
     def immersed1(self, i, j):
         if self.mask is None:
-            return 0.0
-        b = self.s.ibc_u
-        qW = (-b[0] if self.ipcc(i - 1, j) else 0.0) * self.m("dy", CC, i - 1, j)
-        qE = (b[1] if self.ipcc(i, j) else 0.0) * self.m("dy", CC, i, j)
-        qS = (-b[2] if self.ipff(i, j) else 0.0) * self.m("dx", FF, i, j)
-        qN = (b[3] if self.ipff(i, j + 1) else 0.0) * self.m("dx", FF, i, j + 1)
+            return self.zero
+        b = [self.N(x) for x in self.s.ibc_u]
+        qW = (-b[0] if self.ipcc(i - 1, j) else self.zero) * self.m("dy", CC, i - 1, j)
+        qE = (b[1] if self.ipcc(i, j) else self.zero) * self.m("dy", CC, i, j)
+        qS = (-b[2] if self.ipff(i, j) else self.zero) * self.m("dx", FF, i, j)
+        qN = (b[3] if self.ipff(i, j + 1) else self.zero) * self.m("dx", FF, i, j + 1)
         return (qE - qW + qN - qS) / self.m("az", FC, i, j)
 
     def immersed2(self, i, j):
         if self.mask is None:
-            return 0.0
-        b = self.s.ibc_v
-        qW = (-b[0] if self.ipff(i, j) else 0.0) * self.m("dy", FF, i, j)
-        qE = (b[1] if self.ipff(i + 1, j) else 0.0) * self.m("dy", FF, i + 1, j)
-        qS = (-b[2] if self.ipcc(i, j - 1) else 0.0) * self.m("dx", CC, i, j - 1)
-        qN = (b[3] if self.ipcc(i, j) else 0.0) * self.m("dx", CC, i, j)
+            return self.zero
+        b = [self.N(x) for x in self.s.ibc_v]
+        qW = (-b[0] if self.ipff(i, j) else self.zero) * self.m("dy", FF, i, j)
+        qE = (b[1] if self.ipff(i + 1, j) else self.zero) * self.m("dy", FF, i + 1, j)
+        qS = (-b[2] if self.ipcc(i, j - 1) else self.zero) * self.m("dx", CC, i, j - 1)
+        qN = (b[3] if self.ipcc(i, j) else self.zero) * self.m("dx", CC, i, j)
         return (qE - qW + qN - qS) / self.m("az", CF, i, j)
 
     # ---- external stresses, sea_ice_external_stress.jl:8-27,176-202 ---------------------------------------------------------------
@@ -145,7 +178,7 @@ class Ref:
         kind, val = (st.ue_kind, st.ue) if comp == "u" else (st.ve_kind, st.ve)
         if kind == O.VEL_FIELD:
             return self.at(self._arr(st.fu if comp == "u" else st.fv, comp), i, j)
-        return val if kind == O.VEL_CONST else 0.0
+        return self.N(val) if kind == O.VEL_CONST else self.zero
 
     @staticmethod
     def _avg4(x):
@@ -160,31 +193,31 @@ class Ref:
         d1 = self._ext(st, comp, i, j) - self.at(own, i, j)
         pts = self._pts(comp, i, j)
         d2 = self._avg4([self._ext(st, oc, *q) for q in pts]) - self._avg4([self.at(other, *q) for q in pts])
-        return math.sqrt(d1 * d1 + d2 * d2)
+        return self.sqrt(d1 * d1 + d2 * d2)
 
     def explicit_tau(self, st, comp, u, v, i, j):
         if st.kind == O.STRESS_CONST:
-            return st.tau_u if comp == "u" else st.tau_v
+            return self.N(st.tau_u if comp == "u" else st.tau_v)
         if st.kind == O.STRESS_FIELD:
             return self.at(self._arr(st.fu if comp == "u" else st.fv, comp), i, j)
         if st.kind == O.STRESS_SEMI_IMPLICIT:
-            return st.rho_e * st.Cd * self._drag_norm(st, comp, u, v, i, j) * self._ext(st, comp, i, j)
-        return 0.0
+            return self.N(st.rho_e) * self.N(st.Cd) * self._drag_norm(st, comp, u, v, i, j) * self._ext(st, comp, i, j)
+        return self.zero
 
     def implicit_tau(self, st, comp, u, v, i, j):
-        return st.rho_e * st.Cd * self._drag_norm(st, comp, u, v, i, j) if st.kind == O.STRESS_SEMI_IMPLICIT else 0.0
+        return self.N(st.rho_e) * self.N(st.Cd) * self._drag_norm(st, comp, u, v, i, j) if st.kind == O.STRESS_SEMI_IMPLICIT else self.zero
 
     def fcor(self, comp, i, j):
         s = self.s
         pts = s.fu_points if comp == "u" else s.fv_points
         if pts:
-            return pts[(i + s.Hx - 1) + (j + s.Hy - 1) * s.f_points_ld]
+            return self.N(pts[(i + s.Hx - 1) + (j + s.Hy - 1) * s.f_points_ld])
         rows = s.fu_rows if comp == "u" else s.fv_rows
-        return rows[j + s.Hy - 1] if rows else s.f_coriolis
+        return self.N(rows[j + s.Hy - 1] if rows else s.f_coriolis)
 
     # ---- interpolated mass / concentration ---------------------------------------------------------------------------------------
     def mass_conc(self, comp, i, j):
-        h, a, rho = self.p.f["h"], self.p.f["aice"], self.s.rho_ice
+        h, a, rho = self.p.f["h"], self.p.f["aice"], self.N(self.s.rho_ice)
         (i0, j0) = (i - 1, j) if comp == "u" else (i, j - 1)
         mi = (self.at(h, i0, j0) * rho * self.at(a, i0, j0) + self.at(h, i, j) * rho * self.at(a, i, j)) / 2
         ai = (self.at(a, i0, j0) + self.at(a, i, j)) / 2
@@ -195,31 +228,31 @@ class Ref:
         s, f = self.s, self.p.f
         mi, ai = self.mass_conc(comp, i, j)
         if comp == "u":
-            cor = -self.fcor("u", i, j) * self._avg4([self.at(v, *q) for q in self._pts("u", i, j)]) if s.has_coriolis else 0.0
+            cor = -self.fcor("u", i, j) * self._avg4([self.at(v, *q) for q in self._pts("u", i, j)]) if s.has_coriolis else self.zero
             div, imm = self.div1(u, v, i, j), self.immersed1(i, j)
-            user = self.at(self._arr(s.forcing_u, "u"), i, j) if s.has_forcing else 0.0
+            user = self.at(self._arr(s.forcing_u, "u"), i, j) if s.has_forcing else self.zero
             own, n, al_pts = u, f["un"], ((i - 1, j), (i, j))
         else:
-            cor = self.fcor("v", i, j) * self._avg4([self.at(u, *q) for q in self._pts("v", i, j)]) if s.has_coriolis else 0.0
+            cor = self.fcor("v", i, j) * self._avg4([self.at(u, *q) for q in self._pts("v", i, j)]) if s.has_coriolis else self.zero
             div, imm = self.div2(u, v, i, j), self.immersed2(i, j)
-            user = self.at(self._arr(s.forcing_v, "v"), i, j) if s.has_forcing else 0.0
+            user = self.at(self._arr(s.forcing_v, "v"), i, j) if s.has_forcing else self.zero
             own, n, al_pts = v, f["vn"], ((i, j - 1), (i, j))
         forcing = user                                    # Rheologies.jl:52-53
         if not self.viscous:                              # elasto_visco_plastic_rheology.jl:391-401
             abar = (self.at(f["alpha"], *al_pts[0]) + self.at(f["alpha"], *al_pts[1])) / 2
-            forcing = user + (self.at(n, i, j) - self.at(own, i, j)) / dt_forcing / abar
+            forcing = user + (self.at(n, i, j) - self.at(own, i, j)) / self.N(dt_forcing) / abar
         G = (-cor
              - self.explicit_tau(s.top, comp, u, v, i, j) / mi * ai
              + self.explicit_tau(s.bottom, comp, u, v, i, j) / mi * ai
              + div / mi
              + imm / mi
-             + forcing) if mi != 0 else math.nan
-        return (0.0 if mi <= 0 else G), mi, ai
+             + forcing) if mi != 0 else self.nan
+        return (self.zero if mi <= 0 else G), mi, ai
 
     def free_drift(self, comp, i, j):
         if not self.s.free_drift_kind:
-            return 0.0
-        return (self.p.L.ora_free_drift_u if comp == "u" else self.p.L.ora_free_drift_v)(self.p.ptr, i, j)
+            return self.zero
+        return self.N((self.p.L.ora_free_drift_u if comp == "u" else self.p.L.ora_free_drift_v)(self.p.ptr, i, j))
 
     def fill(self, comp):
         (self.p.L.ora_fill_halo_u if comp == "u" else self.p.L.ora_fill_halo_v)(self.p.ptr)
@@ -237,17 +270,21 @@ class Ref:
         old_u, old_v = f["u"].copy(), f["v"].copy()
         new = (old_u if comp == "u" else old_v).copy()
         s = self.s
-        for (i, j) in self.points(order):
-            G, mi, ai = self.tendency(comp, old_u, old_v, i, j, 0.0)
-            tau = ((self.implicit_tau(s.bottom, comp, old_u, old_v, i, j) - self.implicit_tau(s.top, comp, old_u, old_v, i, j)) / mi * ai
-                   if mi != 0 else math.nan)
-            tau = 0.0 if mi <= 0 else tau
-            c0 = self.at(old_u if comp == "u" else old_v, i, j)
-            D = (c0 + dtau * G) / (1 + dtau * tau)
-            F = self.free_drift(comp, i, j)
-            marginal, active = (mi > EPS64) and (ai > EPS64), (mi >= s.min_mass) and (ai >= s.min_conc)
-            sel = D if active else (F if marginal else 0.0)
-            new[j + self.Hy - 1, i + self.Hx - 1] = math.copysign(0.0, sel) if self.peripheral(comp, i, j) else sel
+        with self.ctx():
+            dtau = self.N(dtau)
+            for (i, j) in self.points(order):
+                G, mi, ai = self.tendency(comp, old_u, old_v, i, j, 0.0)
+                tau = ((self.implicit_tau(s.bottom, comp, old_u, old_v, i, j) - self.implicit_tau(s.top, comp, old_u, old_v, i, j)) / mi * ai
+                       if mi != 0 else self.nan)
+                tau = self.zero if mi <= 0 else tau
+                c0 = self.at(old_u if comp == "u" else old_v, i, j)
+                D = (c0 + dtau * G) / (1 + dtau * tau)
+                F = self.free_drift(comp, i, j)
+                marginal, active = (mi > EPS64) and (ai > EPS64), (mi >= s.min_mass) and (ai >= s.min_conc)
+                sel = D if active else (F if marginal else self.zero)
+                sel = self.szero(sel) if self.peripheral(comp, i, j) else sel
+                self.q[comp][j - 1, i - 1] = sel
+                new[j + self.Hy - 1, i + self.Hx - 1] = float(sel)
         np.copyto(f[comp], new)
         self.fill(comp)
 
@@ -271,9 +308,12 @@ class Ref:
     # ---- ExplicitSolver ----------------------------------------------------------------------------------------------------------
     def compute_tendencies(self, dt):
         u, v = self.p.f["u"], self.p.f["v"]
-        for (i, j) in self.points():
-            self.Gu[j + self.Hy - 1, i + self.Hx - 1] = self.tendency("u", u, v, i, j, dt)[0]
-            self.Gv[j + self.Hy - 1, i + self.Hx - 1] = self.tendency("v", u, v, i, j, dt)[0]
+        with self.ctx():
+            for (i, j) in self.points():
+                for comp, G in (("u", self.Gu), ("v", self.Gv)):
+                    g = self.tendency(comp, u, v, i, j, dt)[0]
+                    self.q["G" + comp][j - 1, i - 1] = g
+                    G[j + self.Hy - 1, i + self.Hx - 1] = float(g)
 
     def explicit_step(self, dt, rk_reset=False):
         f, s = self.p.f, self.s
@@ -281,14 +321,18 @@ class Ref:
             prev = (f["um"] if comp == "u" else f["vm"]) if rk_reset else f[comp]
             u, v = f["u"].copy(), f["v"].copy()
             new = f[comp].copy()
-            for (i, j) in self.points():
-                mi, ai = self.mass_conc(comp, i, j)
-                tau = ((self.implicit_tau(s.bottom, comp, u, v, i, j) - self.implicit_tau(s.top, comp, u, v, i, j)) / mi * ai
-                       if mi != 0 else math.nan)
-                D = (self.at(prev, i, j) + dt * self.at(G, i, j)) / (1 + dt * tau)
-                F = self.free_drift(comp, i, j)
-                marginal, active = (mi > EPS64) and (ai > EPS64), (mi >= s.min_mass) and (ai >= s.min_conc)
-                new[j + self.Hy - 1, i + self.Hx - 1] = D if active else (F if marginal else 0.0)
+            with self.ctx():
+                dtn = self.N(dt)
+                for (i, j) in self.points():
+                    mi, ai = self.mass_conc(comp, i, j)
+                    tau = ((self.implicit_tau(s.bottom, comp, u, v, i, j) - self.implicit_tau(s.top, comp, u, v, i, j)) / mi * ai
+                           if mi != 0 else self.nan)
+                    D = (self.at(prev, i, j) + dtn * self.at(G, i, j)) / (1 + dtn * tau)
+                    F = self.free_drift(comp, i, j)
+                    marginal, active = (mi > EPS64) and (ai > EPS64), (mi >= s.min_mass) and (ai >= s.min_conc)
+                    sel = D if active else (F if marginal else self.zero)
+                    self.q[comp][j - 1, i - 1] = sel
+                    new[j + self.Hy - 1, i + self.Hx - 1] = float(sel)
             np.copyto(f[comp], new)
             self.fill(comp)                                                             # fill_halo_regions!, :33, :36
 
