@@ -1,14 +1,34 @@
-// csi_abi.hip -- the C ABI of libcsi_hip.so (include/csi.h): argument checks, binding, the entry points of the time steppers.
+// csi_abi.hip -- the C ABI of libcsi_hip.so (include/csi.h): argument checks, binding, settings, the plan queries and the entry points.
+// Nothing here launches a kernel or sequences a step.
 //
 // The host code behind it (round 4: split out of this file, see csi_ctx.h) replaces the host side of the reference's
 //   time_step_momentum!   SeaIceDynamics/split_explicit_momentum_equations.jl:103-195      csi_launch.hip
-//   rk_substep! / cache_current_fields! / dynamic_time_step!   sea_ice_rk_substep.jl:29-152   csi_launch.hip, this file
-//   time_step!(::FESeaIceModel)   sea_ice_fe_step.jl:13-34                                  this file
+//   rk_substep! / cache_current_fields! / dynamic_time_step!   sea_ice_rk_substep.jl:29-152   csi_launch.hip, csi_step.hip
+//   time_step!(::FESeaIceModel)   sea_ice_fe_step.jl:13-34                                  csi_step.hip
 //   thermodynamic_time_step!   SeaIceThermodynamics/thermodynamic_time_step.jl              csi_thermo.hip (do_thermo)
 // All work is ordered on the context's stream; nothing here synchronises with the host
 // except csi_sync / csi_context_destroy.
 #include "csi_ctx.h"
 
+
+// A strictly checked integer choice from the environment: unset or empty leaves *out alone; anything but an integer in 0 .. max is an error
+static int32_t env_choice(const char* name, long max, const char* choices, int* out) {
+    const char* e = getenv(name);
+    if (!e || !*e) return CSI_OK;
+    char* end = nullptr;
+    const long v = strtol(e, &end, 10);
+    if (*end || v < 0 || v > max) return fail(nullptr, CSI_ERR_INVALID_ARGUMENT, std::string(name) + "=" + e + ": " + choices);
+    *out = (int)v;
+    return CSI_OK;
+}
+// A context that holds a grid's sizes and sides only (uniform metrics): what the plan queries hand to the range and geometry functions
+struct PlanContext : csi_context {
+    PlanContext(int Nx_, int Ny_, int Hx_, int Hy_, int topo_x_, int topo_y_) {
+        Nx = Nx_; Ny = Ny_; Hx = Hx_; Hy = Hy_;
+        set_sides(g, topo_x_, topo_y_);
+        coef.uniform = 1; metric_kind = CSI_METRIC_UNIFORM;   // (per-row metrics with a periodic y side are the one grid kind that never pairs)
+    }
+};
 
 // ============================================================================================
 extern "C" {
@@ -26,22 +46,9 @@ int32_t csi_context_create(int32_t device_id, void* hip_stream, csi_context** ou
         return fail(nullptr, CSI_ERR_NO_DEVICE, "no HIP device visible (libcsi_hip has no CPU fallback)");
     if (device_id < 0 || device_id >= n) return fail(nullptr, CSI_ERR_INVALID_ARGUMENT, "device_id out of range");
     HIP_TRY(nullptr, hipSetDevice(device_id));
-    int adv_shape = -1;
-    if (const char* e = getenv("CSI_ADV_SHAPE"); e && *e) {
-        char* end = nullptr;
-        const long v = strtol(e, &end, 10);
-        if (*end || v < 0 || v > 3)
-            return fail(nullptr, CSI_ERR_INVALID_ARGUMENT, std::string("CSI_ADV_SHAPE=") + e + ": 0 (by grid size), 1 (64 x 8), 2 (63 x 7) or 3 (63 x 11)");
-        adv_shape = (int)v;
-    }
-    int enth_path = 0;
-    if (const char* e = getenv("CSI_ENTH_PATH"); e && *e) {
-        char* end = nullptr;
-        const long v = strtol(e, &end, 10);
-        if (*end || v < 0 || v > 2)
-            return fail(nullptr, CSI_ERR_INVALID_ARGUMENT, std::string("CSI_ENTH_PATH=") + e + ": 0 (by the rule of csi_enthalpy_plan), 1 (per step) or 2 (on chip)");
-        enth_path = (int)v;
-    }
+    int adv_shape = -1, enth_path = 0;
+    if (int32_t rc = env_choice("CSI_ADV_SHAPE", 3, "0 (by grid size), 1 (64 x 8), 2 (63 x 7) or 3 (63 x 11)", &adv_shape)) return rc;
+    if (int32_t rc = env_choice("CSI_ENTH_PATH", 2, "0 (by the rule of csi_enthalpy_plan), 1 (per step) or 2 (on chip)", &enth_path)) return rc;
     csi_context* c = new csi_context();
     c->device = device_id;
     if (hip_stream) {
@@ -210,7 +217,7 @@ int32_t csi_grid_set(csi_context* c, int32_t Nx, int32_t Ny, int32_t Hx, int32_t
     GridDev& g = c->g;
     g = GridDev{};   // a new grid also drops any mask
     g.Nx = Nx; g.Ny = Ny; g.Hx = Hx; g.Hy = Hy;
-    g.xlo = side_lo(topo_x); g.xhi = side_hi(topo_x); g.ylo = side_lo(topo_y); g.yhi = side_hi(topo_y);
+    set_sides(g, topo_x, topo_y);
     g.metric_kind = metric_kind;
     g.dx = m->dx; g.dy = m->dy;
     HIP_TRY(c, hipStreamSynchronize(c->stream));      // kernels still in flight may read the tables freed below
@@ -448,32 +455,7 @@ int32_t csi_dynamic_step_tracers(csi_context* c, double dt, int32_t from_cache) 
 
 int32_t csi_cache_current_fields(csi_context* c) {
     if (!c) return CSI_ERR_INVALID_ARGUMENT;
-    int32_t rc = need(c, {CSI_F_H, CSI_F_A, CSI_F_HM, CSI_F_AM});
-    if (rc) return rc;
-    // Psi^- = the prognostic fields, whole parents, in one launch
-    CopyBatch B{};
-    B.aligned16 = 1;
-    auto add = [&](int dst, int src) -> int32_t {
-        const Bound &d = c->f[dst], &q = c->f[src];
-        if (d.ld != q.ld || d.nj != q.nj) return fail(c, CSI_ERR_INVALID_ARGUMENT, std::string("parent shape mismatch: ") + slot_name(dst) + " vs " + slot_name(src));
-        B.src[B.count] = q.p; B.dst[B.count] = d.p; B.n[B.count] = (long)d.ld * d.nj; ++B.count;
-        if ((((uintptr_t)q.p) | ((uintptr_t)d.p)) & 15) B.aligned16 = 0;
-        return CSI_OK;
-    };
-    if ((rc = add(CSI_F_HM, CSI_F_H))) return rc;
-    if ((rc = add(CSI_F_AM, CSI_F_A))) return rc;
-    if (c->f[CSI_F_HS].p && c->f[CSI_F_HSM].p && (rc = add(CSI_F_HSM, CSI_F_HS))) return rc;
-    if (c->f[CSI_F_U].p && c->f[CSI_F_UM].p) {
-        if ((rc = need(c, {CSI_F_V, CSI_F_VM}))) return rc;
-        if ((rc = add(CSI_F_UM, CSI_F_U))) return rc;
-        if ((rc = add(CSI_F_VM, CSI_F_V))) return rc;
-    }
-    // (the mixed-layer temperature is a prognostic field of the step like h and aice: the sixth and last entry of the batch)
-    if (c->f[CSI_F_ML_TEMPERATURE].p && c->f[CSI_F_ML_TEMPERATURE_M].p && (rc = add(CSI_F_ML_TEMPERATURE_M, CSI_F_ML_TEMPERATURE))) return rc;
-    launch_copy_batch(B, c->stream);
-    HIP_TRY(c, hipGetLastError());
-    if (c->trc.set && (rc = tracers_cache(c))) return rc;      // (advected tracers: c -> c^-, a batch of their own)
-    return CSI_OK;
+    return cache_current_fields(c);
 }
 
 int32_t csi_update_state(csi_context* c) {
@@ -490,112 +472,25 @@ int32_t csi_fill_halo_local(csi_context* c, int32_t fid) {
     return fill_halo(c, fid);
 }
 
-// Every path of a whole step ends by imaging h, aice [, hs] (update_state!, or the tracer update's own stores) and, with dynamics, u and
-// v: a grid too narrow for one image per side (fill_width_check) is refused HERE, before the step has written anything -- not at its end,
-// and also where the fused stores would have skipped update_state!'s check.
-static int32_t step_width_check(csi_context* c, bool dynamics) {
-    int32_t rc;
-    if ((rc = fill_width_check(c, CSI_F_H))) return rc;          // (aice, hs: the same location)
-    if (dynamics && ((rc = fill_width_check(c, CSI_F_U)) || (rc = fill_width_check(c, CSI_F_V)))) return rc;
-    return CSI_OK;
-}
-
+// The two steppers (csi_step.hip): the shared checks, then stages
 int32_t csi_time_step_fe(csi_context* c, double dt, int32_t substeps, int32_t scheme, int32_t first_iteration) {
     if (!c) return CSI_ERR_INVALID_ARGUMENT;
-    // dynamics = nothing (csi_evp_params_set never called): prescribed velocities, time_step_momentum! is a no-op
-    // (SeaIceDynamics.jl:40) -- the advection-only models of examples/ice_advected_by_anticyclone.jl's family
-    const bool dynamics = has_dynamics(c);      // (or csi_dynamics_set(ctx, CSI_DYNAMICS_FREE_DRIFT))
-    int32_t rc = dynamics ? need_momentum(c) : need(c, {CSI_F_H, CSI_F_A});
+    const bool dynamics = has_dynamics(c);
+    int32_t rc = step_checks(c, dynamics, false);
     if (rc) return rc;
-    if ((rc = step_width_check(c, dynamics))) return rc;
     if (first_iteration && (rc = do_update_state(c))) return rc;          // sea_ice_fe_step.jl:16
-    if ((rc = do_tendencies_or_zero(c, scheme))) return rc;               // :19 (compute_tracer_tendencies!)
-    if (c->trc.set && (rc = tracers_first_half(c, scheme, dt, 0))) return rc;      // (advected tracers: the first half, include/csi.h)
-    if (dynamics && (rc = do_momentum_tendencies(c, dt))) return rc;      // :19 (compute_momentum_tendencies!: ExplicitSolver only)
-    if (dynamics && (rc = do_momentum(c, dt, substeps, 0))) return rc;    // :22
-    // without a mask and without a thermodynamic step the tracer update's stores write the halo images themselves
-    const bool fused_fill = !c->g.has_mask && !c->slab_set;
-    if ((rc = do_tracer_step(c, dt, 0, fused_fill))) return rc;           // :25
-    if ((rc = do_thermo(c, dt))) return rc;                               // :28 thermodynamic_time_step!
-    if (c->trc.set && (rc = tracers_second_half(c, dt))) return rc;       // (advected tracers: the second half)
-    if ((rc = do_update_state(c, true, fused_fill))) return rc;           // :31
-    return finish_step(c, CSI_OK);
-}
-
-// An RK3 step of an advection-only model (prescribed velocities: examples/ice_advected_by_anticyclone.jl's family, BASELINE
-// config 2) with ONE launch per stage: nothing happens between a stage's tendencies and its tracer update, so the kernel that
-// computes G also applies it -- into another copy of (h, a), because its neighbours still read the stage's input: the state
-// rotates bound arrays -> copy 1 -> copy 2 -> bound arrays.  The first stage also writes Psi^- (cache_current_fields!).  Same
-// arithmetic as the separate kernels, statement for statement: bit-identical (tests/test_gpu_steps.py).
-bool advect_stage_supported(const csi_context* c, int scheme) {
-    const ImageSpec im = image_spec(c, CSI_F_H);
-    for (int side : {im.xlo, im.xhi, im.ylo, im.yhi}) if (side != IMG_WRAP && side != IMG_MIRROR) return false;      // (periodic / no-flux walls)
-    if (c->Nx < 2 * c->Hx || c->Ny < 2 * c->Hy) return false;
-    // Round 3 cut this path off above 3 M cells (2048^2: 768 -> 794 us per RK3 step with it).  Re-measured in round 6 with two tracers
-    // per thread and the round-5 block shapes (scripts/ab_adv_stage.sh, profiles/r06_advection_stage_ab.txt; WENO7, us per RK3 step,
-    // separate launches -> one per stage): 1536^2 314 -> 264, 2048^2 538 -> 476, 3072^2 1205 -> 988, 4096^2 2110 -> 1711 -- the
-    // separate update streams another 7 arrays per stage, which the fused stage never touches: no cut any more (A/B knob:
-    // CSI_ADV_STAGE_MAX_CELLS)
-    if ((long)c->Nx * c->Ny > c->tune.adv_stage_max_cells) return false;
-    if (c->trc.set) return false;      // (advected tracers take the general stage loop)
-    return !has_dynamics(c) && scheme != 0 && c->fusion && !c->slab_set && !c->g.has_mask && !is_tiled(c) &&
-           c->f[CSI_F_HS].p == nullptr && c->f[CSI_F_H].ld == c->f[CSI_F_HM].ld && c->f[CSI_F_A].ld == c->f[CSI_F_AM].ld;
-}
-int32_t rk3_advection_only(csi_context* c, double dt, int scheme) {
-    int32_t rc;
-    if ((rc = need(c, {CSI_F_U, CSI_F_V, CSI_F_H, CSI_F_A, CSI_F_GH, CSI_F_GA, CSI_F_HM, CSI_F_AM}))) return rc;
-    for (ScratchField& s : c->adv_buf) {
-        bool fresh;
-        HIP_TRY(c, s.ensure(c, nullptr, &fresh));
-        // beyond walls the halo holds mirror images the stores rewrite; cells nobody writes (wall corners) start as the state's
-        if (fresh) HIP_TRY(c, hipMemcpyAsync(s.get(), c->f[s.fid].p, s.buf.size() * sizeof(double), hipMemcpyDeviceToDevice, c->stream));
-    }
-    const FRef H0 = ref_of(c, CSI_F_H), A0 = ref_of(c, CSI_F_A), H1 = c->adv_buf[0].view(c), A1 = c->adv_buf[1].view(c),
-               H2 = c->adv_buf[2].view(c), A2 = c->adv_buf[3].view(c);
-    const FRef hin[3] = {H0, H1, H2}, ain[3] = {A0, A1, A2}, hout[3] = {H1, H2, H0}, aout[3] = {A1, A2, A0};
-    int stage = 0;
-    for (int beta = 3; beta >= 1; --beta, ++stage) {
-        AdvDev A = adv_dev(c, scheme, dt / beta, 1);
-        A.h = hin[stage]; A.a = ain[stage];
-        A.hb = stage == 0 ? H0 : A.hm; A.ab = stage == 0 ? A0 : A.am;
-        A.ho = hout[stage]; A.ao = aout[stage];
-        A.write_cache = stage == 0;
-        A.fill_images = 1;
-        c->last_adv = launch_advect_stage(A, c->mode, c->stream);
-        c->last_adv_stage = 1;
-        HIP_TRY(c, hipGetLastError());
-    }
-    return CSI_OK;
+    return finish_step(c, step_stage(c, dt, substeps, scheme, dynamics, 0));
 }
 
 int32_t csi_time_step_rk3(csi_context* c, double dt, int32_t substeps, int32_t scheme) {
     if (!c) return CSI_ERR_INVALID_ARGUMENT;
-    const bool dynamics = has_dynamics(c);                                // see csi_time_step_fe
-    int32_t rc = dynamics ? need_momentum(c) : need(c, {CSI_F_H, CSI_F_A});
+    const bool dynamics = has_dynamics(c);
+    int32_t rc = step_checks(c, dynamics, true);
     if (rc) return rc;
-    if ((rc = dynamics ? need(c, {CSI_F_HM, CSI_F_AM, CSI_F_UM, CSI_F_VM}) : need(c, {CSI_F_HM, CSI_F_AM}))) return rc;
-    if ((rc = step_width_check(c, dynamics))) return rc;
-    if (c->ml_set && c->slab_set && (rc = need(c, {CSI_F_ML_TEMPERATURE, CSI_F_ML_TEMPERATURE_M}))) return rc;
-    if (advect_stage_supported(c, scheme)) {
-        const bool third = scheme == CSI_ADVECT_WENO3 || scheme == CSI_ADVECT_UPWIND3;
-        const int need_h = scheme == CSI_ADVECT_WENO7 ? 4 : (scheme == CSI_ADVECT_UPWIND1 ? 1 : (third ? 2 : 3));
-        if (c->Hx >= need_h && c->Hy >= need_h &&
-            (scheme == CSI_ADVECT_UPWIND1 || scheme == CSI_ADVECT_WENO5 || scheme == CSI_ADVECT_WENO7 || scheme == CSI_ADVECT_UPWIND5 || third))
-            return finish_step(c, rk3_advection_only(c, dt, scheme));
-    }
-    if ((rc = csi_cache_current_fields(c))) return rc;                    // sea_ice_rk_substep.jl:29-42
-    for (int beta = 3; beta >= 1; --beta) {                               // upstream stage loop
-        const double dtau = dt / beta;
-        if ((rc = do_tendencies_or_zero(c, scheme))) return rc;           // :84
-        if (c->trc.set && (rc = tracers_first_half(c, scheme, dtau, 1))) return rc;      // (advected tracers: from Psi^-)
-        if (dynamics && (rc = do_momentum_tendencies(c, dtau))) return rc;               // :84 (ExplicitSolver only)
-        if (dynamics && (rc = do_momentum(c, dtau, substeps, 1))) return rc;             // :87
-        const bool fused_fill = !c->g.has_mask && !c->slab_set;
-        if ((rc = do_tracer_step(c, dtau, 1, fused_fill))) return rc;     // :89
-        if ((rc = do_thermo(c, dtau, 1))) return rc;                      // :91 thermodynamic_time_step! (the mixed layer: from Psi^-)
-        if (c->trc.set && (rc = tracers_second_half(c, dtau))) return rc;
-        if ((rc = do_update_state(c, true, fused_fill))) return rc;
-    }
+    if (advect_stage_supported(c, scheme)) return finish_step(c, rk3_advection_only(c, dt, scheme));
+    if ((rc = cache_current_fields(c))) return rc;                        // sea_ice_rk_substep.jl:29-42
+    for (int beta = 3; beta >= 1; --beta)                                 // upstream stage loop
+        if ((rc = step_stage(c, dt / beta, substeps, scheme, dynamics, 1))) return rc;
     return finish_step(c, CSI_OK);
 }
 
@@ -717,7 +612,7 @@ int32_t csi_plan_exchange(int32_t Nx, int32_t Ny, int32_t Hx, int32_t Hy, int32_
     if (!out40 || Nx < 1 || Ny < 1 || Rx < 1 || Ry < 1) return CSI_ERR_INVALID_ARGUMENT;
     GridDev g{};
     g.Nx = Nx; g.Ny = Ny; g.Hx = Hx; g.Hy = Hy;
-    g.xlo = side_lo(topo_x); g.xhi = side_hi(topo_x); g.ylo = side_lo(topo_y); g.yhi = side_hi(topo_y);
+    set_sides(g, topo_x, topo_y);
     TileInfo t;
     t.rx = rx; t.ry = ry; t.Rx = Rx; t.Ry = Ry; t.periodic_x = periodic_x != 0; t.periodic_y = periodic_y != 0; t.set = true;
     FRef dummy{nullptr, 0};
@@ -821,9 +716,7 @@ int32_t csi_peer_tier(csi_context* c, int32_t* tier) {
 
 int32_t csi_plan_ranges(int32_t Nx, int32_t Ny, int32_t Hx, int32_t Hy, int32_t topo_x, int32_t topo_y, int32_t V, int32_t* out16) {
     if (!out16 || Nx < 1 || Ny < 1 || V < 2) return CSI_ERR_INVALID_ARGUMENT;
-    csi_context tmp;
-    tmp.Nx = Nx; tmp.Ny = Ny; tmp.Hx = Hx; tmp.Hy = Hy;
-    tmp.g.xlo = side_lo(topo_x); tmp.g.xhi = side_hi(topo_x); tmp.g.ylo = side_lo(topo_y); tmp.g.yhi = side_hi(topo_y);
+    PlanContext tmp(Nx, Ny, Hx, Hy, topo_x, topo_y);
     const Range r[4] = {stress_range(&tmp, V), first_u_range(&tmp, V), first_v_range(&tmp, V), second_range(&tmp, V)};
     for (int k = 0; k < 4; ++k) { out16[4 * k] = r[k].i0; out16[4 * k + 1] = r[k].i1; out16[4 * k + 2] = r[k].j0; out16[4 * k + 3] = r[k].j1; }
     return CSI_OK;
@@ -832,10 +725,7 @@ int32_t csi_plan_ranges(int32_t Nx, int32_t Ny, int32_t Hx, int32_t Hy, int32_t 
 int32_t csi_plan_pair(int32_t Nx, int32_t Ny, int32_t Hx, int32_t Hy, int32_t topo_x, int32_t topo_y, int32_t k, int32_t m,
                       int32_t* out32) {
     if (!out32 || Nx < 1 || Ny < 1 || k < 1 || m < 0 || m + 1 >= 2 * ((k + 1) / 2) + (k == 1 ? 1 : 0)) return CSI_ERR_INVALID_ARGUMENT;
-    csi_context tmp;
-    tmp.Nx = Nx; tmp.Ny = Ny; tmp.Hx = Hx; tmp.Hy = Hy;
-    tmp.g.xlo = side_lo(topo_x); tmp.g.xhi = side_hi(topo_x); tmp.g.ylo = side_lo(topo_y); tmp.g.yhi = side_hi(topo_y);
-    tmp.coef.uniform = 1; tmp.metric_kind = CSI_METRIC_UNIFORM;   // (per-row metrics with a periodic y side are the one grid kind that never pairs)
+    PlanContext tmp(Nx, Ny, Hx, Hy, topo_x, topo_y);
     const bool tiled = is_tiled(&tmp);
     memset(out32, 0, 32 * sizeof(int32_t));
     out32[0] = (pair_supported(&tmp) && (!tiled || k % 2 == 0)) ? 1 : 0;
@@ -855,11 +745,7 @@ int32_t csi_plan_pair(int32_t Nx, int32_t Ny, int32_t Hx, int32_t Hy, int32_t to
 int32_t csi_plan_peer_chunks(int32_t Nx, int32_t Ny, int32_t Hx, int32_t Hy, int32_t peer_south, int32_t peer_north, int32_t /*cus*/,
                              int32_t* out8, int32_t* rows_out, int32_t max_chunks) {
     if (!out8 || !rows_out || Nx < 1 || Ny < 1 || max_chunks < 1) return CSI_ERR_INVALID_ARGUMENT;
-    csi_context tmp;
-    tmp.Nx = Nx; tmp.Ny = Ny; tmp.Hx = Hx; tmp.Hy = Hy;
-    // the launch loop of the peer transport sees connected sides as periodic ones (PeerView)
-    tmp.g.xlo = tmp.g.xhi = tmp.g.ylo = tmp.g.yhi = SIDE_PERIODIC;
-    tmp.coef.uniform = 1; tmp.metric_kind = CSI_METRIC_UNIFORM;
+    PlanContext tmp(Nx, Ny, Hx, Hy, CSI_PERIODIC, CSI_PERIODIC);      // the launch loop of the peer transport sees connected sides as periodic ones (PeerView)
     tmp.geom_peer = 1;
     for (int d = 0; d < 8; ++d) tmp.peer.sync_rank[d] = -1;
     if (peer_south) tmp.peer.sync_rank[2] = 0;
@@ -876,7 +762,7 @@ int32_t csi_plan_peer_chunks(int32_t Nx, int32_t Ny, int32_t Hx, int32_t Hy, int
 
 int32_t csi_last_subcycle_ms(csi_context* c, double* ms) {
     if (!c || !ms) return CSI_ERR_INVALID_ARGUMENT;
-    if (!c->timed) return fail(c, CSI_ERR_NOT_BOUND, "no sub-cycle has been timed yet");
+    if (!c->last.timed) return fail(c, CSI_ERR_NOT_BOUND, "no sub-cycle has been timed yet");
     float t = 0.f;
     HIP_TRY(c, hipEventSynchronize(c->ev1));
     HIP_TRY(c, hipEventElapsedTime(&t, c->ev0, c->ev1));
@@ -909,9 +795,9 @@ int32_t csi_subcycle_stats_end(csi_context* c, double* total_ms, int32_t* cycles
 
 int32_t csi_last_path(csi_context* c, int32_t* fused, int32_t* exchange_interval, int32_t* exchanges) {
     if (!c) return CSI_ERR_INVALID_ARGUMENT;
-    if (fused) *fused = c->last_fused;
-    if (exchange_interval) *exchange_interval = c->last_k;
-    if (exchanges) *exchanges = c->last_exchanges;
+    if (fused) *fused = c->last.fused;
+    if (exchange_interval) *exchange_interval = c->last.k;
+    if (exchanges) *exchanges = c->last.exchanges;
     return CSI_OK;
 }
 
@@ -926,14 +812,14 @@ int32_t csi_last_advection(csi_context* c, int32_t* tracers_per_thread, int32_t*
 
 int32_t csi_last_launches(csi_context* c, int32_t* launches, int32_t* substeps) {
     if (!c) return CSI_ERR_INVALID_ARGUMENT;
-    if (launches) *launches = c->last_launches;
-    if (substeps) *substeps = c->last_substeps;
+    if (launches) *launches = c->last.launches;
+    if (substeps) *substeps = c->last.substeps;
     return CSI_OK;
 }
 
 int32_t csi_launches_per_substep(csi_context* c, int32_t* n) {
     if (!c || !n) return CSI_ERR_INVALID_ARGUMENT;
-    *n = c->launches_per_substep;
+    *n = c->last.per_substep;
     return CSI_OK;
 }
 

@@ -32,6 +32,7 @@ int side_hi(int topo) {
         default: return SIDE_CONNECTED;
     }
 }
+void set_sides(GridDev& g, int topo_x, int topo_y) { g.xlo = side_lo(topo_x); g.xhi = side_hi(topo_x); g.ylo = side_lo(topo_y); g.yhi = side_hi(topo_y); }
 int img_of(int side, int loc) {
     if (side == SIDE_PERIODIC) return IMG_WRAP;
     if (side == SIDE_WALL) return loc == LOC_C ? IMG_MIRROR : IMG_NONE;
@@ -208,6 +209,17 @@ Range second_range(const csi_context* c, int V) {
     return Range{g.xlo == SIDE_CONNECTED ? 3 - V : 1, g.xhi == SIDE_CONNECTED ? c->Nx + V - 2 : c->Nx,
                  g.ylo == SIDE_CONNECTED ? 3 - V : 1, g.yhi == SIDE_CONNECTED ? c->Ny + V - 2 : c->Ny};
 }
+SubstepRanges substep_ranges(const csi_context* c, int V) { return SubstepRanges{stress_range(c, V), first_u_range(c, V), first_v_range(c, V), second_range(c, V)}; }
+// The three-kernel sub-step, stated once: the unfused loop of do_subcycle, the in-place fallback of run_fused and the fold band's
+// band_substep launch it.  (csi_profile_substeps times each kernel on its own, and band_substeps_fused launches other kernels.)
+void launch_substep(const EvpDev& P, const FastCoef* fc, const SubstepRanges& R, const ImageSpec& imu, const ImageSpec& imv, bool ufirst, hipStream_t st) {
+    if (fc) launch_fast_stress(P, R.rs, *fc, st);
+    else { launch_strict_visc(P, R.rs, st); launch_strict_stress(P, R.rs, st); }      // compute_stresses!, evp:222-234
+    auto ustep = [&](const Range& r) { if (fc) launch_fast_ustep(P, r, imu, *fc, st); else launch_strict_ustep(P, r, imu, st); };
+    auto vstep = [&](const Range& r) { if (fc) launch_fast_vstep(P, r, imv, *fc, st); else launch_strict_vstep(P, r, imv, st); };
+    if (ufirst) { ustep(R.ru1); vstep(R.r2); }             // :178-182
+    else { vstep(R.rv1); ustep(R.r2); }                    // :184-187
+}
 bool is_tiled(const csi_context* c) {
     const GridDev& g = c->g;
     return g.xlo == SIDE_CONNECTED || g.xhi == SIDE_CONNECTED || g.ylo == SIDE_CONNECTED || g.yhi == SIDE_CONNECTED;
@@ -241,6 +253,20 @@ int32_t copy_parent(csi_context* c, int dst, int src) {
     const Bound &d = c->f[dst], &s = c->f[src];
     if (d.ld != s.ld || d.nj != s.nj) return fail(c, CSI_ERR_INVALID_ARGUMENT, std::string("parent shape mismatch: ") + slot_name(dst) + " vs " + slot_name(src));
     HIP_TRY(c, hipMemcpyAsync(d.p, s.p, sizeof(double) * (size_t)d.ld * (size_t)d.nj, hipMemcpyDeviceToDevice, c->stream));
+    return CSI_OK;
+}
+
+int32_t copy_ping(csi_context* c, bool to_alt) {
+    for (int q = 0; q < 5; ++q) {
+        double *bound = c->f[kPing[q]].p, *alt = c->alt[q].get();
+        HIP_TRY(c, hipMemcpyAsync(to_alt ? alt : bound, to_alt ? bound : alt, c->alt[q].buf.size() * sizeof(double), hipMemcpyDeviceToDevice, c->stream));
+    }
+    return CSI_OK;
+}
+
+int32_t advect_scheme_check(csi_context* c, int scheme) {
+    if (!advect_halo(scheme)) return fail(c, CSI_ERR_INVALID_ARGUMENT, "unknown advection scheme");
+    if (!advect_fits(c, scheme)) return fail(c, CSI_ERR_INVALID_ARGUMENT, "halo too small for the advection scheme");
     return CSI_OK;
 }
 

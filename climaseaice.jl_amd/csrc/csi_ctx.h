@@ -4,7 +4,8 @@
 //   csi_peer.hip    peer halo transport: set-up (IPC mapping, flag arrays), tile sets, kernel tables
 //   csi_fold.hip    north fold: the three-kernel band beside the pair launches
 //   csi_launch.hip  launch loops: sub-cycle, finalize, time_step_momentum!, tracer steps, update_state!, csi_profile_substeps
-//   csi_abi.hip     the C ABI (include/csi.h)
+//   csi_step.hip    whole steps: the checks both steppers share, one step stage, the one-launch RK stages, cache_current_fields!
+//   csi_abi.hip     the C ABI (include/csi.h): argument checks, binding, settings, the entry points
 //   csi_thermo.hip  thermodynamics: parameter structs, the choice of kernel and its binding checks, the mixed layer's launch, their entry points
 //   csi_time_series.hip   forcing time series: time indexing, the device ring of a host-resident series, the interpolation launch
 //   csi_diagnostics.hip   device diagnostics: the two launches, the result copy, the combine over the ranks of a decomposition
@@ -189,8 +190,16 @@ struct csi_context {
     hipEvent_t ev0 = nullptr, ev1 = nullptr;
     // csi_subcycle_stats_begin / _end: one more event pair around every sub-step loop while `on` (bench.py's timed region)
     struct Stats { bool on = false; std::vector<hipEvent_t> ev; std::vector<int> launches; } stats;
-    bool timed = false;
-    int launches_per_substep = 0;
+    // What the last sub-cycle did (csi_last_subcycle_ms, csi_last_path, csi_last_launches, csi_launches_per_substep).  A path assigns the
+    // whole record in ONE statement and names there what it carries over from the record before.
+    struct LastPath {
+        bool timed = false;              // ev0 / ev1 bracket a sub-cycle
+        int fused = 0;                   // level: 0 three kernels (or another rheology / solver), 1 one sub-step per launch, 2 pairs
+        int per_substep = 0;             // launches per sub-step, the halo exchange's included
+        int launches = 0, substeps = 0;  // kernel launches / sub-steps
+        int exchanges = 0, k = 1;        // halo exchanges, sub-steps per exchange
+    } last;
+    int last_used_pairs = 0;             // run_fused: the sub-cycle ran pair launches
     // multi-GPU tiles
     TileInfo tile;
     ncclComm_t comm = nullptr;
@@ -198,7 +207,6 @@ struct csi_context {
     HostGroup* hostg = nullptr;            // host-channel group of PROCESSES (shared memory + HIP IPC, csi_comm_init_host): RCCL-free runs of several ranks on one GPU
     int world = 1, rank = 0;
     DeviceBuf<double> sendbuf, recvbuf;    // pack buffers of the message exchange: they only grow, both to the same size (exchange_refs)
-    int last_exchanges = 0, last_k = 1;
     // Halo transport of the two-sub-steps kernel on tiles.  "peer" (default where it can be set up): the neighbouring tiles'
     // arrays are mapped into this process (HIP IPC; xGMI peer access) and a connected side behaves like a periodic one whose halo
     // lives on another GPU -- the owner's stores write the halo images straight into the neighbour's arrays, and flags in
@@ -339,8 +347,6 @@ struct csi_context {
     ScratchField vis_alt[2] = {{CSI_F_U, kRaw}, {CSI_F_V, kRaw}};
     int fusion = 1;       // 1: use the fused sub-step kernel when the configuration allows it
     int pairing = 1;      // 1: two sub-steps per launch where supported (csi_set_fusion level 2)
-    int last_launches = 0, last_substeps = 0, last_used_pairs = 0;   // kernel launches / sub-steps of the last fused sub-cycle
-    int last_fused = 0;
     AdvLayout last_adv{0, 0, 0};     // csi_last_advection: what the last tendency / stage launch of k_tendencies used (0: none yet)
     int last_adv_stage = 0;          // ... and whether it was a whole RK stage in one launch
     ThermoLaunch last_thermo{0, 0, -1};      // csi_last_thermo: what the last thermodynamic launch used, as its launcher returned it (step 0: none yet)
@@ -455,6 +461,18 @@ struct PeerView {
     int band = -1, peer_was = 0;
     ~PeerView() { c->g = g; c->Ny = Ny; if (band >= 0) c->geom_band = band; c->geom_peer = peer_was; }
 };
+// The ranges of one three-kernel sub-step at one valid halo width V: stress on rs; then u on ru1 and v on r2 (u first), or v on rv1
+// and u on r2
+struct SubstepRanges {
+    Range rs, ru1, rv1, r2;
+    // rows >= jlo of the stress, >= jlo + 1 of the velocities (the fold band)
+    SubstepRanges from_row(int jlo) const {
+        SubstepRanges R = *this;
+        R.rs.j0 = std::max(R.rs.j0, jlo);
+        for (Range* r : {&R.ru1, &R.rv1, &R.r2}) r->j0 = std::max(r->j0, jlo + 1);
+        return R;
+    }
+};
 struct FoldBand {
     int M;
     bool tiled;                     // the fold tile of a y partition: its south side is connected
@@ -463,7 +481,7 @@ struct FoldBand {
     int Ny_full;
     EvpDev P;                       // the whole grid (fold geometry)
     ImageSpec imu, imv;
-    Range rs, ru1, rv1, r2;         // the three kernels' ranges on the whole grid
+    SubstepRanges R;                // the three kernels' ranges on the whole grid
 };
 struct FoldCut {        // RAII: the tile with the band cut off (rows 1 .. M, north side "connected")
     csi_context* c; GridDev g; int Ny, band;
@@ -478,6 +496,10 @@ int img_of(int side, int loc);
 ImageSpec image_spec(const csi_context* c, int fid);
 int32_t fill_width_check(csi_context* c, int fid);      // CSI_ERR_UNSUPPORTED where a local fill of this field would need more than one image per side
 FRef ref_of(const csi_context* c, int fid);
+// a local halo fill of bound slots in one batch
+static inline void halo_add(const csi_context* c, HaloBatch& B, int fid) { B.f[B.n] = ref_of(c, fid); B.im[B.n] = image_spec(c, fid); ++B.n; }
+static inline HaloBatch halo_batch(const csi_context* c, std::initializer_list<int> fids) { HaloBatch B{}; for (int fid : fids) halo_add(c, B, fid); return B; }
+void set_sides(GridDev& g, int topo_x, int topo_y);      // the four sides of a grid descriptor from the two topologies
 int32_t need(csi_context* c, std::initializer_list<int> ids);
 // every id bound, or CSI_ERR_NOT_BOUND "<who>: <group>needs field <name> (not bound<hint>)" (group: empty, or with its trailing blank)
 int32_t need_named(csi_context* c, const char* who, const char* group, std::initializer_list<int> ids, const char* hint);
@@ -500,6 +522,30 @@ Range stress_range(const csi_context* c, int V = 2);
 Range first_u_range(const csi_context* c, int V = 2);
 Range first_v_range(const csi_context* c, int V = 2);
 Range second_range(const csi_context* c, int V = 2);
+SubstepRanges substep_ranges(const csi_context* c, int V = 2);
+// ONE sub-step on the three kernels (split_explicit_momentum_equations.jl:178-187).  fc == nullptr: STRICT (viscosities, stress, the
+// strict velocity steps: four launches)
+void launch_substep(const EvpDev& P, const FastCoef* fc, const SubstepRanges& R, const ImageSpec& imu, const ImageSpec& imv, bool ufirst, hipStream_t st);
+int32_t copy_ping(csi_context* c, bool to_alt);      // the five whole parents of kPing: bound arrays -> c->alt (to_alt) or back
+// A batch of whole-array copies built entry by entry.  copy_batch_aligned() starts one whose aligned16 stays 1 while every pointer added
+// is 16-byte aligned; a batch started as CopyBatch{} keeps aligned16 == 0 whatever is added (the fold band's, csi_fold.hip)
+static inline CopyBatch copy_batch_aligned() { CopyBatch B{}; B.aligned16 = 1; return B; }
+static inline void copy_add(CopyBatch& B, const double* src, double* dst, long n) {
+    B.src[B.count] = src; B.dst[B.count] = dst; B.n[B.count] = n; ++B.count;
+    if ((((uintptr_t)src) | ((uintptr_t)dst)) & 15) B.aligned16 = 0;
+}
+// the halo a scheme's stencil needs (0: no such scheme), and the check of a scheme against the grid's halo
+static inline int advect_halo(int scheme) {
+    switch (scheme) {
+        case CSI_ADVECT_UPWIND1: return 1;
+        case CSI_ADVECT_WENO3: case CSI_ADVECT_UPWIND3: return 2;
+        case CSI_ADVECT_WENO5: case CSI_ADVECT_UPWIND5: return 3;
+        case CSI_ADVECT_WENO7: return 4;
+        default: return 0;
+    }
+}
+static inline bool advect_fits(const csi_context* c, int scheme) { const int h = advect_halo(scheme); return h > 0 && c->Hx >= h && c->Hy >= h; }
+int32_t advect_scheme_check(csi_context* c, int scheme);
 bool is_tiled(const csi_context* c);
 int32_t exchange(csi_context* c, const int* fids, int nf, int W);
 int32_t local_allgather(csi_context* c, const void* mine, size_t nb, std::vector<uint8_t>& out);
@@ -547,6 +593,7 @@ int32_t run_fused(csi_context* c, const EvpDev& P, const FastCoef& fc, int subst
 int32_t run_fused_peer(csi_context* c, double dt, const FastCoef& fc, int substeps, int first);
 bool fold_band_supported(csi_context* c, const EvpDev& Pfull, int substeps);
 int32_t run_fused_fold(csi_context* c, const EvpDev& Pfull, const FastCoef& fc, int substeps, int first);
+FoldBand fold_band(const csi_context* c, const EvpDev& Pfull, bool tiled, int k);      // everything but g_cut, of the tile as it is
 int32_t do_subcycle(csi_context* c, double dt, int substeps, int first);
 int32_t do_finalize(csi_context* c);
 int32_t need_evp(csi_context* c);
@@ -568,6 +615,12 @@ int32_t do_update_state(csi_context* c, bool in_step = false, bool tracers_fille
 int32_t do_tendencies(csi_context* c, int scheme);
 int32_t do_tendencies_or_zero(csi_context* c, int scheme);
 int32_t do_tracer_step(csi_context* c, double dt, int from_cache, bool fill_images = false);
+// csi_step.hip
+int32_t step_checks(csi_context* c, bool dynamics, bool rk3);
+int32_t step_stage(csi_context* c, double dt, int substeps, int scheme, bool dynamics, int from_cache);
+bool advect_stage_supported(const csi_context* c, int scheme);
+int32_t rk3_advection_only(csi_context* c, double dt, int scheme);
+int32_t cache_current_fields(csi_context* c);
 int32_t do_thermo(csi_context* c, double dt, int from_cache = 0);      // csi_thermo.hip: thermodynamic_time_step! of a stage (the mixed layer first, from Psi^- if from_cache)
 int extra_x(const csi_context* c, int fid);
 int extra_y(const csi_context* c, int fid);

@@ -37,11 +37,14 @@ int32_t band_substep(csi_context* c, const FoldBand& bd, const FastCoef& fc, con
     Q.u = b[0]; Q.v = b[1]; Q.s11 = b[2]; Q.s22 = b[3]; Q.s12 = b[4];
     if (d) { Q.al = d[0]; Q.zc = d[1]; Q.zf = d[2]; Q.Dl = d[3]; }
     Q.write_diag = last;
-    auto from = [&](Range r, int j0) { if (j0 > r.j0) r.j0 = j0; return r; };
-    launch_fast_stress(Q, from(bd.rs, jlo), fc, st);
-    if (ufirst) { launch_fast_ustep(Q, from(bd.ru1, jlo + 1), bd.imu, fc, st); launch_fast_vstep(Q, from(bd.r2, jlo + 1), bd.imv, fc, st); }
-    else { launch_fast_vstep(Q, from(bd.rv1, jlo + 1), bd.imv, fc, st); launch_fast_ustep(Q, from(bd.r2, jlo + 1), bd.imu, fc, st); }
+    launch_substep(Q, &fc, bd.R.from_row(jlo), bd.imu, bd.imv, ufirst, st);
     return CSI_OK;
+}
+// rows >= j0 of band array q, as one entry of a copy batch (aligned16 stays 0: these batches take the 8-byte path whatever the pointers)
+static void rows_from(const csi_context* c, int q, int j0, const double* src, double* dst, CopyBatch& B) {
+    const Bound& b = band_bound(c, q);
+    const size_t row = (size_t)(j0 - 1 + c->Hy), off = row * (size_t)b.ld;
+    copy_add(B, src + off, dst + off, (long)(((size_t)b.nj - row) * (size_t)b.ld));
 }
 // The same without the copy kernels (round 6b; evp_fast.hip, k_band_stress / k_band_vel): the band's launches are a chain of dependent,
 // latency-bound kernels beside the pair launch -- eight per pair of sub-steps with 3-4 us between two of them; this is six, each with
@@ -58,7 +61,6 @@ int32_t band_substeps_fused(csi_context* c, const FoldBand& bd, const FastCoef& 
         b[q] = band_ref(c, q);
     }
     for (int q = 0; q < 4; ++q) d[q] = band_ref(c, 5 + q);
-    auto from = [&](Range r, int j0) { if (j0 > r.j0) r.j0 = j0; return r; };
     const FRef none{nullptr, 0};
     // one sub-step: u, v, sigma from `in` (each launch reads the component it replaces at the point itself only), results into the
     // band's copies and -- `out` -- rows >= M + 1 into dst
@@ -68,17 +70,18 @@ int32_t band_substeps_fused(csi_context* c, const FoldBand& bd, const FastCoef& 
         Q.al = d[0]; Q.zc = d[1]; Q.zf = d[2]; Q.Dl = d[3];
         Q.write_diag = diag;
         const int j0 = bd.M + 1;
-        launch_band_stress(Q, from(bd.rs, jlo), fc, BandOut{b[2], b[3], b[4], out ? dst[2] : none, out ? dst[3] : none, out ? dst[4] : none, j0}, st);
+        const SubstepRanges R = bd.R.from_row(jlo);
+        launch_band_stress(Q, R.rs, fc, BandOut{b[2], b[3], b[4], out ? dst[2] : none, out ? dst[3] : none, out ? dst[4] : none, j0}, st);
         Q.s11 = b[2]; Q.s22 = b[3]; Q.s12 = b[4];
         const BandOut ou{b[0], none, none, out ? dst[0] : none, none, none, j0}, ov{b[1], none, none, out ? dst[1] : none, none, none, j0};
         if (ufirst) {
-            launch_band_vel(Q, from(bd.ru1, jlo + 1), bd.imu, fc, true, ou, st);
+            launch_band_vel(Q, R.ru1, bd.imu, fc, true, ou, st);
             Q.u = b[0];                                                              // (v reads the new u)
-            launch_band_vel(Q, from(bd.r2, jlo + 1), bd.imv, fc, false, ov, st);
+            launch_band_vel(Q, R.r2, bd.imv, fc, false, ov, st);
         } else {
-            launch_band_vel(Q, from(bd.rv1, jlo + 1), bd.imv, fc, false, ov, st);
+            launch_band_vel(Q, R.rv1, bd.imv, fc, false, ov, st);
             Q.v = b[1];
-            launch_band_vel(Q, from(bd.r2, jlo + 1), bd.imu, fc, true, ou, st);
+            launch_band_vel(Q, R.r2, bd.imu, fc, true, ou, st);
         }
     };
     if (n == 2) {
@@ -87,12 +90,7 @@ int32_t band_substeps_fused(csi_context* c, const FoldBand& bd, const FastCoef& 
     } else substep(src, (s % 2) == 0, bd.M - 3, last, true);
     if (last) {
         CopyBatch diag{};
-        for (int q = 5; q < 9; ++q) {
-            const Bound& bb = band_bound(c, q);
-            const size_t row = (size_t)(bd.M + 1 - 1 + c->Hy), off = row * (size_t)bb.ld;
-            diag.src[diag.count] = c->band[q].get() + off; diag.dst[diag.count] = bb.p + off; diag.n[diag.count] = (long)(((size_t)bb.nj - row) * (size_t)bb.ld);
-            ++diag.count;
-        }
+        for (int q = 5; q < 9; ++q) rows_from(c, q, bd.M + 1, c->band[q].get(), band_bound(c, q).p, diag);
         launch_copy_batch(diag, st, 64);
     }
     HIP_TRY(c, hipEventRecord(c->band_ev_band, st));
@@ -106,17 +104,11 @@ int32_t band_substeps(csi_context* c, const FoldBand& bd, const FastCoef& fc, in
     if (c->tune.band_fused != 0) return band_substeps_fused(c, bd, fc, cur, s, n, last);
     hipStream_t st = c->band_stream;
     HIP_TRY(c, hipStreamWaitEvent(st, c->band_ev_pair, 0));
-    auto rows_from = [&](int q, int j0, const double* src, double* dst, CopyBatch& B) {
-        const Bound& b = band_bound(c, q);
-        const size_t row = (size_t)(j0 - 1 + c->Hy), off = row * (size_t)b.ld;
-        B.src[B.count] = src + off; B.dst[B.count] = dst + off; B.n[B.count] = (long)(((size_t)b.nj - row) * (size_t)b.ld);
-        ++B.count;
-    };
     CopyBatch in{}, out{}, diag{};
     for (int q = 0; q < 5; ++q) {
         const Bound& b = band_bound(c, q);
-        rows_from(q, bd.M - 7, cur == 0 ? b.p : c->alt[q].get(), c->band[q].get(), in);
-        rows_from(q, bd.M + 1, c->band[q].get(), cur == 0 ? c->alt[q].get() : b.p, out);
+        rows_from(c, q, bd.M - 7, cur == 0 ? b.p : c->alt[q].get(), c->band[q].get(), in);
+        rows_from(c, q, bd.M + 1, c->band[q].get(), cur == 0 ? c->alt[q].get() : b.p, out);
     }
     launch_copy_batch(in, st, 64);
     FRef b[5], d[4];
@@ -130,7 +122,7 @@ int32_t band_substeps(csi_context* c, const FoldBand& bd, const FastCoef& fc, in
     } else if ((rc = band_substep(c, bd, fc, b, d, (s % 2) == 0, bd.M - 3, last, st))) return rc;
     launch_copy_batch(out, st, 64);
     if (last) {
-        for (int q = 5; q < 9; ++q) rows_from(q, bd.M + 1, c->band[q].get(), band_bound(c, q).p, diag);
+        for (int q = 5; q < 9; ++q) rows_from(c, q, bd.M + 1, c->band[q].get(), band_bound(c, q).p, diag);
         launch_copy_batch(diag, st, 64);
     }
     HIP_TRY(c, hipEventRecord(c->band_ev_band, st));
@@ -155,15 +147,19 @@ bool fold_band_supported(csi_context* c, const EvpDev& Pfull, int substeps) {
     P.g = c->g;
     return pair_supported(c) && pair_forcing_kind(P) >= 0;
 }
-int32_t run_fused_fold(csi_context* c, const EvpDev& Pfull, const FastCoef& fc, int substeps, int first) {
-    FoldBand bd;
+FoldBand fold_band(const csi_context* c, const EvpDev& Pfull, bool tiled, int k) {
+    FoldBand bd{};
     bd.M = c->Ny - c->Hy - 4;
-    bd.tiled = c->g.ylo == SIDE_CONNECTED;
-    bd.k = bd.tiled ? exchange_interval(c) : 2;
+    bd.tiled = tiled; bd.k = k;
     bd.g_full = c->g; bd.Ny_full = c->Ny;
     bd.P = Pfull;
     bd.imu = image_spec(c, CSI_F_U); bd.imv = image_spec(c, CSI_F_V);
-    bd.rs = stress_range(c); bd.ru1 = first_u_range(c); bd.rv1 = first_v_range(c); bd.r2 = second_range(c);
+    bd.R = substep_ranges(c);
+    return bd;
+}
+int32_t run_fused_fold(csi_context* c, const EvpDev& Pfull, const FastCoef& fc, int substeps, int first) {
+    const bool tiled = c->g.ylo == SIDE_CONNECTED;
+    FoldBand bd = fold_band(c, Pfull, tiled, tiled ? exchange_interval(c) : 2);
     FoldCut cut(c, bd.M);
     bd.g_cut = c->g;
     EvpDev P = Pfull;

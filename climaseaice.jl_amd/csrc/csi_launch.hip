@@ -1,4 +1,6 @@
-// csi_launch.hip -- launch loops: the EVP sub-cycle on every path, finalize_rheology!, time_step_momentum!, tracer steps, update_state!  (split out of csi_abi.hip in round 4; see csi_ctx.h)
+// csi_launch.hip -- launch loops: the EVP sub-cycle on every path, finalize_rheology!, time_step_momentum!, tracer steps, update_state!,
+// csi_profile_substeps.  The three-kernel sub-step, its ranges, the ping copies and the batch builders they call are stated once in
+// csi_core.hip / csi_ctx.h; whole steps are sequenced in csi_step.hip.  (Split out of csi_abi.hip in round 4; see csi_ctx.h)
 #include "csi_ctx.h"
 
 namespace csi_host {
@@ -247,9 +249,7 @@ int32_t run_fused(csi_context* c, const EvpDev& P, const FastCoef& fc, int subst
     for (int mp = 0; pairs && 2 * mp + 1 < kb; ++mp) GP[mp] = pair_geom(c, pair_dec(mp));
     ActivityPlan act;
     if ((rc = plan_activity(c, c->act.enabled != 0 && pairs && !tiled && substeps >= 8, peer, pair_dec(0), GP[0], &act))) return rc;
-    if ((!every_cell_written || act.q0) && !peer)          // (peer: run_fused_peer has made the copy, BEFORE its exchange)
-        for (int q = 0; q < 5; ++q)
-            HIP_TRY(c, hipMemcpyAsync(c->alt[q].get(), c->f[kPing[q]].p, c->alt[q].buf.size() * sizeof(double), hipMemcpyDeviceToDevice, c->stream));
+    if ((!every_cell_written || act.q0) && !peer && (rc = copy_ping(c, true))) return rc;      // (peer: run_fused_peer has made the copy, BEFORE its exchange)
     // the tables, through the pinned ring
     if (!c->host_ring) {
         HIP_TRY(c, c->host_ring.alloc((size_t)(NSINGLE + NPAIR) * csi_context::kRing, hipHostMallocDefault));
@@ -342,10 +342,7 @@ int32_t run_fused(csi_context* c, const EvpDev& P, const FastCoef& fc, int subst
             const FRef* b = cur == 0 ? orig : alt;
             Q.u = b[0]; Q.v = b[1]; Q.s11 = b[2]; Q.s22 = b[3]; Q.s12 = b[4];
             Q.write_diag = (s + 1 == end);
-            const int V = single_v(m);
-            launch_fast_stress(Q, stress_range(c, V), fc, c->stream);
-            if (ufirst) { launch_fast_ustep(Q, first_u_range(c, V), T.imu, fc, c->stream); launch_fast_vstep(Q, second_range(c, V), T.imv, fc, c->stream); }
-            else { launch_fast_vstep(Q, first_v_range(c, V), T.imv, fc, c->stream); launch_fast_ustep(Q, second_range(c, V), T.imu, fc, c->stream); }
+            launch_substep(Q, &fc, substep_ranges(c, single_v(m)), T.imu, T.imv, ufirst, c->stream);
             m += 1; s += 1;
             cur ^= 1;           // undone below: this sub-step did not switch buffers
             nlaunch += 2;
@@ -373,14 +370,9 @@ int32_t run_fused(csi_context* c, const EvpDev& P, const FastCoef& fc, int subst
     HIP_TRY(c, hipEventRecord(c->ev1, c->stream));
     if ((rc = stats_mark(c))) return rc;
     stats_launches(c, nlaunch);
-    if (cur == 1)   // the result sits in the library's buffers
-        for (int q = 0; q < 5; ++q)
-            HIP_TRY(c, hipMemcpyAsync(c->f[kPing[q]].p, c->alt[q].get(), c->alt[q].buf.size() * sizeof(double), hipMemcpyDeviceToDevice, c->stream));
+    if (cur == 1 && (rc = copy_ping(c, false))) return rc;      // the result sits in the library's buffers
     HIP_TRY(c, hipGetLastError());
-    c->last_exchanges = nex;
-    c->last_k = k;
-    c->last_launches = nlaunch;
-    c->last_substeps = substeps;
+    c->last = csi_context::LastPath{c->last.timed, c->last.fused, c->last.per_substep, nlaunch, substeps, nex, k};      // (the first three: do_subcycle's)
     c->last_used_pairs = pairs && substeps >= 2;
     return CSI_OK;
 }
@@ -398,29 +390,19 @@ int32_t run_fused_peer(csi_context* c, double dt, const FastCoef& fc, int subste
     // need no copy: the neighbours' images rewrite all H layers at every launch.)
     if ((rc = ensure_alt(c))) return rc;
     const bool fold = c->g.yhi == SIDE_FOLD;
-    if (has_walls(c) || fold)
-        for (int q = 0; q < 5; ++q)
-            HIP_TRY(c, hipMemcpyAsync(c->alt[q].get(), c->f[kPing[q]].p, c->alt[q].buf.size() * sizeof(double), hipMemcpyDeviceToDevice, c->stream));
+    if ((has_walls(c) || fold) && (rc = copy_ping(c, true))) return rc;
     const int W = std::min(std::min(c->Hx, c->Hy), 4);
     if ((rc = exchange_refs(c, orig, 5, W))) return rc;
     // the fold tile of a y partition: its three-kernel band works on the tile as it is (FoldBand); the pair launches see the
     // tile cut below the band, like every other tile with its connected sides turned into periodic ones (PeerView)
-    FoldBand bd;
     const EvpDev Pfull = evp_dev(c, dt);
-    if (fold) {
-        bd.M = c->Ny - c->Hy - 4;
-        bd.tiled = false; bd.k = 2;
-        bd.g_full = c->g; bd.Ny_full = c->Ny;
-        bd.P = Pfull;
-        bd.imu = image_spec(c, CSI_F_U); bd.imv = image_spec(c, CSI_F_V);
-        bd.rs = stress_range(c); bd.ru1 = first_u_range(c); bd.rv1 = first_v_range(c); bd.r2 = second_range(c);
-    }
+    FoldBand bd = fold ? fold_band(c, Pfull, false, 2) : FoldBand{};
     PeerView view(c);
     bd.g_cut = c->g;
     EvpDev P = Pfull;           // (arrays and per-row pointers of the tile as it is; only the grid descriptor differs)
     P.g = c->g;
     rc = run_fused(c, P, fc, substeps, first, true, fold ? &bd : nullptr);
-    c->last_exchanges = 1;
+    c->last.exchanges = 1;
     return rc;
 }
 
@@ -429,13 +411,7 @@ int32_t do_subcycle(csi_context* c, double dt, int substeps, int first) {
     int32_t rc;
     if ((rc = peer_check_entry(c))) return rc;
     if ((rc = ensure_row_constant(c))) return rc;
-    {                                                // :170-171, both fields in one batch of two launches
-        HaloBatch B{};
-        B.f[0] = ref_of(c, CSI_F_U); B.im[0] = image_spec(c, CSI_F_U);
-        B.f[1] = ref_of(c, CSI_F_V); B.im[1] = image_spec(c, CSI_F_V);
-        B.n = 2;
-        launch_fill_halo_batch(B, c->g, c->stream);
-    }
+    launch_fill_halo_batch(halo_batch(c, {CSI_F_U, CSI_F_V}), c->g, c->stream);      // :170-171, both fields in one batch of two launches
     const bool tiled = is_tiled(c);
     // halo exchange of u, v every k sub-steps with width 2k (k = 1: every sub-step; the reference is the
     // k = substeps extreme with its 2*substeps+3 halo, split_explicit_momentum_equations.jl:51-64)
@@ -462,9 +438,7 @@ int32_t do_subcycle(csi_context* c, double dt, int substeps, int first) {
     if (!peer && fast && fold_band_supported(c, P, substeps)) {
         c->peer.last = 0;
         if ((rc = run_fused_fold(c, P, fc, substeps, first))) return rc;
-        c->timed = true;
-        c->launches_per_substep = 1;
-        c->last_fused = 2;
+        c->last = csi_context::LastPath{true, 2, 1, c->last.launches, c->last.substeps, c->last.exchanges, c->last.k};      // (the last four: run_fused's)
         return CSI_OK;
     }
     const bool fuse = peer || (fast && c->fusion && substeps > 0 &&
@@ -473,34 +447,18 @@ int32_t do_subcycle(csi_context* c, double dt, int substeps, int first) {
     if (fuse) {
         c->peer.last = peer ? 1 : 0;
         if ((rc = peer ? run_fused_peer(c, dt, fc, substeps, first) : run_fused(c, P, fc, substeps, first))) return rc;
-        c->timed = true;
-        c->launches_per_substep = 1 + ((tiled && k == 1) ? 3 : 0);
-        c->last_fused = c->last_used_pairs ? 2 : 1;
+        c->last = csi_context::LastPath{true, c->last_used_pairs ? 2 : 1, 1 + ((tiled && k == 1) ? 3 : 0), c->last.launches, c->last.substeps, c->last.exchanges, c->last.k};
         return CSI_OK;
     }
-    c->last_fused = 0;
+    c->last.fused = 0;      // (before the exchange: a sub-cycle that fails there has left the fused paths already)
     c->peer.last = 0;
     if (tiled && (rc = exchange(c, uvs, nxf, W))) return rc;
     HIP_TRY(c, hipEventRecord(c->ev0, c->stream));
     if ((rc = stats_mark(c))) return rc;
     int m = 0, nex = 0;   // position inside the exchange batch
     for (int s = first; s < first + substeps; ++s) {
-        const int V = W - 2 * m;
-        const Range rs = stress_range(c, V), ru1 = first_u_range(c, V), rv1 = first_v_range(c, V), r2 = second_range(c, V);
-        if (fast) {
-            P.write_diag = (s == first + substeps - 1);
-            launch_fast_stress(P, rs, fc, c->stream);
-        } else {
-            launch_strict_visc(P, rs, c->stream);          // compute_stresses!, evp:222-234
-            launch_strict_stress(P, rs, c->stream);
-        }
-        if ((s % 2) == 0) {                                // :178-182
-            if (fast) { launch_fast_ustep(P, ru1, imu, fc, c->stream); launch_fast_vstep(P, r2, imv, fc, c->stream); }
-            else { launch_strict_ustep(P, ru1, imu, c->stream); launch_strict_vstep(P, r2, imv, c->stream); }
-        } else {                                           // :184-187
-            if (fast) { launch_fast_vstep(P, rv1, imv, fc, c->stream); launch_fast_ustep(P, r2, imu, fc, c->stream); }
-            else { launch_strict_vstep(P, rv1, imv, c->stream); launch_strict_ustep(P, r2, imu, c->stream); }
-        }
+        if (fast) P.write_diag = (s == first + substeps - 1);
+        launch_substep(P, fast ? &fc : nullptr, substep_ranges(c, W - 2 * m), imu, imv, (s % 2) == 0, c->stream);
         ++m;
         if (tiled && (m == k || s == first + substeps - 1)) {   // RCCL send/recv of the u, v halos
             if ((rc = exchange(c, uvs, nxf, W))) return rc;
@@ -512,16 +470,13 @@ int32_t do_subcycle(csi_context* c, double dt, int substeps, int first) {
     if ((rc = stats_mark(c))) return rc;
     stats_launches(c, substeps * (fast ? 3 : 4));
     HIP_TRY(c, hipGetLastError());
-    c->timed = true;
-    c->launches_per_substep = (fast ? 3 : 4) + ((tiled && k == 1) ? 3 : 0);
-    c->last_exchanges = nex;
-    c->last_k = k;
+    // (launches / sub-steps: not counted on this path -- they stay those of the last path that did)
+    c->last = csi_context::LastPath{true, 0, (fast ? 3 : 4) + ((tiled && k == 1) ? 3 : 0), c->last.launches, c->last.substeps, nex, k};
     return CSI_OK;
 }
 
 int32_t do_finalize(csi_context* c) {
-    HaloBatch B{};
-    for (int fid : {CSI_F_S11, CSI_F_S12, CSI_F_S22}) { B.f[B.n] = ref_of(c, fid); B.im[B.n] = image_spec(c, fid); ++B.n; }
+    const HaloBatch B = halo_batch(c, {CSI_F_S11, CSI_F_S12, CSI_F_S22});
     launch_fill_halo_batch(B, c->g, c->stream);
     HIP_TRY(c, hipGetLastError());
     // fill_halo_regions!(sigma) across tiles.  After a sub-cycle on the peer transport there is nothing to move: the neighbours' last
@@ -618,7 +573,7 @@ int32_t do_update_state(csi_context* c, bool in_step, bool tracers_filled) {
         launch_mask_v(ref_of(c, CSI_F_V), c->g, c->stream);
     }
     HaloBatch B{};
-    auto add = [&](int fid) { B.f[B.n] = ref_of(c, fid); B.im[B.n] = image_spec(c, fid); ++B.n; };
+    auto add = [&](int fid) { halo_add(c, B, fid); };
     if (!tracers_filled) {
         add(CSI_F_H); add(CSI_F_A);
         if (snow) add(CSI_F_HS);
@@ -640,11 +595,7 @@ int32_t do_update_state(csi_context* c, bool in_step, bool tracers_filled) {
 int32_t do_tendencies(csi_context* c, int scheme) {
     int32_t rc;
     if ((rc = need(c, {CSI_F_U, CSI_F_V, CSI_F_H, CSI_F_A, CSI_F_GH, CSI_F_GA}))) return rc;
-    const bool third = scheme == CSI_ADVECT_WENO3 || scheme == CSI_ADVECT_UPWIND3;
-    int need_h = scheme == CSI_ADVECT_WENO7 ? 4 : (scheme == CSI_ADVECT_UPWIND1 ? 1 : (third ? 2 : 3));
-    if (scheme != CSI_ADVECT_UPWIND1 && scheme != CSI_ADVECT_WENO5 && scheme != CSI_ADVECT_WENO7 && scheme != CSI_ADVECT_UPWIND5 && !third)
-        return fail(c, CSI_ERR_INVALID_ARGUMENT, "unknown advection scheme");
-    if (c->Hx < need_h || c->Hy < need_h) return fail(c, CSI_ERR_INVALID_ARGUMENT, "halo too small for the advection scheme");
+    if ((rc = advect_scheme_check(c, scheme))) return rc;
     c->last_adv = launch_tracer_tendencies(adv_dev(c, scheme, 0.0, 0), c->mode, c->stream);
     c->last_adv_stage = 0;
     HIP_TRY(c, hipGetLastError());
@@ -699,7 +650,7 @@ extern "C" int32_t csi_profile_substeps(csi_context* c, double dt, int32_t subst
         HIP_TRY(c, hipStreamSynchronize(c->stream));
         float t = 0.f;
         HIP_TRY(c, hipEventElapsedTime(&t, c->ev0, c->ev1));
-        out_ms4[0] = t / (c->last_launches > 0 ? c->last_launches : substeps); out_ms4[1] = out_ms4[2] = out_ms4[3] = 0.0;
+        out_ms4[0] = t / (c->last.launches > 0 ? c->last.launches : substeps); out_ms4[1] = out_ms4[2] = out_ms4[3] = 0.0;
         return CSI_OK;
     }
     std::vector<hipEvent_t> ev((size_t)substeps * 4 + 1);
@@ -711,7 +662,8 @@ extern "C" int32_t csi_profile_substeps(csi_context* c, double dt, int32_t subst
         if (fast) launch_fast_stress(P, rs, fc, c->stream);
         else { launch_strict_visc(P, rs, c->stream); launch_strict_stress(P, rs, c->stream); }
         HIP_TRY(c, hipEventRecord(ev[k++], c->stream));
-        // u then v on every sub-step here (the order only permutes which kernel has the ring range)
+        // Not launch_substep, on purpose: every kernel is timed on its own, u then v on every sub-step (the order only permutes which
+        // kernel has the ring range), v on the interior range
         if (fast) launch_fast_ustep(P, ru1, imu, fc, c->stream); else launch_strict_ustep(P, ru1, imu, c->stream);
         HIP_TRY(c, hipEventRecord(ev[k++], c->stream));
         if (fast) launch_fast_vstep(P, rv, imv, fc, c->stream); else launch_strict_vstep(P, rv, imv, c->stream);

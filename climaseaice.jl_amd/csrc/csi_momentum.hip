@@ -121,13 +121,7 @@ static int32_t viscous_subcycle(csi_context* c, double dt, int substeps, int rk_
     int32_t rc;
     if (rk_reset && (rc = reset_velocities(c))) return rc;
     if ((rc = fill_forcing_halos(c))) return rc;           // :133-134 (initialize_rheology!: nothing)
-    {                                                       // :170-171
-        HaloBatch B{};
-        B.f[0] = ref_of(c, CSI_F_U); B.im[0] = image_spec(c, CSI_F_U);
-        B.f[1] = ref_of(c, CSI_F_V); B.im[1] = image_spec(c, CSI_F_V);
-        B.n = 2;
-        launch_fill_halo_batch(B, c->g, c->stream);
-    }
+    launch_fill_halo_batch(halo_batch(c, {CSI_F_U, CSI_F_V}), c->g, c->stream);      // :170-171
     if ((rc = free_drift_fields(c, dt))) return rc;
     // the second array of each component.  A launch rewrites every interior point and the halo images of its stores; what no store
     // reaches (halos beyond walls, deeper layers of a ValueBoundaryCondition side) must agree in both arrays: copied once, unless every
@@ -136,13 +130,8 @@ static int32_t viscous_subcycle(csi_context* c, double dt, int substeps, int rk_
     for (ScratchField& a : c->vis_alt) HIP_TRY(c, a.ensure(c));
     const bool every_cell_imaged = c->g.xlo == SIDE_PERIODIC && c->g.xhi == SIDE_PERIODIC && c->g.ylo == SIDE_PERIODIC && c->g.yhi == SIDE_PERIODIC;
     if (!every_cell_imaged && substeps > 0) {
-        CopyBatch B{};
-        B.aligned16 = 1;
-        for (int q = 0; q < 2; ++q) {
-            const Bound& b = c->f[comp[q]];
-            B.src[B.count] = b.p; B.dst[B.count] = c->vis_alt[q].get(); B.n[B.count] = (long)b.ld * b.nj; ++B.count;
-            if ((((uintptr_t)b.p) | ((uintptr_t)c->vis_alt[q].get())) & 15) B.aligned16 = 0;
-        }
+        CopyBatch B = copy_batch_aligned();
+        for (int q = 0; q < 2; ++q) copy_add(B, c->f[comp[q]].p, c->vis_alt[q].get(), (long)c->f[comp[q]].ld * c->f[comp[q]].nj);
         launch_copy_batch(B, c->stream);
     }
     FRef bound[2], alt[2];
@@ -170,24 +159,13 @@ static int32_t viscous_subcycle(csi_context* c, double dt, int substeps, int rk_
     }
     HIP_TRY(c, hipEventRecord(c->ev1, c->stream));
     if (cur[0] | cur[1]) {                                  // one copy back: the components whose result sits in the scratch
-        CopyBatch B{};
-        B.aligned16 = 1;
+        CopyBatch B = copy_batch_aligned();
         for (int q = 0; q < 2; ++q)
-            if (cur[q]) {
-                const Bound& b = c->f[comp[q]];
-                B.src[B.count] = c->vis_alt[q].get(); B.dst[B.count] = b.p; B.n[B.count] = (long)b.ld * b.nj; ++B.count;
-                if ((((uintptr_t)b.p) | ((uintptr_t)c->vis_alt[q].get())) & 15) B.aligned16 = 0;
-            }
+            if (cur[q]) copy_add(B, c->vis_alt[q].get(), c->f[comp[q]].p, (long)c->f[comp[q]].ld * c->f[comp[q]].nj);
         launch_copy_batch(B, c->stream);
     }
     HIP_TRY(c, hipGetLastError());
-    c->timed = true;
-    c->last_fused = 0;
-    c->last_launches = 2 * substeps;
-    c->last_substeps = substeps;
-    c->launches_per_substep = 2;
-    c->last_exchanges = 0;
-    c->last_k = 1;
+    c->last = csi_context::LastPath{true, 0, 2, 2 * substeps, substeps, 0, 1};
     return CSI_OK;                                          // finalize_rheology!: nothing
 }
 
@@ -217,13 +195,7 @@ static int32_t explicit_step(csi_context* c, double dt, int rk_reset) {
     launch_explicit_vstep(M, r, image_spec(c, CSI_F_V), fast, c->stream);     // :34-35
     HIP_TRY(c, hipEventRecord(c->ev1, c->stream));
     HIP_TRY(c, hipGetLastError());
-    c->timed = true;
-    c->last_fused = 0;
-    c->last_launches = 2;                                   // (the tendency launch belongs to csi_compute_momentum_tendencies)
-    c->last_substeps = 1;
-    c->launches_per_substep = 2;
-    c->last_exchanges = 0;
-    c->last_k = 1;
+    c->last = csi_context::LastPath{true, 0, 2, 2, 1, 0, 1};      // (two launches: the tendency launch belongs to csi_compute_momentum_tendencies)
     return CSI_OK;
 }
 
@@ -237,14 +209,8 @@ static int32_t free_drift_dynamics_step(csi_context* c) {
     launch_free_drift_step(evp_dev(c, 0.0), interior_range(c), image_spec(c, CSI_F_U), image_spec(c, CSI_F_V), c->stream);
     HIP_TRY(c, hipEventRecord(c->ev1, c->stream));
     HIP_TRY(c, hipGetLastError());
-    c->timed = true;
-    c->last_fused = 0;
+    c->last = csi_context::LastPath{true, 0, 1, 1, 1, 0, 1};
     c->peer.last = 0;
-    c->last_launches = 1;
-    c->last_substeps = 1;
-    c->launches_per_substep = 1;
-    c->last_exchanges = 0;
-    c->last_k = 1;
     return CSI_OK;
 }
 

@@ -66,13 +66,7 @@ int32_t tracers_first_half(csi_context* c, int scheme, double dt, int from_cache
     }
     for (int id : {CSI_F_GA, CSI_F_AM})
         if (c->f[id].p && c->f[id].ld != c->trc.shape.ld) return fail(c, CSI_ERR_INVALID_ARGUMENT, std::string("tracers: parent shape mismatch: ") + slot_name(id) + " vs h");
-    if (scheme) {
-        const bool third = scheme == CSI_ADVECT_WENO3 || scheme == CSI_ADVECT_UPWIND3;
-        const int need_h = scheme == CSI_ADVECT_WENO7 ? 4 : (scheme == CSI_ADVECT_UPWIND1 ? 1 : (third ? 2 : 3));
-        if (scheme != CSI_ADVECT_UPWIND1 && scheme != CSI_ADVECT_WENO5 && scheme != CSI_ADVECT_WENO7 && scheme != CSI_ADVECT_UPWIND5 && !third)
-            return fail(c, CSI_ERR_INVALID_ARGUMENT, "unknown advection scheme");
-        if (c->Hx < need_h || c->Hy < need_h) return fail(c, CSI_ERR_INVALID_ARGUMENT, "halo too small for the advection scheme");
-    }
+    if (scheme && (rc = advect_scheme_check(c, scheme))) return rc;
     c->trc.star_from_cache = from_cache != 0;
     const TracersDev T = tracers_dev(c, scheme, dt, from_cache);
     if (scheme) {
@@ -108,13 +102,8 @@ int32_t tracers_cache(csi_context* c) {
     const csi_context::Tracers& R = c->trc;
     const size_t plane = (size_t)R.shape.ld * (size_t)R.shape.nj;
     for (int k0 = 0; k0 < R.t.n; k0 += 6) {
-        CopyBatch B{};
-        B.aligned16 = 1;
-        for (int k = k0; k < R.t.n && k < k0 + 6; ++k) {
-            double* dst = R.base.get() + (size_t)k * plane;
-            B.src[B.count] = R.t.c[k]; B.dst[B.count] = dst; B.n[B.count] = (long)plane; ++B.count;
-            if ((((uintptr_t)R.t.c[k]) | ((uintptr_t)dst)) & 15) B.aligned16 = 0;
-        }
+        CopyBatch B = copy_batch_aligned();
+        for (int k = k0; k < R.t.n && k < k0 + 6; ++k) copy_add(B, R.t.c[k], R.base.get() + (size_t)k * plane, (long)plane);
         launch_copy_batch(B, c->stream);
     }
     HIP_TRY(c, hipGetLastError());
