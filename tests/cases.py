@@ -11,12 +11,23 @@ import numpy as np
 import climaseaice_jl_amd as csi
 
 
+def marginal_rows(marginal=None):
+    """The (aice, h) of the two rows of make_case's thin-ice patch: the default pair, one pair for both rows, or one pair per row."""
+    if marginal is None:
+        marginal = (5e-4, 1e-3)
+    return tuple(marginal) if np.ndim(marginal) == 2 else (tuple(marginal),) * 2
+
+
 def make_case(Nx=64, Ny=48, H=4, topo=("periodic", "periodic"), grid="rectilinear", spacing=2000.0,
               substeps=10, dt=120.0, coriolis=1e-4, top=(0.01, 0.01), bottom="semi", ue=0.0, ve=0.0,
               patches=True, noise=0.05, seed=3, u0=0.1, v0=0.0, random_uv=0.0, pressure="replacement",
               field_forcing=False, land=0.0, free_drift=False, beta=None, curvilinear=None, noslip=False,
               user_forcing=False, immersed_bc=None, coriolis_points=False, wind_drag=None,
-              tripolar=None, ice_edge=None, ice_free_rows=None):
+              tripolar=None, ice_edge=None, ice_free_rows=None, cell=None, evp=None, marginal=None):
+    """cell = (dx, dy): rectangular cells on the rectilinear grid (`spacing` stays the scalar of the square ones).
+    evp: overrides of the rheology / dynamics parameters, keyed like the oracle's (EVP_KEYS); absent keys keep the defaults.
+    marginal = (aice, h), or one such pair for each of the two rows: the values of the thin-ice patch (default (5e-4, 1e-3): below the
+    default minimum_concentration)."""
     rng = np.random.default_rng(seed)
     Hx, Hy = (H, H) if np.isscalar(H) else (int(H[0]), int(H[1]))       # H: one halo width, or (Hx, Hy)
     c = dict(Nx=Nx, Ny=Ny, H=H, Hx=Hx, Hy=Hy, topo=topo, grid=grid, spacing=spacing, substeps=substeps, dt=dt, coriolis=coriolis,
@@ -27,6 +38,12 @@ def make_case(Nx=64, Ny=48, H=4, topo=("periodic", "periodic"), grid="rectilinea
              immersed_bc=immersed_bc,              # ((uW, uE, uS, uN), (vW, vE, vS, vN)): immersed FluxBoundaryCondition numbers
              coriolis_points=coriolis_points,      # per-point f planes on a curvilinear grid (PointwiseCoriolis)
              wind_drag=wind_drag)                  # top stress = SemiImplicitStress(air velocities; rho 1.3, Cd 1.2e-3): "numbers" / "arrays"
+    if evp:
+        assert set(evp) <= set(EVP_KEYS), sorted(set(evp) - set(EVP_KEYS))
+        c["evp"] = dict(evp)
+    if cell is not None:
+        assert grid == "rectilinear", "cell = (dx, dy) describes the rectilinear grid"
+        c["cell"] = (float(cell[0]), float(cell[1]))
     T = {"periodic": csi.Periodic, "bounded": csi.Bounded, "folded": csi.RightFolded}     # "folded": y of a TripolarGrid
     tt = (T[topo[0]], T[topo[1]])
     # grid = "tripolar": csi.TripolarGrid(size, **tripolar) -- latitude-longitude rows below a bipolar cap, north fold, the reference's
@@ -39,7 +56,8 @@ def make_case(Nx=64, Ny=48, H=4, topo=("periodic", "periodic"), grid="rectilinea
         c["topo"] = topo
         g = csi.TripolarGrid((Nx, Ny), halo=(Hx, Hy), **(tripolar or {}))
     elif grid == "rectilinear":
-        g = csi.RectilinearGrid((Nx, Ny), x=(0.0, Nx * spacing), y=(0.0, Ny * spacing), topology=tt, halo=(Hx, Hy))
+        cdx, cdy = c.get("cell", (spacing, spacing))
+        g = csi.RectilinearGrid((Nx, Ny), x=(0.0, Nx * cdx), y=(0.0, Ny * cdy), topology=tt, halo=(Hx, Hy))
     else:
         g = csi.LatitudeLongitudeGrid((Nx, Ny), longitude=(0, 60), latitude=(20, 70), topology=tt, halo=(Hx, Hy))
     if curvilinear is not None:
@@ -58,8 +76,9 @@ def make_case(Nx=64, Ny=48, H=4, topo=("periodic", "periodic"), grid="rectilinea
         i0, i1, j0, j1 = Nx // 8, Nx // 4, Ny // 6, Ny // 3
         a[j0:j1, i0:i1] = 0.0                       # open water: zero branch
         h[j0:j1, i0:i1] = 0.0
-        a[j1:j1 + 2, i0:i1] = 5e-4                  # below minimum_concentration: marginal branch
-        h[j1:j1 + 2, i0:i1] = 1e-3
+        for r, (am, hm) in enumerate(marginal_rows(marginal)):
+            a[j1 + r, i0:i1] = am                   # below minimum_concentration: marginal branch
+            h[j1 + r, i0:i1] = hm
     nxu, nyu = g.interior_size(csi.Face, csi.Center)
     nxv, nyv = g.interior_size(csi.Center, csi.Face)
     u = np.full((nyu, nxu), float(u0)) + random_uv * rng.standard_normal((nyu, nxu))
@@ -140,6 +159,19 @@ def make_case(Nx=64, Ny=48, H=4, topo=("periodic", "periodic"), grid="rectilinea
     return c
 
 
+# the overrides `make_case(evp=...)` takes: the oracle's name -> (where the model takes it, its keyword there)
+EVP_KEYS = {"P_star": ("rheology", "ice_compressive_strength"), "C_star": ("rheology", "ice_compaction_hardening"),
+            "ecc": ("rheology", "yield_curve_eccentricity"), "delta_min": ("rheology", "minimum_plastic_stress"),
+            "alpha_min": ("rheology", "min_relaxation_parameter"), "alpha_max": ("rheology", "max_relaxation_parameter"),
+            "c_alpha": ("rheology", "relaxation_strength"), "min_mass": ("dynamics", "minimum_mass"),
+            "min_conc": ("dynamics", "minimum_concentration"), "rho_ice": ("model", "sea_ice_density")}
+
+
+def evp_keywords(case, where):
+    """the overrides of case["evp"] that `where` ("rheology" / "dynamics" / "model") takes, under its own keyword names"""
+    return {kw: float(case["evp"][k]) for k, (w, kw) in EVP_KEYS.items() if w == where and k in case.get("evp", {})}
+
+
 def _fill_parent_like(p, name, interior):
     """numpy parent array of oracle field `name` holding `interior` with locally filled halos."""
     import oracle as O
@@ -187,6 +219,10 @@ def oracle_problem(case, omp=False):
             p.set_value_bc("v", side, 0.0)
     if case["pressure"] != "replacement":
         p.s.pressure_kind = O.PRESSURE_ICE_STRENGTH
+    for k, val in case.get("evp", {}).items():
+        setattr(p.s, k, float(val))
+    if "alpha_max" in case.get("evp", {}):
+        p.f["alpha"][...] = p.s.alpha_max          # (Auxiliaries: fill!(alpha, alpha+) with the rheology's own alpha+)
     if case.get("field_forcing"):
         tu = _fill_parent_like(p, "u", case["top_u"]); tv = _fill_parent_like(p, "v", case["top_v"])
         p.set_stress("top", O.STRESS_FIELD, fu=tu, fv=tv)
@@ -280,13 +316,14 @@ def csi_model(case, mode="fast", timestepper="ForwardEuler", advection=None, dev
         if tile is not None:
             ua, va = g.local_interior(ua, csi.Face, csi.Center), g.local_interior(va, csi.Center, csi.Face)
         top = csi.SemiImplicitStress(ue=ua, ve=va, rho_e=1.3, Cd=1.2e-3)
-    rheo = csi.ElastoViscoPlasticRheology()
+    rheo = csi.ElastoViscoPlasticRheology(**evp_keywords(case, "rheology"))
     if case["pressure"] != "replacement":
         rheo.pressure_formulation = csi.IceStrength()
     dyn = csi.SeaIceMomentumEquation(g, coriolis=coriolis_of(case),
                                      rheology=rheo, top_momentum_stress=top, bottom_momentum_stress=bottom,
                                      free_drift=csi.StressBalanceFreeDrift() if case.get("free_drift") else None,
-                                     solver=csi.SplitExplicitSolver(substeps=case["substeps"]), device=device)
+                                     solver=csi.SplitExplicitSolver(substeps=case["substeps"]), device=device,
+                                     **evp_keywords(case, "dynamics"))
     ubc, vbc_ = {}, {}
     if case.get("noslip"):
         vbc = csi.ValueBoundaryCondition(0.0)
@@ -303,6 +340,7 @@ def csi_model(case, mode="fast", timestepper="ForwardEuler", advection=None, dev
         if tile is not None:
             fu, fv = g.local_interior(fu, csi.Face, csi.Center), g.local_interior(fv, csi.Center, csi.Face)
         model_kw = dict(model_kw, forcing=dict(u=fu, v=fv))
+    model_kw = dict(evp_keywords(case, "model"), **model_kw)
     model = csi.SeaIceModel(g, dynamics=dyn, advection=advection, timestepper=timestepper, device=device, mode=mode, **model_kw)
     if case.get("field_forcing") or case.get("wind_drag") == "arrays" or case.get("bottom") == "arrays":
         slots = [sl for sl, on in (("TOP", (case.get("field_forcing") and case.get("wind_drag") != "numbers") or case.get("wind_drag") == "arrays"),

@@ -257,9 +257,10 @@ def test_fast_vs_oracle_full_cycle(name, oracle_lib):
         # diagnostics of the last sub-step, where every path defines them (cmp_region)
         ga, pa = cmp_region(c, "alpha", g["alpha"]), cmp_region(c, "alpha", p.f["alpha"])
         # alpha clamp decisions agree (alpha- / alpha+ plateaus are the same cells)
-        for bound in (50.0, 300.0):
+        amin, amax = (c.get("evp", {}).get(k, default) for k, default in (("alpha_min", 50.0), ("alpha_max", 300.0)))     # the case's clamp bounds
+        for bound in (amin, amax):
             assert np.array_equal(ga == bound, pa == bound)
-        assert np.abs(ga - pa).max() <= 1e-11 * 300.0
+        assert np.abs(ga - pa).max() <= 1e-11 * amax
         for k in ("zeta_c", "zeta_f", "Delta"):
             scale = np.abs(p.f[k]).max()
             assert np.abs(cmp_region(c, k, g[k]) - cmp_region(c, k, p.f[k])).max() <= 1e-10 * scale, k

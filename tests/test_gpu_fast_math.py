@@ -15,6 +15,7 @@ import numpy as np
 import pytest
 import torch
 
+import evp_parameter_sets as ps
 import fast_math_build
 import fast_math_ref as R
 from fast_math_ref import D, U
@@ -105,13 +106,15 @@ def masses(rng, n):
 STRESS_ROWS = ["e11c", "e22c", "e12f", "e11f", "e22f", "e12c", "Pc", "Pf", "mc", "mf", "rmc", "rmf", "hkc", "hkf", "s11", "s22", "s12"]
 
 
-def stress_inputs(probe, n, seed, gamma_targets=0.3, own_set_apart=False):
+def stress_inputs(probe, n, seed, gamma_targets=0.3, own_set_apart=False, consts=None):
     """(17, n) rows in stress_update_r's argument order; rmc, rmf from fm::rcp itself.  Every row is drawn independently of the others
     (P = 0 under an ordinary mass, P > 0 over no mass, ...).  A fraction of the elements gets an hkc / hkf that puts gamma between the
     clamps (elsewhere the broad magnitudes leave it on a plateau almost always).
     own_set_apart: the comparison with the REFERENCE leaves one combination to a test of its own
     (test_subnormal_mass_under_zero_ice_strength): P == 0 under a SUBNORMAL mass, where evp_fast_math.h documents alpha+ against the
-    reference's alpha-.  Exactly those elements get the smallest normal mass instead; nothing else is touched."""
+    reference's alpha-.  Exactly those elements get the smallest normal mass instead; nothing else is touched.
+    consts: the stress constants of a non-default parameter set (fast_math_ref.stress_constants); the targeted gammas then lie between
+    that set's clamps, 4 % of their distance inside, as 60 .. 290 do between the default 50 and 300."""
     rng = np.random.default_rng(seed)
     a = {k: logmag(rng, n, 1e-30, 1e3) for k in STRESS_ROWS[:6]}
     small = rng.random(n) < 0.5                                  # half of the cells at geophysical rates (1e-10 .. 1e-4 s^-1)
@@ -125,12 +128,14 @@ def stress_inputs(probe, n, seed, gamma_targets=0.3, own_set_apart=False):
     if own_set_apart:
         for P, m in (("Pc", "mc"), ("Pf", "mf")):
             a[m][(a[P] == 0) & (a[m] > 0) & (a[m] < DBL_MIN)] = DBL_MIN
-    k0 = R.stress_constants()
+    k0 = R.stress_constants() if consts is None else consts
+    inside = 0.04 * (k0["amax"] - k0["amin"])
+    g_lo, g_hi = (60.0, 290.0) if consts is None else (k0["amin"] + inside, k0["amax"] - inside)
     t = rng.random(n) < gamma_targets
     for (P, m, hk, e1, e2, e12, other) in (("Pc", "mc", "hkc", "e11c", "e22c", "e12c", None), ("Pf", "mf", "hkf", "e11f", "e22f", "e12f", None)):
         delta = np.maximum(np.sqrt((a[e1] + a[e2]) ** 2 + ((a[e1] - a[e2]) ** 2 + 4 * a[e12] ** 2) * k0["em2"]), k0["Dmin"])
         ok = t & (a[P] > 0) & (a[m] > 1e-3)
-        g = rng.uniform(60.0, 290.0, n)
+        g = rng.uniform(g_lo, g_hi, n)
         a[hk] = np.where(ok, g * g * delta * a[m] / np.where(ok, a[P], 1.0), a[hk])
     rows = np.stack([a.get(k, np.zeros(n)) for k in STRESS_ROWS])
     rows[10], rows[11] = primitives(probe, rows[8])[2], primitives(probe, rows[9])[2]
@@ -346,17 +351,34 @@ def ratios(got, ref, bound, K):
         return R.worst_ratio(got, ref, [K * b for b in bound])
 
 
+# the parameter sets of tests/evp_parameter_sets.py as fast_math_ref.stress_constants keywords: e = 1.7 and 2.7 (e^-2 and (1 - e^-2) / 2 are
+# not exact there, as they are at the default e = 2), clamps 6 / 11 and 4 / 9, Delta_min 8e-6 and 1.3e-5
+PARAMETER_SETS = {name: dict(ecc=s["ecc"], Dmin=s["delta_min"], amin=s["alpha_min"], amax=s["alpha_max"]) for name, s in (("A", ps.SET_A), ("B", ps.SET_B))}
+
+
 @pytest.mark.parametrize("pressure_kind", [0, 1])
 def test_stress_update_against_the_reference(probe, pressure_kind):
+    stress_update_against_the_reference(probe, pressure_kind)
+
+
+@pytest.mark.parametrize("pressure_kind", [0, 1])
+@pytest.mark.parametrize("name", sorted(PARAMETER_SETS))
+def test_stress_update_against_the_reference_on_parameter_sets(probe, name, pressure_kind):
+    """The same comparison, under the same derived bounds, with the constants of the non-default parameter sets: 3000 elements each, the
+    targeted gammas between that set's clamps, the plateaus at that set's alpha-, alpha+."""
+    stress_update_against_the_reference(probe, pressure_kind, consts=PARAMETER_SETS[name], n=3000, seed=160 + 2 * sorted(PARAMETER_SETS).index(name))
+
+
+def stress_update_against_the_reference(probe, pressure_kind, consts=None, n=10000, seed=60):
     """stress_update_r, 10 000 elements of the domain per pressure kind, against fast_math_ref.stress_cell under
         |sigma - ref| <= K_SIGMA u (|sigma| + (|2 eta eps| + |(zeta - eta) div| + |P_r / 2| + |sigma|) / gamma),   |alpha - ref| <= K_ALPHA u alpha
     (K_SIGMA = 594, K_ALPHA = 168: derived in fast_math_ref.py, never fitted).  Where the exact gamma^2 lies beyond a clamp by more than
     its own error bound alpha must be alpha+- exactly; ice-free cells / corners keep sigma bit for bit.
     Power: the reference evaluated once more with e^-2, hk1 or hkc off by 2^-40 must violate a bound somewhere."""
-    n = 10000
-    k = R.stress_constants(pressure_kind=pressure_kind)
-    rows = stress_inputs(probe, n, seed=60 + pressure_kind, own_set_apart=True)
-    assert ((rows[6] == 0) & (rows[8] >= DBL_MIN)).sum() > 100 and ((rows[7] == 0) & (rows[9] >= DBL_MIN)).sum() > 100   # P = 0 under ice
+    k = R.stress_constants(pressure_kind=pressure_kind, **(consts or {}))
+    amin, amax = k["amin"], k["amax"]
+    rows = stress_inputs(probe, n, seed=seed + pressure_kind, own_set_apart=True, consts=None if consts is None else k)
+    assert ((rows[6] == 0) & (rows[8] >= DBL_MIN)).sum() > n // 100 and ((rows[7] == 0) & (rows[9] >= DBL_MIN)).sum() > n // 100   # P = 0 under ice
     out = launch(probe.fmp_stress, (0, stress_consts(k)), rows, 8)
     assert np.isfinite(out).all()
     args = lambda i: [rows[q][i] for q in (0, 1, 2, 3, 4, 5, 6, 7, 8, 9, 12, 13, 14, 15, 16)]
@@ -378,7 +400,7 @@ def test_stress_update_against_the_reference(probe, pressure_kind):
     KK = dict(s11=R.K_SIGMA, s22=R.K_SIGMA, s12=R.K_SIGMA, alpha=R.K_ALPHA)
     col = dict(s11=0, s22=1, s12=2, alpha=3)
     worst = {name: ratios(out[col[name]], ref[name], bnd[name], KK[name]) for name in KK}
-    between = sum(1 for a in ref["alpha"] if 50 < a < 300)
+    between = sum(1 for a in ref["alpha"] if amin < a < amax)
     print(f"stress_update_r, pressure kind {pressure_kind}: worst error / bound " + ", ".join(f"{name} {worst[name][0]:.4f}" for name in KK)
           + f" ({between} of {n} cells with alpha between the clamps)")
     assert between > n // 10
@@ -391,27 +413,27 @@ def test_stress_update_against_the_reference(probe, pressure_kind):
         for i in idx:
             zc = D(float(out[4][i])) / 2
             if rows[8][i] > 0:
-                g2 = float(zc * 2 * D(float(rows[12][i])) / D(float(rows[8][i])) / D(300.0 ** 2)) if zc > 0 else 0.0
+                g2 = float(zc * 2 * D(float(rows[12][i])) / D(float(rows[8][i])) / D(amax ** 2)) if zc > 0 else 0.0
                 if g2 > 1 + margin:
-                    assert out[3][i] == 300.0, i
+                    assert out[3][i] == amax, i
                     on_plateau += 1
-                elif g2 < (50.0 / 300.0) ** 2 * (1 - margin):
-                    assert out[3][i] == 50.0, i
+                elif g2 < (amin / amax) ** 2 * (1 - margin):
+                    assert out[3][i] == amin, i
                     on_plateau += 1
             else:
-                assert out[3][i] == 300.0, i
+                assert out[3][i] == amax, i
     assert on_plateau > n // 10
     free_c, free_f = rows[8] <= 0, rows[9] <= 0
-    assert free_c.sum() > 100 and free_f.sum() > 100
+    assert free_c.sum() > n // 100 and free_f.sum() > n // 100
     assert same_bits(out[0][free_c], rows[14][free_c]) and same_bits(out[1][free_c], rows[15][free_c]) and same_bits(out[2][free_f], rows[16][free_f])
     # power of the test
-    sub = range(2500)
+    sub = range(min(2500, n))
     with R.hp():
         eps = 1 + D(2) ** -40
         perturbed = dict(em2=dict(em2=D(k["em2"]) * eps), hk1=dict(hk1=(1 - D(k["em2"])) / 2 * eps), hkc=dict(hkc_scale=eps))
     for what, pert in perturbed.items():
         pref, pbnd = evaluate(sub, **pert)
-        w = max(ratios(out[col[name]][:2500], pref[name], pbnd[name], KK[name])[0] for name in KK)
+        w = max(ratios(out[col[name]][:len(sub)], pref[name], pbnd[name], KK[name])[0] for name in KK)
         print(f"  reference with {what} off by 2^-40: worst error / bound {w:.2f}")
         assert w > 1.0, what
 
