@@ -29,11 +29,11 @@ def advection_of(scheme, weight_dtype="f64"):
     return csi.WENO(order=scheme, weight_dtype=weight_dtype) if scheme > 0 and scheme != 1 else csi.UpwindBiased(order=abs(scheme))
 
 
-def flow_case(Nx, Ny, topo, metric=0, land=True, seed=5, cfl=0.2, **kw):
+def flow_case(Nx, Ny, topo, metric=0, land=True, seed=5, cfl=0.2, H=4, **kw):
     """seeded divergent velocities with |U| dt / dx <= cfl, aice in [0.2, 0.9] with an open-water patch, hand-placed land: a block in
     the interior, cells on the first and last column and row, a cell in a corner"""
     rng = np.random.default_rng(seed)
-    c = cases.make_case(Nx=Nx, Ny=Ny, H=4, topo=topo, spacing=1000.0, patches=False, noise=0.0, top=None, bottom=None, coriolis=None,
+    c = cases.make_case(Nx=Nx, Ny=Ny, H=H, topo=topo, spacing=1000.0, patches=False, noise=0.0, top=None, bottom=None, coriolis=None,
                         **dict(METRICS[metric], **kw))
     g = c["g"]
     dxmin = 1000.0 if metric == 0 else float(np.min(g.metrics()["dxc" if metric == 1 else "dxcc"]))

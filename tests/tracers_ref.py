@@ -12,6 +12,7 @@ import ctypes as C
 import numpy as np
 
 import oracle as O
+from advect_ref import same_bits      # noqa: F401  (bit for bit, signs of zero included, a NaN matching any NaN)
 
 
 def tracer(p, interior, weighted=False, nonneg=True, source=0.0):
@@ -72,16 +73,24 @@ def first_half(G, cb, ab, Ga, dt, weighted):
         return np.where(a_star > 0, ((ab * cb) + dt * G) / a_star, 0.0)
 
 
+def jmax(a, b):
+    """Julia's max, as csrc/advect_dev.h jmax states it: NaN where either argument is NaN, otherwise b where a < b and a elsewhere --
+    so jmax(0.0, -0.0) is +0.0, where numpy's maximum is free to return either zero"""
+    a, b = np.broadcast_arrays(np.asarray(a, dtype=np.float64), np.asarray(b, dtype=np.float64))
+    with np.errstate(invalid="ignore"):
+        return np.where(np.isnan(a) | np.isnan(b), np.nan, np.where(a < b, b, a))
+
+
 def second_half(star, a, act, dt, nonneg, source):
     with np.errstate(over="ignore", invalid="ignore"):
-        x = np.maximum(0.0, star) if nonneg else star          # (numpy's maximum propagates NaN like Julia's max)
+        x = jmax(0.0, star) if nonneg else star
         return np.where((a > 0) & act, x + dt * source, 0.0)
 
 
 def free_half(star, a, act, nonneg):
     """the second half without the source: the field the next RK3 stage's stencil reads"""
     with np.errstate(over="ignore", invalid="ignore"):
-        x = np.maximum(0.0, star) if nonneg else star
+        x = jmax(0.0, star) if nonneg else star
         return np.where((a > 0) & act, x, 0.0)
 
 
